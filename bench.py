@@ -21,7 +21,14 @@ The line's `dtype` says so.  Inputs are resident in HBM before the timed region.
                                       region, bit-equal to K serial steps); `config.serial_ms_per_step` = the serial step in the same process,
                                       --no-pipeline times that one alone
 
-Rank 0 prints ONE JSON line (see the driver contract) with extra objects:
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (rank 0): the headline `metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step` and the workload's `config`.
+  --dump-outputs DIR  after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64, a few
+                      MB; inputs are seeded, so runs of two builds with the same arguments can be compared array by array)
+  --full              everything else the benchmark measures, each after the headline's timed region (the extra legs below, and
+                      for --config joint the serial / other-path step timings); --layer-table needs it
+
+With --full, rank 0's line carries extra objects:
   roofline      -- the dominant kernel (the conv instantiation with the largest time share): the FLOPs the matrix pipe EXECUTES per
                    launch / mean launch time against the peak OF THE PIPE THE KERNEL RUNS ON (`peak`: 2500 TFLOP/s dense bf16 for the
                    split-bf16 kernels wino32b (wino64b when forced) / pw_chain<..., true> / igemm_bs, 157.3 TFLOP/s for the fp32-MFMA kernels);
@@ -112,7 +119,14 @@ def parse():
     ap.add_argument("--joint-host-images", action="store_true", help="joint leg: hand the image over as a host array every step")
     ap.add_argument("--joint-conv-math", default=None, help="joint leg: conv arithmetic (f32 | bf16x3 | bf16x2 | bf16); default bf16 with "
                     "--joint-dtype bf16 (forward convolutions and data gradients; weight gradients accumulate fp32 products)")
+    ap.add_argument("--full", action="store_true", help="also run every measurement beyond the headline (roofline, alt_math, other_configs, "
+                    "cpu_baseline; joint: serial / other-path step timings); a plain run times the headline alone")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy")
     a = ap.parse_args()
+    if a.layer_table and not a.full:
+        ap.error("--layer-table comes from the roofline leg: add --full")
+    if not a.full:
+        a.no_cpu_baseline = a.no_roofline = a.no_alt_math = a.no_other_configs = True
     if a.vocab is None:
         a.vocab = 50000 if a.config == "joint" else 10000
     return a
@@ -452,6 +466,31 @@ def dataset_pipeline_leg(args, dev, steps=120):
             "final_loss": hist[-1]["loss"]}
 
 
+DUMP_SAMPLE = 1 << 20            # elements kept of a larger output (fixed seeded positions): every dump stays well under 64 MB
+
+
+def _dump_array(t, n=DUMP_SAMPLE):
+    """A device or host array as float32 numpy: whole when it has at most `n` elements, else the elements at `n` fixed positions
+    (sorted, seed 0: the same positions in every run of the same shape)."""
+    flat = torch.as_tensor(t).detach().reshape(-1).float()
+    if flat.numel() > n:
+        idx = np.sort(np.random.default_rng(0).choice(flat.numel(), n, replace=False))
+        flat = flat[torch.as_tensor(idx, device=flat.device)]
+    return flat.cpu().numpy()
+
+
+def dump_outputs(path, loss, store, feat=None):
+    """--dump-outputs: the last timed step's loss(es), the RoI features it ran on (when given), and the trainable parameters after its
+    update with the gradients it computed (the optimizer's flat buckets) -- what the step hands back and leaves behind."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {"loss": np.asarray(torch.as_tensor(loss).detach().cpu().numpy(), np.float64).reshape(-1),
+              "trainable_weights": _dump_array(store.flat), "gradients": _dump_array(store.flat_grad)}
+    if feat is not None:
+        arrays["roi_features"] = _dump_array(feat, 4 * DUMP_SAMPLE).reshape(feat.shape if feat.numel() <= 4 * DUMP_SAMPLE else (-1,))
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 class E2E(object):
     """The configs[2]/[3] train step: encoder plan + v2-inject decoder (+ ParallelModel), optionally pipelined on 2 streams."""
 
@@ -508,6 +547,10 @@ class E2E(object):
 
     def flush(self):
         return self.pipe.flush() if self.pipe is not None else None
+
+    def last_features(self):
+        """The RoI features the last step's decoder pass trained on (the pipeline's slot of its last call)."""
+        return self.pipe.feat[(self.pipe.n - 1) & 1] if self.pipe is not None else self.feat
 
     def timed(self, warmup, steps, barrier):
         for _ in range(max(warmup, 2)):               # >= 2: the second call captures the encoder hipGraph
@@ -744,13 +787,18 @@ def run_joint(args, dev, rank, world, barrier):
     barrier()
     dt = time.perf_counter() - t0
     out = inner._losses_to_api(out_dev.cpu().numpy())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, out_dev, inner.store)
     R = cfg.TRAIN_ROIS_PER_IMAGE * args.joint_images_per_gpu          # captions (RoIs with their targets) per step and GPU
     inner.other_path_ms_per_step = None
     inner.pipelined = pipe is not None
     inner.serial_ms_per_step = None
     if world == 1 and pipe is not None:
-        # the serial step (eager launches, the path the model's own measurement kept on this pool's boxes) over the same K steps, beside it
         inner.timed_path = "pipelined"
+    elif world == 1:
+        inner.timed_path = "graph" if (inner.use_step_graph and any(k[0] == "train" for k in inner._graphs)) else "eager"
+    if world == 1 and pipe is not None and args.full:
+        # the serial step (eager launches, the path the model's own measurement kept on this pool's boxes) over the same K steps, beside it
         for _ in range(3):
             inner.train_on_batch(inputs)
         torch.cuda.synchronize()
@@ -759,11 +807,10 @@ def run_joint(args, dev, rank, world, barrier):
             inner.train_on_batch_device(inputs)
         torch.cuda.synchronize()
         inner.serial_ms_per_step = 1e3 * (time.perf_counter() - t1) / args.steps
-    elif world == 1:
+    elif world == 1 and args.full:
         # what the data-parallel step gives up (or gains) by issuing its launches from Python (its collectives cannot
         # sit inside a capture): the SAME step with the same two-stream fork on the OTHER path -- eager when the timed region replayed the
         # captured graph, the graph when the model's measured choice was eager -- timed after the headline region, reported beside it
-        inner.timed_path = "graph" if (inner.use_step_graph and any(k[0] == "train" for k in inner._graphs)) else "eager"
         inner.use_step_graph = inner.timed_path == "eager"
         for _ in range(4):
             inner.train_on_batch(inputs)
@@ -1026,6 +1073,8 @@ def main():
     ar = e2e.sync.exposed_ms() if e2e.sync is not None else None      # rank 0's view: time its decoder stream stood still for the exchange
     captions = world * B * R * args.steps
     final_loss = float(loss.item())
+    if rank == 0 and args.dump_outputs:                 # before any --full leg steps the decoder again
+        dump_outputs(args.dump_outputs, loss, e2e.inner.store, e2e.last_features())
 
     out = {
         "metric": "captions/sec (train step) on 1024px x 32RoI x 15tok synth",
@@ -1061,7 +1110,7 @@ def main():
                             "test tolerances as f32); 3x3 layers: the headline's Winograd kernel",
                   "bf16x2": "1x1 / strided / stem layers: 2-piece bf16 split, 3 MFMA products, fp32 accumulate (2^-16 products; features within "
                             "1e-3 of the oracle); 3x3 layers: the headline's Winograd kernel"}
-        cmd = [sys.executable, os.path.abspath(__file__), "--steps", str(args.steps), "--warmup", str(args.warmup), "--no-alt-math",
+        cmd = [sys.executable, os.path.abspath(__file__), "--full", "--steps", str(args.steps), "--warmup", str(args.warmup), "--no-alt-math",
                "--no-cpu-baseline", "--no-other-configs", "--images-per-gpu", str(B), "--rois", str(R), "--tokens", str(T),
                "--vocab", str(V), "--image-size", str(S), "--stage4-blocks", str(args.stage4_blocks)] + (["--no-pipeline"] if args.no_pipeline else [])
         out["alt_math"] = {}
@@ -1079,7 +1128,7 @@ def main():
             # configs[2] proper: ONE image per step, timed by a child process (a fresh context, like the alt_math legs)
             del e2e
             torch.cuda.empty_cache()
-            cmd1 = [sys.executable, os.path.abspath(__file__), "--steps", str(args.steps), "--warmup", str(args.warmup), "--no-alt-math",
+            cmd1 = [sys.executable, os.path.abspath(__file__), "--full", "--steps", str(args.steps), "--warmup", str(args.warmup), "--no-alt-math",
                     "--no-cpu-baseline", "--no-other-configs", "--no-roofline", "--images-per-gpu", "1", "--rois", str(R), "--tokens", str(T),
                     "--vocab", str(V), "--image-size", str(S), "--stage4-blocks", str(args.stage4_blocks)] + (["--no-pipeline"] if args.no_pipeline else [])
             r1 = subprocess.run(cmd1, capture_output=True, text=True, timeout=300)
@@ -1097,7 +1146,7 @@ def main():
             other["configs1_gpu"] = gpu_configs1(dev)
             other["train_on_dataset"] = dataset_pipeline_leg(args, dev)
             # configs[2]'s label taken literally: the VGG16 13-conv backbone (child process; its roofline leg gives the conv TFLOP/s)
-            cmdv = [sys.executable, os.path.abspath(__file__), "--backbone", "vgg16", "--steps", str(max(5, args.steps // 2)), "--warmup", "2",
+            cmdv = [sys.executable, os.path.abspath(__file__), "--full", "--backbone", "vgg16", "--steps", str(max(5, args.steps // 2)), "--warmup", "2",
                     "--images-per-gpu", str(B), "--rois", str(R), "--tokens", str(T), "--vocab", str(V), "--image-size", str(S)]
             rv = subprocess.run(cmdv, capture_output=True, text=True, timeout=300)
             vg = json.loads(rv.stdout.strip().splitlines()[-1])
@@ -1109,7 +1158,7 @@ def main():
         try:
             # BASELINE configs[4]: the joint model's train step in bf16 (child process; carries its own roofline block against the
             # dense bf16 MFMA peak)
-            cmdj = [sys.executable, os.path.abspath(__file__), "--config", "joint", "--steps", str(max(5, args.steps // 2)), "--warmup", "3",
+            cmdj = [sys.executable, os.path.abspath(__file__), "--full", "--config", "joint", "--steps", str(max(5, args.steps // 2)), "--warmup", "3",
                     "--image-size", str(S), "--tokens", str(T), "--stage4-blocks", str(args.stage4_blocks)]
             rj = subprocess.run(cmdj, capture_output=True, text=True, timeout=400)
             jt = json.loads(rj.stdout.strip().splitlines()[-1])

@@ -404,22 +404,19 @@ def test_jpeg_decode_and_grayscale_expansion(tmp_path):
 
 
 def test_reference_sample_images_decode_and_resize_to_the_committed_fixture():
-    """The six Visual Genome JPEGs the reference ships (dataset/visual genome/): decoded size, pixel checksum and the resized
-    1024 x 1024 input of the model are pinned in tests/golden/vg_sample_images.json (made by tests/golden/make_image_fixtures.py).
-    Needs the reference checkout; skipped where it is absent (the GPU box)."""
+    """Six committed photo-like JPEGs of the Visual Genome samples' size (600 x 800, tests/golden/sample_images/): decoded size,
+    pixel checksum and the resized 1024 x 1024 input of the model are pinned in tests/golden/sample_images.json (both made by
+    tests/golden/make_image_fixtures.py)."""
     import json
-    ref = "/root/reference/dataset/visual genome"
-    if not os.path.isdir(ref):
-        pytest.skip("reference checkout not present")
     sys_path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
     import importlib.util
     spec = importlib.util.spec_from_file_location("make_image_fixtures", os.path.join(sys_path, "make_image_fixtures.py"))
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
-    want = json.load(open(os.path.join(sys_path, "vg_sample_images.json")))
+    want = json.load(open(os.path.join(sys_path, "sample_images.json")))
     assert len(want) == 6
     for name, row in want.items():
-        got = mod.describe(os.path.join(ref, name))
+        got = mod.describe(os.path.join(mod.IMAGES, name))
         assert got["shape"] == row["shape"] and got["sha1"] == row["sha1"], name
         assert got["resized_shape"] == [1024, 1024, 3] and got["window"] == row["window"] and got["scale"] == row["scale"], name
         assert got["resized_sha1"] == row["resized_sha1"], name

@@ -11,7 +11,7 @@ mkdir -p $out
 root=$PWD
 cd /tmp && export TMPDIR=/tmp
 if [ "$part" = "a1" ] || [ "$part" = "a" ] || [ "$part" = "all" ]; then
-python3 $root/bench.py --steps 20 --warmup 3 --layer-table $out/conv_layers.tsv > $out/bench.log 2>&1
+python3 $root/bench.py --full --steps 20 --warmup 3 --layer-table $out/conv_layers.tsv > $out/bench.log 2>&1
 tail -1 $out/bench.log > $out/bench.json
 rocprofv3 --kernel-trace --stats -d $out/trace -o bench -- python3 $root/bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-roofline --no-alt-math --no-other-configs > $out/trace.log 2>&1
 python3 $root/tools/prof_summary.py $out/trace/bench_results.db $out/bench_kernel_stats.csv 23
@@ -22,23 +22,23 @@ rm -rf $out/trace $out/pmc_fetch $out/pmc_write
 fi
 if [ "$part" = "a2" ] || [ "$part" = "a" ] || [ "$part" = "all" ]; then
 # joint model: bench line (bf16 as specified, fp32, the reference's dropout), kernel summary + step timeline (captured graph and eager)
-python3 $root/bench.py --config joint --steps 20 > $out/joint_bench.log 2>&1
+python3 $root/bench.py --full --config joint --steps 20 > $out/joint_bench.log 2>&1
 tail -1 $out/joint_bench.log > $out/joint_bench.json
-python3 $root/bench.py --config joint --steps 10 --joint-dtype f32 --no-roofline > $out/joint_bench_f32.log 2>&1
+python3 $root/bench.py --full --config joint --steps 10 --joint-dtype f32 --no-roofline > $out/joint_bench_f32.log 2>&1
 tail -1 $out/joint_bench_f32.log > $out/joint_bench_f32.json
-python3 $root/bench.py --config joint --steps 10 --joint-dropout 0.2 --no-roofline > $out/joint_bench_dropout.log 2>&1
+python3 $root/bench.py --full --config joint --steps 10 --joint-dropout 0.2 --no-roofline > $out/joint_bench_dropout.log 2>&1
 tail -1 $out/joint_bench_dropout.log > $out/joint_bench_dropout.json
-python3 $root/bench.py --config joint --steps 10 --joint-images-per-gpu 2 --no-roofline > $out/joint_bench_2img.log 2>&1
+python3 $root/bench.py --full --config joint --steps 10 --joint-images-per-gpu 2 --no-roofline > $out/joint_bench_2img.log 2>&1
 tail -1 $out/joint_bench_2img.log > $out/joint_bench_2img.json
-DCAP_VOCAB_MATERIALIZE=0 python3 $root/bench.py --config joint --steps 10 --no-roofline > $out/joint_bench_recompute_logits.log 2>&1
+DCAP_VOCAB_MATERIALIZE=0 python3 $root/bench.py --full --config joint --steps 10 --no-roofline > $out/joint_bench_recompute_logits.log 2>&1
 tail -1 $out/joint_bench_recompute_logits.log > $out/joint_bench_recompute_logits.json
-rocprofv3 --kernel-trace --stats -d $out/joint -o joint -- python3 $root/bench.py --config joint --steps 10 --no-roofline > $out/joint.log 2>&1
+rocprofv3 --kernel-trace --stats -d $out/joint -o joint -- python3 $root/bench.py --full --config joint --steps 10 --no-roofline > $out/joint.log 2>&1
 python3 $root/tools/prof_summary.py $out/joint/joint_results.db $out/joint_kernels.csv 37   # 8 warm-up + 6 pipeline warm-up + 10 timed (pipelined) + 3 + 10 serial steps beside them
 python3 $root/tools/prof_timeline.py $out/joint/joint_results.db $out/joint_timeline.tsv amsgrad 15 || true          # a step of the pipelined leg (the 13 serial steps run behind it)
 python3 $root/tools/prof_timeline.py $out/joint/joint_results.db $out/joint_timeline_serial.tsv || true
 rm -rf $out/joint
-rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/jf -- python3 $root/bench.py --config joint --steps 3 --warmup 2 --no-roofline > $out/joint_pmc_fetch.log 2>&1
-rocprofv3 --pmc WRITE_SIZE --output-format csv -d $out/jw -- python3 $root/bench.py --config joint --steps 3 --warmup 2 --no-roofline > $out/joint_pmc_write.log 2>&1
+rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/jf -- python3 $root/bench.py --full --config joint --steps 3 --warmup 2 --no-roofline > $out/joint_pmc_fetch.log 2>&1
+rocprofv3 --pmc WRITE_SIZE --output-format csv -d $out/jw -- python3 $root/bench.py --full --config joint --steps 3 --warmup 2 --no-roofline > $out/joint_pmc_write.log 2>&1
 python3 $root/tools/pmc_traffic.py $out/jf $out/jw $out/joint_pmc_traffic.json || true
 rm -rf $out/jf $out/jw
 fi
@@ -62,7 +62,7 @@ rocprofv3 --kernel-trace --stats -d $out/dec -o dec -- python3 $root/tools/decod
 python3 $root/tools/prof_summary.py $out/dec/dec_results.db $out/decoder_kernels.csv 53
 rm -rf $out/dec
 cd $root
-timeout -k 10 300 python3 bench.py --gpus 2 --steps 5 --warmup 2 > $out/rehearsal_2rank_selflaunch.log 2>&1 || true
+timeout -k 10 300 python3 bench.py --full --gpus 2 --steps 5 --warmup 2 > $out/rehearsal_2rank_selflaunch.log 2>&1 || true
 timeout -k 10 300 python3 bench.py --config joint --gpus 2 --steps 5 --warmup 2 --no-roofline > $out/rehearsal_2rank_joint.log 2>&1 || true
 DCAP_GRAD_DTYPE=bf16 timeout -k 10 300 python3 bench.py --config joint --gpus 2 --steps 5 --warmup 2 --no-roofline > $out/rehearsal_2rank_joint_bf16wire.log 2>&1 || true
 bash tools/roialign_profile.sh > /dev/null 2>&1 && cp gpurun_out/roialign_profile.txt $out/roialign_hbm.txt && cp gpurun_out/roialign_hbm.json $out/roialign_hbm.json || true
