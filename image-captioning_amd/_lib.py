@@ -102,6 +102,19 @@ class VocabCeDesc(C.Structure):
                 ("dlogits", C.c_void_p), ("lddl", C.c_int), ("dl_bf16", C.c_int), ("dbias", C.c_void_p), ("materialize_bf16", C.c_int)]
 
 
+class VocabTop1Desc(C.Structure):
+    _fields_ = [("M", C.c_int), ("V", C.c_int), ("K", C.c_int),
+                ("X", C.c_void_p), ("ldx", C.c_int), ("W", C.c_void_p), ("ldw", C.c_int),
+                ("bias", C.c_void_p), ("tokens", C.c_void_p),
+                ("ids", C.c_void_p), ("ld_ids", C.c_int), ("probs", C.c_void_p), ("ld_probs", C.c_int), ("mask", C.c_void_p)]
+
+
+class LstmStepDesc(C.Structure):
+    _fields_ = [("B", C.c_int), ("U", C.c_int),
+                ("z", C.c_void_p), ("U_rec", C.c_void_p), ("U_packed", C.c_void_p),
+                ("h_prev", C.c_void_p), ("c_prev", C.c_void_p), ("mask", C.c_void_p), ("h", C.c_void_p), ("c", C.c_void_p)]
+
+
 class BnReluDesc(C.Structure):
     _fields_ = [("M", C.c_int), ("N", C.c_int), ("ld", C.c_int), ("acc", C.c_void_p),
                 ("bias", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p), ("mean", C.c_void_p), ("var", C.c_void_p),
@@ -203,9 +216,14 @@ SYMBOLS = {
     "dc_lstm_seq_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "dc_lstm_seq_fwd_f32": (C.c_int, [C.POINTER(LstmFwdDesc), C.c_void_p, C.c_size_t, C.c_void_p]),
     "dc_lstm_seq_bwd_f32": (C.c_int, [C.POINTER(LstmBwdDesc), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "dc_lstm_pack_urec_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "dc_lstm_step_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "dc_lstm_step_f32": (C.c_int, [C.POINTER(LstmStepDesc), C.c_void_p, C.c_size_t, C.c_void_p]),
     "dc_softmax_ce_f32": (C.c_int, [C.POINTER(SoftmaxCeDesc), C.c_void_p]),
     "dc_vocab_ce_workspace_bytes": (C.c_size_t, [C.POINTER(VocabCeDesc)]),
     "dc_vocab_ce": (C.c_int, [C.POINTER(VocabCeDesc), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "dc_vocab_top1_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "dc_vocab_top1_f32": (C.c_int, [C.POINTER(VocabTop1Desc), C.c_void_p, C.c_size_t, C.c_void_p]),
     "dc_argmax_rows_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "dc_gather_rows_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "dc_bn_relu_fwd_f32": (C.c_int, [C.POINTER(BnReluDesc), C.c_void_p]),

@@ -553,6 +553,22 @@ static dc_gemm_desc dU_desc(int B, int T, int U, const float* h_seq, const float
     return g;
 }
 
+// One fused forward timestep (U % 32 == 0, h_prev / c_prev given), the block shape chosen from (B, U) alone: dc_lstm_seq_fwd_f32 and
+// dc_lstm_step_f32 run the same kernel instance at the same batch, so a decode step by step reproduces the sequence bit for bit.
+static int launch_fused_fwd_step(float* z_t, const float* Upk, const float* hp, const float* cp, const uint8_t* mk, float* h_t, float* c_t,
+                                 int B, int U, hipStream_t s) {
+    const int frt = ((U / 8) * ((B + 31) / 32) <= 2 * kNumCU) ? 1 : 2;      // 32- or 64-row blocks (measured again in round 5 at 200 x 512: 12.3 vs 13.2 us)
+    const int fnw = (frt == 2 && (U & 63) == 0) ? 8 : 4;                     // measured: 4 waves at 32 rows, 8 at 64
+    const dim3 grid(U / 8, (B + 32 * frt - 1) / (32 * frt));
+#define LAUNCH_FWD_STEP(RT_, NW_) hipLaunchKernelGGL((lstm_step_fused_kernel<RT_, NW_>), grid, dim3(NW_ * 64), 0, s, z_t, Upk, hp, cp, mk, h_t, c_t, B, U)
+    if (frt == 1 && fnw == 8) LAUNCH_FWD_STEP(1, 8);
+    else if (frt == 1) LAUNCH_FWD_STEP(1, 4);
+    else if (fnw == 8) LAUNCH_FWD_STEP(2, 8);
+    else LAUNCH_FWD_STEP(2, 4);
+#undef LAUNCH_FWD_STEP
+    return check_launch("lstm_step_fused_kernel");
+}
+
 }  // namespace dcap
 
 using namespace dcap;
@@ -598,8 +614,6 @@ extern "C" int dc_lstm_seq_fwd_f32(const dc_lstm_fwd_desc* d, void* workspace, s
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int B = d->B, U = d->U, n = B * U, blocks = (n + 255) / 256;
     const bool fused = (U & 31) == 0 && d->T > 1;   // (else: per-step GEMM + gate kernel, with masks a mask kernel + four per-gate GEMMs)
-    int frt = ((U / 8) * ((B + 31) / 32) <= 2 * kNumCU) ? 1 : 2;      // 32- or 64-row blocks (measured again in round 5 at 200 x 512: 12.3 vs 13.2 us)
-    int fnw = (frt == 2 && (U & 63) == 0) ? 8 : 4;                     // measured: 4 waves at 32 rows, 8 at 64
     float* Upk = nullptr;
     float* hm = nullptr;                            // dropout: [4][B][U] masked copies of h_{t-1}, at the END of the workspace
     void* gws = workspace;
@@ -629,7 +643,6 @@ extern "C" int dc_lstm_seq_fwd_f32(const dc_lstm_fwd_desc* d, void* workspace, s
             const uint8_t* mk = d->mask ? d->mask + (long)t * B : nullptr;
             float* h_t = d->h_seq + (long)t * n;
             float* c_t = d->c_seq + (long)t * n;
-            const dim3 grid(U / 8, (B + 32 * frt - 1) / (32 * frt));
             if (d->rec_masks) {                        // recurrent dropout: one wave per gate, masks applied to the A fragments (lstm_step_masked_kernel)
                 const bool two = (U / 16) * ((B + 15) / 16) > kNumCU;              // 32-row blocks once 16-row blocks no longer fit the chip at once (measured: B = 200)
                 const dim3 gridm(U / 16, (B + (two ? 31 : 15)) / (two ? 32 : 16));
@@ -639,13 +652,7 @@ extern "C" int dc_lstm_seq_fwd_f32(const dc_lstm_fwd_desc* d, void* workspace, s
                 if (rc) return rc;
                 continue;
             }
-#define LAUNCH_FWD_STEP(RT_, NW_) hipLaunchKernelGGL((lstm_step_fused_kernel<RT_, NW_>), grid, dim3(NW_ * 64), 0, s, z_t, Upk, hp, cp, mk, h_t, c_t, B, U)
-            if (frt == 1 && fnw == 8) LAUNCH_FWD_STEP(1, 8);
-            else if (frt == 1) LAUNCH_FWD_STEP(1, 4);
-            else if (fnw == 8) LAUNCH_FWD_STEP(2, 8);
-            else LAUNCH_FWD_STEP(2, 4);
-#undef LAUNCH_FWD_STEP
-            int rc = check_launch("lstm_step_fused_kernel");
+            int rc = launch_fused_fwd_step(z_t, Upk, hp, cp, mk, h_t, c_t, B, U, s);
             if (rc) return rc;
             continue;
         }
@@ -773,4 +780,51 @@ extern "C" int dc_lstm_seq_bwd_f32(const dc_lstm_bwd_desc* d, void* workspace, s
         if (zrc) return zrc;
     }
     return DC_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// One timestep with carried state (incremental greedy decoding): the body of dc_lstm_seq_fwd_f32's step t for given h_prev / c_prev.
+// ------------------------------------------------------------------------------------------------
+extern "C" int dc_lstm_pack_urec_f32(const float* U_rec, int U, float* U_packed, void* stream) {
+    DC_REQUIRE(U_rec && U_packed, DC_EINVAL, "dc_lstm_pack_urec: null pointer");
+    DC_REQUIRE(U > 0 && (U & 31) == 0, DC_EINVAL, "dc_lstm_pack_urec: U must be a positive multiple of 32");
+    const long total = (long)4 * U * U;
+    hipLaunchKernelGGL(lstm_pack_urec_kernel, dim3((int)std::min<long>((total + 255) / 256, (long)kNumCU * 8)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), U_rec, U_packed, U);
+    return check_launch("lstm_pack_urec_kernel");
+}
+
+extern "C" size_t dc_lstm_step_workspace_bytes(int B, int U) {
+    if (B <= 0 || U <= 0) return 0;
+    dc_gemm_desc g = hU_desc(B, U, nullptr, nullptr, nullptr);
+    return align_up(dc_gemm_workspace_bytes(&g)) + ((U & 31) == 0 ? align_up((size_t)4 * U * U * sizeof(float)) : 0);
+}
+
+extern "C" int dc_lstm_step_f32(const dc_lstm_step_desc* d, void* workspace, size_t workspace_bytes, void* stream) {
+    DC_REQUIRE(d && d->z && d->U_rec && d->h && d->c, DC_EINVAL, "dc_lstm_step: null pointer");
+    DC_REQUIRE(d->B > 0 && d->U > 0 && (d->U & 3) == 0, DC_EINVAL, "dc_lstm_step: bad B/U (U %% 4 == 0)");
+    DC_REQUIRE((d->h_prev == nullptr) == (d->c_prev == nullptr), DC_EINVAL, "dc_lstm_step: h_prev and c_prev are both given or both NULL");
+    DC_REQUIRE(d->h != d->h_prev && d->c != d->c_prev && d->h != d->c, DC_EINVAL, "dc_lstm_step: h / c must not alias h_prev / c_prev / each other");
+    const size_t need = dc_lstm_step_workspace_bytes(d->B, d->U);
+    DC_REQUIRE(workspace_bytes >= need && (workspace || need == 0), DC_EWORKSPACE, "dc_lstm_step: needs %zu workspace bytes, got %zu", need, workspace_bytes);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int B = d->B, U = d->U, n = B * U;
+    if (d->h_prev && (U & 31) == 0) {
+        const float* Upk = d->U_packed;
+        if (!Upk) {                                     // packed here, at the END of the workspace (dc_lstm_pack_urec_f32 once per decode avoids it)
+            const size_t pack_bytes = align_up((size_t)4 * U * U * sizeof(float));
+            float* p = reinterpret_cast<float*>(static_cast<char*>(workspace) + (workspace_bytes - pack_bytes) / 256 * 256);
+            int rc = dc_lstm_pack_urec_f32(d->U_rec, U, p, stream);
+            if (rc) return rc;
+            Upk = p;
+        }
+        return launch_fused_fwd_step(d->z, Upk, d->h_prev, d->c_prev, d->mask, d->h, d->c, B, U, s);
+    }
+    if (d->h_prev) {
+        dc_gemm_desc g = hU_desc(B, U, d->h_prev, d->U_rec, d->z);
+        int rc = dc_gemm_f32(&g, workspace, workspace_bytes, stream);
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(lstm_gate_fwd_kernel, dim3((n + 255) / 256), dim3(256), 0, s, d->z, d->h_prev, d->c_prev, d->mask, d->h, d->c, B, U);
+    return check_launch("lstm_gate_fwd_kernel");
 }

@@ -11,7 +11,7 @@ import torch
 
 from . import _lib
 from ._lib import (PwChainDesc, ConvBf16Desc, AmsgradDesc, DetectionTargetsDesc, BnReluDesc, ConvDesc, ConvWgradBf16Desc, GemmBf16Desc, VocabCeDesc, ProposalDesc, RpnLossDesc, GemmDesc, LstmBwdDesc, LstmFwdDesc, RoiAlignDesc,
-                   SoftmaxCeDesc, check)
+                   SoftmaxCeDesc, VocabTop1Desc, LstmStepDesc, check)
 
 
 def _stream():
@@ -623,6 +623,55 @@ def lstm_seq_fwd(z, U_rec, mask, B, T, h_seq=None, c_seq=None, rec_masks=None):
     return h_seq, c_seq
 
 
+def lstm_pack_urec(U_rec, out=None):
+    """The line-contiguous copy of the recurrent kernel [U,4U] that lstm_step's fused step reads (dc_lstm_pack_urec_f32; U % 32 == 0):
+    made once per decode instead of once per step."""
+    _chk(U_rec, name="U_rec")
+    lib = _lib.load()
+    U = U_rec.shape[0]
+    if not U_rec.is_contiguous() or tuple(U_rec.shape) != (U, 4 * U):
+        raise _lib.DcapError("lstm_pack_urec: U_rec must be contiguous [U,4U]")
+    if out is None:
+        out = torch.empty((U, 4 * U), dtype=torch.float32, device=U_rec.device)
+    if not _chk(out, name="out").is_contiguous() or out.numel() != 4 * U * U:
+        raise _lib.DcapError("lstm_pack_urec: out must be a contiguous tensor of 4*U*U floats")
+    check(lib.dc_lstm_pack_urec_f32(_ptr(U_rec), U, _ptr(out), _stream()), "dc_lstm_pack_urec_f32")
+    return out
+
+
+def lstm_step(z, U_rec, h_prev=None, c_prev=None, mask=None, h=None, c=None, U_packed=None):
+    """ONE LSTM timestep with carried state (dc_lstm_step_f32): z [B,4U] (x-projection + bias, overwritten with the full pre-activation),
+    h_prev / c_prev [B,U] (None: zeros), mask uint8 [B] (None: every row live; rows with 0 copy h_prev / c_prev) -> h, c [B,U].
+    U_packed: lstm_pack_urec(U_rec) (None: repacked on every call when U % 32 == 0)."""
+    _chk(z, name="z"), _chk(U_rec, name="U_rec")
+    lib = _lib.load()
+    U = U_rec.shape[0]
+    B = z.shape[0]
+    if not z.is_contiguous() or not U_rec.is_contiguous() or tuple(z.shape) != (B, 4 * U) or tuple(U_rec.shape) != (U, 4 * U):
+        raise _lib.DcapError("lstm_step: z must be contiguous [B,4U], U_rec contiguous [U,4U]")
+    if (h_prev is None) != (c_prev is None):
+        raise _lib.DcapError("lstm_step: h_prev and c_prev are both given or both None")
+    h = torch.empty((B, U), dtype=torch.float32, device=z.device) if h is None else h
+    c = torch.empty((B, U), dtype=torch.float32, device=z.device) if c is None else c
+    for name, t in (("h_prev", h_prev), ("c_prev", c_prev), ("h", h), ("c", c)):
+        if t is not None and (not _chk(t, name=name).is_contiguous() or tuple(t.shape) != (B, U)):
+            raise _lib.DcapError("lstm_step: %s must be contiguous [B,U]" % name)
+    if mask is not None and (not _chk(mask, torch.uint8, "mask").is_contiguous() or mask.numel() != B):
+        raise _lib.DcapError("lstm_step: mask must be a contiguous uint8 [B] tensor")
+    if U_packed is not None and (not _chk(U_packed, name="U_packed").is_contiguous() or U_packed.numel() != 4 * U * U):
+        raise _lib.DcapError("lstm_step: U_packed must be lstm_pack_urec's contiguous 4*U*U floats")
+    if B == 0:
+        return h, c
+    d = LstmStepDesc()
+    d.B, d.U = B, U
+    d.z, d.U_rec, d.U_packed = z.data_ptr(), U_rec.data_ptr(), _ptr(U_packed)
+    d.h_prev, d.c_prev, d.mask = _ptr(h_prev), _ptr(c_prev), _ptr(mask)
+    d.h, d.c = h.data_ptr(), c.data_ptr()
+    ws, wsb = WORKSPACE.get(lib.dc_lstm_step_workspace_bytes(B, U), z.device)
+    check(lib.dc_lstm_step_f32(C.byref(d), _ptr(ws), wsb, _stream()), "dc_lstm_step_f32")
+    return h, c
+
+
 def lstm_seq_bwd(z, U_rec, mask, h_seq, c_seq, B, T, dh_seq=None, dh_last=None, dz=None, dU=None, accumulate_dU=False, rec_masks=None):
     lib = _lib.load()
     U = U_rec.shape[0]
@@ -707,6 +756,66 @@ def vocab_ce(X, W, bias, targets, loss_rows=None, dlogits=None, dbias=None, grad
     d.materialize_bf16 = int(bool(materialize_bf16) and bf and dlogits is not None and dlogits.dtype == BF16)
     ws, wsb = WORKSPACE.get(lib.dc_vocab_ce_workspace_bytes(C.byref(d)), X.device)
     check(lib.dc_vocab_ce(C.byref(d), _ptr(ws), wsb, _stream()), "dc_vocab_ce")
+
+
+def _row_out(t, M, dtype, name):
+    """A strided length-M device vector (e.g. column j of a row-major [B,T] matrix) -> (pointer, element stride)."""
+    if t is None:
+        return None, 1
+    if not t.is_cuda or t.dtype != dtype or t.dim() != 1 or t.shape[0] != M or (M > 1 and t.stride(0) < 1):
+        raise _lib.DcapError("vocab_top1: %s must be a %s device vector of %d elements" % (name, dtype, M))
+    return C.c_void_p(t.data_ptr()), max(1, t.stride(0))
+
+
+def vocab_top1(X, W, bias=None, tokens=None, ids=None, probs=None, mask=None):
+    """Fused Dense(V) + greedy top-1 (dc_vocab_top1_f32): per row of X [M,K] (float32, K % 32 == 0) the argmax of X W + bias (lowest
+    index on ties) into tokens int32 [M] (contiguous), optionally also into ids / probs (int32 / float32 length-M vectors with any
+    stride -- e.g. column j of [B,T] outputs; probs = the softmax probability of the chosen word) and mask uint8 [M] (id != 0).  The
+    [M,V] logits are never materialised.  Every V >= 1: a W whose rows are not 16-byte chunks is copied once into a padded buffer."""
+    _chk(X, name="X"), _chk(W, name="W")
+    if bias is not None:
+        _chk(bias, name="bias")
+    lib = _lib.load()
+    M, K = X.shape
+    V = W.shape[1]
+    if W.shape[0] != K:
+        raise _lib.DcapError("vocab_top1: inner dimensions differ (%d vs %d)" % (K, W.shape[0]))
+    if K % 32:
+        raise _lib.DcapError("vocab_top1: K must be a multiple of 32, got %d" % K)
+    if bias is not None and tuple(bias.shape) != (V,):
+        raise _lib.DcapError("vocab_top1: bias must be [V]")
+    if tokens is None:
+        tokens = torch.empty((M,), dtype=torch.int32, device=X.device)
+    if not _chk(tokens, torch.int32, "tokens").is_contiguous() or tokens.numel() != M:
+        raise _lib.DcapError("vocab_top1: tokens must be a contiguous int32 [M] tensor")
+    if mask is not None and (not _chk(mask, torch.uint8, "mask").is_contiguous() or mask.numel() != M):
+        raise _lib.DcapError("vocab_top1: mask must be a contiguous uint8 [M] tensor")
+    ids_p, ld_ids = _row_out(ids, M, torch.int32, "ids")
+    probs_p, ld_probs = _row_out(probs, M, torch.float32, "probs")
+    if M == 0:
+        return tokens
+    Vp = (V + 3) // 4 * 4
+    esz = W.element_size()
+    w_ok = (W.stride(0) % 4 == 0 and W.stride(0) >= Vp and W.data_ptr() % 16 == 0 and
+            (W.storage_offset() + (K - 1) * W.stride(0) + Vp) * esz <= W.untyped_storage().nbytes())
+    if not w_ok:                                       # (the kernel reads whole 16-byte column quads of W's rows)
+        Wp = torch.zeros((K, Vp), dtype=torch.float32, device=W.device)
+        Wp[:, :V].copy_(W)
+        W = Wp
+    if X.stride(0) % 4 or X.data_ptr() % 16:
+        X = torch.empty((M, K), dtype=torch.float32, device=X.device).copy_(X)
+    if bias is not None and (bias.data_ptr() % 16 or not bias.is_contiguous()):
+        bias = torch.empty((V,), dtype=torch.float32, device=bias.device).copy_(bias)
+    d = VocabTop1Desc()
+    d.M, d.V, d.K = M, V, K
+    d.X, d.ldx, d.W, d.ldw = X.data_ptr(), X.stride(0), W.data_ptr(), W.stride(0)
+    d.bias = _ptr(bias)
+    d.tokens = tokens.data_ptr()
+    d.ids, d.ld_ids, d.probs, d.ld_probs = ids_p, ld_ids, probs_p, ld_probs
+    d.mask = _ptr(mask)
+    ws, wsb = WORKSPACE.get(lib.dc_vocab_top1_workspace_bytes(M, V), X.device)
+    check(lib.dc_vocab_top1_f32(C.byref(d), _ptr(ws), wsb, _stream()), "dc_vocab_top1_f32")
+    return tokens
 
 
 def argmax_rows(x, out=None):

@@ -627,10 +627,76 @@ class CaptionModelV1(KerasLikeModel):
     def test_on_batch(self, inputs, targets):
         return float(self.test_on_batch_device(inputs, targets).item())
 
-    def generate(self, feat, return_probabilities=None):
+    DECODERS = ("prefix", "incremental")
+
+    @classmethod
+    def check_decoder(cls, decoder, return_probabilities):
+        """decoder='incremental' never forms the per-step [B,V] probability rows: it needs return_probabilities=False."""
+        if decoder not in cls.DECODERS:
+            raise ValueError("decoder must be one of %s, got %r" % (cls.DECODERS, decoder))
+        if decoder == "incremental" and return_probabilities is not False:
+            raise ValueError("decoder='incremental' returns no word probabilities: pass return_probabilities=False")
+
+    def decode_greedy(self, feat):
+        """Greedy decoding of ROICaptionInferenceLayer (:192-232) ONE token per step, entirely on the device: the RoI head and the per-RoI
+        halves of the first LSTM's and the Dense-1024's inputs once, then per token j the embedding-gather GEMM over the B rows, one
+        carried-state step of each LSTM (a generated id 0 is masked, as Keras masks it in the reference's padded prefix: the state is
+        carried over it), the Dense-1024 and the vocabulary layer fused with its argmax (ops.vocab_top1: no [B,V] logits).  The same
+        results as the prefix decoder: under the mask carry, the last row of the prefix-j pass IS the state after feeding token j.
+        Returns device tensors (ids int32 [B,T], word_scores float32 [B,T] = the softmax probability of each chosen word), two views
+        of one [2,B,T] buffer (one copy brings both to the host).  No host synchronisation."""
+        out = self._decode_greedy(feat)
+        return out[0], out[1].view(torch.float32)
+
+    def _decode_greedy(self, feat):
+        """decode_greedy into one int32 [2,B,T] device buffer: [0] the ids, [1] the word scores' float32 bits."""
+        feat = self._dev_feat(feat)
+        B, T, u, w = feat.shape[0], self.T, self.units, self.store.w
+        out = torch.empty((2, B, T), dtype=torch.int32, device=self.device)
+        ids, scores = out[0], out[1].view(torch.float32)
+        if B == 0:
+            return out
+        self._draw_rec_masks(B, training=False)
+        f = self._head_forward(feat.reshape(B, -1))
+        zf = self._mm(f, self._wview('imgcap_lstm1/kernel', (self.E, self.E + self.FEAT)), key='dec_zf').f
+        zdf = self._mm(f, self._wview('imgcap_lstm_d1/kernel', (u, u + self.FEAT)), key='dec_zdf').f
+        U1, U2 = w['imgcap_lstm1/recurrent_kernel'], w['imgcap_lstm2/recurrent_kernel']
+        pk = [ops.lstm_pack_urec(Ur, out=self._buf('dec_upk%d' % l, (u, 4 * u))) if u % 32 == 0 else None for l, Ur in enumerate((U1, U2))]
+        emb_b = self._emb_bf16()
+        Wv, _ = self._wview('imgcap_lstm_d2/kernel')
+        tok = self._buf('dec_tok', (B,), torch.int32).fill_(1)          # start token (:203)
+        live = self._buf('dec_live', (B,), torch.uint8)
+        st = [[self._buf('dec_%s%d_%d' % (k, l, q), (B, u)) for q in range(2) for k in 'hc'] for l in range(2)]    # ping-pong (h, c, h', c')
+        for j in range(T):
+            if emb_b is not None:
+                z1 = ops.gemm_bf16(emb_b, self.store.wb['imgcap_lstm1/kernel'][:emb_b.shape[1]], gather=tok, shift=w['imgcap_lstm1/bias'],
+                                   residual=zf, res_rows=B, out=self._buf('dec_z1', (B, 4 * u)))
+            else:
+                z1 = ops.gemm(w['imgcap_embedding_layer/embeddings'], w['imgcap_lstm1/kernel'][:self.E], gather=tok, shift=w['imgcap_lstm1/bias'],
+                              residual=zf, res_rows=B, out=self._buf('dec_z1', (B, 4 * u)))
+            mask = live if j else None                                   # token 1 is never masked; then id != 0 of the step before
+            cur, prev = (0, 2) if j % 2 == 0 else (2, 0)
+            first = j == 0
+            h1, c1 = ops.lstm_step(z1, U1, None if first else st[0][prev], None if first else st[0][prev + 1], mask,
+                                   st[0][cur], st[0][cur + 1], U_packed=pk[0])
+            z2 = self._mm(self._act('dec_h1', h1), self._wview('imgcap_lstm2/kernel'), key='dec_z2', shift=w['imgcap_lstm2/bias']).f
+            h2, c2 = ops.lstm_step(z2, U2, None if first else st[1][prev], None if first else st[1][prev + 1], mask,
+                                   st[1][cur], st[1][cur + 1], U_packed=pk[1])
+            a1 = self._mm(self._act('dec_h2', h2), self._wview('imgcap_lstm_d1/kernel', (0, u)), key='dec_a1', shift=w['imgcap_lstm_d1/bias'],
+                          residual=zdf, res_rows=B, relu=True)
+            ops.vocab_top1(a1.f, Wv, w['imgcap_lstm_d2/bias'], tokens=tok, ids=ids[:, j], probs=scores[:, j], mask=live)
+        return out
+
+    def generate(self, feat, return_probabilities=None, decoder="prefix"):
         """ROICaptionInferenceLayer (:192-232): start token 1; step j feeds [prev..., 0...] through the word
         model and appends float(argmax).  Returns (probs [B,T,V], ids [B,T]); with return_probabilities given (the joint
-        model) returns (probs or None, ids, word_scores [B,T] = the probability of each chosen word)."""
+        model) returns (probs or None, ids, word_scores [B,T] = the probability of each chosen word).
+        decoder='incremental' (needs return_probabilities=False): decode_greedy -- one token per step on the device, no [B,V] rows --
+        returning (None, ids, word_scores) through one device-to-host copy; 'prefix' (default): the reference's T-prefix loop below."""
+        self.check_decoder(decoder, return_probabilities)
+        if decoder == "incremental":
+            host = self._decode_greedy(feat).cpu().numpy()
+            return None, host[0], host[1].view(np.float32)
         feat = self._dev_feat(feat)
         B, T = feat.shape[0], self.T
         self._draw_rec_masks(B, training=False)

@@ -410,6 +410,32 @@ typedef struct {
 int dc_lstm_seq_bwd_f32(const dc_lstm_bwd_desc* d, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * ONE timestep of the recurrence above with carried state: incremental greedy decoding feeds one token per call instead of
+ * re-running the whole zero-padded prefix (ROICaptionInferenceLayer, text_generation_model.py:192-232; dense_img_cap/dense_model.py:820).
+ *   z [B][4U] in/out (x*kernel + bias in, the full pre-activation out), U_rec [U][4U], h_prev / c_prev [B][U] (both NULL: zeros,
+ *   the sequence's first step), mask [B] uint8 or NULL (all live): rows with mask 0 copy h_prev / c_prev (Keras' mask carry),
+ *   h / c [B][U] out (must not alias h_prev / c_prev).  The same kernels as dc_lstm_seq_fwd_f32 at the same B: T calls that feed
+ *   h, c forward give its h_seq / c_seq bit for bit.
+ *   U_packed: U % 32 == 0 runs the fused step on a line-contiguous copy of U_rec (4U^2 floats) made by dc_lstm_pack_urec_f32 --
+ *   once per decode instead of once per step; NULL repacks into the workspace on every call.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct {
+    int B, U;
+    float* z;
+    const float* U_rec;
+    const float* U_packed;
+    const float* h_prev;
+    const float* c_prev;
+    const uint8_t* mask;
+    float* h;
+    float* c;
+} dc_lstm_step_desc;
+
+int    dc_lstm_pack_urec_f32(const float* U_rec, int U, float* U_packed, void* stream);   /* U % 32 == 0; U_packed: 4*U*U floats */
+size_t dc_lstm_step_workspace_bytes(int B, int U);
+int    dc_lstm_step_f32(const dc_lstm_step_desc* d, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * softmax + K.categorical_crossentropy (clip 1e-7) forward and d/dlogits in one pass per row.
  * Replaces Dense(..., activation='softmax') + keras.losses.categorical_crossentropy /
  * roi_caption_loss: text_generation_model.py:154,286-294; _v2.py:164,267.
@@ -467,6 +493,35 @@ typedef struct {
 
 size_t dc_vocab_ce_workspace_bytes(const dc_vocab_ce_desc* d);
 int    dc_vocab_ce(const dc_vocab_ce_desc* d, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Vocabulary projection FUSED with the row top-1 (greedy decoding): logits = X[M,K] * W[K,V] + bias are reduced tile by tile inside
+ * the GEMM and never written.  Replaces, per decoded token, Dense(V, activation='softmax') + tf.argmax + the chosen word's probability
+ * of ROICaptionInferenceLayer (text_generation_model.py:192-232, :222-225; dense_img_cap/dense_model.py:820).
+ *   X, W float32 (fp32 MFMA products, as dc_gemm_f32), K % 32 == 0, ldx % 4 == 0, ldw % 4 == 0, ldw >= V rounded up to 4 (the
+ *   columns up to that are read, never used: any V >= 1); X, W, bias 16-byte aligned; bias [V] or NULL.
+ *   tokens [M] int32 (out): id = argmax_v z_v, the LOWEST index on ties (dc_argmax_rows_f32, tf.argmax) -- the next decode step's
+ *   embedding-gather rows;  ids (optional): ids[m * ld_ids] = id (e.g. column j of a row-major [B,T] matrix);  probs (optional):
+ *   probs[m * ld_probs] = softmax(z)_id = 1 / sum_v exp(z_v - max z);  mask (optional) [M] uint8: id != 0 (the Keras mask of the token).
+ * Per (row, 128-column tile) the epilogue keeps max, argmax and sum exp; a second launch combines the tiles of a row in a fixed order,
+ * so the result is deterministic and the same at every M.  Workspace: dc_vocab_top1_workspace_bytes(M, V) (16 bytes per row and tile).
+ * Cost model: one GEMM pass (2 M K V flops; W streamed about once: the row tiles of a column panel run side by side) + M ceil(V/128)
+ * x 16 bytes of partials, against the unfused [M,V] logits store + a softmax pass + an argmax pass + a gather (4 sweeps of 4 M V
+ * bytes).  Greedy decoding with it runs the vocabulary layer over the B live rows once per token instead of T*B rows per token.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct {
+    int M, V, K;
+    const float* X;  int ldx;
+    const float* W;  int ldw;
+    const float* bias;
+    int32_t* tokens;
+    int32_t* ids;    int ld_ids;
+    float* probs;    int ld_probs;
+    uint8_t* mask;
+} dc_vocab_top1_desc;
+
+size_t dc_vocab_top1_workspace_bytes(int M, int V);
+int    dc_vocab_top1_f32(const dc_vocab_top1_desc* d, void* workspace, size_t workspace_bytes, void* stream);
 
 /* tf.argmax over the last axis, lowest index wins ties (text_generation_model.py:222-225). */
 int dc_argmax_rows_f32(const float* x, int M, int V, int ld, int32_t* out, void* stream);

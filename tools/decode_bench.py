@@ -1,0 +1,107 @@
+"""Greedy caption decoding per image: CaptionModelV1.generate(decoder='prefix') -- the reference's T zero-padded prefix passes -- against
+decoder='incremental' (decode_greedy: one token per step with carried LSTM state, ops.vocab_top1), on synthetic weights, plus
+ops.vocab_top1 alone as a fraction of the fp32 matrix peak.  Both decoders run with return_probabilities=False (the prefix path then
+still writes and reads its [T*B, V] logits every step, but copies no [B,V] rows to the host).
+
+Shapes: configs[4] inference (K = 1000 RoIs = POST_NMS_ROIS_INFERENCE, T = 15, V = 50 000, 512 units) and a configs[2]-style one
+(K = 200, V = 10 000).  Times: torch.cuda.Event around the whole call (host copies of the ids included), warm-up first, median of
+--repeats.  Prints one JSON line per measurement and, with --out, writes them all to that JSON file (profiles/decode_bench.json).
+
+    python tools/decode_bench.py [--repeats 5] [--out decode_bench.json]
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+FP32_PEAK = 157e12          # MI355X dense fp32 matrix peak (TFLOP/s x 1e12)
+
+
+def timed(fn, warm, reps):
+    for _ in range(warm):
+        fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ts.append(a.elapsed_time(b))
+    return float(np.median(ts)), [round(t, 3) for t in ts]
+
+
+def model_for(V, T, K, units, dtype, seed=0):
+    from image_captioning_amd import synth
+    from image_captioning_amd.text_generation_model import DenseCapConfig, CaptionModelV1
+    cfg = DenseCapConfig(V, synth.embedding_matrix(seed + 3, V), K)
+    cfg.PADDING_SIZE = T
+    return CaptionModelV1([7, 7, 256], cfg, units, 'inference', seed=seed, compute_dtype=dtype)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--out", default=None, help="JSON file for all rows (default: print only)")
+    ap.add_argument("--shapes", default="c4,c2")
+    ap.add_argument("--dtypes", default="f32,bf16")
+    args = ap.parse_args()
+    from image_captioning_amd import ops
+    torch.cuda.set_device(0)
+    rows = []
+    shapes = {"c4": dict(name="configs[4] inference", K=1000, T=15, V=50000, units=512),
+              "c2": dict(name="configs[2]-style", K=200, T=15, V=10000, units=512)}
+    for key in args.shapes.split(","):
+        sh = shapes[key]
+        for dtype in args.dtypes.split(","):
+            model = model_for(sh["V"], sh["T"], sh["K"], sh["units"], dtype)
+            feat = torch.tensor(np.random.default_rng(1).standard_normal((sh["K"], 7, 7, 256)).astype(np.float32), device="cuda:0")
+            got = {}
+            for dec in ("prefix", "incremental"):
+                got[dec] = model.generate(feat, return_probabilities=False, decoder=dec)
+                ms, all_ms = timed(lambda: model.generate(feat, return_probabilities=False, decoder=dec), args.warmup, args.repeats)
+                rows.append(dict(what="decode_per_image", shape=sh["name"], dtype=dtype, decoder=dec, K=sh["K"], T=sh["T"], V=sh["V"],
+                                 units=sh["units"], ms=round(ms, 3), runs_ms=all_ms))
+                print(json.dumps(rows[-1]), flush=True)
+            same = bool(np.array_equal(got["prefix"][1], got["incremental"][1]))
+            rel = float(np.max(np.abs(got["prefix"][2] - got["incremental"][2]) / np.maximum(got["prefix"][2], 1e-30)))
+            p, i = rows[-2]["ms"], rows[-1]["ms"]
+            rows.append(dict(what="decode_speedup", shape=sh["name"], dtype=dtype, speedup=round(p / i, 2), ids_identical=same,
+                             max_rel_score_diff=rel))
+            print(json.dumps(rows[-1]), flush=True)
+            del model
+            torch.cuda.empty_cache()
+        # the fused vocabulary top-1 alone, at the decode step's shape (M = K live rows, 1024 inputs)
+        M_, Kd, V = sh["K"], 1024, sh["V"]
+        rng = np.random.default_rng(2)
+        X = torch.tensor(rng.standard_normal((M_, Kd)).astype(np.float32), device="cuda:0")
+        W = torch.tensor((rng.standard_normal((Kd, V)) / 32).astype(np.float32), device="cuda:0")
+        b = torch.zeros(V, dtype=torch.float32, device="cuda:0")
+        tok = torch.empty(M_, dtype=torch.int32, device="cuda:0")
+        ms, all_ms = timed(lambda: ops.vocab_top1(X, W, b, tokens=tok), 3, 20)
+        flops = 2.0 * M_ * Kd * V
+        rows.append(dict(what="vocab_top1", shape=sh["name"], M=M_, K=Kd, V=V, ms=round(ms, 4), tflops=round(flops / ms / 1e9, 1),
+                         fraction_of_fp32_peak=round(flops / (ms * 1e-3) / FP32_PEAK, 3), runs_ms=all_ms))
+        print(json.dumps(rows[-1]), flush=True)
+        logits = torch.empty((M_, V), dtype=torch.float32, device="cuda:0")
+        ms_g, _ = timed(lambda: ops.gemm(X, W, shift=b, out=logits), 3, 20)
+        rows.append(dict(what="unfused_gemm_same_shape", shape=sh["name"], M=M_, K=Kd, V=V, ms=round(ms_g, 4),
+                         fraction_of_fp32_peak=round(flops / (ms_g * 1e-3) / FP32_PEAK, 3)))
+        print(json.dumps(rows[-1]), flush=True)
+        del X, W, logits
+        torch.cuda.empty_cache()
+    if args.out:
+        os.makedirs(os.path.dirname(args.out) or ".", exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(dict(device=torch.cuda.get_device_name(0), rows=rows), f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
