@@ -27,6 +27,13 @@
 //     from the patch --, persistent blocks, vector-memory instructions issued one per MFMA: 639 us.  fp32 products: 64-tile items
 //     (512 threads, one block per CU) where every CU gets one, 32-tile items (256 threads, two blocks per CU) for the small layers;
 //     split-bf16 products (the default plan): 32-tile items everywhere since round 6 (conv_winograd_tiles below).
+//   wino32b_kernel<2>: split-bf16 32-tile items of 64 output channels where a layer has 512 or more of them (stages 2 - 3, fpn_p2 - p3;
+//     conv_winograd_cout).  A wave prepares each V fragment (row / column combination and three-piece split: 52 VALU) once and feeds
+//     it to the 12 MFMAs of both 32-channel halves instead of 6 -- 4.3 VALU per MFMA instead of 8.7 --, and the patch is staged once
+//     per 64 channels.  Every accumulator sums the same products in the same order: bit-identical to 32-channel items.  Still two
+//     blocks per CU (256 VGPRs, no scratch in the loop): the patch goes through t one column at a time and U pieces 1 / 2 one step
+//     ahead.  Those layers 1054 -> 912 us per pass in the pipeline, HBM traffic of the 37 launches 3.73 -> 2.96 x compulsory,
+//     headline 5.84 -> 5.71 ms (profiles/r07_wino_wide.txt).
 #include "igemm_bf16s.h"
 #include <algorithm>
 
@@ -191,8 +198,9 @@ __device__ __forceinline__ f32x16 mfma_b(const u32x4& a, const u32x4& b, const f
 // instead of 32 of 64 (the fp32 matrix pipe's floor per 32-channel pair 3.41 us -> 1.28); the patch staging, the transform, the
 // output transform and the persistent item walk are the fp32 kernel's.  A lane's fragment of a K = 16 MFMA is its 8 channels
 // 8 h .. 8 h + 7 of the chunk: the values of the fp32 kernel's steps j = 0 and j = 1 side by side.
-template <int HALVES, bool B3>
+template <int HALVES, bool B3, int NCH = 1>
 __device__ __forceinline__ void wino_body(const Args& a) {
+    static_assert(NCH == 1 || (NCH == 2 && HALVES == 1 && B3), "64-channel items: the split-bf16 32-tile kernel only");
     using namespace wp;
     typedef Cfg<HALVES> C;
     constexpr int NT64 = C::NT, SLOTS = C::SLOTS, BUF = C::BUF;
@@ -202,7 +210,7 @@ __device__ __forceinline__ void wino_body(const Args& a) {
     const int wa = wave & 3, th = wave >> 2;
     const int gpi = a.gy * a.gx;
     const int NTG = a.Cout >> 5, KC = a.Cin >> 4, KP = a.Cin >> 5;
-    const int total = a.groups * NTG;                      // work items (slice, tile group); this block takes blockIdx.x, + gridDim.x, ...
+    const int total = a.groups * (NTG / NCH);              // work items (slice, tile group); this block takes blockIdx.x, + gridDim.x, ...
     const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.x), 0, (int)a.x_bytes, 0x00020000);
 
     // ---- per work item: coordinates, patch DMA sources (slot s = n * 512 + tid of the image <-> pixel s >> 3, image chunk
@@ -229,7 +237,7 @@ __device__ __forceinline__ void wino_body(const Args& a) {
             doff[n] = in ? (unsigned)(((((long)img * a.H + iy) * a.W + ix) * a.Cin + 4 * c8) * 4) : kOobOffset;
         }
         ubase = a.u + lane + (((long)(4 * wa) * NTG + nb) * KC << 7);
-        ubyte3 = (unsigned)((4 * wa) * NTG + nb) * (unsigned)KC * 3072u;
+        ubyte3 = (unsigned)((4 * wa) * NTG + NCH * nb) * (unsigned)KC * 3072u;
     };
     auto issue_dma_pieces = [&](int pair, int buf, int n0, int n1) {
 #pragma unroll
@@ -252,8 +260,8 @@ __device__ __forceinline__ void wino_body(const Args& a) {
     // block-uniform SGPR offset: no address VALU beside the loads
     const __amdgpu_buffer_rsrc_t rsrc_u = __builtin_amdgcn_make_buffer_rsrc(const_cast<f4*>(a.u), 0, (int)a.u_bytes, 0x00020000);
     const unsigned ustep3 = (unsigned)NTG * KC * 3 * 1024u;                  // bytes: xi -> xi + 1
-    auto load_u3 = [&](u32x4 (&dst)[3], int kc, int b) {
-        const unsigned so = __builtin_amdgcn_readfirstlane(ubyte3 + (unsigned)b * ustep3 + (unsigned)kc * 3072u);
+    auto load_u3 = [&](u32x4 (&dst)[3], int kc, int b, int hc) {                // hc: the 32-channel half of a 64-channel item
+        const unsigned so = __builtin_amdgcn_readfirstlane(ubyte3 + (unsigned)b * ustep3 + (unsigned)(hc * KC + kc) * 3072u);
         dst[0] = __builtin_bit_cast(u32x4, buf_f4s(rsrc_u, (unsigned)lane * 16u, so));
         dst[1] = __builtin_bit_cast(u32x4, buf_f4s(rsrc_u, (unsigned)lane * 16u, so + 1024u));
         dst[2] = __builtin_bit_cast(u32x4, buf_f4s(rsrc_u, (unsigned)lane * 16u, so + 2048u));
@@ -295,23 +303,113 @@ __device__ __forceinline__ void wino_body(const Args& a) {
     issue_dma(0, 0);
     f4 ub[2][4][2];
     u32x4 u3[4][3];                                        // B3: the chunk's U fragments, refilled in place one chunk ahead
-    if constexpr (B3) {
+    // 64-channel items (the register budget of two blocks per CU): piece 0 two position steps ahead (slot q & 1), pieces 1 and 2 one
+    // step ahead, each refilled right behind the last MFMA that reads it
+    u32x4 w0[2][2], w1[2], w2[2];
+    auto load_piece = [&](u32x4& dst, int kc, int b, int hc, int piece) {
+        const unsigned so = __builtin_amdgcn_readfirstlane(ubyte3 + (unsigned)b * ustep3 + (unsigned)(hc * KC + kc) * 3072u + (unsigned)piece * 1024u);
+        dst = __builtin_bit_cast(u32x4, buf_f4s(rsrc_u, (unsigned)lane * 16u, so));
+    };
+    auto load_u3_first = [&]() {                           // an item's first U fragments (chunk 0)
+        if constexpr (NCH == 2) {
 #pragma unroll
-        for (int b = 0; b < 4; ++b) load_u3(u3[b], 0, b);
+            for (int hc = 0; hc < 2; ++hc) {
+                load_piece(w0[0][hc], 0, 0, hc, 0);
+                load_piece(w1[hc], 0, 0, hc, 1);
+                load_piece(w2[hc], 0, 0, hc, 2);
+                load_piece(w0[1][hc], 0, 1, hc, 0);
+            }
+        } else {
+#pragma unroll
+            for (int b = 0; b < 4; ++b) load_u3(u3[b], 0, b, 0);
+        }
+    };
+    if constexpr (B3) {
+        load_u3_first();
     } else {
         load_u(ub[0], 0);
     }
     for (;;) {
-        f32x16 acc[4];
+        f32x16 acc[NCH][4];
 #pragma unroll
-        for (int b = 0; b < 4; ++b)
+        for (int hc = 0; hc < NCH; ++hc)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc[b][r] = 0.f;
+            for (int b = 0; b < 4; ++b)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[hc][b][r] = 0.f;
         auto pair = [&](int p, auto more_c) {
             constexpr bool more = decltype(more_c)::value;      // a pair p + 1 of this item exists: request its patch
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's pieces of the patch (and its U fragments) have landed
             __syncthreads();                               // every wave's have; every wave is done with the other buffer
-            if constexpr (B3) {
+            if constexpr (B3 && NCH == 2) {
+                // 64-channel items: the eight position steps of the 32-channel kernel (below), each with twelve MFMAs -- the two channel
+                // halves take turns on every V fragment.  Registers for two blocks per CU: the accumulators double, so the patch rows go
+                // through t one column at a time, each read at the step that frees its column of t (t[0] after position 0 is prepared,
+                // t[2] after position 2, t[1] and t[3] after position 3) and combined within that step.
+                f4 t0[4], t1[4];
+                u32x4 V[2][3];
+                auto fetch_col = [&](int hf, int c) {      // column c of row wa of B^T d, channels 16 hf + 8 h + 0..3 / + 4..7
+                    const unsigned ka = (unsigned)(hf << 6), kb = ka ^ 16u;
+                    const f4 a0 = *reinterpret_cast<const f4*>(smem + (paddr[0][c] ^ ka));
+                    const f4 a1 = *reinterpret_cast<const f4*>(smem + (paddr[1][c] ^ ka));
+                    const f4 b0 = *reinterpret_cast<const f4*>(smem + (paddr[0][c] ^ kb));
+                    const f4 b1 = *reinterpret_cast<const f4*>(smem + (paddr[1][c] ^ kb));
+                    t0[c] = a1 * sgn + a0;
+                    t1[c] = b1 * sgn + b0;
+                };
+                auto prep = [&](u32x4 (&dst)[3], int b) {
+                    const f4 va = b == 0 ? t0[0] - t0[2] : (b == 1 ? t0[1] + t0[2] : (b == 2 ? t0[2] - t0[1] : t0[1] - t0[3]));
+                    const f4 vb = b == 0 ? t1[0] - t1[2] : (b == 1 ? t1[1] + t1[2] : (b == 2 ? t1[2] - t1[1] : t1[1] - t1[3]));
+                    split8(va, vb, dst[0], dst[1], dst[2]);
+                };
+                fetch_col(0, 0);
+                fetch_col(0, 2);
+                prep(V[0], 0);
+#pragma unroll
+                for (int q = 0; q < 8; ++q) {
+                    const int b = q & 3;
+                    __builtin_amdgcn_sched_barrier(0);
+                    if constexpr (more) if (q < NDMA) issue_dma_pieces(p + 1, (p + 1) & 1, q, q + 1);
+                    const u32x4 (&vq)[3] = V[q & 1];
+                    const int kc1 = min(2 * p + ((q + 1) >> 2), KC - 1), kc2 = min(2 * p + ((q + 2) >> 2), KC - 1);   // (re-reads past the end)
+#pragma unroll
+                    for (int hc = 0; hc < 2; ++hc) acc[hc][b] = mfma_b(w0[q & 1][hc], vq[2], acc[hc][b]);      // small terms first
+#pragma unroll
+                    for (int hc = 0; hc < 2; ++hc) acc[hc][b] = mfma_b(w1[hc], vq[1], acc[hc][b]);
+#pragma unroll
+                    for (int hc = 0; hc < 2; ++hc) acc[hc][b] = mfma_b(w2[hc], vq[0], acc[hc][b]);
+#pragma unroll
+                    for (int hc = 0; hc < 2; ++hc) load_piece(w2[hc], kc1, (q + 1) & 3, hc, 2);
+#pragma unroll
+                    for (int hc = 0; hc < 2; ++hc) acc[hc][b] = mfma_b(w1[hc], vq[0], acc[hc][b]);
+#pragma unroll
+                    for (int hc = 0; hc < 2; ++hc) load_piece(w1[hc], kc1, (q + 1) & 3, hc, 1);
+#pragma unroll
+                    for (int hc = 0; hc < 2; ++hc) acc[hc][b] = mfma_b(w0[q & 1][hc], vq[1], acc[hc][b]);
+#pragma unroll
+                    for (int hc = 0; hc < 2; ++hc) acc[hc][b] = mfma_b(w0[q & 1][hc], vq[0], acc[hc][b]);
+#pragma unroll
+                    for (int hc = 0; hc < 2; ++hc) load_piece(w0[q & 1][hc], kc2, (q + 2) & 3, hc, 0);
+                    if (q == 0) fetch_col(0, 1);
+                    if (q == 1) { fetch_col(0, 3); fetch_col(1, 0); }
+                    if (q == 2) fetch_col(1, 2);
+                    if (q == 3) fetch_col(1, 1);
+                    if (q == 4) fetch_col(1, 3);
+                    if (q < 7) prep(V[(q + 1) & 1], (q + 1) & 3);
+#pragma unroll
+                    for (int m = 0; m < 12; ++m) {
+                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);      // one MFMA
+                        __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);      // one vector-memory instruction (U, the DMA piece), where there is one
+                        __builtin_amdgcn_sched_group_barrier(0x002, 6, 0);
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+#pragma unroll
+                for (int rr = 0; rr < 2; ++rr)
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) paddr[rr][c] ^= (unsigned)BUF;
+                return;
+            } else if constexpr (B3) {
                 // Eight position steps q = 4 half + b per pair.  Step q issues the six MFMAs of position b on the operands prepared during
                 // step q - 1 and, BETWEEN them (one MFMA : nine VALU, sched_group_barrier -- a 32x32x16 MFMA holds the vector issue for 8 of
                 // its 32 cycles, so the six dependent MFMAs of a position leave room for ~36 VALU instructions that would otherwise run
@@ -344,15 +442,15 @@ __device__ __forceinline__ void wino_body(const Args& a) {
                     __builtin_amdgcn_sched_barrier(0);
                     if constexpr (more) if (q < NDMA) issue_dma_pieces(p + 1, (p + 1) & 1, q, q + 1);
                     const u32x4 (&vq)[3] = V[q & 1];
-                    acc[b] = mfma_b(u3[b][0], vq[2], acc[b]);       // small terms first
-                    acc[b] = mfma_b(u3[b][1], vq[1], acc[b]);
-                    acc[b] = mfma_b(u3[b][2], vq[0], acc[b]);
-                    acc[b] = mfma_b(u3[b][1], vq[0], acc[b]);
-                    acc[b] = mfma_b(u3[b][0], vq[1], acc[b]);
-                    acc[b] = mfma_b(u3[b][0], vq[0], acc[b]);
+                    acc[0][b] = mfma_b(u3[b][0], vq[2], acc[0][b]);       // small terms first
+                    acc[0][b] = mfma_b(u3[b][1], vq[1], acc[0][b]);
+                    acc[0][b] = mfma_b(u3[b][2], vq[0], acc[0][b]);
+                    acc[0][b] = mfma_b(u3[b][1], vq[0], acc[0][b]);
+                    acc[0][b] = mfma_b(u3[b][0], vq[1], acc[0][b]);
+                    acc[0][b] = mfma_b(u3[b][0], vq[0], acc[0][b]);
                     if (q == 3) make_t();                           // (the first half's t is dead: position 3 was prepared during step 2)
                     if (q < 7) prep(V[(q + 1) & 1], (q + 1) & 3);
-                    load_u3(u3[b], min(2 * p + half + 1, KC - 1), b);          // (the last chunk re-reads: uniform counts)
+                    load_u3(u3[b], min(2 * p + half + 1, KC - 1), b, 0);       // (the last chunk re-reads: uniform counts)
 #pragma unroll
                     for (int m = 0; m < 6; ++m) {
                         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);      // one MFMA
@@ -388,7 +486,7 @@ __device__ __forceinline__ void wino_body(const Args& a) {
 #pragma unroll
                 for (int e = 0; e < 2; ++e)
 #pragma unroll
-                    for (int b = 0; b < 4; ++b) acc[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(ub[half][b][j][e], vcur[b][e], acc[b], 0, 0, 0);
+                    for (int b = 0; b < 4; ++b) acc[0][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(ub[half][b][j][e], vcur[b][e], acc[0][b], 0, 0, 0);
 #pragma unroll
                 for (int m = 0; m < 8; ++m) {
                     __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);          // one MFMA
@@ -399,7 +497,7 @@ __device__ __forceinline__ void wino_body(const Args& a) {
 #pragma unroll
                 for (int e = 2; e < 4; ++e)
 #pragma unroll
-                    for (int b = 0; b < 4; ++b) acc[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(ub[half][b][j][e], vcur[b][e], acc[b], 0, 0, 0);
+                    for (int b = 0; b < 4; ++b) acc[0][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(ub[half][b][j][e], vcur[b][e], acc[0][b], 0, 0, 0);
                 if (st < 3) {                              // the transform's VALU work spread over the eight MFMAs: none of them waits for it
 #pragma unroll
                     for (int m = 0; m < 8; ++m) {
@@ -432,51 +530,58 @@ __device__ __forceinline__ void wino_body(const Args& a) {
         const int next = item + (int)gridDim.x;
         // this item's epilogue operands, requested BEFORE anything of the next item: vmcnt retires in issue order, so waiting for them
         // later must not mean waiting for the next patch
-        const int oq = tid & 7, ocout = onb * 32 + 4 * oq;
-        f4 sc = (f4)(1.f), sh = (f4)(0.f);
-        if (a.scale) sc = *reinterpret_cast<const f4*>(a.scale + ocout);
-        if (a.shift) sh = *reinterpret_cast<const f4*>(a.shift + ocout);
+        const int oq = tid & 7, ocout = onb * (32 * NCH) + 4 * oq;
+        f4 sc[NCH], sh[NCH];
+#pragma unroll
+        for (int hc = 0; hc < NCH; ++hc) {
+            sc[hc] = a.scale ? *reinterpret_cast<const f4*>(a.scale + ocout + 32 * hc) : (f4)(1.f);
+            sh[hc] = a.shift ? *reinterpret_cast<const f4*>(a.shift + ocout + 32 * hc) : (f4)(0.f);
+        }
         __syncthreads();                                   // every wave is done with both patch buffers
         if (next < total) {
             setup(next);
             issue_dma(0, 0);
             if constexpr (B3) {
-#pragma unroll
-                for (int b = 0; b < 4; ++b) load_u3(u3[b], 0, b);
+                load_u3_first();
             } else {
                 load_u(ub[0], 0);
             }
         }
         // output transform.  In registers: the column half (A applied to this wave's row a): s[qx] from M[a][0..3]; through LDS (the
         // SECOND buffer: the first is being filled): the row half across the four waves of a tile half.  Plane 2 a + qx of half th.
-        {
-            const f32x16 s0 = acc[0] + acc[1] + acc[2], s1 = acc[1] - acc[2] - acc[3];
+        // A 64-channel item passes its two 32-channel halves through the same image one after the other.
 #pragma unroll
-            for (int gq = 0; gq < 4; ++gq) {
-                const f4 m0 = {s0[4 * gq], s0[4 * gq + 1], s0[4 * gq + 2], s0[4 * gq + 3]};
-                const f4 m1 = {s1[4 * gq], s1[4 * gq + 1], s1[4 * gq + 2], s1[4 * gq + 3]};
-                *reinterpret_cast<f4*>(smem + BUF + th * 32768 + img32_addr(2 * wa, fi, 2 * gq + fh)) = m0;      // couts 8 gq + 4 h .. + 3 of tile fi
-                *reinterpret_cast<f4*>(smem + BUF + th * 32768 + img32_addr(2 * wa + 1, fi, 2 * gq + fh)) = m1;
+        for (int hc = 0; hc < NCH; ++hc) {
+            if (hc) __syncthreads();                       // the first half's image has been read
+            {
+                const f32x16 s0 = acc[hc][0] + acc[hc][1] + acc[hc][2], s1 = acc[hc][1] - acc[hc][2] - acc[hc][3];
+#pragma unroll
+                for (int gq = 0; gq < 4; ++gq) {
+                    const f4 m0 = {s0[4 * gq], s0[4 * gq + 1], s0[4 * gq + 2], s0[4 * gq + 3]};
+                    const f4 m1 = {s1[4 * gq], s1[4 * gq + 1], s1[4 * gq + 2], s1[4 * gq + 3]};
+                    *reinterpret_cast<f4*>(smem + BUF + th * 32768 + img32_addr(2 * wa, fi, 2 * gq + fh)) = m0;      // couts 8 gq + 4 h .. + 3 of tile fi
+                    *reinterpret_cast<f4*>(smem + BUF + th * 32768 + img32_addr(2 * wa + 1, fi, 2 * gq + fh)) = m1;
+                }
             }
-        }
-        __syncthreads();
-        {
-            const int oth = tid >> 8, ti = (tid >> 3) & 31;
-            f4 sv[4][2];
+            __syncthreads();
+            {
+                const int oth = tid >> 8, ti = (tid >> 3) & 31;
+                f4 sv[4][2];
 #pragma unroll
-            for (int r = 0; r < 4; ++r)
+                for (int r = 0; r < 4; ++r)
 #pragma unroll
-                for (int qx = 0; qx < 2; ++qx) sv[r][qx] = *reinterpret_cast<const f4*>(smem + BUF + oth * 32768 + img32_addr(2 * r + qx, ti, oq));
-            const int otile = 32 * oth + ti, ty = ogy * C::TGY + (otile >> 3), tx = ogx * C::TGX + (otile & 7), cout = ocout;
+                    for (int qx = 0; qx < 2; ++qx) sv[r][qx] = *reinterpret_cast<const f4*>(smem + BUF + oth * 32768 + img32_addr(2 * r + qx, ti, oq));
+                const int otile = 32 * oth + ti, ty = ogy * C::TGY + (otile >> 3), tx = ogx * C::TGX + (otile & 7), cout = ocout + 32 * hc;
 #pragma unroll
-            for (int qx = 0; qx < 2; ++qx) {
-                const f4 o[2] = {sv[0][qx] + sv[1][qx] + sv[2][qx], sv[1][qx] - sv[2][qx] - sv[3][qx]};
+                for (int qx = 0; qx < 2; ++qx) {
+                    const f4 o[2] = {sv[0][qx] + sv[1][qx] + sv[2][qx], sv[1][qx] - sv[2][qx] - sv[3][qx]};
 #pragma unroll
-                for (int pr = 0; pr < 2; ++pr) {
-                    f4 val = o[pr] * sc + sh;
-                    if (a.relu) val = f4{fmaxf(val[0], 0.f), fmaxf(val[1], 0.f), fmaxf(val[2], 0.f), fmaxf(val[3], 0.f)};
-                    if (2 * ty + pr < a.H && 2 * tx + qx < a.W)
-                        *reinterpret_cast<f4*>(a.y + (((long)oimg * a.H + 2 * ty + pr) * a.W + 2 * tx + qx) * a.Cout + cout) = val;
+                    for (int pr = 0; pr < 2; ++pr) {
+                        f4 val = o[pr] * sc[hc] + sh[hc];
+                        if (a.relu) val = f4{fmaxf(val[0], 0.f), fmaxf(val[1], 0.f), fmaxf(val[2], 0.f), fmaxf(val[3], 0.f)};
+                        if (2 * ty + pr < a.H && 2 * tx + qx < a.W)
+                            *reinterpret_cast<f4*>(a.y + (((long)oimg * a.H + 2 * ty + pr) * a.W + 2 * tx + qx) * a.Cout + cout) = val;
+                    }
                 }
             }
         }
@@ -488,7 +593,11 @@ __device__ __forceinline__ void wino_body(const Args& a) {
 __global__ __launch_bounds__(512, 1) void wino64_kernel(Args a) { wino_body<2, false>(a); }
 __global__ __launch_bounds__(256, 2) void wino32_kernel(Args a) { wino_body<1, false>(a); }
 __global__ __launch_bounds__(512, 1) void wino64b_kernel(Args a) { wino_body<2, true>(a); }
-__global__ __launch_bounds__(256, 2) void wino32b_kernel(Args a) { wino_body<1, true>(a); }
+// the split-bf16 32-tile kernel: 32 (NCH = 1) or 64 (NCH = 2) output channels per item, two blocks per CU either way
+template <int NCH>
+__global__ __launch_bounds__(256, 2) void wino32b_kernel(Args a) { wino_body<1, true, NCH>(a); }
+template __global__ void wino32b_kernel<1>(Args);
+template __global__ void wino32b_kernel<2>(Args);
 
 }  // namespace wino
 
@@ -538,6 +647,25 @@ int conv_winograd_tiles(const dc_conv_desc* d) {
     return items64 >= kNumCU ? 64 : 32;
 }
 
+// Output channels per split-bf16 32-tile item: 64 (wino32b_kernel<2>: every V fragment feeds both 32-channel halves, the patch is
+// staged once per 64 channels) on the layers that still give 512 or more items -- two rounds of work per block slot at least: stages
+// 2 - 3, fpn_p2 - p3 of the benchmark --, else 32.  Measured in the training pipeline (bench.py, profiles/r07_wino_wide.txt): with every
+// layer on 64-channel items the step took 6.19 ms against 5.76 (stage 4 / 5 and fpn_p4 / p5 then fill half the block slots or fewer);
+// with the rule at 512 items 5.63, at 1024 items 5.65.  Layers with Cout % 64 != 0 keep 32.  DCAP_WINO_COUT = 32 / 64 forces one.
+static int wino_cout_force() {
+    static const int force = env_int("DCAP_WINO_COUT", 0);
+    return force;
+}
+
+static int conv_winograd_cout(const dc_conv_desc* d) {
+    if (!wino_b3(d) || conv_winograd_tiles(d) != 32 || d->Cout % 64) return 32;
+    const int force = wino_cout_force();
+    if (force == 32 || force == 64) return force;
+    const int th = (d->H + 1) / 2, tw = (d->W + 1) / 2;
+    const long items = (long)d->N * ((th + 3) / 4) * ((tw + 7) / 8) * (d->Cout / 64);
+    return items >= 2 * kNumCU ? 64 : 32;
+}
+
 int conv2d_winograd(const dc_conv_desc* d, hipStream_t s) {
     wino::Args a;
     a.x = d->x;
@@ -558,22 +686,27 @@ int conv2d_winograd(const dc_conv_desc* d, hipStream_t s) {
     a.gy = (th + (big ? 8 : 4) - 1) / (big ? 8 : 4);
     a.gx = (tw + 7) / 8;
     a.groups = d->N * a.gy * a.gx;
-    const long items = (long)a.groups * (d->Cout / 32);
+    const bool wide = b3 && !big && conv_winograd_cout(d) == 64;
+    const long items = (long)a.groups * (d->Cout / (wide ? 64 : 32));
     DC_REQUIRE(items < (1l << 31), DC_EINVAL, "dc_conv2d (winograd): grid too large");
     // persistent: the blocks that fit the chip walk the work items (a multiple of 8 blocks, so that an item's XCD is fixed by item % 8)
     // the CU budget (dc_set_persistent_cus) applies to the LONG launches only -- eight or more rounds of work items per block -- where a
     // grid that never yields would keep another queue's kernels (RCCL) waiting for hundreds of microseconds.  On a short launch a smaller
     // grid costs a whole extra round (256 items on 248 blocks: two rounds instead of one, measured 69 -> 102 us on the stage-4 layers) and
     // buys nothing: the launch is over in tens of microseconds.
-    const long full = big ? kNumCU : 2 * kNumCU;
-    const long slots = items >= 8 * full ? (big ? persistent_cus() : 2 * persistent_cus()) : full;
+    const int per_cu = big ? 1 : 2;                        // blocks per CU
+    const long full = (long)per_cu * kNumCU;
+    const long slots = items >= 8 * full ? per_cu * persistent_cus() : full;
     const unsigned grid = items >= slots ? (unsigned)slots : (unsigned)std::max<long>(8, items / 8 * 8);
     if (b3 && big) {
         DC_ENSURE_DYN_LDS(wino::wino64b_kernel, wino::wp::Cfg<2>::LDS_BYTES);
         hipLaunchKernelGGL(wino::wino64b_kernel, dim3(grid), dim3(wino::wp::Cfg<2>::NT), wino::wp::Cfg<2>::LDS_BYTES, s, a);
+    } else if (wide) {
+        DC_ENSURE_DYN_LDS((&wino::wino32b_kernel<2>), wino::wp::Cfg<1>::LDS_BYTES);
+        hipLaunchKernelGGL((wino::wino32b_kernel<2>), dim3(grid), dim3(wino::wp::Cfg<1>::NT), wino::wp::Cfg<1>::LDS_BYTES, s, a);
     } else if (b3) {
-        DC_ENSURE_DYN_LDS(wino::wino32b_kernel, wino::wp::Cfg<1>::LDS_BYTES);
-        hipLaunchKernelGGL(wino::wino32b_kernel, dim3(grid), dim3(wino::wp::Cfg<1>::NT), wino::wp::Cfg<1>::LDS_BYTES, s, a);
+        DC_ENSURE_DYN_LDS((&wino::wino32b_kernel<1>), wino::wp::Cfg<1>::LDS_BYTES);
+        hipLaunchKernelGGL((wino::wino32b_kernel<1>), dim3(grid), dim3(wino::wp::Cfg<1>::NT), wino::wp::Cfg<1>::LDS_BYTES, s, a);
     } else if (big) {
         DC_ENSURE_DYN_LDS(wino::wino64_kernel, wino::wp::Cfg<2>::LDS_BYTES);
         hipLaunchKernelGGL(wino::wino64_kernel, dim3(grid), dim3(wino::wp::Cfg<2>::NT), wino::wp::Cfg<2>::LDS_BYTES, s, a);
