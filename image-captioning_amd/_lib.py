@@ -109,6 +109,19 @@ class VocabTop1Desc(C.Structure):
                 ("ids", C.c_void_p), ("ld_ids", C.c_int), ("probs", C.c_void_p), ("ld_probs", C.c_int), ("mask", C.c_void_p)]
 
 
+class VocabTopkDesc(C.Structure):
+    _fields_ = [("M", C.c_int), ("V", C.c_int), ("K", C.c_int), ("k", C.c_int),
+                ("X", C.c_void_p), ("ldx", C.c_int), ("W", C.c_void_p), ("ldw", C.c_int),
+                ("bias", C.c_void_p), ("ids", C.c_void_p), ("probs", C.c_void_p)]
+
+
+class BeamSelectDesc(C.Structure):
+    _fields_ = [("R", C.c_int), ("k", C.c_int), ("nb", C.c_int), ("steps", C.c_int), ("j", C.c_int), ("log_score", C.c_int),
+                ("cand_ids", C.c_void_p), ("cand_probs", C.c_void_p), ("scores_in", C.c_void_p), ("scores_out", C.c_void_p),
+                ("parents", C.c_void_p), ("tokens_hist", C.c_void_p), ("tokens", C.c_void_p), ("mask", C.c_void_p),
+                ("U", C.c_int), ("h_in", C.c_void_p), ("c_in", C.c_void_p), ("h_out", C.c_void_p), ("c_out", C.c_void_p)]
+
+
 class LstmStepDesc(C.Structure):
     _fields_ = [("B", C.c_int), ("U", C.c_int),
                 ("z", C.c_void_p), ("U_rec", C.c_void_p), ("U_packed", C.c_void_p),
@@ -224,6 +237,10 @@ SYMBOLS = {
     "dc_vocab_ce": (C.c_int, [C.POINTER(VocabCeDesc), C.c_void_p, C.c_size_t, C.c_void_p]),
     "dc_vocab_top1_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "dc_vocab_top1_f32": (C.c_int, [C.POINTER(VocabTop1Desc), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "dc_vocab_topk_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "dc_vocab_topk_f32": (C.c_int, [C.POINTER(VocabTopkDesc), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "dc_beam_select_f32": (C.c_int, [C.POINTER(BeamSelectDesc), C.c_void_p]),
+    "dc_beam_backtrace": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "dc_argmax_rows_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "dc_gather_rows_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "dc_bn_relu_fwd_f32": (C.c_int, [C.POINTER(BnReluDesc), C.c_void_p]),

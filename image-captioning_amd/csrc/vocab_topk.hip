@@ -1,0 +1,298 @@
+// vocab_topk.hip -- beam-search decoding on the device:
+//   dc_vocab_topk_f32   the vocabulary projection FUSED with the row top-k (k <= 8) and the softmax probabilities of those k words;
+//   dc_beam_select_f32  per RoI, the k best of the k live beams' k proposals each (score + p or score + log p), with the parents'
+//                       word-LSTM rows gathered into the next state buffers;
+//   dc_beam_backtrace   the [steps,R,k] parent / token history -> [R,k,steps] sequences.
+//
+// Replaces the reference's beam loop (image captioning/test.py:23-64: per beam a full model.predict on the pre-padded prefix, a host
+// argsort of the [V] probability row, a host sort of the k*k candidates) for the v2 decoders (text_generation_model_v2.py:140-166).
+// dc_vocab_topk_f32 is dc_vocab_top1_f32 (vocab_top1.hip) with a wider epilogue: the same fp32 MFMA main loop (128 x 128 tiles, row
+// tiles fastest, xcd_remap), and per (row, 128-column tile) the max, the sum of exp(z - max) and the tile's k best (value, column)
+// pairs -- found in k threshold rounds of the 32-lane shuffle reduction of top1_epilogue, each round taking the best pair that comes
+// after the previous round's winner in the order (value descending, column ascending), so no per-lane lists are needed.  A row kernel
+// (one wave per row) runs the same rounds over the row's tiles_n * k candidates.  The [M,V] logits are never written.
+#include "igemm_core.h"
+#include <algorithm>
+#include <climits>
+
+namespace dcap {
+
+constexpr int TK_MAX = 8;
+
+struct TopkArgs {
+    int M, V, tiles_m, tiles_n, k;
+    const float* bias;                   // [V] or null
+    float2* ms;                          // [M][tiles_n]: max, sum exp
+    float2* cand;                        // [M][tiles_n][k]: value, column (int bits); column INT_MAX = none
+};
+
+// (v, c) comes strictly after (tv, tc) in the order value descending, column ascending.  NaN never does.
+__device__ __forceinline__ bool tk_after(float v, int c, float tv, int tc) {
+    return v < tv || (v == tv && c > tc);
+}
+
+// the better of two (value, column) pairs: the larger value, the lower column on equal values (vocab_top1.hip's top1_take)
+__device__ __forceinline__ void tk_take(float& m, int& i, float om, int oi) {
+    if (om > m || (om == m && oi < i)) { m = om; i = oi; }
+}
+
+__device__ __forceinline__ void topk_epilogue(f32x16 (&acc)[2][2], float* Cs, const TopkArgs& ta, int m0, int n0, int wm, int wn, int tile_n) {
+    constexpr int LDC = 128 + 4;
+    const int tid = threadIdx.x, lane = tid & 63;
+    {
+        const int i = lane & 31, h = lane >> 5;
+#pragma unroll
+        for (int tm = 0; tm < 2; ++tm)
+#pragma unroll
+            for (int tn = 0; tn < 2; ++tn)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) Cs[(wm + tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * h) * LDC + wn + tn * 32 + i] = acc[tm][tn][r];
+    }
+    __syncthreads();
+    const int c4 = tid & 31, rp = tid >> 5;                    // 32 lanes x 4 columns per row, 8 rows per pass
+    const int col = n0 + 4 * c4;
+    float4 b4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (ta.bias && col + 3 < ta.V) b4 = *reinterpret_cast<const float4*>(ta.bias + col);
+    else if (ta.bias) {
+        if (col < ta.V) b4.x = ta.bias[col];
+        if (col + 1 < ta.V) b4.y = ta.bias[col + 1];
+        if (col + 2 < ta.V) b4.z = ta.bias[col + 2];
+    }
+    const bool v0 = col < ta.V, v1 = col + 1 < ta.V, v2 = col + 2 < ta.V, v3 = col + 3 < ta.V;
+    for (int p = 0; p < 16; ++p) {
+        const int lr = p * 8 + rp, row = m0 + lr;
+        float4 z = *reinterpret_cast<const float4*>(&Cs[lr * LDC + 4 * c4]);
+        z.x += b4.x; z.y += b4.y; z.z += b4.z; z.w += b4.w;
+        float2* out = ta.cand + ((long)row * ta.tiles_n + tile_n) * ta.k;
+        float tv = INFINITY, mx = -INFINITY;
+        int tc = INT_MIN;
+        for (int r = 0; r < ta.k; ++r) {                       // round r: the tile's (r+1)-th best pair
+            float bm = -INFINITY;
+            int bi = INT_MAX;
+            if (v0 && tk_after(z.x, col, tv, tc)) tk_take(bm, bi, z.x, col);
+            if (v1 && tk_after(z.y, col + 1, tv, tc)) tk_take(bm, bi, z.y, col + 1);
+            if (v2 && tk_after(z.z, col + 2, tv, tc)) tk_take(bm, bi, z.z, col + 2);
+            if (v3 && tk_after(z.w, col + 3, tv, tc)) tk_take(bm, bi, z.w, col + 3);
+#pragma unroll
+            for (int o = 16; o > 0; o >>= 1) {
+                const float om = __shfl_xor(bm, o, 64);
+                const int oi = __shfl_xor(bi, o, 64);
+                tk_take(bm, bi, om, oi);
+            }
+            if (r == 0) mx = bm;
+            if (row < ta.M && c4 == 0) out[r] = make_float2(bm, __int_as_float(bi));
+            tv = bm; tc = bi;                                  // (no pair left: (-inf, INT_MAX), after which nothing comes)
+        }
+        float s = (v0 ? expf(z.x - mx) : 0.f) + (v1 ? expf(z.y - mx) : 0.f) + (v2 ? expf(z.z - mx) : 0.f) + (v3 ? expf(z.w - mx) : 0.f);
+#pragma unroll
+        for (int o = 16; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+        if (row < ta.M && c4 == 0) ta.ms[(long)row * ta.tiles_n + tile_n] = make_float2(mx, s);
+    }
+}
+
+using TKA = DenseKCT<true>;
+using TKB = DenseMCT<true>;
+
+__global__ __launch_bounds__(256, 2) void vocab_topk_f32_kernel(TKA al, TKB bl, TopkArgs ta, int K) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int wave = threadIdx.x >> 6;
+    const int lid = xcd_remap(blockIdx.x, gridDim.x);
+    const int tile_m = lid % ta.tiles_m, tile_n = lid / ta.tiles_m;
+    const int m0 = tile_m * 128, n0 = tile_n * 128;
+    const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
+    f32x16 acc[2][2];
+    igemm_mainloop<128, 128, TKA, TKB>(al, bl, smem, m0, n0, 0, K, acc, wm, wn);
+    topk_epilogue(acc, smem, ta, m0, n0, wm, wn, tile_n);
+}
+
+// One wave per row.  m = max_j m_j and s = sum_j s_j exp(m_j - m) as in vocab_top1_rows_kernel (lane-strided over j, then a fixed xor
+// tree); then k threshold rounds over the tiles_n * k candidates, each a lane-strided scan + a 64-lane xor reduction.  The top k of a
+// strict total order does not depend on the scan order, and s is summed in an order fixed by tiles_n alone: the result is the same at
+// every M.  p_r = exp(z_r - m) / s.
+__global__ __launch_bounds__(256) void vocab_topk_rows_kernel(int M, int tiles_n, int k, const float2* __restrict__ ms,
+                                                              const float2* __restrict__ cand, int32_t* __restrict__ ids,
+                                                              float* __restrict__ probs) {
+    const int row = (blockIdx.x * 256 + threadIdx.x) >> 6, lane = threadIdx.x & 63;
+    if (row >= M) return;
+    const float2* st = ms + (long)row * tiles_n;
+    float m = -INFINITY;
+    for (int j = lane; j < tiles_n; j += 64) m = fmaxf(m, st[j].x);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    float s = 0.f;
+    for (int j = lane; j < tiles_n; j += 64) {
+        const float2 q = st[j];
+        s += q.y * expf(q.x - m);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    const float2* cd = cand + (long)row * tiles_n * k;
+    const int n = tiles_n * k;
+    float tv = INFINITY;
+    int tc = INT_MIN;
+    for (int r = 0; r < k; ++r) {
+        float bm = -INFINITY;
+        int bi = INT_MAX;
+        for (int j = lane; j < n; j += 64) {
+            const float2 q = cd[j];
+            const int c = __float_as_int(q.y);
+            if (c != INT_MAX && tk_after(q.x, c, tv, tc)) tk_take(bm, bi, q.x, c);
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float om = __shfl_xor(bm, o, 64);
+            const int oi = __shfl_xor(bi, o, 64);
+            tk_take(bm, bi, om, oi);
+        }
+        if (lane == 0) {
+            ids[(long)row * k + r] = bi == INT_MAX ? 0 : bi;   // (a row with fewer than k finite logits: tf.argmax's first column)
+            probs[(long)row * k + r] = bi == INT_MAX ? 0.f : expf(bm - m) / s;
+        }
+        tv = bm; tc = bi;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ beam selection
+// One wave per RoI.  Lane l < nb * k holds candidate (beam b = l / k, rank i = l % k) of the beam-major candidate rows b * R + roi:
+// score = scores_in[roi][b] + (p or log p).  k threshold rounds in the order (score descending, parent ascending, word id ascending)
+// give the new beams best first; round q writes beam q's score, history entries and next token, then the whole wave copies the
+// parent's h / c rows into row q * R + roi of the next state buffers.
+__device__ __forceinline__ bool bs_before(float s, int b, int t, float os, int ob, int ot) {
+    return s > os || (s == os && (b < ob || (b == ob && t < ot)));
+}
+
+__global__ __launch_bounds__(256) void beam_select_kernel(dc_beam_select_desc d) {
+    const int roi = (blockIdx.x * 256 + threadIdx.x) >> 6, lane = threadIdx.x & 63;
+    if (roi >= d.R) return;
+    const int k = d.k, R = d.R;
+    float s = -INFINITY;
+    int b = INT_MAX, t = INT_MAX;
+    if (lane < d.nb * k) {
+        b = lane / k;
+        const long c = ((long)b * R + roi) * k + lane % k;
+        t = d.cand_ids[c];
+        const float p = d.cand_probs[c];
+        s = (d.scores_in ? d.scores_in[roi * k + b] : 0.f) + (d.log_score ? logf(p) : p);
+    }
+    float ts = INFINITY;
+    int tb = INT_MIN, tt = INT_MIN;
+    for (int q = 0; q < k; ++q) {
+        const bool ok = bs_before(ts, tb, tt, s, b, t);       // this lane's candidate comes after the previous winner
+        float bs = ok ? s : -INFINITY;
+        int bb = ok ? b : INT_MAX, bt = ok ? t : INT_MAX;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float os = __shfl_xor(bs, o, 64);
+            const int ob = __shfl_xor(bb, o, 64), ot = __shfl_xor(bt, o, 64);
+            if (bs_before(os, ob, ot, bs, bb, bt)) { bs = os; bb = ob; bt = ot; }
+        }
+        ts = bs; tb = bb; tt = bt;
+        if (bb == INT_MAX) { bb = 0; bt = 0; }                // (no candidate left, only with NaN probabilities: beam 0, token 0)
+        const long dst = (long)q * R + roi;
+        if (lane == 0) {
+            const long hix = ((long)d.j * R + roi) * k + q;
+            d.scores_out[roi * k + q] = bs;
+            d.parents[hix] = bb;
+            d.tokens_hist[hix] = bt;
+            if (d.tokens) d.tokens[dst] = bt;
+            if (d.mask) d.mask[dst] = bt != 0 ? 1 : 0;
+        }
+        if (d.h_in) {
+            const long src = (long)bb * R + roi;
+            const float4* hs = reinterpret_cast<const float4*>(d.h_in + src * d.U);
+            const float4* cs = reinterpret_cast<const float4*>(d.c_in + src * d.U);
+            float4* hd = reinterpret_cast<float4*>(d.h_out + dst * d.U);
+            float4* cdst = reinterpret_cast<float4*>(d.c_out + dst * d.U);
+            for (int u = lane; u < d.U / 4; u += 64) { hd[u] = hs[u]; cdst[u] = cs[u]; }
+        }
+    }
+}
+
+// One thread per (roi, beam): walk the parents from the last step back.
+__global__ __launch_bounds__(256) void beam_backtrace_kernel(const int32_t* __restrict__ parents, const int32_t* __restrict__ tokens_hist,
+                                                             int steps, int R, int k, int32_t* __restrict__ seq) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= R * k) return;
+    const int roi = i / k;
+    int cur = i - roi * k;
+    int32_t* out = seq + (long)i * steps;
+    for (int j = steps - 1; j >= 0; --j) {
+        const long hix = ((long)j * R + roi) * k + cur;
+        out[j] = tokens_hist[hix];
+        cur = parents[hix];
+    }
+}
+
+static size_t tk_align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+static int topk_validate(const dc_vocab_topk_desc* d) {
+    DC_REQUIRE(d != nullptr, DC_EINVAL, "dc_vocab_topk: null descriptor");
+    DC_REQUIRE(d->M > 0 && d->V > 0 && d->K > 0 && d->X && d->W && d->ids && d->probs, DC_EINVAL, "dc_vocab_topk: bad arguments");
+    DC_REQUIRE(d->k >= 1 && d->k <= TK_MAX && d->V >= d->k, DC_EINVAL, "dc_vocab_topk: need 1 <= k <= 8 and V >= k (k = %d, V = %d)", d->k, d->V);
+    DC_REQUIRE((d->K & 31) == 0 && (d->ldx & 3) == 0 && (d->ldw & 3) == 0, DC_EALIGN,
+               "dc_vocab_topk: K must be a multiple of 32 and ldx, ldw multiples of 4");
+    DC_REQUIRE(d->ldx >= d->K && d->ldw >= (d->V + 3) / 4 * 4, DC_EINVAL, "dc_vocab_topk: ldx < K or ldw < V rounded up to 4");
+    DC_REQUIRE(aligned16(d->X) && aligned16(d->W) && (!d->bias || aligned16(d->bias)), DC_EALIGN, "dc_vocab_topk: X, W, bias must be 16-byte aligned");
+    DC_REQUIRE((size_t)d->M * d->ldx * 4 < (size_t)0xFFFFFFF0u && (size_t)d->K * d->ldw * 4 < (size_t)0xFFFFFFF0u, DC_EINVAL,
+               "dc_vocab_topk: operands must span < 4 GiB");
+    return DC_OK;
+}
+
+}  // namespace dcap
+
+using namespace dcap;
+
+extern "C" size_t dc_vocab_topk_workspace_bytes(int M, int V, int k) {
+    if (M <= 0 || V <= 0 || k <= 0) return 0;
+    const size_t cells = (size_t)M * ((V + 127) / 128);
+    return tk_align256(cells * sizeof(float2)) + tk_align256(cells * k * sizeof(float2));
+}
+
+extern "C" int dc_vocab_topk_f32(const dc_vocab_topk_desc* d, void* workspace, size_t workspace_bytes, void* stream) {
+    int rc = topk_validate(d);
+    if (rc) return rc;
+    const size_t need = dc_vocab_topk_workspace_bytes(d->M, d->V, d->k);
+    DC_REQUIRE(workspace && workspace_bytes >= need, DC_EWORKSPACE, "dc_vocab_topk: needs %zu workspace bytes, got %zu", need, workspace_bytes);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    TopkArgs ta{};
+    ta.M = d->M; ta.V = d->V; ta.k = d->k;
+    ta.tiles_m = (d->M + 127) / 128;
+    ta.tiles_n = (d->V + 127) / 128;
+    ta.bias = d->bias;
+    ta.ms = static_cast<float2*>(workspace);
+    ta.cand = reinterpret_cast<float2*>(static_cast<char*>(workspace) + tk_align256((size_t)d->M * ta.tiles_n * sizeof(float2)));
+    // as dc_vocab_top1_f32: the B loader reads whole 16-byte column quads inside the row (ldw >= round4(V)); those columns are guarded off
+    TKA al{d->X, d->ldx, d->M, nullptr};
+    TKB bl{d->W, d->ldw, (d->V + 3) / 4 * 4, nullptr};
+    DC_ENSURE_DYN_LDS((&vocab_topk_f32_kernel), 160 * 1024);
+    constexpr size_t lds = igemm_lds_bytes<128, 128, TKA, TKB>();
+    hipLaunchKernelGGL(vocab_topk_f32_kernel, dim3(ta.tiles_m * ta.tiles_n), dim3(256), lds, s, al, bl, ta, d->K);
+    rc = check_launch("vocab_topk_f32_kernel");
+    if (rc) return rc;
+    hipLaunchKernelGGL(vocab_topk_rows_kernel, dim3((d->M + 3) / 4), dim3(256), 0, s, d->M, ta.tiles_n, d->k, ta.ms, ta.cand, d->ids, d->probs);
+    return check_launch("vocab_topk_rows_kernel");
+}
+
+extern "C" int dc_beam_select_f32(const dc_beam_select_desc* d, void* stream) {
+    DC_REQUIRE(d != nullptr, DC_EINVAL, "dc_beam_select: null descriptor");
+    DC_REQUIRE(d->R > 0 && d->k >= 1 && d->k <= TK_MAX && d->nb >= 1 && d->nb <= d->k && d->j >= 0 && d->j < d->steps, DC_EINVAL,
+               "dc_beam_select: need R > 0, 1 <= nb <= k <= 8, 0 <= j < steps");
+    DC_REQUIRE(d->cand_ids && d->cand_probs && d->scores_out && d->parents && d->tokens_hist, DC_EINVAL, "dc_beam_select: null pointer");
+    DC_REQUIRE(d->scores_out != d->scores_in, DC_EINVAL, "dc_beam_select: scores_out must not alias scores_in");
+    if (d->h_in) {
+        DC_REQUIRE(d->c_in && d->h_out && d->c_out && d->U > 0 && (d->U & 3) == 0, DC_EINVAL, "dc_beam_select: h/c rows need U %% 4 == 0 and four buffers");
+        DC_REQUIRE(aligned16(d->h_in) && aligned16(d->c_in) && aligned16(d->h_out) && aligned16(d->c_out), DC_EALIGN,
+                   "dc_beam_select: h/c buffers must be 16-byte aligned");
+        DC_REQUIRE(d->h_out != d->h_in && d->c_out != d->c_in && d->h_out != d->c_out, DC_EINVAL,
+                   "dc_beam_select: h_out / c_out must not alias h_in / c_in / each other");
+    }
+    hipLaunchKernelGGL(beam_select_kernel, dim3((d->R + 3) / 4), dim3(256), 0, static_cast<hipStream_t>(stream), *d);
+    return check_launch("beam_select_kernel");
+}
+
+extern "C" int dc_beam_backtrace(const int32_t* parents, const int32_t* tokens_hist, int steps, int R, int k, int32_t* seq, void* stream) {
+    DC_REQUIRE(parents && tokens_hist && seq && steps > 0 && R > 0 && k >= 1 && k <= TK_MAX, DC_EINVAL, "dc_beam_backtrace: bad arguments");
+    hipLaunchKernelGGL(beam_backtrace_kernel, dim3((R * k + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), parents, tokens_hist,
+                       steps, R, k, seq);
+    return check_launch("beam_backtrace_kernel");
+}

@@ -11,7 +11,7 @@ import torch
 
 from . import _lib
 from ._lib import (PwChainDesc, ConvBf16Desc, AmsgradDesc, DetectionTargetsDesc, BnReluDesc, ConvDesc, ConvWgradBf16Desc, GemmBf16Desc, VocabCeDesc, ProposalDesc, RpnLossDesc, GemmDesc, LstmBwdDesc, LstmFwdDesc, RoiAlignDesc,
-                   SoftmaxCeDesc, VocabTop1Desc, LstmStepDesc, check)
+                   SoftmaxCeDesc, VocabTop1Desc, VocabTopkDesc, BeamSelectDesc, LstmStepDesc, check)
 
 
 def _stream():
@@ -767,6 +767,26 @@ def _row_out(t, M, dtype, name):
     return C.c_void_p(t.data_ptr()), max(1, t.stride(0))
 
 
+def _vocab_operands(X, W, bias):
+    """X [M,K], W [K,V], bias [V] as the fused vocabulary kernels read them: W rows readable in whole 16-byte column quads up to V
+    rounded up to 4, X rows and bias 16-byte aligned (a padded / aligned copy otherwise)."""
+    M, K = X.shape
+    V = W.shape[1]
+    Vp = (V + 3) // 4 * 4
+    esz = W.element_size()
+    w_ok = (W.stride(0) % 4 == 0 and W.stride(0) >= Vp and W.data_ptr() % 16 == 0 and
+            (W.storage_offset() + (K - 1) * W.stride(0) + Vp) * esz <= W.untyped_storage().nbytes())
+    if not w_ok:                                       # (the kernel reads whole 16-byte column quads of W's rows)
+        Wp = torch.zeros((K, Vp), dtype=torch.float32, device=W.device)
+        Wp[:, :V].copy_(W)
+        W = Wp
+    if X.stride(0) % 4 or X.data_ptr() % 16:
+        X = torch.empty((M, K), dtype=torch.float32, device=X.device).copy_(X)
+    if bias is not None and (bias.data_ptr() % 16 or not bias.is_contiguous()):
+        bias = torch.empty((V,), dtype=torch.float32, device=bias.device).copy_(bias)
+    return X, W, bias
+
+
 def vocab_top1(X, W, bias=None, tokens=None, ids=None, probs=None, mask=None):
     """Fused Dense(V) + greedy top-1 (dc_vocab_top1_f32): per row of X [M,K] (float32, K % 32 == 0) the argmax of X W + bias (lowest
     index on ties) into tokens int32 [M] (contiguous), optionally also into ids / probs (int32 / float32 length-M vectors with any
@@ -794,18 +814,7 @@ def vocab_top1(X, W, bias=None, tokens=None, ids=None, probs=None, mask=None):
     probs_p, ld_probs = _row_out(probs, M, torch.float32, "probs")
     if M == 0:
         return tokens
-    Vp = (V + 3) // 4 * 4
-    esz = W.element_size()
-    w_ok = (W.stride(0) % 4 == 0 and W.stride(0) >= Vp and W.data_ptr() % 16 == 0 and
-            (W.storage_offset() + (K - 1) * W.stride(0) + Vp) * esz <= W.untyped_storage().nbytes())
-    if not w_ok:                                       # (the kernel reads whole 16-byte column quads of W's rows)
-        Wp = torch.zeros((K, Vp), dtype=torch.float32, device=W.device)
-        Wp[:, :V].copy_(W)
-        W = Wp
-    if X.stride(0) % 4 or X.data_ptr() % 16:
-        X = torch.empty((M, K), dtype=torch.float32, device=X.device).copy_(X)
-    if bias is not None and (bias.data_ptr() % 16 or not bias.is_contiguous()):
-        bias = torch.empty((V,), dtype=torch.float32, device=bias.device).copy_(bias)
+    X, W, bias = _vocab_operands(X, W, bias)
     d = VocabTop1Desc()
     d.M, d.V, d.K = M, V, K
     d.X, d.ldx, d.W, d.ldw = X.data_ptr(), X.stride(0), W.data_ptr(), W.stride(0)
@@ -816,6 +825,108 @@ def vocab_top1(X, W, bias=None, tokens=None, ids=None, probs=None, mask=None):
     ws, wsb = WORKSPACE.get(lib.dc_vocab_top1_workspace_bytes(M, V), X.device)
     check(lib.dc_vocab_top1_f32(C.byref(d), _ptr(ws), wsb, _stream()), "dc_vocab_top1_f32")
     return tokens
+
+
+TOPK_MAX = 8
+
+
+def vocab_topk(X, W, bias, k, ids=None, probs=None):
+    """Fused Dense(V) + row top-k (dc_vocab_topk_f32; beam search): per row of X [M,K] (float32, K % 32 == 0) the k best words of
+    X W + bias in the order logit descending, then index ascending, into ids int32 [M,k], and their softmax probabilities into probs
+    float32 [M,k] (both contiguous; allocated when None).  1 <= k <= 8 and V >= k; any V (W padded as for vocab_top1).  The [M,V]
+    logits are never materialised.  k = 1 gives vocab_top1's ids and probabilities.  Returns (ids, probs)."""
+    _chk(X, name="X"), _chk(W, name="W")
+    if bias is not None:
+        _chk(bias, name="bias")
+    lib = _lib.load()
+    M, K = X.shape
+    V = W.shape[1]
+    k = int(k)
+    if W.shape[0] != K:
+        raise _lib.DcapError("vocab_topk: inner dimensions differ (%d vs %d)" % (K, W.shape[0]))
+    if K % 32:
+        raise _lib.DcapError("vocab_topk: K must be a multiple of 32, got %d" % K)
+    if not 1 <= k <= TOPK_MAX or V < k:
+        raise _lib.DcapError("vocab_topk: need 1 <= k <= %d and V >= k, got k = %d, V = %d" % (TOPK_MAX, k, V))
+    if bias is not None and tuple(bias.shape) != (V,):
+        raise _lib.DcapError("vocab_topk: bias must be [V]")
+    if ids is None:
+        ids = torch.empty((M, k), dtype=torch.int32, device=X.device)
+    if probs is None:
+        probs = torch.empty((M, k), dtype=torch.float32, device=X.device)
+    for name, t, dt in (("ids", ids, torch.int32), ("probs", probs, torch.float32)):
+        if not _chk(t, dt, name).is_contiguous() or tuple(t.shape) != (M, k):
+            raise _lib.DcapError("vocab_topk: %s must be a contiguous %s [M,k] tensor" % (name, dt))
+    if M == 0:
+        return ids, probs
+    X, W, bias = _vocab_operands(X, W, bias)
+    d = VocabTopkDesc()
+    d.M, d.V, d.K, d.k = M, V, K, k
+    d.X, d.ldx, d.W, d.ldw = X.data_ptr(), X.stride(0), W.data_ptr(), W.stride(0)
+    d.bias = _ptr(bias)
+    d.ids, d.probs = ids.data_ptr(), probs.data_ptr()
+    ws, wsb = WORKSPACE.get(lib.dc_vocab_topk_workspace_bytes(M, V, k), X.device)
+    check(lib.dc_vocab_topk_f32(C.byref(d), _ptr(ws), wsb, _stream()), "dc_vocab_topk_f32")
+    return ids, probs
+
+
+def beam_select(cand_ids, cand_probs, scores_in, scores_out, parents, tokens_hist, j, nb, log_score=False, tokens=None, mask=None,
+                h_in=None, c_in=None, h_out=None, c_out=None):
+    """One beam-search step (dc_beam_select_f32) for R RoIs x k beams, beam-major rows (beam b of RoI r = row b * R + r):
+    cand_ids / cand_probs [k*R,k] (vocab_topk's output), scores_in [R,k] (None: zeros, the first step) -> the k best of the first nb
+    beams' candidates (score + p, or + log p with log_score), best first: scores_out [R,k], parents / tokens_hist [steps,R,k] at step j,
+    tokens int32 [k*R] and mask uint8 [k*R] (token != 0) when given, and h_in / c_in [k*R,U] gathered by parent into h_out / c_out."""
+    lib = _lib.load()
+    R, k = scores_out.shape
+    _chk(scores_out, name="scores_out")
+    for name, t, dt, shape in (("cand_ids", cand_ids, torch.int32, (k * R, k)), ("cand_probs", cand_probs, torch.float32, (k * R, k)),
+                               ("scores_in", scores_in, torch.float32, (R, k)), ("tokens", tokens, torch.int32, (k * R,)),
+                               ("mask", mask, torch.uint8, (k * R,))):
+        if t is not None and (not _chk(t, dt, name).is_contiguous() or tuple(t.shape) != shape):
+            raise _lib.DcapError("beam_select: %s must be a contiguous %s %s tensor" % (name, dt, shape))
+    steps = parents.shape[0]
+    for name, t in (("parents", parents), ("tokens_hist", tokens_hist)):
+        if not _chk(t, torch.int32, name).is_contiguous() or tuple(t.shape) != (steps, R, k):
+            raise _lib.DcapError("beam_select: %s must be a contiguous int32 [steps,R,k] tensor" % name)
+    if not scores_out.is_contiguous() or not 1 <= k <= TOPK_MAX or not 1 <= nb <= k or not 0 <= j < steps:
+        raise _lib.DcapError("beam_select: need contiguous scores_out, 1 <= nb <= k <= %d, 0 <= j < steps" % TOPK_MAX)
+    rows = (h_in, c_in, h_out, c_out)
+    U = 0
+    if any(t is not None for t in rows):
+        if any(t is None for t in rows):
+            raise _lib.DcapError("beam_select: h_in, c_in, h_out, c_out are all given or all None")
+        U = h_in.shape[-1]
+        for name, t in zip(("h_in", "c_in", "h_out", "c_out"), rows):
+            if not _chk(t, name=name).is_contiguous() or tuple(t.shape) != (k * R, U):
+                raise _lib.DcapError("beam_select: %s must be a contiguous float32 [k*R,U] tensor" % name)
+    if R == 0:
+        return scores_out
+    d = BeamSelectDesc()
+    d.R, d.k, d.nb, d.steps, d.j, d.log_score = R, k, int(nb), steps, int(j), int(bool(log_score))
+    d.cand_ids, d.cand_probs, d.scores_in, d.scores_out = cand_ids.data_ptr(), cand_probs.data_ptr(), _ptr(scores_in), scores_out.data_ptr()
+    d.parents, d.tokens_hist, d.tokens, d.mask = parents.data_ptr(), tokens_hist.data_ptr(), _ptr(tokens), _ptr(mask)
+    d.U, d.h_in, d.c_in, d.h_out, d.c_out = U, _ptr(h_in), _ptr(c_in), _ptr(h_out), _ptr(c_out)
+    check(lib.dc_beam_select_f32(C.byref(d), _stream()), "dc_beam_select_f32")
+    return scores_out
+
+
+def beam_backtrace(parents, tokens_hist, out=None):
+    """parents / tokens_hist int32 [steps,R,k] (beam_select's history) -> the beams' token sequences int32 [R,k,steps] (dc_beam_backtrace)."""
+    lib = _lib.load()
+    for name, t in (("parents", parents), ("tokens_hist", tokens_hist)):
+        if not _chk(t, torch.int32, name).is_contiguous() or t.dim() != 3:
+            raise _lib.DcapError("beam_backtrace: %s must be a contiguous int32 [steps,R,k] tensor" % name)
+    steps, R, k = parents.shape
+    if tuple(tokens_hist.shape) != (steps, R, k):
+        raise _lib.DcapError("beam_backtrace: parents and tokens_hist differ in shape")
+    if out is None:
+        out = torch.empty((R, k, steps), dtype=torch.int32, device=parents.device)
+    if not _chk(out, torch.int32, "out").is_contiguous() or tuple(out.shape) != (R, k, steps):
+        raise _lib.DcapError("beam_backtrace: out must be a contiguous int32 [R,k,steps] tensor")
+    if R == 0 or steps == 0:
+        return out
+    check(lib.dc_beam_backtrace(parents.data_ptr(), tokens_hist.data_ptr(), steps, R, k, out.data_ptr(), _stream()), "dc_beam_backtrace")
+    return out
 
 
 def argmax_rows(x, out=None):

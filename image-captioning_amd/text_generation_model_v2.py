@@ -599,3 +599,193 @@ class CaptionModelV2(KerasLikeModel):
             rows.append(probs[0].cpu().numpy())
             ids.append(nxt)
         return np.array(ids[1:], np.int32), np.array(rows)
+
+    # ---------------------------------------------------------------------------------- on-device decoding
+    DECODERS = ("prefix", "incremental", "beam")
+    SCORES = ("prob", "logprob")
+
+    @classmethod
+    def check_decoder(cls, decoder, beam_size=None, start_ids=None, score="prob"):
+        """generate()'s argument rules (no GPU needed): a known decoder, beam_size in 1..8 with decoder='beam' only, no start_ids for
+        'prefix' (greedy_decode always starts from 0) and a known score rule."""
+        if decoder not in cls.DECODERS:
+            raise ValueError("decoder must be one of %s, got %r" % (cls.DECODERS, decoder))
+        if decoder == "beam":
+            if beam_size is None or isinstance(beam_size, bool) or int(beam_size) != beam_size or not 1 <= beam_size <= ops.TOPK_MAX:
+                raise ValueError("decoder='beam' needs beam_size in 1..%d, got %r" % (ops.TOPK_MAX, beam_size))
+        elif beam_size is not None:
+            raise ValueError("beam_size is only for decoder='beam' (got decoder=%r)" % (decoder,))
+        if decoder == "prefix" and start_ids is not None:
+            raise ValueError("decoder='prefix' (greedy_decode) always starts from id 0: start_ids needs 'incremental' or 'beam'")
+        if score not in cls.SCORES:
+            raise ValueError("score must be one of %s, got %r" % (cls.SCORES, score))
+
+    def _decode_steps(self, steps):
+        """steps <= Tw: a carried state is the prefix path's state only while pad_sequences has truncated nothing."""
+        Tw = self.word_shape[0]
+        steps = Tw - 1 if steps is None else int(steps)
+        if not 1 <= steps <= Tw:
+            raise ValueError("incremental decoding needs 1 <= steps <= Tw = %d (longer prefixes are truncated by pad_sequences, "
+                             "which a carried state cannot undo: use decoder='prefix'), got %d" % (Tw, steps))
+        return steps
+
+    def _start_tokens(self, start_ids, R, k):
+        """int32 [k*R] device tensor (beam-major: row b*R + r holds RoI r's start id) and its mask (id != 0)."""
+        if start_ids is None:
+            tok = torch.zeros((k * R,), dtype=torch.int32, device=self.device)
+        else:
+            if isinstance(start_ids, torch.Tensor):
+                s = start_ids.to(self.device, torch.int32).reshape(-1)
+            else:
+                a = np.asarray(start_ids)
+                if a.size and (a.min() < 0 or a.max() >= self.V):
+                    raise ValueError("start_ids must lie in [0, V)")
+                s = torch.tensor(a.astype(np.int32).reshape(-1), device=self.device)
+            if s.numel() != R:
+                raise ValueError("start_ids must hold one id per RoI (%d), got %d" % (R, s.numel()))
+            tok = s.repeat(k).contiguous()
+        return tok, (tok != 0).to(torch.uint8)
+
+    def _decode_setup(self, feat, n):
+        """Once per decode, for n = k*R beam-major rows: the RoI head f [R,1024], the constant half of the inject LSTM's input
+        (f kernel[:1024] + bias: the residual of the per-token GEMM over kernel[1024:]) or the merge concat buffer with f in place, and
+        the word LSTM's packed recurrent kernel."""
+        w = self.store.w
+        R = feat.shape[0]
+        (K1, s1, h1), (K2, s2, h2) = self._head
+        a1 = ops.gemm(feat.reshape(R, -1), K1, out=self._buf('dec_a1', (R, self.FEAT)), scale=s1, shift=h1, relu=True)
+        f = ops.gemm(a1, K2, out=self._buf('dec_f', (R, self.FEAT)), scale=s2, shift=h2, relu=True)
+        ctx = dict(n=n, R=R)
+        if self.inject:
+            ctx['zf'] = ops.gemm(f, w['imgcap_lstm/kernel'][:self.FEAT], shift=w['imgcap_lstm/bias'], out=self._buf('dec_zf', (R, 4 * self.units)))
+        else:
+            rows = torch.arange(n, dtype=torch.int32, device=self.device)
+            ctx['cat'] = cat = self._buf('dec_cat', (n, self.FEAT + self.WORD_UNITS))
+            ops.gather_rows(f, (rows % R).to(torch.int32), cat[:, :self.FEAT])
+            ctx['rows'] = rows
+        U = self.WORD_UNITS
+        ctx['Upk'] = ops.lstm_pack_urec(w[V2_WORD_LSTM + '/recurrent_kernel'], out=self._buf('dec_upk', (U, 4 * U)))
+        return ctx
+
+    def _decode_word(self, ctx, tok, h_prev, c_prev, mask, h, c):
+        """One word-LSTM step per row: the embedding-gather GEMM of tok, then the carried-state step (mask: id != 0)."""
+        w, U = self.store.w, self.WORD_UNITS
+        z = ops.gemm(w['imgcap_embedding_layer/embeddings'], w[V2_WORD_LSTM + '/kernel'], gather=tok, shift=w[V2_WORD_LSTM + '/bias'],
+                     out=self._buf('dec_zw', (ctx['n'], 4 * U)))
+        return ops.lstm_step(z, w[V2_WORD_LSTM + '/recurrent_kernel'], h_prev, c_prev, mask, h, c,
+                             U_packed=None if h_prev is None else ctx['Upk'])
+
+    def _decode_top(self, ctx, h_word):
+        """The vocabulary layer's input for the rows' word states: inject -- one zero-state step of imgcap_lstm on [f, h_word]; merge --
+        [f, h_word] itself."""
+        n, w = ctx['n'], self.store.w
+        if self.inject:
+            u = self.units
+            z2 = ops.gemm(h_word, w['imgcap_lstm/kernel'][self.FEAT:], residual=ctx['zf'], res_rows=ctx['R'], out=self._buf('dec_z2', (n, 4 * u)))
+            top, _ = ops.lstm_step(z2, w['imgcap_lstm/recurrent_kernel'], h=self._buf('dec_h2', (n, u)), c=self._buf('dec_c2', (n, u)))
+            return top
+        ops.gather_rows(h_word, ctx['rows'], ctx['cat'][:, self.FEAT:])
+        return ctx['cat']
+
+    def _decode_state(self, n):
+        U = self.WORD_UNITS
+        return [self._buf('dec_%s%d' % (x, q), (n, U)) for q in range(2) for x in 'hc']           # (h, c, h', c')
+
+    def decode_greedy(self, feat, steps=None, start_ids=None):
+        """Greedy decoding of the reference's test / eval loops (_v2.py:328-346; eval_text_generation_model_v2.py:164-189) for every
+        RoI at once, ONE token per step on the device: the RoI head, the constant inject half and the packed recurrent kernel once, then
+        per token one embedding-gather GEMM + one carried-state word-LSTM step (a chosen 0 is masked: the state carries over it, as
+        Keras masks the pre-padded prefix), the inject GEMM + zero-state step (merge: h_word into the concat buffer) and ops.vocab_top1.
+        The first id fed is start_ids (int [R]; default 0, as the test loop).  steps <= Tw (default Tw - 1).
+        Returns device tensors: ids int32 [R,steps] and word_scores float32 [R,steps] (each chosen word's softmax probability), two
+        views of one [2,R,steps] buffer.  No host synchronisation."""
+        out = self._decode_greedy(feat, steps, start_ids)
+        return out[0], out[1].view(torch.float32)
+
+    def _decode_greedy(self, feat, steps, start_ids):
+        steps = self._decode_steps(steps)
+        feat = self._dev_feat(feat)
+        R = feat.shape[0]
+        out = torch.empty((2, R, steps), dtype=torch.int32, device=self.device)
+        if R == 0:
+            return out
+        ids, scores = out[0], out[1].view(torch.float32)
+        tok, live = self._start_tokens(start_ids, R, 1)
+        ctx = self._decode_setup(feat, R)
+        st = self._decode_state(R)
+        w = self.store.w
+        h, c = self._decode_word(ctx, tok, None, None, live, st[0], st[1])
+        for j in range(steps):
+            ops.vocab_top1(self._decode_top(ctx, h), w['imgcap_d1/kernel'], w['imgcap_d1/bias'], tokens=tok, ids=ids[:, j],
+                           probs=scores[:, j], mask=live)
+            if j + 1 < steps:
+                q = 2 * ((j + 1) % 2)
+                h, c = self._decode_word(ctx, tok, h, c, live, st[q], st[q + 1])
+        return out
+
+    def decode_beam(self, feat, beam_size, steps=None, start_ids=None, score="prob"):
+        """Beam search of the authors' captioner (image captioning/test.py:23-64) over the v2 decoders, for every RoI at once on the
+        device.  From one beam (start_ids, default 0), each step every beam proposes its k = beam_size most probable next words
+        (ops.vocab_topk over the k*R beam rows); a candidate scores the beam's score + p (score='prob', the reference's rule) or + log p
+        ('logprob'); the k best of the k*k survive (ops.beam_select: score descending, then parent beam, then word id ascending), the
+        word LSTM's state follows its parent and then takes the chosen word (0 is masked: the state carries over it).  Fixed length
+        steps <= Tw (default Tw - 1), no end token.  Returns device tensors: tokens int32 [R,k,steps] and scores float32 [R,k], best
+        first.  No host synchronisation."""
+        R, k, steps, out = self._decode_beam(feat, beam_size, steps, start_ids, score)
+        return out[:R * k * steps].view(R, k, steps), out[R * k * steps:].view(torch.float32).view(R, k)
+
+    def _decode_beam(self, feat, beam_size, steps, start_ids, score):
+        """decode_beam into one flat int32 device buffer: the [R,k,steps] tokens, then the [R,k] scores' float32 bits."""
+        self.check_decoder("beam", beam_size, start_ids, score)
+        k = int(beam_size)
+        if k > self.V:
+            raise ValueError("beam_size %d exceeds the vocabulary (%d words)" % (k, self.V))
+        steps = self._decode_steps(steps)
+        feat = self._dev_feat(feat)
+        R = feat.shape[0]
+        out = torch.empty((R * k * (steps + 1),), dtype=torch.int32, device=self.device)
+        if R == 0:
+            return R, k, steps, out
+        n = k * R
+        tokens, final = out[:n * steps].view(R, k, steps), out[n * steps:].view(torch.float32).view(R, k)
+        tok, live = self._start_tokens(start_ids, R, k)
+        ctx = self._decode_setup(feat, n)
+        st = self._decode_state(n)
+        w = self.store.w
+        parents, hist = self._buf('dec_par', (steps, R, k), torch.int32), self._buf('dec_hist', (steps, R, k), torch.int32)
+        sc = [self._buf('dec_sc%d' % q, (R, k)) for q in range(2)]
+        cids, cprobs = self._buf('dec_cid', (n, k), torch.int32), self._buf('dec_cp', (n, k))
+        self._decode_word(ctx, tok, None, None, live, st[0], st[1])
+        for j in range(steps):
+            ops.vocab_topk(self._decode_top(ctx, st[0]), w['imgcap_d1/kernel'], w['imgcap_d1/bias'], k, ids=cids, probs=cprobs)
+            last = j + 1 == steps
+            gather = {} if last else dict(h_in=st[0], c_in=st[1], h_out=st[2], c_out=st[3])
+            ops.beam_select(cids, cprobs, None if j == 0 else sc[j % 2], final if last else sc[(j + 1) % 2], parents, hist, j,
+                            1 if j == 0 else k, score == "logprob", tokens=tok, mask=live, **gather)
+            if not last:                  # the parents' states (gathered into st[2:]) take the chosen words, back into st[:2]
+                self._decode_word(ctx, tok, st[2], st[3], live, st[0], st[1])
+        ops.beam_backtrace(parents, hist, out=tokens)
+        return R, k, steps, out
+
+    def generate(self, feat, steps=None, decoder="prefix", beam_size=None, start_ids=None, score="prob"):
+        """Caption every RoI of feat [R,7,7,256].  decoder='prefix': greedy_decode per RoI (the reference's loop: the whole model on
+        the pre-padded prefix per token); 'incremental': decode_greedy; both return numpy (ids int32 [R,steps], word_scores float32
+        [R,steps]).  'beam': decode_beam, returning numpy (tokens int32 [R,k,steps], scores float32 [R,k]).  The device decoders make
+        one device-to-host copy."""
+        self.check_decoder(decoder, beam_size, start_ids, score)
+        if decoder == "incremental":
+            host = self._decode_greedy(feat, steps, start_ids).cpu().numpy()
+            return host[0], host[1].view(np.float32)
+        if decoder == "beam":
+            R, k, steps, out = self._decode_beam(feat, beam_size, steps, start_ids, score)
+            host = out.cpu().numpy()
+            return host[:R * k * steps].reshape(R, k, steps), host[R * k * steps:].view(np.float32).reshape(R, k)
+        Tw = self.word_shape[0]
+        n_steps = Tw - 1 if steps is None else int(steps)
+        R = len(feat)
+        ids = np.zeros((R, n_steps), np.int32)
+        word_scores = np.zeros((R, n_steps), np.float32)
+        for r in range(R):
+            ids[r], rows = self.greedy_decode(feat[r], n_steps)
+            word_scores[r] = rows[np.arange(n_steps), ids[r]]
+        return ids, word_scores

@@ -523,6 +523,61 @@ typedef struct {
 size_t dc_vocab_top1_workspace_bytes(int M, int V);
 int    dc_vocab_top1_f32(const dc_vocab_top1_desc* d, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Vocabulary projection FUSED with the row top-k (beam search, 1 <= k <= 8, V >= k): the k best words of each row and their softmax
+ * probabilities, from logits = X[M,K] * W[K,V] + bias that are never written.  Replaces, per beam and token, model.predict's softmax
+ * row + np.argsort(...)[-k:] of the reference's beam loop (image captioning/test.py:33-44) for the v2 decoders.
+ *   X, W, bias: as dc_vocab_top1_f32 (any V >= k).  ids [M][k] int32, probs [M][k] float32 (out, contiguous): the k best words in the
+ *   order value descending, then column ascending; probs[m][r] = exp(z_r - max z) / sum_v exp(z_v - max z).  k = 1 gives
+ *   dc_vocab_top1_f32's id and probability.
+ * Per (row, 128-column tile) the epilogue keeps max, sum exp and the tile's k best (value, column) pairs (k threshold rounds of the
+ * 32-lane shuffle reduction); a second launch, one wave per row, combines the tiles_n * k candidates in an order fixed by V alone, so
+ * the result is deterministic and the same at every M.  Workspace: dc_vocab_topk_workspace_bytes(M, V, k) (8 (k + 1) bytes per row
+ * and tile).
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct {
+    int M, V, K, k;
+    const float* X;  int ldx;
+    const float* W;  int ldw;
+    const float* bias;
+    int32_t* ids;
+    float* probs;
+} dc_vocab_topk_desc;
+
+size_t dc_vocab_topk_workspace_bytes(int M, int V, int k);
+int    dc_vocab_topk_f32(const dc_vocab_topk_desc* d, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * One beam-search step for R RoIs with k beams each (image captioning/test.py:33-56), one wave per RoI.  Rows of the per-beam
+ * tensors are BEAM-MAJOR: beam b of RoI r is row b * R + r.
+ *   cand_ids / cand_probs [k*R][k]: dc_vocab_topk_f32's output for every beam row;  nb: live beams (1 at the first step, then k);
+ *   scores_in [R][k] (NULL: zeros).  Candidate (b, i) scores scores_in[r][b] + p (log_score 0, the reference's rule) or + log p.
+ *   The k best of the nb * k candidates, in the order score descending, parent beam ascending, word id ascending, become beams 0..k-1:
+ *   scores_out [R][k], parents / tokens_hist [steps][R][k] at step j, tokens [k*R] (optional: the next embedding-gather rows),
+ *   mask [k*R] (optional: token != 0).  h_in / c_in -> h_out / c_out [k*R][U] (optional, U % 4 == 0, 16-byte aligned): row q * R + r
+ *   receives row parent * R + r (the word LSTM's state follows its beam).
+ * dc_beam_backtrace: parents / tokens_hist [steps][R][k] -> seq [R][k][steps], the beams' token sequences.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct {
+    int R, k, nb, steps, j, log_score;
+    const int32_t* cand_ids;
+    const float* cand_probs;
+    const float* scores_in;
+    float* scores_out;
+    int32_t* parents;
+    int32_t* tokens_hist;
+    int32_t* tokens;
+    uint8_t* mask;
+    int U;
+    const float* h_in;
+    const float* c_in;
+    float* h_out;
+    float* c_out;
+} dc_beam_select_desc;
+
+int    dc_beam_select_f32(const dc_beam_select_desc* d, void* stream);
+int    dc_beam_backtrace(const int32_t* parents, const int32_t* tokens_hist, int steps, int R, int k, int32_t* seq, void* stream);
+
 /* tf.argmax over the last axis, lowest index wins ties (text_generation_model.py:222-225). */
 int dc_argmax_rows_f32(const float* x, int M, int V, int ld, int32_t* out, void* stream);
 

@@ -1,0 +1,472 @@
+"""On-device decoding of the v2 caption decoders (inject and merge): ops.vocab_topk (the vocabulary GEMM fused with the row top-k),
+ops.beam_select / ops.beam_backtrace, CaptionModelV2.decode_greedy / decode_beam / generate.  The references are float64 restatements
+of the reference's loops over oracle.np_models.v2_forward: the test loop (_v2.py:328-346), the eval loop that starts from a caption's
+first id (eval_text_generation_model_v2.py:164-189) and the authors' beam search (image captioning/test.py:23-64).  GPU tests are
+marked; the argument checks at the end run without a GPU."""
+import numpy as np
+import pytest
+import torch
+
+from oracle import np_models as M
+
+
+@pytest.fixture(scope="module")
+def gpu():
+    if not torch.cuda.is_available():
+        pytest.skip("needs a GPU")
+    from image_captioning_amd import _lib
+    _lib.load()
+    return torch.device("cuda:0")
+
+
+def _dev(a, dt=torch.float32):
+    return torch.tensor(np.ascontiguousarray(a), dtype=dt, device="cuda:0")
+
+
+def _exact_operands(rng, Mr, K, V):
+    """X, W, bias on coarse binary grids (X in 1/8, W in 1/256, bias in 1/2048 steps), as in test_gpu_decode.py: every product and
+    partial sum of X W + bias is exact in fp32 at these sizes, so the logits are exact (exact ties included) whatever the summation
+    order, and a comparison with float64 measures the kernel's own reductions."""
+    X = (rng.integers(-8, 9, (Mr, K)) / 8.0).astype(np.float32)
+    W = (rng.integers(-16, 17, (K, V)) / 256.0).astype(np.float32)
+    b = (rng.integers(-1024, 1025, V) / 2048.0).astype(np.float32)
+    return X, W, b
+
+
+def _ref_topk(X, W, b, k):
+    """float64 top-k in the kernel's order (logit descending, then index ascending: a stable sort of -z) and its softmax probabilities."""
+    z = X.astype(np.float64) @ W.astype(np.float64) + b.astype(np.float64)
+    ids = np.argsort(-z, axis=1, kind="stable")[:, :k]
+    m = z.max(1, keepdims=True)
+    p = np.exp(z - m) / np.exp(z - m).sum(1, keepdims=True)
+    return ids, np.take_along_axis(p, ids, 1)
+
+
+def _topk(X, W, b, k):
+    from image_captioning_amd import ops
+    ids, p = ops.vocab_topk(X, W, b, k)
+    torch.cuda.synchronize()
+    return ids.cpu().numpy(), p.cpu().numpy()
+
+
+# ---------------------------------------------------------------------------------------------- vocab_topk
+@pytest.mark.gpu
+@pytest.mark.parametrize("Mr", [1, 37, 1000])
+@pytest.mark.parametrize("V", [24, 1001, 10000, 50000])
+@pytest.mark.parametrize("k", [1, 3, 8])
+def test_vocab_topk_against_float64(gpu, k, V, Mr):
+    """Exact logits: the ids equal the float64 top-k in the tie order (exact ties are frequent on these grids), probabilities within
+    1e-6 relative, two calls bit-identical; with k = 1 the ids and probabilities equal vocab_top1's."""
+    from image_captioning_amd import ops
+    K = 256
+    rng = np.random.default_rng(Mr * 7 + V + k)
+    X, W, b = _exact_operands(rng, Mr, K, V)
+    want_ids, want_p = _ref_topk(X, W, b, k)
+    ids, p = _topk(_dev(X), _dev(W), _dev(b), k)
+    assert ids.shape == (Mr, k) and p.shape == (Mr, k)
+    np.testing.assert_array_equal(ids, want_ids)
+    np.testing.assert_allclose(p, want_p, rtol=1e-6, atol=0)
+    ids2, p2 = _topk(_dev(X), _dev(W), _dev(b), k)
+    assert np.array_equal(ids, ids2) and np.array_equal(p.view(np.int32), p2.view(np.int32))
+    if k == 1:
+        probs = torch.empty((Mr,), dtype=torch.float32, device="cuda:0")
+        tok = ops.vocab_top1(_dev(X), _dev(W), _dev(b), probs=probs).cpu().numpy()
+        np.testing.assert_array_equal(ids[:, 0], tok)
+        np.testing.assert_array_equal(p[:, 0].view(np.int32), probs.cpu().numpy().view(np.int32))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("k", [3, 8])
+def test_vocab_topk_planted_ties(gpu, k):
+    """Duplicated columns give bit-identical logits: the lower index comes first, inside one 128-column tile and across tiles, and a
+    tie group longer than k is cut at k."""
+    K, Mr, V = 128, 70, 5000
+    rng = np.random.default_rng(3 + k)
+    X, W, b = _exact_operands(rng, Mr, K, V)
+    groups = ((5, 9, 4000), (131, 300, 4999, 17, 2600, 2601, 2602, 640, 641))
+    for g, bias in zip(groups, (8.0, 7.5)):
+        for c in g[1:]:
+            W[:, c] = W[:, g[0]]
+        b[list(g)] = bias
+    want_ids, want_p = _ref_topk(X, W, b, k)
+    ids, p = _topk(_dev(X), _dev(W), _dev(b), k)
+    np.testing.assert_array_equal(ids, want_ids)
+    np.testing.assert_allclose(p, want_p, rtol=1e-6)
+    assert set(ids[:, 0]) <= {5, 17}                    # a planted group leads every row, from its lowest index
+    assert np.all(np.diff(ids[ids[:, 0] == 17][:, :3], axis=1) > 0)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("V,ldw,k", [(3, 8, 3), (8, 12, 8), (1001, 1004, 5), (130, 132, 8)])
+def test_vocab_topk_ragged_v_in_place(gpu, V, ldw, k):
+    """V % 4 != 0 or a last column tile with fewer than k columns, handed to the kernel directly (a [K,ldw] buffer viewed as [K,V]): the
+    columns past V never enter the top k."""
+    K, Mr = 64, 45
+    rng = np.random.default_rng(V + k)
+    X, Wfull, _ = _exact_operands(rng, Mr, K, ldw)
+    _, _, b = _exact_operands(rng, 1, 32, V)
+    Wfull[:, V:] = 64.0                                 # columns past V would win every row
+    want_ids, want_p = _ref_topk(X, Wfull[:, :V], b, k)
+    Wd = _dev(Wfull)[:, :V]
+    assert Wd.stride(0) == ldw
+    ids, p = _topk(_dev(X), Wd, _dev(b), k)
+    np.testing.assert_array_equal(ids, want_ids)
+    np.testing.assert_allclose(p, want_p, rtol=1e-6)
+
+
+# ---------------------------------------------------------------------------------------------- models and float64 loops
+def _make_v2(V, inject, Tw, seed=0, scale=1.0):
+    """The v2 model on synthetic weights (as tests/test_gpu_models.make_v2), with the vocabulary kernel scaled by `scale` (more peaked
+    word distributions: clearer decisions for the comparisons below).  Returns (model, float64 weights)."""
+    from image_captioning_amd import synth
+    from image_captioning_amd.text_generation_model_v2 import DenseCapConfig, build_model
+    cfg = DenseCapConfig(V, synth.embedding_matrix(seed + 3, V))
+    cfg.PADDING_SIZE = Tw
+    model = build_model((7, 7, 256), (Tw,), cfg, 256, inject, seed=seed)
+    if scale != 1.0:
+        model.load_weights({'imgcap_d1/kernel': model.get_weights_dict()['imgcap_d1/kernel'] * np.float32(scale)})
+    return model, {k: v.astype(np.float64) for k, v in model.get_weights_dict().items()}
+
+
+def _feat(seed, R):
+    return np.random.default_rng(seed).standard_normal((R, 7, 7, 256)).astype(np.float32)
+
+
+def _oracle_greedy(Wt, feat, Tw, steps, inject, start=None):
+    """The test loop (start 0, M.v2_greedy_decode) or the eval loop (start = each RoI's first id) per RoI, batched over the RoIs (the
+    RoIs never meet: every row of v2_forward is its own RoI).  Returns ids [R,steps], the chosen words' probabilities, each step's top-two
+    relative gap and log(max p / p[0])."""
+    R = len(feat)
+    seqs = [[0 if start is None else int(start[r])] for r in range(R)]
+    chosen, gap, behind0 = (np.zeros((R, steps)) for _ in range(3))
+    for j in range(steps):
+        p, _ = M.v2_forward(Wt, feat, M.pad_sequences_pre(seqs, Tw), inject)
+        top2 = np.sort(p, 1)[:, -2:]
+        ids = p.argmax(1)
+        chosen[:, j], gap[:, j] = top2[:, 1], (top2[:, 1] - top2[:, 0]) / top2[:, 1]
+        behind0[:, j] = np.log(top2[:, 1]) - np.log(p[:, 0])
+        for r in range(R):
+            seqs[r].append(int(ids[r]))
+    return np.array(seqs, np.int32)[:, 1:], chosen, gap, behind0
+
+
+def _oracle_beam(Wt, feat, Tw, steps, k, inject, log, start=None):
+    """test.py's loop in float64, batched over the RoIs' beams: from one beam, every beam proposes its k most probable words, a
+    candidate scores score + p (or + log p), the k best survive.  Returns per RoI the k (sequence, score) best first, and the smallest
+    margin of any keep/drop decision (a word proposed or not within its beam, a candidate kept or dropped), in score units."""
+    f = np.log if log else (lambda x: x)
+    R = len(feat)
+    beams = [[([0 if start is None else int(start[r])], 0.0)] for r in range(R)]
+    margin = np.full(R, np.inf)
+    for _ in range(steps):
+        flat = [(r, b) for r in range(R) for b in range(len(beams[r]))]
+        p, _ = M.v2_forward(Wt, feat[[r for r, _ in flat]], M.pad_sequences_pre([beams[r][b][0] for r, b in flat], Tw), inject)
+        cands = [[] for _ in range(R)]
+        for (r, b), row in zip(flat, p):
+            order = np.argsort(-row, kind="stable")
+            margin[r] = min(margin[r], f(row[order[k - 1]]) - f(row[order[k]]))
+            seq, sc = beams[r][b]
+            cands[r] += [(sc + f(row[w]), b, int(w), seq + [int(w)]) for w in order[:k]]
+        for r in range(R):
+            c = sorted(cands[r], key=lambda x: (-x[0], x[1], x[2]))
+            if len(c) > k:
+                margin[r] = min(margin[r], c[k - 1][0] - c[k][0])
+            beams[r] = [(x[3], x[0]) for x in c[:k]]
+    return [[(np.array(s[1:], np.int32), sc) for s, sc in beams[r]] for r in range(R)], margin
+
+
+def _rescore(Wt, feat, Tw, tokens, inject, log, start=None):
+    """float64 score of given sequences tokens [R,k,steps]: the sum over steps of p (or log p) of each token after its prefix."""
+    f = np.log if log else (lambda x: x)
+    R, k, steps = tokens.shape
+    first = np.zeros(R, np.int64) if start is None else np.asarray(start)
+    seqs = [[int(first[r])] + tokens[r, b].tolist() for r in range(R) for b in range(k)]
+    feat_rk = np.repeat(feat, k, axis=0)
+    total = np.zeros(R * k)
+    for j in range(steps):
+        p, _ = M.v2_forward(Wt, feat_rk, M.pad_sequences_pre([s[:j + 1] for s in seqs], Tw), inject)
+        total += f(p[np.arange(R * k), [s[j + 1] for s in seqs]])
+    return total.reshape(R, k)
+
+
+# ---------------------------------------------------------------------------------------------- greedy
+@pytest.mark.gpu
+@pytest.mark.parametrize("inject", [True, False], ids=["inject", "merge"])
+@pytest.mark.parametrize("V", [1000, 10000])
+@pytest.mark.parametrize("R", [1, 37, 300])
+def test_decode_greedy_against_oracle(gpu, R, V, inject):
+    """ids equal to the float64 loop (checked against M.v2_greedy_decode itself on the first RoIs) wherever every oracle decision has a
+    top-two gap above 1e-5 relative -- more than 93 % of the RoIs (a closer call is inside fp32 rounding, and the caption diverges after
+    it); word scores within 1e-5 of the oracle's probabilities; ids equal to greedy_decode's (generate('prefix')).  Both
+    at the default steps = Tw - 1 and at steps = Tw."""
+    Tw = 10
+    model, Wt = _make_v2(V, inject, Tw, seed=7 + R, scale=4.0)
+    feat = _feat(8 + R, R)
+    want_ids, want_p, gap, _ = _oracle_greedy(Wt, feat, Tw, Tw, inject)
+    if inject:
+        for r in range(min(R, 2)):
+            np.testing.assert_array_equal(want_ids[r, :Tw - 1], M.v2_greedy_decode(Wt, feat[r], Tw, Tw - 1)[0])
+    sure = (gap > 1e-5).all(1)
+    assert sure.all() if R == 1 else sure.mean() > 0.93
+    for steps in (None, Tw):
+        n = Tw - 1 if steps is None else steps
+        ids, scores = model.decode_greedy(feat, steps)
+        assert ids.is_cuda and ids.dtype == torch.int32 and scores.dtype == torch.float32 and tuple(ids.shape) == (R, n)
+        ids, scores = ids.cpu().numpy(), scores.cpu().numpy()
+        np.testing.assert_array_equal(ids[sure], want_ids[sure, :n])
+        assert np.abs(scores[sure] - want_p[sure, :n]).max() < 1e-5
+        g_ids, g_scores = model.generate(feat, steps, decoder="incremental")
+        np.testing.assert_array_equal(g_ids, ids)
+        np.testing.assert_array_equal(g_scores.view(np.int32), scores.view(np.int32))
+        p_ids, p_scores = model.generate(feat, steps, decoder="prefix")
+        np.testing.assert_array_equal(ids[sure], p_ids[sure])
+        assert np.abs(scores[sure] - p_scores[sure]).max() < 1e-5
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("inject", [True, False], ids=["inject", "merge"])
+def test_decode_greedy_start_ids_match_the_eval_loop(gpu, inject):
+    """start_ids reproduce the eval loop, which feeds each caption's first id first (RoIs with start 0 included)."""
+    V, Tw, R = 1000, 10, 40
+    model, Wt = _make_v2(V, inject, Tw, seed=21, scale=4.0)
+    feat = _feat(22, R)
+    start = np.random.default_rng(23).integers(1, V, R).astype(np.int32)
+    start[::7] = 0
+    want_ids, want_p, gap, _ = _oracle_greedy(Wt, feat, Tw, Tw - 1, inject, start)
+    sure = (gap > 1e-5).all(1)
+    assert sure.all()
+    ids, scores = model.generate(feat, decoder="incremental", start_ids=start)
+    np.testing.assert_array_equal(ids, want_ids)
+    assert np.abs(scores - want_p).max() < 1e-5
+    ids_t, _ = model.decode_greedy(feat, start_ids=_dev(start, torch.int32))
+    np.testing.assert_array_equal(ids_t.cpu().numpy(), ids)
+    plain, _ = model.generate(feat, decoder="incremental")
+    assert not np.array_equal(plain[start != 0], ids[start != 0])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("inject", [True, False], ids=["inject", "merge"])
+def test_decode_greedy_mask_carry_through_mid_caption_zeros(gpu, inject):
+    """imgcap_d1/bias[0] raised so that some RoIs pick 0 after a non-zero word: a chosen 0 is masked (the state carries over it), so those
+    RoIs repeat 0 with bit-identical scores, and the ids match the prefix path's (which pads with the same zeros)."""
+    V, Tw, R = 1000, 10, 40
+    model, Wt = _make_v2(V, inject, Tw, seed=31)
+    feat = _feat(32, R)
+    _, _, _, behind0 = _oracle_greedy(Wt, feat, Tw, Tw - 1, inject)
+    later = behind0[:, 1:].min(1)
+    order = np.argsort(later - behind0[:, 0])
+    delta = 0.5 * (behind0[order[0], 0] + later[order[0]])
+    assert behind0[order[0], 0] - later[order[0]] > 1e-2
+    bias = model.get_weights_dict()['imgcap_d1/bias'].copy()
+    bias[0] += np.float32(delta)
+    model.load_weights({'imgcap_d1/bias': bias})
+    Wt['imgcap_d1/bias'] = bias.astype(np.float64)
+    ids, scores = model.generate(feat, decoder="incremental")
+    p_ids, p_scores = model.generate(feat, decoder="prefix")
+    want_ids, want_p, gap, _ = _oracle_greedy(Wt, feat, Tw, Tw - 1, inject)
+    sure = (gap > 1e-5).all(1)
+    assert sure.mean() > 0.9
+    np.testing.assert_array_equal(ids[sure], want_ids[sure])
+    np.testing.assert_array_equal(ids[sure], p_ids[sure])
+    assert np.abs(scores[sure] - p_scores[sure]).max() < 1e-5
+    mid = [r for r in range(R) if ids[r, 0] != 0 and (ids[r] == 0).any()]
+    assert mid, "no RoI picks 0 in mid-caption"
+    for r in range(R):
+        z = np.flatnonzero(ids[r] == 0)
+        if z.size:
+            j = z[0]
+            assert np.all(ids[r, j:] == 0) and np.all(scores[r, j:].view(np.int32) == scores[r, j].view(np.int32)), (r, ids[r], scores[r])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("inject", [True, False], ids=["inject", "merge"])
+def test_decode_is_independent_of_the_batch(gpu, inject):
+    """A RoI decoded alone gives the ids it gets inside a batch of 300 (greedy and beam)."""
+    V, Tw, R = 1000, 10, 300
+    model, Wt = _make_v2(V, inject, Tw, seed=41, scale=4.0)
+    feat = _feat(42, R)
+    ids, _ = model.generate(feat, decoder="incremental")
+    toks, _ = model.generate(feat, decoder="beam", beam_size=3)
+    for r in (0, 1, 150, 299):
+        one, _ = model.generate(feat[r:r + 1], decoder="incremental")
+        np.testing.assert_array_equal(one[0], ids[r])
+        one_b, _ = model.generate(feat[r:r + 1], decoder="beam", beam_size=3)
+        np.testing.assert_array_equal(one_b[0], toks[r])
+
+
+# ---------------------------------------------------------------------------------------------- beam search
+@pytest.mark.gpu
+@pytest.mark.parametrize("inject", [True, False], ids=["inject", "merge"])
+def test_beam_size_1_is_greedy(gpu, inject):
+    V, Tw, R = 1000, 10, 37
+    model, _ = _make_v2(V, inject, Tw, seed=51)
+    feat = _feat(52, R)
+    ids, scores = model.generate(feat, decoder="incremental")
+    toks, bsc = model.generate(feat, decoder="beam", beam_size=1)
+    assert toks.shape == (R, 1, Tw - 1) and bsc.shape == (R, 1)
+    np.testing.assert_array_equal(toks[:, 0], ids)
+    np.testing.assert_allclose(bsc[:, 0], scores.astype(np.float64).sum(1), rtol=0, atol=1e-6)
+    toks, bsc = model.generate(feat, decoder="beam", beam_size=1, score="logprob")
+    np.testing.assert_array_equal(toks[:, 0], ids)
+    np.testing.assert_allclose(bsc[:, 0], np.log(scores.astype(np.float64)).sum(1), rtol=1e-6)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("inject", [True, False], ids=["inject", "merge"])
+@pytest.mark.parametrize("score", ["prob", "logprob"])
+@pytest.mark.parametrize("k", [2, 3, 5])
+def test_decode_beam_against_float64_beam_loop(gpu, k, score, inject):
+    """Every returned score equals the float64 re-score of its sequence within 1e-5 (relative to max(1, |score|): a sum of log p carries
+    the fp32 rounding of logits of magnitude ~10 as an absolute error of ~1e-5 at scores near -10), the scores are ordered best first,
+    the best is no worse than the oracle's best; on RoIs where every oracle keep/drop decision has a margin above 1e-5 (at least 80 %)
+    the sequences and their order are the oracle's."""
+    V, Tw, R = 1000, 5, 32
+    log = score == "logprob"
+    model, Wt = _make_v2(V, inject, Tw, seed=61, scale=25.0 if inject else 6.0)
+    feat = _feat(62, R)
+    start = np.random.default_rng(63).integers(0, V, R).astype(np.int32) if k == 3 else None
+    toks_d, sc_d = model.decode_beam(feat, k, start_ids=None if start is None else start, score=score)
+    assert toks_d.is_cuda and toks_d.dtype == torch.int32 and sc_d.dtype == torch.float32
+    toks, sc = model.generate(feat, decoder="beam", beam_size=k, start_ids=start, score=score)
+    np.testing.assert_array_equal(toks, toks_d.cpu().numpy())
+    assert toks.shape == (R, k, Tw - 1) and sc.shape == (R, k)
+    want, margin = _oracle_beam(Wt, feat, Tw, Tw - 1, k, inject, log, start)
+    re = _rescore(Wt, feat, Tw, toks, inject, log, start)
+    tol = 1e-5 * np.maximum(1.0, np.abs(re))
+    assert np.all(np.abs(sc - re) < tol), np.abs(sc - re).max()
+    assert np.all(np.diff(sc, axis=1) <= 0)
+    best = np.array([w[0][1] for w in want])
+    assert np.all(re[:, 0] >= best - tol[:, 0])
+    sure = margin > 1e-5
+    assert sure.mean() >= 0.8, sure.mean()
+    for r in np.flatnonzero(sure):
+        np.testing.assert_array_equal(toks[r], np.stack([s for s, _ in want[r]]))
+        assert np.all(np.abs(sc[r] - [x for _, x in want[r]]) < tol[r])
+
+
+@pytest.mark.gpu
+def test_beam_select_and_backtrace_kernels(gpu):
+    """ops.beam_select on planted candidates: the tie rule (score, then parent, then word id), the first step's single beam, the gathered
+    h / c rows and mask; ops.beam_backtrace over a two-step history."""
+    from image_captioning_amd import ops
+    R, k, U, steps = 3, 2, 8, 2
+    cid = np.array([[5, 6], [7, 8], [9, 4], [3, 2], [1, 0], [0, 11]], np.int32)          # rows b * R + r
+    cp = np.array([[.5, .25], [.4, .3], [.6, .1], [.5, .125], [.4, .3], [.6, .4]], np.float32)
+    h = np.arange(k * R * U, dtype=np.float32).reshape(k * R, U)
+    par, hist = (torch.full((steps, R, k), -1, dtype=torch.int32, device="cuda:0") for _ in range(2))
+    s0, s1 = (torch.zeros((R, k), device="cuda:0") for _ in range(2))
+    tok = torch.empty((k * R,), dtype=torch.int32, device="cuda:0")
+    mask = torch.empty((k * R,), dtype=torch.uint8, device="cuda:0")
+    ho, co = torch.zeros((k * R, U), device="cuda:0"), torch.zeros((k * R, U), device="cuda:0")
+    ops.beam_select(_dev(cid, torch.int32), _dev(cp), None, s0, par, hist, 0, 1, tokens=tok, mask=mask, h_in=_dev(h), c_in=_dev(-h),
+                    h_out=ho, c_out=co)
+    np.testing.assert_array_equal(s0.cpu().numpy(), cp[:R])                           # one beam: its two proposals, in order
+    np.testing.assert_array_equal(par[0].cpu().numpy(), np.zeros((R, k)))
+    np.testing.assert_array_equal(hist[0].cpu().numpy(), cid[:R])
+    np.testing.assert_array_equal(ho.cpu().numpy(), h[np.tile(np.arange(R), k)])
+    np.testing.assert_array_equal(co.cpu().numpy(), -h[np.tile(np.arange(R), k)])
+    sin = np.array([[0., .25], [0., .0], [0., 0.]], np.float32)
+    ops.beam_select(_dev(cid, torch.int32), _dev(cp), _dev(sin), s1, par, hist, 1, k, tokens=tok, mask=mask)
+    # RoI 0: (b0: 5 .5, 6 .25; b1: 3 .75, 2 .375) -> 3 .75, 5 .5;  RoI 1: (b0: 7 .4, 8 .3; b1: 1 .4, 0 .3) -> tie .4: parent 0 first
+    # RoI 2: (b0: 9 .6, 4 .1; b1: 0 .6, 11 .4) -> tie .6 -> parent 0 (9), then parent 1 (0)
+    np.testing.assert_allclose(s1.cpu().numpy(), [[.75, .5], [.4, .4], [.6, .6]])
+    np.testing.assert_array_equal(par[1].cpu().numpy(), [[1, 0], [0, 1], [0, 1]])
+    np.testing.assert_array_equal(hist[1].cpu().numpy(), [[3, 5], [7, 1], [9, 0]])
+    np.testing.assert_array_equal(tok.cpu().numpy(), [3, 7, 9, 5, 1, 0])
+    np.testing.assert_array_equal(mask.cpu().numpy(), [1, 1, 1, 1, 1, 0])
+    seq = ops.beam_backtrace(par, hist).cpu().numpy()
+    h0 = cid[:R]
+    np.testing.assert_array_equal(seq, [[[h0[0, 1], 3], [h0[0, 0], 5]], [[h0[1, 0], 7], [h0[1, 1], 1]], [[h0[2, 0], 9], [h0[2, 1], 0]]])
+
+
+# ---------------------------------------------------------------------------------------------- no host sync, edge cases
+@pytest.mark.gpu
+@pytest.mark.parametrize("inject", [True, False], ids=["inject", "merge"])
+def test_device_decoders_never_sync_with_the_host(gpu, monkeypatch, inject):
+    model, _ = _make_v2(1000, inject, 8, seed=71)
+    feat = torch.tensor(_feat(72, 5), device="cuda:0")
+    model.decode_greedy(feat)                              # warm: buffers and workspaces
+    model.decode_beam(feat, 3)
+    calls = []
+    for name in ("cpu", "item", "numpy", "tolist"):
+        orig = getattr(torch.Tensor, name)
+        monkeypatch.setattr(torch.Tensor, name, (lambda o, n: lambda self, *a, **k: (calls.append(n), o(self, *a, **k))[1])(orig, name))
+    ids, scores = model.decode_greedy(feat)
+    toks, bsc = model.decode_beam(feat, 3, score="logprob")
+    monkeypatch.undo()
+    assert calls == []
+    assert ids.is_cuda and scores.is_cuda and tuple(ids.shape) == (5, 7) and tuple(scores.shape) == (5, 7)
+    assert toks.is_cuda and bsc.is_cuda and tuple(toks.shape) == (5, 3, 7) and tuple(bsc.shape) == (5, 3)
+    want_ids, _ = model.generate(feat, decoder="incremental")
+    np.testing.assert_array_equal(ids.cpu().numpy(), want_ids)
+
+
+@pytest.mark.gpu
+def test_decoder_edge_cases(gpu):
+    model, _ = _make_v2(1000, True, 6, seed=81)
+    empty = np.zeros((0, 7, 7, 256), np.float32)
+    ids, sc = model.generate(empty, decoder="incremental")
+    assert ids.shape == (0, 5) and sc.shape == (0, 5)
+    toks, bsc = model.generate(empty, decoder="beam", beam_size=4)
+    assert toks.shape == (0, 4, 5) and bsc.shape == (0, 4)
+    feat = _feat(82, 3)
+    with pytest.raises(ValueError, match="steps"):
+        model.decode_greedy(feat, steps=7)
+    with pytest.raises(ValueError, match="steps"):
+        model.decode_beam(feat, 2, steps=7)
+    ids, _ = model.generate(feat, steps=7, decoder="prefix")           # the prefix path keeps accepting steps > Tw
+    assert ids.shape == (3, 7)
+    with pytest.raises(ValueError, match="beam_size"):
+        model.decode_beam(feat, 9)
+    with pytest.raises(ValueError, match="start_ids"):
+        model.decode_greedy(feat, start_ids=[1, 2])
+    small, _ = _make_v2(4, True, 6, seed=83)
+    with pytest.raises(ValueError, match="vocabulary"):
+        small.decode_beam(feat, 5)
+    toks, _ = small.generate(feat, decoder="beam", beam_size=4)
+    assert toks.shape == (3, 4, 5) and toks.min() >= 0 and toks.max() < 4
+
+
+# ---------------------------------------------------------------------------------------------- CPU
+def test_check_decoder_rules():
+    from image_captioning_amd.text_generation_model_v2 import CaptionModelV2
+    for dec in ("prefix", "incremental"):
+        CaptionModelV2.check_decoder(dec)
+    CaptionModelV2.check_decoder("incremental", start_ids=[1])
+    for k in range(1, 9):
+        CaptionModelV2.check_decoder("beam", k, score="logprob")
+    with pytest.raises(ValueError, match="decoder"):
+        CaptionModelV2.check_decoder("sample")
+    for k in (None, 0, 9, 2.5, True):
+        with pytest.raises(ValueError, match="beam_size"):
+            CaptionModelV2.check_decoder("beam", k)
+    for dec in ("prefix", "incremental"):
+        with pytest.raises(ValueError, match="beam_size"):
+            CaptionModelV2.check_decoder(dec, 3)
+    with pytest.raises(ValueError, match="start_ids"):
+        CaptionModelV2.check_decoder("prefix", start_ids=[1])
+    with pytest.raises(ValueError, match="score"):
+        CaptionModelV2.check_decoder("beam", 2, score="lengthnorm")
+
+
+def test_generate_refuses_bad_arguments_before_touching_the_gpu():
+    from image_captioning_amd.text_generation_model_v2 import CaptionModelV2
+    stub = object.__new__(CaptionModelV2)
+    feat = np.zeros((2, 7, 7, 256), np.float32)
+    for kw in (dict(decoder="greedy"), dict(decoder="beam"), dict(decoder="beam", beam_size=9), dict(decoder="incremental", beam_size=2),
+               dict(decoder="prefix", start_ids=[1, 2]), dict(decoder="beam", beam_size=2, score="p")):
+        with pytest.raises(ValueError):
+            CaptionModelV2.generate(stub, feat, **kw)
+    with pytest.raises(ValueError, match="beam_size"):
+        CaptionModelV2.decode_beam(stub, feat, 0)
+
+
+def test_beam_ops_refuse_cpu_tensors():
+    from image_captioning_amd import ops, _lib
+    with pytest.raises(_lib.DcapError):
+        ops.vocab_topk(torch.zeros(4, 32), torch.zeros(32, 8), torch.zeros(8), 3)
+    i = torch.zeros((2, 1, 2), dtype=torch.int32)
+    with pytest.raises(_lib.DcapError):
+        ops.beam_backtrace(i, i)
+    with pytest.raises(_lib.DcapError):
+        ops.beam_select(torch.zeros((2, 2), dtype=torch.int32), torch.zeros(2, 2), None, torch.zeros(1, 2), i, i, 0, 1)
