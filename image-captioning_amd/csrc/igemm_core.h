@@ -592,6 +592,22 @@ constexpr size_t igemm_lds_bytes() {
 // ------------------------------------------------------------------------------------------------
 // Tile epilogue shared by the f32 and the split-bf16 main loops.
 // ------------------------------------------------------------------------------------------------
+// Writes a wave's TM x TN 32x32 accumulator blocks (MFMA layout, wave origin wm, wn inside the tile) into the row-major tile image Cs
+// (row pitch LDC floats), then waits for the block: afterwards any thread may read any element of the tile.  Callers are past the
+// main loop's final barrier, so the LDS is free.
+template <int TM, int TN, int LDC>
+__device__ __forceinline__ void stage_acc_tile(f32x16 (&acc)[TM][TN], float* Cs, int wm, int wn) {
+    const int lane = threadIdx.x & 63, i = lane & 31, h = lane >> 5;
+#pragma unroll
+    for (int tm = 0; tm < TM; ++tm)
+#pragma unroll
+        for (int tn = 0; tn < TN; ++tn)
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+                Cs[(wm + tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * h) * LDC + wn + tn * 32 + i] = acc[tm][tn][r];
+    __syncthreads();
+}
+
 // TM x TN = 32x32 accumulator blocks per wave (wave origin wm, wn inside the tile); NT = threads taking part (waves 0..NT/64-1).
 template <int BM, int BN, int TM = BM / 64, int TN = BN / 64, int NT = 256>
 __device__ __forceinline__ void store_tile(f32x16 (&acc)[TM][TN], float* smem, const Epilogue& ep, float* __restrict__ partial,
@@ -621,6 +637,8 @@ __device__ __forceinline__ void store_tile(f32x16 (&acc)[TM][TN], float* smem, c
     };
     prefetch(0);                                         // in flight while the tile goes through LDS
     float* Cs = smem;                       // all waves are past the loop's final barrier: LDS is free
+    // stage_acc_tile<TM, TN, LDC>, written out: through the helper the compiler orders the zero moves of the shift operand differently
+    // in every store_tile kernel (same instructions, other order), so the generic epilogue keeps its own copy
     {
         const int i = lane & 31, h = lane >> 5;
 #pragma unroll

@@ -81,17 +81,8 @@ __device__ __forceinline__ float half_sum(float v) {
 template <int MODE>
 __device__ __forceinline__ void ce_epilogue(f32x16 (&acc)[2][2], float* Cs, const CeArgs& ce, int m0, int n0, int wm, int wn, int tile_m, int tile_n) {
     constexpr int LDC = 128 + 4;
-    const int tid = threadIdx.x, lane = tid & 63;
-    {
-        const int i = lane & 31, h = lane >> 5;
-#pragma unroll
-        for (int tm = 0; tm < 2; ++tm)
-#pragma unroll
-            for (int tn = 0; tn < 2; ++tn)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) Cs[(wm + tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * h) * LDC + wn + tn * 32 + i] = acc[tm][tn][r];
-    }
-    __syncthreads();
+    const int tid = threadIdx.x;
+    stage_acc_tile<2, 2, LDC>(acc, Cs, wm, wn);
     const int c4 = tid & 31, rp = tid >> 5;                    // 32 lanes x 4 columns per row, 8 rows per pass
     const int col = n0 + 4 * c4;
     float4 b4 = make_float4(0.f, 0.f, 0.f, 0.f);

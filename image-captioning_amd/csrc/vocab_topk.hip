@@ -1,16 +1,22 @@
-// vocab_topk.hip -- beam-search decoding on the device:
+// vocab_topk.hip -- greedy and beam-search decoding on the device:
+//   dc_vocab_top1_f32   the vocabulary projection FUSED with the row top-1 (greedy decoding): the next token, its softmax probability
+//                       and the mask byte;
 //   dc_vocab_topk_f32   the vocabulary projection FUSED with the row top-k (k <= 8) and the softmax probabilities of those k words;
 //   dc_beam_select_f32  per RoI, the k best of the k live beams' k proposals each (score + p or score + log p), with the parents'
 //                       word-LSTM rows gathered into the next state buffers;
 //   dc_beam_backtrace   the [steps,R,k] parent / token history -> [R,k,steps] sequences.
 //
-// Replaces the reference's beam loop (image captioning/test.py:23-64: per beam a full model.predict on the pre-padded prefix, a host
-// argsort of the [V] probability row, a host sort of the k*k candidates) for the v2 decoders (text_generation_model_v2.py:140-166).
-// dc_vocab_topk_f32 is dc_vocab_top1_f32 (vocab_top1.hip) with a wider epilogue: the same fp32 MFMA main loop (128 x 128 tiles, row
-// tiles fastest, xcd_remap), and per (row, 128-column tile) the max, the sum of exp(z - max) and the tile's k best (value, column)
-// pairs -- found in k threshold rounds of the 32-lane shuffle reduction of top1_epilogue, each round taking the best pair that comes
-// after the previous round's winner in the order (value descending, column ascending), so no per-lane lists are needed.  A row kernel
-// (one wave per row) runs the same rounds over the row's tiles_n * k candidates.  The [M,V] logits are never written.
+// Replaces, per decoded token, Dense(V, activation='softmax') + tf.argmax + the chosen word's probability of the reference's
+// ROICaptionInferenceLayer (dense_img_cap_separate_models/text_generation_model.py:192-232; dense_img_cap/dense_model.py:820), and
+// the reference's beam loop (image captioning/test.py:23-64: per beam a full model.predict on the pre-padded prefix, a host argsort of
+// the [V] probability row, a host sort of the k*k candidates) for the v2 decoders (text_generation_model_v2.py:140-166).
+// Both vocabulary entry points run one kernel pair; top-1 is top-k at k = 1.  The fp32 MFMA main loop of dc_vocab_ce (igemm_core.h,
+// 128 x 128 tiles, row tiles fastest, xcd_remap) runs ONCE over the output tiles, and each tile ends in a reduction epilogue while it
+// sits in LDS: per (row, 128-column tile) the max, the sum of exp(z - max) and the tile's k best (value, column) pairs -- found in k
+// threshold rounds of a 32-lane shuffle reduction, each round taking the best pair that comes after the previous round's winner in
+// the order (value descending, column ascending), so no per-lane lists are needed.  A row kernel (one wave per row) runs the same
+// rounds over the row's tiles_n * k candidates in an order that does not depend on M.  The [M,V] logits are never written.  No
+// persistent grid, no cross-block spin: an ordinary grid plus one combine launch.
 #include "igemm_core.h"
 #include <algorithm>
 #include <climits>
@@ -22,8 +28,7 @@ constexpr int TK_MAX = 8;
 struct TopkArgs {
     int M, V, tiles_m, tiles_n, k;
     const float* bias;                   // [V] or null
-    float2* ms;                          // [M][tiles_n]: max, sum exp
-    float2* cand;                        // [M][tiles_n][k]: value, column (int bits); column INT_MAX = none
+    float2* cells;                       // [M][tiles_n][1 + k]: (max, sum exp), then k (value, column (int bits)); column INT_MAX = none
 };
 
 // (v, c) comes strictly after (tv, tc) in the order value descending, column ascending.  NaN never does.
@@ -31,24 +36,16 @@ __device__ __forceinline__ bool tk_after(float v, int c, float tv, int tc) {
     return v < tv || (v == tv && c > tc);
 }
 
-// the better of two (value, column) pairs: the larger value, the lower column on equal values (vocab_top1.hip's top1_take)
+// the better of two (value, column) pairs: the larger value, the lower column on equal values.  -inf / NaN columns never win against
+// a finite logit (NaN compares false both ways).
 __device__ __forceinline__ void tk_take(float& m, int& i, float om, int oi) {
     if (om > m || (om == m && oi < i)) { m = om; i = oi; }
 }
 
 __device__ __forceinline__ void topk_epilogue(f32x16 (&acc)[2][2], float* Cs, const TopkArgs& ta, int m0, int n0, int wm, int wn, int tile_n) {
     constexpr int LDC = 128 + 4;
-    const int tid = threadIdx.x, lane = tid & 63;
-    {
-        const int i = lane & 31, h = lane >> 5;
-#pragma unroll
-        for (int tm = 0; tm < 2; ++tm)
-#pragma unroll
-            for (int tn = 0; tn < 2; ++tn)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) Cs[(wm + tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * h) * LDC + wn + tn * 32 + i] = acc[tm][tn][r];
-    }
-    __syncthreads();
+    const int tid = threadIdx.x;
+    stage_acc_tile<2, 2, LDC>(acc, Cs, wm, wn);
     const int c4 = tid & 31, rp = tid >> 5;                    // 32 lanes x 4 columns per row, 8 rows per pass
     const int col = n0 + 4 * c4;
     float4 b4 = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -63,7 +60,7 @@ __device__ __forceinline__ void topk_epilogue(f32x16 (&acc)[2][2], float* Cs, co
         const int lr = p * 8 + rp, row = m0 + lr;
         float4 z = *reinterpret_cast<const float4*>(&Cs[lr * LDC + 4 * c4]);
         z.x += b4.x; z.y += b4.y; z.z += b4.z; z.w += b4.w;
-        float2* out = ta.cand + ((long)row * ta.tiles_n + tile_n) * ta.k;
+        float2* out = ta.cells + ((long)row * ta.tiles_n + tile_n) * (ta.k + 1);
         float tv = INFINITY, mx = -INFINITY;
         int tc = INT_MIN;
         for (int r = 0; r < ta.k; ++r) {                       // round r: the tile's (r+1)-th best pair
@@ -80,19 +77,20 @@ __device__ __forceinline__ void topk_epilogue(f32x16 (&acc)[2][2], float* Cs, co
                 tk_take(bm, bi, om, oi);
             }
             if (r == 0) mx = bm;
-            if (row < ta.M && c4 == 0) out[r] = make_float2(bm, __int_as_float(bi));
+            if (row < ta.M && c4 == 0) out[1 + r] = make_float2(bm, __int_as_float(bi));
             tv = bm; tc = bi;                                  // (no pair left: (-inf, INT_MAX), after which nothing comes)
         }
         float s = (v0 ? expf(z.x - mx) : 0.f) + (v1 ? expf(z.y - mx) : 0.f) + (v2 ? expf(z.z - mx) : 0.f) + (v3 ? expf(z.w - mx) : 0.f);
 #pragma unroll
         for (int o = 16; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-        if (row < ta.M && c4 == 0) ta.ms[(long)row * ta.tiles_n + tile_n] = make_float2(mx, s);
+        if (row < ta.M && c4 == 0) out[0] = make_float2(mx, s);
     }
 }
 
 using TKA = DenseKCT<true>;
 using TKB = DenseMCT<true>;
 
+// Row tiles fastest: the tiles_m blocks that share a column panel of W run side by side, so W streams from HBM about once.
 __global__ __launch_bounds__(256, 2) void vocab_topk_f32_kernel(TKA al, TKB bl, TopkArgs ta, int K) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int wave = threadIdx.x >> 6;
@@ -105,50 +103,57 @@ __global__ __launch_bounds__(256, 2) void vocab_topk_f32_kernel(TKA al, TKB bl, 
     topk_epilogue(acc, smem, ta, m0, n0, wm, wn, tile_n);
 }
 
-// One wave per row.  m = max_j m_j and s = sum_j s_j exp(m_j - m) as in vocab_top1_rows_kernel (lane-strided over j, then a fixed xor
-// tree); then k threshold rounds over the tiles_n * k candidates, each a lane-strided scan + a 64-lane xor reduction.  The top k of a
-// strict total order does not depend on the scan order, and s is summed in an order fixed by tiles_n alone: the result is the same at
-// every M.  p_r = exp(z_r - m) / s.
-__global__ __launch_bounds__(256) void vocab_topk_rows_kernel(int M, int tiles_n, int k, const float2* __restrict__ ms,
-                                                              const float2* __restrict__ cand, int32_t* __restrict__ ids,
-                                                              float* __restrict__ probs) {
+// One wave per row.  k threshold rounds over the tiles_n * k candidates, each a scan strided over the tiles (a lane takes all k
+// candidates of its tiles) + a 64-lane xor reduction; lane r keeps round r's winner (z_r, id_r), and round 0's value is the row
+// maximum m (every tile's maximum is among its candidates).  Then s = sum_j s_j exp(m_j - m) (lane-strided over j, then a fixed xor
+// tree).  The top k of a strict total order does not depend on the scan order, and s is summed in an order fixed by tiles_n alone:
+// the result is the same at every M.
+// Lane r < k writes ids[row * ld_ids + r] and probs[row * ld_probs + r] = exp(z_r - m) / s (either may be null).  A top-1 call
+// (dc_vocab_top1_f32: k = 1, tokens given) also writes tokens[row] and the optional mask[row] = id != 0, and its probability is
+// 1 / s: the same value (z_0 = m), and also what it reports for a row without an orderable logit.
+__global__ __launch_bounds__(256) void vocab_topk_rows_kernel(int M, int tiles_n, int k, const float2* __restrict__ cells,
+                                                              int32_t* __restrict__ ids, long ld_ids,
+                                                              float* __restrict__ probs, long ld_probs, int32_t* __restrict__ tokens,
+                                                              uint8_t* __restrict__ mask) {
     const int row = (blockIdx.x * 256 + threadIdx.x) >> 6, lane = threadIdx.x & 63;
     if (row >= M) return;
-    const float2* st = ms + (long)row * tiles_n;
-    float m = -INFINITY;
-    for (int j = lane; j < tiles_n; j += 64) m = fmaxf(m, st[j].x);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-    float s = 0.f;
-    for (int j = lane; j < tiles_n; j += 64) {
-        const float2 q = st[j];
-        s += q.y * expf(q.x - m);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    const float2* cd = cand + (long)row * tiles_n * k;
-    const int n = tiles_n * k;
-    float tv = INFINITY;
-    int tc = INT_MIN;
+    const float2* cl = cells + (long)row * tiles_n * (k + 1);
+    float tv = INFINITY, m = -INFINITY, z = -INFINITY;
+    int tc = INT_MIN, id = INT_MAX;
     for (int r = 0; r < k; ++r) {
         float bm = -INFINITY;
         int bi = INT_MAX;
-        for (int j = lane; j < n; j += 64) {
-            const float2 q = cd[j];
-            const int c = __float_as_int(q.y);
-            if (c != INT_MAX && tk_after(q.x, c, tv, tc)) tk_take(bm, bi, q.x, c);
-        }
+        for (int j = lane; j < tiles_n; j += 64)
+            for (int i = 1; i <= k; ++i) {
+                const float2 q = cl[j * (k + 1) + i];
+                const int c = __float_as_int(q.y);
+                if (c != INT_MAX && tk_after(q.x, c, tv, tc)) tk_take(bm, bi, q.x, c);
+            }
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
             const float om = __shfl_xor(bm, o, 64);
             const int oi = __shfl_xor(bi, o, 64);
             tk_take(bm, bi, om, oi);
         }
-        if (lane == 0) {
-            ids[(long)row * k + r] = bi == INT_MAX ? 0 : bi;   // (a row with fewer than k finite logits: tf.argmax's first column)
-            probs[(long)row * k + r] = bi == INT_MAX ? 0.f : expf(bm - m) / s;
-        }
-        tv = bm; tc = bi;
+        if (r == 0) m = bm;
+        if (lane == r) { z = bm; id = bi; }
+        tv = bm; tc = bi;                                      // (no pair left: (-inf, INT_MAX), after which nothing comes)
+    }
+    float s = 0.f;
+    for (int j = lane; j < tiles_n; j += 64) {
+        const float2 q = cl[j * (k + 1)];
+        s += q.y * expf(q.x - m);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    if (lane >= k) return;
+    const bool none = id == INT_MAX;                           // (a row with fewer than k orderable logits: tf.argmax's first column)
+    if (none) id = 0;
+    if (ids) ids[row * ld_ids + lane] = id;
+    if (probs) probs[row * ld_probs + lane] = tokens ? 1.f / s : (none ? 0.f : expf(z - m) / s);
+    if (tokens) {
+        tokens[row] = id;
+        if (mask) mask[row] = id != 0 ? 1 : 0;
     }
 }
 
@@ -225,16 +230,13 @@ __global__ __launch_bounds__(256) void beam_backtrace_kernel(const int32_t* __re
 
 static size_t tk_align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
-static int topk_validate(const dc_vocab_topk_desc* d) {
-    DC_REQUIRE(d != nullptr, DC_EINVAL, "dc_vocab_topk: null descriptor");
-    DC_REQUIRE(d->M > 0 && d->V > 0 && d->K > 0 && d->X && d->W && d->ids && d->probs, DC_EINVAL, "dc_vocab_topk: bad arguments");
-    DC_REQUIRE(d->k >= 1 && d->k <= TK_MAX && d->V >= d->k, DC_EINVAL, "dc_vocab_topk: need 1 <= k <= 8 and V >= k (k = %d, V = %d)", d->k, d->V);
-    DC_REQUIRE((d->K & 31) == 0 && (d->ldx & 3) == 0 && (d->ldw & 3) == 0, DC_EALIGN,
-               "dc_vocab_topk: K must be a multiple of 32 and ldx, ldw multiples of 4");
-    DC_REQUIRE(d->ldx >= d->K && d->ldw >= (d->V + 3) / 4 * 4, DC_EINVAL, "dc_vocab_topk: ldx < K or ldw < V rounded up to 4");
-    DC_REQUIRE(aligned16(d->X) && aligned16(d->W) && (!d->bias || aligned16(d->bias)), DC_EALIGN, "dc_vocab_topk: X, W, bias must be 16-byte aligned");
-    DC_REQUIRE((size_t)d->M * d->ldx * 4 < (size_t)0xFFFFFFF0u && (size_t)d->K * d->ldw * 4 < (size_t)0xFFFFFFF0u, DC_EINVAL,
-               "dc_vocab_topk: operands must span < 4 GiB");
+// The operand checks of both vocabulary entry points; fn names the entry point in the messages.
+static int vocab_f32_validate(const char* fn, const dc_vocab_topk_desc& d) {
+    DC_REQUIRE((d.K & 31) == 0 && (d.ldx & 3) == 0 && (d.ldw & 3) == 0, DC_EALIGN, "%s: K must be a multiple of 32 and ldx, ldw multiples of 4", fn);
+    DC_REQUIRE(d.ldx >= d.K && d.ldw >= (d.V + 3) / 4 * 4, DC_EINVAL, "%s: ldx < K or ldw < V rounded up to 4", fn);
+    DC_REQUIRE(aligned16(d.X) && aligned16(d.W) && (!d.bias || aligned16(d.bias)), DC_EALIGN, "%s: X, W, bias must be 16-byte aligned", fn);
+    DC_REQUIRE((size_t)d.M * d.ldx * 4 < (size_t)0xFFFFFFF0u && (size_t)d.K * d.ldw * 4 < (size_t)0xFFFFFFF0u, DC_EINVAL,
+               "%s: operands must span < 4 GiB", fn);
     return DC_OK;
 }
 
@@ -244,33 +246,52 @@ using namespace dcap;
 
 extern "C" size_t dc_vocab_topk_workspace_bytes(int M, int V, int k) {
     if (M <= 0 || V <= 0 || k <= 0) return 0;
-    const size_t cells = (size_t)M * ((V + 127) / 128);
-    return tk_align256(cells * sizeof(float2)) + tk_align256(cells * k * sizeof(float2));
+    return tk_align256((size_t)M * ((V + 127) / 128) * (k + 1) * sizeof(float2));
+}
+
+// Both entry points: the tile kernel, then the row kernel with the caller's output strides (and, for top-1, tokens and mask).
+static int vocab_topk_run(const char* fn, const dc_vocab_topk_desc& d, long ld_ids, long ld_probs, int32_t* tokens, uint8_t* mask,
+                          void* workspace, size_t workspace_bytes, void* stream) {
+    int rc = vocab_f32_validate(fn, d);
+    if (rc) return rc;
+    const size_t need = dc_vocab_topk_workspace_bytes(d.M, d.V, d.k);
+    DC_REQUIRE(workspace && workspace_bytes >= need, DC_EWORKSPACE, "%s: needs %zu workspace bytes, got %zu", fn, need, workspace_bytes);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    TopkArgs ta{};
+    ta.M = d.M; ta.V = d.V; ta.k = d.k;
+    ta.tiles_m = (d.M + 127) / 128;
+    ta.tiles_n = (d.V + 127) / 128;
+    ta.bias = d.bias;
+    ta.cells = static_cast<float2*>(workspace);
+    // the B loader reads whole 16-byte column quads: the columns V .. round4(V) - 1 it then also reads lie inside the row (ldw >= round4(V))
+    // and feed only the tile's guarded-off lanes
+    TKA al{d.X, d.ldx, d.M, nullptr};
+    TKB bl{d.W, d.ldw, (d.V + 3) / 4 * 4, nullptr};
+    DC_ENSURE_DYN_LDS((&vocab_topk_f32_kernel), 160 * 1024);
+    constexpr size_t lds = igemm_lds_bytes<128, 128, TKA, TKB>();
+    hipLaunchKernelGGL(vocab_topk_f32_kernel, dim3(ta.tiles_m * ta.tiles_n), dim3(256), lds, s, al, bl, ta, d.K);
+    rc = check_launch("vocab_topk_f32_kernel");
+    if (rc) return rc;
+    hipLaunchKernelGGL(vocab_topk_rows_kernel, dim3((d.M + 3) / 4), dim3(256), 0, s, d.M, ta.tiles_n, d.k, ta.cells, d.ids, ld_ids, d.probs,
+                       ld_probs, tokens, mask);
+    return check_launch("vocab_topk_rows_kernel");
 }
 
 extern "C" int dc_vocab_topk_f32(const dc_vocab_topk_desc* d, void* workspace, size_t workspace_bytes, void* stream) {
-    int rc = topk_validate(d);
-    if (rc) return rc;
-    const size_t need = dc_vocab_topk_workspace_bytes(d->M, d->V, d->k);
-    DC_REQUIRE(workspace && workspace_bytes >= need, DC_EWORKSPACE, "dc_vocab_topk: needs %zu workspace bytes, got %zu", need, workspace_bytes);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    TopkArgs ta{};
-    ta.M = d->M; ta.V = d->V; ta.k = d->k;
-    ta.tiles_m = (d->M + 127) / 128;
-    ta.tiles_n = (d->V + 127) / 128;
-    ta.bias = d->bias;
-    ta.ms = static_cast<float2*>(workspace);
-    ta.cand = reinterpret_cast<float2*>(static_cast<char*>(workspace) + tk_align256((size_t)d->M * ta.tiles_n * sizeof(float2)));
-    // as dc_vocab_top1_f32: the B loader reads whole 16-byte column quads inside the row (ldw >= round4(V)); those columns are guarded off
-    TKA al{d->X, d->ldx, d->M, nullptr};
-    TKB bl{d->W, d->ldw, (d->V + 3) / 4 * 4, nullptr};
-    DC_ENSURE_DYN_LDS((&vocab_topk_f32_kernel), 160 * 1024);
-    constexpr size_t lds = igemm_lds_bytes<128, 128, TKA, TKB>();
-    hipLaunchKernelGGL(vocab_topk_f32_kernel, dim3(ta.tiles_m * ta.tiles_n), dim3(256), lds, s, al, bl, ta, d->K);
-    rc = check_launch("vocab_topk_f32_kernel");
-    if (rc) return rc;
-    hipLaunchKernelGGL(vocab_topk_rows_kernel, dim3((d->M + 3) / 4), dim3(256), 0, s, d->M, ta.tiles_n, d->k, ta.ms, ta.cand, d->ids, d->probs);
-    return check_launch("vocab_topk_rows_kernel");
+    DC_REQUIRE(d != nullptr, DC_EINVAL, "dc_vocab_topk: null descriptor");
+    DC_REQUIRE(d->M > 0 && d->V > 0 && d->K > 0 && d->X && d->W && d->ids && d->probs, DC_EINVAL, "dc_vocab_topk: bad arguments");
+    DC_REQUIRE(d->k >= 1 && d->k <= TK_MAX && d->V >= d->k, DC_EINVAL, "dc_vocab_topk: need 1 <= k <= 8 and V >= k (k = %d, V = %d)", d->k, d->V);
+    return vocab_topk_run("dc_vocab_topk", *d, d->k, d->k, nullptr, nullptr, workspace, workspace_bytes, stream);
+}
+
+extern "C" size_t dc_vocab_top1_workspace_bytes(int M, int V) { return dc_vocab_topk_workspace_bytes(M, V, 1); }
+
+extern "C" int dc_vocab_top1_f32(const dc_vocab_top1_desc* d, void* workspace, size_t workspace_bytes, void* stream) {
+    DC_REQUIRE(d != nullptr, DC_EINVAL, "dc_vocab_top1: null descriptor");
+    DC_REQUIRE(d->M > 0 && d->V > 0 && d->K > 0 && d->X && d->W && d->tokens, DC_EINVAL, "dc_vocab_top1: bad arguments");
+    DC_REQUIRE((!d->ids || d->ld_ids >= 1) && (!d->probs || d->ld_probs >= 1), DC_EINVAL, "dc_vocab_top1: ld_ids / ld_probs must be >= 1");
+    const dc_vocab_topk_desc tk{d->M, d->V, d->K, 1, d->X, d->ldx, d->W, d->ldw, d->bias, d->ids, d->probs};
+    return vocab_topk_run("dc_vocab_top1", tk, d->ld_ids, d->ld_probs, d->tokens, d->mask, workspace, workspace_bytes, stream);
 }
 
 extern "C" int dc_beam_select_f32(const dc_beam_select_desc* d, void* stream) {

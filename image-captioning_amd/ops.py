@@ -787,11 +787,8 @@ def _vocab_operands(X, W, bias):
     return X, W, bias
 
 
-def vocab_top1(X, W, bias=None, tokens=None, ids=None, probs=None, mask=None):
-    """Fused Dense(V) + greedy top-1 (dc_vocab_top1_f32): per row of X [M,K] (float32, K % 32 == 0) the argmax of X W + bias (lowest
-    index on ties) into tokens int32 [M] (contiguous), optionally also into ids / probs (int32 / float32 length-M vectors with any
-    stride -- e.g. column j of [B,T] outputs; probs = the softmax probability of the chosen word) and mask uint8 [M] (id != 0).  The
-    [M,V] logits are never materialised.  Every V >= 1: a W whose rows are not 16-byte chunks is copied once into a padded buffer."""
+def _vocab_args(fn, X, W, bias):
+    """The argument checks of vocab_top1 and vocab_topk (fn: the caller, for the messages) -> (lib, M, K, V)."""
     _chk(X, name="X"), _chk(W, name="W")
     if bias is not None:
         _chk(bias, name="bias")
@@ -799,11 +796,20 @@ def vocab_top1(X, W, bias=None, tokens=None, ids=None, probs=None, mask=None):
     M, K = X.shape
     V = W.shape[1]
     if W.shape[0] != K:
-        raise _lib.DcapError("vocab_top1: inner dimensions differ (%d vs %d)" % (K, W.shape[0]))
+        raise _lib.DcapError("%s: inner dimensions differ (%d vs %d)" % (fn, K, W.shape[0]))
     if K % 32:
-        raise _lib.DcapError("vocab_top1: K must be a multiple of 32, got %d" % K)
+        raise _lib.DcapError("%s: K must be a multiple of 32, got %d" % (fn, K))
     if bias is not None and tuple(bias.shape) != (V,):
-        raise _lib.DcapError("vocab_top1: bias must be [V]")
+        raise _lib.DcapError("%s: bias must be [V]" % fn)
+    return lib, M, K, V
+
+
+def vocab_top1(X, W, bias=None, tokens=None, ids=None, probs=None, mask=None):
+    """Fused Dense(V) + greedy top-1 (dc_vocab_top1_f32): per row of X [M,K] (float32, K % 32 == 0) the argmax of X W + bias (lowest
+    index on ties) into tokens int32 [M] (contiguous), optionally also into ids / probs (int32 / float32 length-M vectors with any
+    stride -- e.g. column j of [B,T] outputs; probs = the softmax probability of the chosen word) and mask uint8 [M] (id != 0).  The
+    [M,V] logits are never materialised.  Every V >= 1: a W whose rows are not 16-byte chunks is copied once into a padded buffer."""
+    lib, M, K, V = _vocab_args("vocab_top1", X, W, bias)
     if tokens is None:
         tokens = torch.empty((M,), dtype=torch.int32, device=X.device)
     if not _chk(tokens, torch.int32, "tokens").is_contiguous() or tokens.numel() != M:
@@ -835,21 +841,10 @@ def vocab_topk(X, W, bias, k, ids=None, probs=None):
     X W + bias in the order logit descending, then index ascending, into ids int32 [M,k], and their softmax probabilities into probs
     float32 [M,k] (both contiguous; allocated when None).  1 <= k <= 8 and V >= k; any V (W padded as for vocab_top1).  The [M,V]
     logits are never materialised.  k = 1 gives vocab_top1's ids and probabilities.  Returns (ids, probs)."""
-    _chk(X, name="X"), _chk(W, name="W")
-    if bias is not None:
-        _chk(bias, name="bias")
-    lib = _lib.load()
-    M, K = X.shape
-    V = W.shape[1]
+    lib, M, K, V = _vocab_args("vocab_topk", X, W, bias)
     k = int(k)
-    if W.shape[0] != K:
-        raise _lib.DcapError("vocab_topk: inner dimensions differ (%d vs %d)" % (K, W.shape[0]))
-    if K % 32:
-        raise _lib.DcapError("vocab_topk: K must be a multiple of 32, got %d" % K)
     if not 1 <= k <= TOPK_MAX or V < k:
         raise _lib.DcapError("vocab_topk: need 1 <= k <= %d and V >= k, got k = %d, V = %d" % (TOPK_MAX, k, V))
-    if bias is not None and tuple(bias.shape) != (V,):
-        raise _lib.DcapError("vocab_topk: bias must be [V]")
     if ids is None:
         ids = torch.empty((M, k), dtype=torch.int32, device=X.device)
     if probs is None:

@@ -503,8 +503,10 @@ int    dc_vocab_ce(const dc_vocab_ce_desc* d, void* workspace, size_t workspace_
  *   tokens [M] int32 (out): id = argmax_v z_v, the LOWEST index on ties (dc_argmax_rows_f32, tf.argmax) -- the next decode step's
  *   embedding-gather rows;  ids (optional): ids[m * ld_ids] = id (e.g. column j of a row-major [B,T] matrix);  probs (optional):
  *   probs[m * ld_probs] = softmax(z)_id = 1 / sum_v exp(z_v - max z);  mask (optional) [M] uint8: id != 0 (the Keras mask of the token).
- * Per (row, 128-column tile) the epilogue keeps max, argmax and sum exp; a second launch combines the tiles of a row in a fixed order,
- * so the result is deterministic and the same at every M.  Workspace: dc_vocab_top1_workspace_bytes(M, V) (16 bytes per row and tile).
+ * Runs the kernels of dc_vocab_topk_f32 at k = 1: per (row, 128-column tile) the epilogue keeps max, argmax and sum exp; a second
+ * launch combines the tiles of a row in a fixed order, so the result is deterministic and the same at every M.  A row without an
+ * orderable logit (NaNs only) gets id 0 and probability 1 / s.  Workspace: dc_vocab_top1_workspace_bytes(M, V) =
+ * dc_vocab_topk_workspace_bytes(M, V, 1) (16 bytes per row and tile).
  * Cost model: one GEMM pass (2 M K V flops; W streamed about once: the row tiles of a column panel run side by side) + M ceil(V/128)
  * x 16 bytes of partials, against the unfused [M,V] logits store + a softmax pass + an argmax pass + a gather (4 sweeps of 4 M V
  * bytes).  Greedy decoding with it runs the vocabulary layer over the B live rows once per token instead of T*B rows per token.
@@ -528,8 +530,8 @@ int    dc_vocab_top1_f32(const dc_vocab_top1_desc* d, void* workspace, size_t wo
  * probabilities, from logits = X[M,K] * W[K,V] + bias that are never written.  Replaces, per beam and token, model.predict's softmax
  * row + np.argsort(...)[-k:] of the reference's beam loop (image captioning/test.py:33-44) for the v2 decoders.
  *   X, W, bias: as dc_vocab_top1_f32 (any V >= k).  ids [M][k] int32, probs [M][k] float32 (out, contiguous): the k best words in the
- *   order value descending, then column ascending; probs[m][r] = exp(z_r - max z) / sum_v exp(z_v - max z).  k = 1 gives
- *   dc_vocab_top1_f32's id and probability.
+ *   order value descending, then column ascending; probs[m][r] = exp(z_r - max z) / sum_v exp(z_v - max z); ranks past the
+ *   row's orderable (non-NaN) logits get id 0 and probability 0.  k = 1 gives dc_vocab_top1_f32's id and probability (the same kernels).
  * Per (row, 128-column tile) the epilogue keeps max, sum exp and the tile's k best (value, column) pairs (k threshold rounds of the
  * 32-lane shuffle reduction); a second launch, one wave per row, combines the tiles_n * k candidates in an order fixed by V alone, so
  * the result is deterministic and the same at every M.  Workspace: dc_vocab_topk_workspace_bytes(M, V, k) (8 (k + 1) bytes per row
