@@ -227,12 +227,22 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const float* __restric
     }
 }
 
+// The BatchNorm pre-activation gamma * (acc + bias - mean) / sd + beta (sd = sqrtf(var + eps)), n = the normalised value.  ONE
+// expression for the forward and the backward: the backward's ReLU decision must be the forward's (TF's ReluGrad passes the gradient
+// exactly where the forward output is > 0), and a reciprocal multiply or another association puts entries within a few ulps of zero on
+// the other side.  fmaf pins the one contraction both kernels make.
+__device__ __forceinline__ float bn_preact(float acc, float bias, float mean, float sd, float gamma, float beta, float& n) {
+    n = (acc + bias - mean) / sd;
+    return fmaf(gamma, n, beta);
+}
+
 __global__ __launch_bounds__(256) void bn_relu_fwd_kernel(dc_bn_relu_desc d) {
     const long total = (long)d.M * d.N;
     for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
         const int r = (int)(idx / d.N), c = (int)(idx - (long)r * d.N);
-        const float n = (d.acc[(long)r * d.ld + c] + d.bias[c] - d.mean[c]) / sqrtf(d.var[c] + d.eps);
-        d.y[(long)r * d.ld + c] = fmaxf(d.gamma[c] * n + d.beta[c], 0.f);
+        float n;
+        const float z = bn_preact(d.acc[(long)r * d.ld + c], d.bias[c], d.mean[c], sqrtf(d.var[c] + d.eps), d.gamma[c], d.beta[c], n);
+        d.y[(long)r * d.ld + c] = fmaxf(z, 0.f);
     }
 }
 
@@ -242,10 +252,11 @@ __global__ __launch_bounds__(256) void bn_relu_bwd_kernel(dc_bn_relu_desc d) {
     const int c = blockIdx.x * 64 + (threadIdx.x & 63), rl = threadIdx.x >> 6;
     float sg = 0.f, sb = 0.f, sc = 0.f;
     if (c < d.N) {
-        const float inv = 1.f / sqrtf(d.var[c] + d.eps), g = d.gamma[c], be = d.beta[c], off = d.bias[c] - d.mean[c];
+        const float sd = sqrtf(d.var[c] + d.eps), inv = 1.f / sd, g = d.gamma[c], be = d.beta[c], bi = d.bias[c], mu = d.mean[c];
         for (int r = rl; r < d.M; r += 4) {
-            const float n = (d.acc[(long)r * d.ld + c] + off) * inv;
-            const float dz = (g * n + be > 0.f) ? d.dy[(long)r * d.ld + c] : 0.f;
+            float n;
+            const float z = bn_preact(d.acc[(long)r * d.ld + c], bi, mu, sd, g, be, n);
+            const float dz = (z > 0.f) ? d.dy[(long)r * d.ld + c] : 0.f;
             const float da = dz * g * inv;
             d.dacc[(long)r * d.ld + c] = da;
             sg += dz * n; sb += dz; sc += da;
