@@ -287,13 +287,10 @@ class DenseImageCapRCNN(object):
             raise ValueError("at most 3 anchors per location")
         self._seed = int(seed)
         # DCAP_STEP_GRAPH: 0 = every step eagerly, 1 = the captured step graph, unset / auto (round 6) = capture, then KEEP whichever of the
-        # two measured faster on this machine over the first steps (HIP events around whole steps: _choose_step_path) -- on the pool's
+        # two measured faster on this machine over the first steps (HIP events around whole steps: step_graph.PathChooser) -- on the pool's
         # boxes the eager step has been 1 - 2.5 % faster in two rounds of measurements (the replay of a two-branch graph costs more than
         # issuing its launches from a host that stays ahead); a slow or busy host turns that around.  Assigning use_step_graph pins it.
-        self._use_step_graph = step_graph.enabled()
-        self._step_path_auto = os.environ.get("DCAP_STEP_GRAPH", "auto") not in ("0", "1")
-        self._path_events = {"eager": [], "graph": []}
-        self.step_path_choice = None                         # dict(eager_ms, graph_ms, kept) once the automatic choice has been made
+        self._path = step_graph.PathChooser(step_graph.enabled(), auto=os.environ.get("DCAP_STEP_GRAPH", "auto") not in ("0", "1"))
         self.use_side_stream = True                          # RPN backward beside the proposals / decoder-forward chain (False: serial order)
         self._side_stream = None
         self.step_graph_fallback = None                      # set to the error text when a step-graph capture failed and the model went eager
@@ -317,24 +314,21 @@ class DenseImageCapRCNN(object):
 
     @property
     def use_step_graph(self):
-        return self._use_step_graph
+        return self._path.use_graph
 
     @use_step_graph.setter
     def use_step_graph(self, value):
-        self._use_step_graph = bool(value)
-        self._step_path_auto = False                          # an explicit choice is kept
+        self._path.pin(value)                                 # an explicit choice is kept
+
+    @property
+    def step_path_choice(self):
+        """dict(eager_ms, graph_ms, kept) once the automatic choice has been made, else None."""
+        return self._path.choice
 
     def _choose_step_path(self):
-        """Automatic mode: two eager steps and two replays have been timed (events around the whole step incl. the encoder pass): keep the
-        faster path.  Called at the start of a later step, when those events completed long ago."""
-        ev = self._path_events
-        if not self._step_path_auto or len(ev["eager"]) < 2 or len(ev["graph"]) < 2:
-            return
-        t = {k: min(a.elapsed_time(b) for a, b in v) for k, v in ev.items()}
-        self._step_path_auto = False
-        keep_graph = t["graph"] <= t["eager"]
-        self._use_step_graph = keep_graph
-        self.step_path_choice = dict(eager_ms=round(t["eager"], 4), graph_ms=round(t["graph"], 4), kept="graph" if keep_graph else "eager")
+        """Automatic mode, at the start of every step: once two eager steps and two replays have been timed (events around the whole
+        step incl. the encoder pass) and those events have completed, keep the faster path."""
+        self._path.decide()
 
     # ---- construction -----------------------------------------------------------------------
     @staticmethod
@@ -401,7 +395,12 @@ class DenseImageCapRCNN(object):
     def _invalidate_graphs(self):
         """Captured step graphs bake buffer addresses, the plan's outputs, the trainable subset and the optimizer state: anything
         that replaces one of those drops them (the next steps run eagerly and re-capture)."""
-        self._graphs, self._graph_warm, self._graph_out = {}, {}, {}
+        self._steps = step_graph.drop_all(getattr(self, "_steps", {}))      # {key: step_graph.CapturedStep}
+
+    @property
+    def _graphs(self):
+        """{key: graph} of the steps that are captured (a key's first element is "train")."""
+        return {k: cs.graph for k, cs in self._steps.items() if cs.graph is not None}
 
     def _buf(self, key, shape, dtype=torch.float32, zero=False):
         b = self._bufs.get(key)
@@ -1191,9 +1190,9 @@ class DenseImageCapRCNN(object):
         dev = self.device
         gt_norm = self._check_batch(p, images, gt_boxes)
         rpn_up = self._step_uploads(p, rpn_match, rpn_bbox, gt_norm, gt_caps, True)
+        path = self._path
         self._choose_step_path()
-        timing = self._step_path_auto and self._use_step_graph
-        if timing:
+        if path.auto and path.use_graph:                     # (this step may be one of the timed ones)
             e0 = torch.cuda.Event(enable_timing=True)
             e0.record()
         if trunk_done:
@@ -1202,58 +1201,45 @@ class DenseImageCapRCNN(object):
             p.forward(self._images_u8(images))
         opt = self.optimizer
 
-        def timed(kind, out):
-            if timing and len(self._path_events[kind]) < 2:
-                e1 = torch.cuda.Event(enable_timing=True)
-                e1.record()
-                self._path_events[kind].append((e0, e1))
-            return out
-
         def body():
             segs = self._reg_segments()
             losses = self._after_encoder(p, rpn_up, "rng", True, gt_caps, gt_norm, fuse_reg=segs is not None)
             opt.apply(self.store, grad_scale=1.0, lr_t_dev=rpn_up["lr_t"], reg=segs, reg_loss=None if segs is None else losses[3:4])
             return losses
 
-        def step():
-            if not self.use_step_graph:
-                return body()
-            key = ("train", float(cm.recurrent_dropout or 0.0), opt.baked_key())      # (with dropout the mask kernels are launches of the step)
-            graph = self._graphs.get(key)
-            if graph is not None:
-                graph.replay()
-                opt.iterations += 1                              # what the captured Python did once: the host-side counters
-                if float(cm.recurrent_dropout or 0.0) > 0.0:
-                    cm._drop_step += 1
-                return timed("graph", self._graph_out[key])
-            warm_steps = 3 if self._step_path_auto else 2        # (automatic mode: the first eager step allocates; the next two are timed)
-            if self._graph_warm.get(key, 0) < warm_steps:
-                self._graph_warm[key] = n_warm = self._graph_warm.get(key, 0) + 1  # eager: sizes every buffer and workspace, builds the masks
-                out = body()
-                return timed("eager", out) if n_warm > 1 else out
-            saved = (opt.iterations, cm._drop_step)
-            try:
-                torch.cuda.synchronize()
-                graph = torch.cuda.CUDAGraph()
-                with ops.no_gc_during_capture(), torch.cuda.graph(graph, capture_error_mode="thread_local"):
-                    out = body()
-            except RuntimeError as e:                            # a capture error (torch raises RuntimeError): stay eager from here on
-                import warnings
-                warnings.warn("joint step: hipGraph capture failed (%s); running eagerly" % (repr(e)[:200],))
-                opt.iterations, cm._drop_step = saved
-                self.use_step_graph = False
-                self.step_graph_fallback = repr(e)[:200]         # queryable (bench.py reports it): the eager step is a different schedule
-                # the failed capture may have pulled the side stream in (between fork and join): it is in an invalidated-capture state,
-                # so the eager retry forks onto a fresh one
-                torch.cuda.synchronize()
-                if self._side_stream is not None:
-                    ops.WORKSPACE.release(self._side_stream)
-                self._side_stream = None
-                return body()
-            self._graphs[key], self._graph_out[key] = graph, out
-            graph.replay()                                       # (capture records, it does not run: this is the step itself)
-            return out
-        return step()
+        if not path.use_graph:
+            return body()
+        dropout = float(cm.recurrent_dropout or 0.0)
+        key = ("train", dropout, opt.baked_key())            # (with dropout the mask kernels are launches of the step)
+        cs = self._steps.get(key)
+        if cs is None:
+            cs = self._steps[key] = step_graph.CapturedStep()
+
+        def restore(v):
+            opt.iterations, cm._drop_step = v
+
+        def bump():                                          # what the captured Python did once: the host-side counters
+            opt.iterations += 1
+            if dropout > 0.0:
+                cm._drop_step += 1
+
+        def failed(err):
+            self.use_step_graph = False                      # the whole model goes eager
+            self.step_graph_fallback = err                   # queryable (bench.py reports it): the eager step is a different schedule
+            # the failed capture may have pulled the side stream in (between fork and join): it is in an invalidated-capture state,
+            # so the eager retry forks onto a fresh one
+            if self._side_stream is not None:
+                ops.WORKSPACE.release(self._side_stream)
+            self._side_stream = None
+
+        # automatic mode: the first eager step allocates, the next two are timed, then the capture (not timed) and two timed replays
+        out = cs.run(body, lambda: (opt.iterations, cm._drop_step), restore, bump, warm_calls=3 if path.auto else 2, on_failure=failed)
+        kind = "graph" if cs.last == "replay" else "eager" if cs.last == "eager" and cs.warm > 1 else None
+        if kind is not None and path.wants(kind):
+            e1 = torch.cuda.Event(enable_timing=True)
+            e1.record()
+            path.add(kind, e0, e1)
+        return out
 
     def train_on_batch(self, inputs, targets=None):
         """One optimizer step; returns [loss, rpn_class_loss, rpn_bbox_loss, imgcap_loss] like the compiled Keras model

@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib, ops
+from . import _lib, ops, step_graph
 from ._lib import ConvBf16Desc, ConvDesc, PwChainDesc, check
 from .layers import ConvSpec, resnet_fpn_convs
 from .packing import fold_bn, pack_conv_kernel, pack_stem_kernel
@@ -101,9 +101,7 @@ class EncoderPlan:
         self.mean_pixel = [float(v) for v in mean_pixel]
         self.stage4_blocks = stage4_blocks
         self.use_graph = bool(use_graph)
-        self._graph = None
-        self._part_graphs, self._part_warm = {}, set()
-        self._warm = False
+        self._steps = {}                                 # captured passes: "all", "trunk", "top" (step_graph.CapturedStep)
         self._specs = {s.name: s for s in resnet_fpn_convs(stage4_blocks)}
         self.rpn = rpn
         self._external = dict(external or {})
@@ -536,54 +534,34 @@ class EncoderPlan:
             # memory really is asynchronous, and the caller's array may be freed or refilled right away: round 3 found the training
             # pipeline reading half-overwritten images that way.  Device tensors and pinned buffers stay asynchronous.)
             self.images.copy_(images_u8, non_blocking=bool(images_u8.is_cuda or images_u8.is_pinned()))
-        if not self.use_graph:
-            self._run_ops()
-        elif self._graph is not None:
-            self._graph.replay()
-        elif not self._warm:
-            self._run_ops()                 # first call: eager (sets kernel attributes, sizes the workspace)
-            self._warm = True
-        else:
-            g = torch.cuda.CUDAGraph()
-            # thread-local capture: the RCCL watchdog thread of a multi-GPU run polls events while this thread captures;
-            # under the default (global) mode that would invalidate the capture
-            with ops.no_gc_during_capture(), torch.cuda.graph(g, capture_error_mode="thread_local"):
-                self._run_ops()
-            self._graph = g
-            g.replay()
+        self._run_part("all", self._run_ops)
         return self.P
 
     # The pass in two halves, for a caller that runs the frozen backbone of the NEXT batch beside the rest of this batch's step
     # (pipeline.JointTrainPipeline): forward_trunk() = image -> C2..C5 (reads nothing a train step changes when no ResNet stage is
     # trainable), forward_top() = the FPN and the RPN on the C maps of the last forward_trunk().  Each half is its own hipGraph;
     # forward_trunk(); forward_top() enqueues exactly the launches of forward().
-    def _run_part(self, part, lo, hi):
+    def _run_part(self, part, body):
+        """body() as it stands (use_graph=False), or through the captured step of this part: the first call runs eagerly (it sets
+        kernel attributes and sizes the workspace), the second captures, later ones replay.  A capture error propagates."""
         if not self.use_graph:
-            self._run_ops(lo, hi)
+            body()
             return
-        g = self._part_graphs.get(part)
-        if g is not None:
-            g.replay()
-        elif part not in self._part_warm:
-            self._run_ops(lo, hi)                           # first call: eager (kernel attributes, workspace sizes)
-            self._part_warm.add(part)
-        else:
-            g = torch.cuda.CUDAGraph()
-            with ops.no_gc_during_capture(), torch.cuda.graph(g, capture_error_mode="thread_local"):
-                self._run_ops(lo, hi)
-            self._part_graphs[part] = g
-            g.replay()
+        cs = self._steps.get(part)
+        if cs is None:
+            cs = self._steps[part] = step_graph.CapturedStep()
+        cs.run(body, warm_calls=1, propagate=True)
 
     def forward_trunk(self, images_u8=None):
         if self._external_bn:
             raise RuntimeError("forward_trunk: this plan folds trainable BatchNorm layers inside the backbone pass; use forward()")
         if images_u8 is not None:
             self.images.copy_(images_u8, non_blocking=bool(images_u8.is_cuda or images_u8.is_pinned()))
-        self._run_part("trunk", 0, self._n_trunk)
+        self._run_part("trunk", lambda: self._run_ops(0, self._n_trunk))
         return self.C
 
     def forward_top(self):
-        self._run_part("top", self._n_trunk, None)
+        self._run_part("top", lambda: self._run_ops(self._n_trunk, None))
         return self.P
 
     def proposals(self, debug=False):
@@ -635,8 +613,7 @@ class Vgg16Plan(EncoderPlan):
         self.device = torch.device(device)
         self.mean_pixel = [float(v) for v in mean_pixel]
         self.use_graph = use_graph
-        self._graph = None
-        self._warm = False
+        self._steps = {}
         self._specs = {s.name: s for s in vgg16_convs()}
         self.rpn = None
         self._external = {}

@@ -6,7 +6,9 @@ import csv
 import os
 
 import numpy as np
+import torch
 
+from . import ops, step_graph
 from .modified_dense_model import load_weight_file, save_weight_file
 
 
@@ -44,10 +46,12 @@ class CSVLogger(object):
 
 
 class KerasLikeModel(object):
-    """Sub-classes provide: self.store (ParamStore), _forward_loss(inputs, targets, train) and predict()."""
+    """Sub-classes provide: self.store (ParamStore), self.device, self._bufs, self.grad_sync, _forward_train(), _backward(), train_step() and predict()."""
 
     optimizer = None
     loss = None
+    MAX_STEP_GRAPHS = 4        # batch shapes kept as captured graphs; further shapes run eagerly
+    use_step_graph = True      # (one GPU) replay the train step from a hipGraph; DCAP_STEP_GRAPH=0 overrides
 
     def compile(self, optimizer, loss=None):
         self.optimizer, self.loss = optimizer, loss
@@ -55,7 +59,50 @@ class KerasLikeModel(object):
 
     def _invalidate_graphs(self):
         """Drop the captured train steps (step_graph.CapturedStep per batch shape): something they baked has moved."""
-        self._steps = {}
+        self._steps = step_graph.drop_all(getattr(self, "_steps", {}))      # (first called while the model is built)
+
+    # ---- the train step: eager, or through the captured step of its batch shape ------------------------------------------
+    def _buf(self, key, shape, dtype=torch.float32):
+        b = self._bufs.get(key)
+        if b is None or tuple(b.shape) != tuple(shape) or b.dtype != dtype:
+            b = torch.empty(shape, dtype=dtype, device=self.device)
+            self._bufs[key] = b
+        return b
+
+    def _dev_feat(self, feat):
+        if isinstance(feat, torch.Tensor):
+            return feat.to(self.device, torch.float32).contiguous()
+        return torch.tensor(np.ascontiguousarray(feat, np.float32), device=self.device)
+
+    def _captured_step(self, key, feat):
+        """-> (the CapturedStep this batch runs through, is it new) or (None, False): the step runs eagerly -- a gradient exchange is
+        attached (its collectives are issued from Python; a hook without `.world` counts as one), graphs are switched off, or
+        MAX_STEP_GRAPHS other shapes are held already.  cs.feat: the persistent device tensor the caller copies the features into."""
+        world = 1 if self.grad_sync is None else getattr(self.grad_sync, "world", None)
+        cs = self._steps.get(key)
+        if world != 1 or not self.use_step_graph or not step_graph.enabled() or (cs is None and len(self._steps) >= self.MAX_STEP_GRAPHS):
+            return None, False
+        new = cs is None
+        if new:
+            cs = self._steps[key] = step_graph.CapturedStep()
+            cs.feat = torch.empty(tuple(feat.shape), dtype=torch.float32, device=self.device)
+        return cs, new
+
+    def _run_captured(self, cs, body, counters_get, counters_set, on_replay):
+        own, self._bufs = self._bufs, cs.bufs                # this shape's private scratch buffers (see CapturedStep)
+        try:
+            return cs.run(body, counters_get, counters_set, on_replay)
+        finally:
+            self._bufs = own
+
+    def _train_step_eager(self, *batch):
+        """The step launch by launch: forward (batch: what the sub-class's _forward_train takes), loss, backward, (all-reduce), AMSGrad."""
+        loss_rows, _ = self._forward_train(*batch, want_grad=True)
+        loss = ops.mean(loss_rows, out=self._buf('loss', (1,)))
+        self._backward()
+        scale = self.grad_sync(self.store.flat_grad) if self.grad_sync is not None else 1.0
+        self.optimizer.apply(self.store, grad_scale=scale)
+        return loss
 
     @property
     def trainable_weights(self):

@@ -2,6 +2,7 @@
 the current HIP stream and (elsewhere) torch.distributed; every arithmetic op is a dc_* kernel.
 All wrappers enqueue on torch's current stream and never synchronise.
 """
+import contextlib
 import ctypes as C
 import os
 
@@ -59,11 +60,13 @@ class _Workspace:
     every size) starts at the largest size any stream of the device has asked for, so that the capture never has to grow (= free) a
     buffer whose address earlier nodes have baked; outside a capture a new stream's buffer is sized by what that stream asks for
     (round 5, ADVICE r4: side / pipeline streams no longer pin a copy of the device-wide high-water mark each).  release() drops the
-    buffers of streams the caller has retired."""
+    buffers of streams the caller has retired; replacing or releasing an entry never frees memory a captured graph points into, because
+    the captured step holds what handed_out() saw during its capture."""
 
     def __init__(self):
         self.buf = {}
         self.hi = {}
+        self._seen = None             # {(device, stream handle): [buffers]} while handed_out() lasts
 
     def get(self, nbytes, device):
         if nbytes == 0:
@@ -79,18 +82,24 @@ class _Workspace:
             want = hi if torch.cuda.is_current_stream_capturing() else nbytes + nbytes // 4
             b = torch.empty(max(want, 1 << 20), dtype=torch.uint8, device=device)
             self.buf[key] = b
+        if self._seen is not None:
+            held = self._seen.setdefault(key, [])
+            if not any(h is b for h in held):
+                held.append(b)
         return b, b.numel()
 
-    def reserve(self, nbytes, device):
-        self.get(nbytes, device)
-
-    def current(self, device=None):
-        """The scratch buffer of the current stream (or None): a captured graph keeps a reference to the one its launches point into."""
-        device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        return self.buf.get((device, torch.cuda.current_stream(device).cuda_stream))
+    @contextlib.contextmanager
+    def handed_out(self):
+        """While it lasts (a hipGraph capture), collect every buffer get() hands out, on whichever stream: yields the dictionary
+        {(device, stream handle): [buffers]} the captured step keeps."""
+        self._seen = seen = {}
+        try:
+            yield seen
+        finally:
+            self._seen = None
 
     def release(self, stream):
-        """Drop the scratch buffer of a torch.cuda.Stream the caller is done with (no captured graph may still reference it)."""
+        """Drop the scratch buffer of a torch.cuda.Stream the caller is done with."""
         for key in [k for k in self.buf if k[1] == stream.cuda_stream]:
             del self.buf[key]
 

@@ -1,5 +1,6 @@
-"""A train step as ONE replayed hipGraph (the train_on_batch path of text_generation_model.py:425-438 and
-text_generation_model_v2.py:262-287; the joint model's step has its own driver in dense_model.py).
+"""A launch sequence as ONE replayed hipGraph: the capture-and-replay driver of every hot path (CapturedStep: the decoders' train steps,
+SURVEY 8a, text_generation_model.py:425-438 and text_generation_model_v2.py:262-287; the joint model's step behind the encoder; the
+encoder pass, whole or as trunk + top) and the joint model's choice between replaying and issuing eagerly (PathChooser).
 
 The decoder-only configurations (BASELINE configs[0] / configs[1]) are chains of 60 - 150 kernels of 5 - 20 us each: issued one by one
 from Python the host is the bottleneck (10 us per launch through ctypes), not the GPU.  Here the step is enqueued once into a hipGraph
@@ -86,45 +87,109 @@ class PackedInputs(object):
 
 
 class CapturedStep(object):
-    """One shape of one model's train step: two eager runs (they size every buffer and workspace), then a capture, then replays.
-    `bufs` is the scratch-buffer dictionary the step's kernels use -- private to this shape, so that another batch shape or a
-    predict() call in between can never free a buffer whose address the graph has baked."""
-    WARM = 2
+    """ONE launch sequence as a replayed hipGraph -- a model's train step for one batch shape, an encoder pass or one half of it: eager
+    calls first (they size every buffer and workspace), then a capture, then replays.  The only place of the package that builds,
+    captures and replays a graph.  What a captured step holds for as long as its graph exists: the graph, the body's outputs, every
+    scratch buffer ops.WORKSPACE handed out during the capture (`kept`: {(device, stream handle): [buffers]} -- the capture stream's
+    and those of streams the capture pulled in; a later, larger request on one of those streams replaces WORKSPACE's entry, not the
+    memory the graph's launches point into) and `bufs`, a scratch-buffer dictionary private to this step that a model swaps in around
+    run(), so that another batch shape or a predict() call in between can never free a buffer whose address the graph has baked."""
 
     def __init__(self):
         self.graph = None
         self.out = None
         self.warm = 0
         self.bufs = {}
-        self.failed = None            # the error text when the capture failed: this shape then stays eager
-        self._keep = None             # the split-K workspace the captured launches point into
+        self.kept = {}
+        self.failed = None            # the error text when the capture failed: this step then stays eager
+        self.last = None              # what the last run() did: "eager" | "capture" | "replay"
 
-    def run(self, body, counters_get, counters_set, on_replay):
-        """body(): enqueue the step, return its output tensor(s).  counters_get() / counters_set(v): the host-side counters body()
-        advances (restored when a capture fails, since the eager retry advances them again); on_replay(): advance them by one step."""
+    def run(self, body, counters_get=None, counters_set=None, on_replay=None, warm_calls=2, propagate=False, on_failure=None):
+        """body(): enqueue the launches, return the output tensor(s).  The first warm_calls calls run it eagerly, the next one captures
+        it (and replays once: that call's work), later ones replay.  counters_get() / counters_set(v): the host-side counters body()
+        advances (restored when a capture fails, since the eager retry advances them again); on_replay(): advance them by one step.
+        A capture that raises: warn, restore the counters, synchronise, on_failure(error text), run body() eagerly and stay eager --
+        or, with propagate, raise (an encoder pass must not silently become a hundred eager launches)."""
         if self.graph is not None:
+            self.last = "replay"
             self.graph.replay()
-            on_replay()
+            if on_replay is not None:
+                on_replay()
             return self.out
-        if self.failed is not None or self.warm < self.WARM:
+        self.last = "eager"
+        if self.failed is not None or self.warm < warm_calls:
             self.warm += 1
             return body()
-        saved = counters_get()
+        saved = counters_get() if counters_get is not None else None
         try:
             torch.cuda.synchronize()
             graph = torch.cuda.CUDAGraph()
-            with ops.no_gc_during_capture(), torch.cuda.graph(graph, capture_error_mode="thread_local"):
+            # thread-local capture: the RCCL watchdog thread of a multi-GPU run polls events while this thread captures; under the
+            # default (global) mode that would invalidate the capture
+            with ops.no_gc_during_capture(), ops.WORKSPACE.handed_out() as kept, torch.cuda.graph(graph, capture_error_mode="thread_local"):
                 out = body()
-                keep = ops.WORKSPACE.current()
-        except RuntimeError as e:                            # a capture error (torch raises RuntimeError): this shape stays eager
-            warnings.warn("train step: hipGraph capture failed (%s); running eagerly" % (repr(e)[:200],))
+        except RuntimeError as e:                            # a capture error (torch raises RuntimeError)
+            if propagate:
+                raise
+            warnings.warn("hipGraph capture failed (%s); running eagerly" % (repr(e)[:200],))
             self.failed = repr(e)[:200]
-            counters_set(saved)
+            if counters_set is not None:
+                counters_set(saved)
             torch.cuda.synchronize()
+            if on_failure is not None:
+                on_failure(self.failed)
             return body()
-        self.graph, self.out, self._keep = graph, out, keep
-        graph.replay()                                       # (a capture records, it does not run: this is the step itself)
+        self.graph, self.out, self.kept, self.last = graph, out, kept, "capture"
+        graph.replay()                                       # (a capture records, it does not run: this is the call's work itself)
         return out
+
+    def drop(self):
+        """Let go of the graph, then of what its launches point into: outputs, kept scratch buffers, the private buffers."""
+        self.graph = None
+        self.out = None
+        self.kept = {}
+        self.bufs = {}
+
+
+def drop_all(steps):
+    """drop() every CapturedStep of a dictionary (something they baked has moved); returns the empty dictionary that replaces it."""
+    for cs in steps.values():
+        cs.drop()
+    return {}
+
+
+class PathChooser(object):
+    """Replay the captured step or issue its launches eagerly?  Automatic mode times SAMPLES steps of either path with event pairs
+    around whole steps and keeps the faster one (the minimum of its samples; a tie keeps the graph).  pin() -- an explicit choice --
+    ends the automatic mode.  decide() never waits: while the end event of a recorded pair has not completed it returns without
+    deciding and is asked again at the start of the next step."""
+    SAMPLES = 2
+
+    def __init__(self, use_graph, auto):
+        self.use_graph, self.auto = bool(use_graph), bool(auto)
+        self.choice = None                                   # dict(eager_ms, graph_ms, kept) once the automatic choice has been made
+        self._events = {"eager": [], "graph": []}
+
+    def pin(self, use_graph):
+        self.use_graph, self.auto = bool(use_graph), False
+
+    def wants(self, kind):
+        """Is a step of this kind ("eager" | "graph") still to be timed?"""
+        return self.auto and self.use_graph and len(self._events[kind]) < self.SAMPLES
+
+    def add(self, kind, start, end):
+        self._events[kind].append((start, end))
+
+    def decide(self):
+        ev = self._events
+        if not self.auto or any(len(v) < self.SAMPLES for v in ev.values()):
+            return
+        if not all(end.query() for v in ev.values() for _, end in v):
+            return
+        t = {k: min(a.elapsed_time(b) for a, b in v) for k, v in ev.items()}
+        keep_graph = t["graph"] <= t["eager"]
+        self.pin(keep_graph)
+        self.choice = dict(eager_ms=round(t["eager"], 4), graph_ms=round(t["graph"], 4), kept="graph" if keep_graph else "eager")
 
 
 def lr_word(opt):

@@ -224,10 +224,6 @@ class CaptionModelV1(KerasLikeModel):
             return None
         return [m.cpu().numpy() for m in self._rec_masks]
 
-    def compile(self, optimizer, loss=None):
-        self.optimizer, self.loss = optimizer, loss
-        self._invalidate_graphs()              # captured train steps hold the previous optimizer's state tensors
-
     def _prefix_rows(self, training):
         if self.dropout_rows not in ("roi", "prefix"):
             raise ValueError("dropout_rows must be 'roi' or 'prefix'")
@@ -249,13 +245,6 @@ class CaptionModelV1(KerasLikeModel):
             return
         self._rec_masks = tuple(ops.dropout_mask(self._buf('rec_mask%d' % l, (4, B, self.units)), rate, self._drop_seed, 2 * self._drop_step + l)
                                 for l in range(2))
-
-    def _buf(self, key, shape, dtype=torch.float32):
-        b = self._bufs.get(key)
-        if b is None or tuple(b.shape) != tuple(shape) or b.dtype != dtype:
-            b = torch.empty(shape, dtype=dtype, device=self.device)
-            self._bufs[key] = b
-        return b
 
     def _grads_ready(self, *layers):
         """Data parallel: these layers' gradients are final -- start their all-reduce while the backward goes on."""
@@ -516,28 +505,22 @@ class CaptionModelV1(KerasLikeModel):
                 return self._mm(dacc, self._wview(conv + '/kernel'), key='dX', b_trans=True).f
         return None
 
-    MAX_STEP_GRAPHS = 4        # batch shapes kept as captured graphs; further shapes run eagerly
-
     def train_step(self, feat, caps, targets):
         """forward + roi_caption_loss + backward + (all-reduce) + AMSGrad; the loss as a DEVICE scalar (no sync).
         One GPU, one mask set per RoI: the whole step is replayed from a hipGraph captured on the third call with the same batch
         shape (step_graph.py); captions, targets, lr_t and the dropout stream position travel in ONE upload, the features in one copy."""
         if self.optimizer is None:
             raise RuntimeError("compile(optimizer, loss) first")
-        world = 1 if self.grad_sync is None else getattr(self.grad_sync, "world", None)
         caps = np.asarray(caps)
         B, T = caps.shape
         # what the captured launches bake: the batch shape and whether (and at which rate) the mask kernels are part of the step
         key = (tuple(feat.shape), B, T, float(self.recurrent_dropout or 0.0), self.optimizer.baked_key())
-        steps = self._steps
-        cs = steps.get(key)
-        if world != 1 or not step_graph.enabled() or self._prefix_rows(True) or (cs is None and len(steps) >= self.MAX_STEP_GRAPHS):
+        cs, new = (None, False) if self._prefix_rows(True) else self._captured_step(key, feat)
+        if cs is None:
             return self._train_step_eager(feat, caps, targets)
         opt = self.optimizer
         N = T * B
-        if cs is None:
-            cs = steps[key] = step_graph.CapturedStep()
-            cs.feat = torch.empty(tuple(feat.shape), dtype=torch.float32, device=self.device)
+        if new:
             cs.inputs = step_graph.PackedInputs(self.device, [("ids_tm", N), ("targets", N), ("mask", (N + 3) // 4), ("scalars", 4)])
         ids = caps.astype(np.int32)                        # Embedding casts float ids to int32 (_tables)
         scal = np.zeros(4, np.int32)
@@ -571,26 +554,9 @@ class CaptionModelV1(KerasLikeModel):
             if dropout:
                 self._drop_step += 1
 
-        own, self._bufs = self._bufs, cs.bufs                # this shape's private scratch buffers (see CapturedStep)
-        try:
-            return cs.run(body, lambda: (opt.iterations, self._drop_step), restore, bump)
-        finally:
-            self._bufs = own
-
-    def _train_step_eager(self, feat, caps, targets):
-        loss_rows, _ = self._forward_train(feat, caps, targets, want_grad=True)
-        loss = ops.mean(loss_rows, out=self._buf('loss', (1,)))
-        self._backward()
-        scale = self.grad_sync(self.store.flat_grad) if self.grad_sync is not None else 1.0
-        self.optimizer.apply(self.store, grad_scale=scale)
-        return loss
+        return self._run_captured(cs, body, lambda: (opt.iterations, self._drop_step), restore, bump)
 
     # ---------------------------------------------------------------------------------- Keras surface
-    def _dev_feat(self, feat):
-        if isinstance(feat, torch.Tensor):
-            return feat.to(self.device, torch.float32).contiguous()
-        return torch.tensor(np.ascontiguousarray(feat, np.float32), device=self.device)
-
     @staticmethod
     def _target_ids(y):
         y = np.asarray(y)

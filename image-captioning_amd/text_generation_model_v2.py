@@ -400,13 +400,6 @@ class CaptionModelV2(KerasLikeModel):
             k = self.store.w[conv + '/kernel']
             self._head.append((k.view(-1, k.shape[-1]), torch.tensor(sc, device=dev), torch.tensor(sh, device=dev)))
 
-    def _buf(self, key, shape, dtype=torch.float32):
-        b = self._bufs.get(key)
-        if b is None or tuple(b.shape) != tuple(shape):
-            b = torch.empty(shape, dtype=dtype, device=self.device)
-            self._bufs[key] = b
-        return b
-
     # ---------------------------------------------------------------------------------- engine
     def _forward(self, feat, tb, want_probs=False, want_grad=False):
         """feat [R,7,7,256] device tensor; tb SampleTables.  Returns (loss_rows or None, probs or None)."""
@@ -478,13 +471,14 @@ class CaptionModelV2(KerasLikeModel):
         ops.gemm(w['imgcap_embedding_layer/embeddings'], dz, a_trans=True, gather=tb.ids_tm, out=g[V2_WORD_LSTM + '/kernel'])
         ops.colsum(dz, out=g[V2_WORD_LSTM + '/bias'])
 
+    _forward_train = _forward          # (the name KerasLikeModel._train_step_eager calls; v1's takes captions and targets instead of tables)
+
     def _grads_ready(self, layer):
         """Data parallel: this layer's gradients are final -- start their all-reduce while the backward goes on."""
         if self.grad_sync is not None and hasattr(self.grad_sync, 'ready'):
             lo, hi = self.store.layer_range(layer)
             self.grad_sync.ready(self.store.flat_grad, lo, hi)
 
-    MAX_STEP_GRAPHS = 4        # batch shapes kept as captured graphs; further shapes run eagerly
     # Replaying the step from a captured hipGraph is OPT-IN for this model: at the reference's batch (64 samples, 1024 units) every kernel
     # runs 10 us or longer, the eager step is already GPU-bound (0.70 ms) and the replay's three input copies make it 0.73 ms
     # (bench.py other_configs.configs1_gpu reports both).  The v1 decoder at B = 8 is launch-bound and replays by default.
@@ -496,16 +490,11 @@ class CaptionModelV2(KerasLikeModel):
         (step_graph.py); the batch reaches it through two device-to-device copies (features, packed tables) and one word (lr_t)."""
         if self.optimizer is None:
             raise RuntimeError("compile(optimizer, loss) first")
-        world = 1 if self.grad_sync is None else getattr(self.grad_sync, "world", None)
-        key = (tuple(feat.shape), tb.N, tb.T, tb.Bw, self.optimizer.baked_key())
-        steps = self._steps
-        cs = steps.get(key)
-        if world != 1 or not self.use_step_graph or not step_graph.enabled() or (cs is None and len(steps) >= self.MAX_STEP_GRAPHS):
+        cs, new = self._captured_step((tuple(feat.shape), tb.N, tb.T, tb.Bw, self.optimizer.baked_key()), feat)
+        if cs is None:
             return self._train_step_eager(feat, tb)
         opt = self.optimizer
-        if cs is None:
-            cs = steps[key] = step_graph.CapturedStep()
-            cs.feat = torch.empty(tuple(feat.shape), dtype=torch.float32, device=self.device)
+        if new:
             cs.tb = tb.like(torch.empty_like(tb.packed))
             cs.scalars = step_graph.PackedInputs(self.device, [("lr_t", 1)])
         cs.feat.copy_(self._dev_feat(feat))
@@ -523,26 +512,9 @@ class CaptionModelV2(KerasLikeModel):
         def bump():
             opt.iterations += 1
 
-        own, self._bufs = self._bufs, cs.bufs                # this shape's private scratch buffers (see CapturedStep)
-        try:
-            return cs.run(body, lambda: opt.iterations, lambda v: setattr(opt, "iterations", v), bump)
-        finally:
-            self._bufs = own
-
-    def _train_step_eager(self, feat, tb):
-        loss_rows, _ = self._forward(feat, tb, want_grad=True)
-        loss = ops.mean(loss_rows, out=self._buf('loss', (1,)))
-        self._backward()
-        scale = self.grad_sync(self.store.flat_grad) if self.grad_sync is not None else 1.0
-        self.optimizer.apply(self.store, grad_scale=scale)
-        return loss
+        return self._run_captured(cs, body, lambda: opt.iterations, lambda v: setattr(opt, "iterations", v), bump)
 
     # ---------------------------------------------------------------------------------- Keras surface
-    def _dev_feat(self, feat):
-        if isinstance(feat, torch.Tensor):
-            return feat.to(self.device, torch.float32).contiguous()
-        return torch.tensor(np.ascontiguousarray(feat, np.float32), device=self.device)
-
     @staticmethod
     def _target_ids(y):
         y = np.asarray(y)

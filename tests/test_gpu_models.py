@@ -1143,6 +1143,81 @@ def test_joint_step_graph_is_dropped_and_recaptured_when_what_it_baked_changes(g
     np.testing.assert_array_equal(out["graph"], out["eager"])
 
 
+def test_joint_automatic_path_choice_never_reads_an_event_that_has_not_completed(gpu, monkeypatch):
+    """Automatic mode (DCAP_STEP_GRAPH unset, use_step_graph not assigned): nine train_on_batch_device calls back to back with no
+    read-back between them -- three eager steps, the capture, replays; the choice is due at the start of the seventh, when the events
+    around the sixth are still in flight.  No exception; after a synchronize and one more step the choice is made; the weights equal
+    those of a model pinned to eager after the same ten steps, bit for bit (either path runs the same launches)."""
+    S, V, T, blocks = 128, 24, 5, 1
+    _, cfg, Wt = make_joint(S, V, T, blocks)
+    from image_captioning_amd.dense_model import DenseImageCapRCNN
+    monkeypatch.delenv("DCAP_STEP_GRAPH", raising=False)
+    inp = joint_inputs(S, V, T)
+    inp[0] = torch.tensor(inp[0], device="cuda")
+    flats = {}
+    for mode in ("auto", "eager"):
+        model = DenseImageCapRCNN("training", cfg, "logs", stage4_blocks=blocks)
+        model.set_weights(Wt)
+        model.compile(1e-4)
+        if mode == "eager":
+            model.use_step_graph = False
+        assert model.step_path_choice is None
+        for _ in range(9):
+            model.train_on_batch_device(inp)
+        torch.cuda.synchronize()
+        model.train_on_batch_device(inp)
+        if mode == "auto":
+            choice = model.step_path_choice
+            assert choice is not None and sorted(choice) == ["eager_ms", "graph_ms", "kept"], choice
+            assert choice["eager_ms"] > 0 and choice["graph_ms"] > 0
+            assert choice["kept"] == ("graph" if choice["graph_ms"] <= choice["eager_ms"] else "eager")
+            assert model.use_step_graph == (choice["kept"] == "graph")
+            assert any(k[0] == "train" for k in model._graphs)      # the captured graph stays, whichever path won
+        else:
+            assert model.step_path_choice is None and not any(k[0] == "train" for k in model._graphs)
+        assert model.optimizer.iterations == 10
+        flats[mode] = model.store.flat.clone()
+    assert torch.equal(flats["auto"], flats["eager"])
+
+
+def test_joint_captured_step_keeps_the_scratch_buffers_of_every_stream_it_baked(gpu):
+    """The captured joint step points into two of ops.WORKSPACE's scratch buffers: the capture stream's and the side stream's (RPN
+    backward).  WORKSPACE replaces a stream's buffer when a later caller on that stream asks for more; the captured step holds the ones
+    its launches baked, so they outlive that -- and go when _invalidate_graphs() drops the step."""
+    import gc
+    import weakref
+    from image_captioning_amd import ops
+    from image_captioning_amd.dense_model import DenseImageCapRCNN
+    S, V, T, blocks = 128, 24, 5, 1
+    _, cfg, Wt = make_joint(S, V, T, blocks)
+    inp = joint_inputs(S, V, T)
+    inp[0] = torch.tensor(inp[0], device="cuda")
+    model = DenseImageCapRCNN("training", cfg, "logs", stage4_blocks=blocks)
+    model.set_weights(Wt)
+    model.compile(1e-4)
+    model.use_step_graph = True
+    for _ in range(4):
+        model.train_on_batch(inp)
+    (cs,) = [cs for k, cs in model._steps.items() if k[0] == "train" and cs.graph is not None]
+    streams = sorted(handle for _, handle in cs.kept)
+    assert model._side_stream.cuda_stream in streams and len(streams) == 2, streams      # the side stream and the capture stream
+    sizes = {key: max(b.numel() for b in held) for key, held in cs.kept.items()}
+    refs = [weakref.ref(b) for held in cs.kept.values() for b in held]
+    assert len(refs) == 2
+    for (device, handle), size in sizes.items():
+        with torch.cuda.stream(torch.cuda.ExternalStream(handle, device=device)):
+            now, _ = ops.WORKSPACE.get(size + (1 << 20), device)
+        assert now.numel() > size and all(now is not r() for r in refs)      # WORKSPACE let go of the baked buffer
+        del now
+    gc.collect()
+    assert all(r() is not None for r in refs)
+    model.train_on_batch(inp)                                    # (a replay into the buffers the step kept)
+    del cs
+    model._invalidate_graphs()
+    gc.collect()
+    assert all(r() is None for r in refs)
+
+
 def test_joint_model_two_images_per_gpu_small(gpu, tmp_path):
     """IMAGES_PER_GPU = 2 at 128 px (the 512-px oracle comparison is tests/test_gpu_oracle_fullsize.py): losses and gradients pooled over
     the batch against M.joint_loss_and_grads_batch with images whose counts differ; the captured optimizer step equals the eager one

@@ -679,3 +679,74 @@ def test_evaluator_decode_rois_equals_the_reference_per_roi_loop():
             res = Fake().predict([np.array([feats[j]]), np.array([pad_sequences([[np.argmax(c) for c in prev]], T)[0]])])
             prev.append(res[0])
         np.testing.assert_allclose(got[j], np.vstack(prev[1:]), rtol=1e-12)
+
+
+class _StubEvent:
+    """A HIP event as step_graph.PathChooser sees it: query() and elapsed_time(end).  `at` is the time of the record in ms."""
+    asked = 0                                                  # elapsed_time() calls over all stubs
+
+    def __init__(self, at, done=True):
+        self.at, self.done = at, done
+
+    def query(self):
+        return self.done
+
+    def elapsed_time(self, end):
+        _StubEvent.asked += 1
+        assert self.done and end.done, "Both events must be completed before calculating elapsed time."
+        return end.at - self.at
+
+
+def _timed_chooser(eager_ms, graph_ms, done=True):
+    from image_captioning_amd.step_graph import PathChooser
+    ch = PathChooser(True, auto=True)
+    ends = []
+    for kind, samples in (("eager", eager_ms), ("graph", graph_ms)):
+        for k, ms in enumerate(samples):
+            assert ch.wants(kind)
+            ends.append(_StubEvent(100.0 * k + ms, done))
+            ch.add(kind, _StubEvent(100.0 * k), ends[-1])
+        assert not ch.wants(kind)                               # two samples per path, no third
+    return ch, ends
+
+
+def test_step_path_chooser_waits_for_its_events_and_keeps_the_faster_path():
+    """The joint model's automatic choice between the captured step graph and eager launches (step_graph.PathChooser), driven with stub
+    events: nothing is decided -- and no elapsed time is read -- while the end event of any recorded pair is incomplete; once all are
+    complete the decision is recorded with the minimum of each path's two samples; a tie keeps the graph; a pin before the decision
+    wins and ends the automatic mode."""
+    from image_captioning_amd.step_graph import PathChooser
+    _StubEvent.asked = 0
+    ch = PathChooser(True, auto=True)
+    ch.decide()                                                 # nothing timed yet
+    assert ch.auto and ch.use_graph and ch.choice is None
+    # eager 7.5 / 7.0 ms, graph 7.25 / 9.0 ms: the minima decide (7.0 < 7.25), not the means or the last samples
+    ch, ends = _timed_chooser((7.5, 7.0), (7.25, 9.0), done=False)
+    for k in range(len(ends)):                                  # the events complete one by one, a decide() (= a step) after each
+        ch.decide()
+        assert ch.auto and ch.use_graph and ch.choice is None and _StubEvent.asked == 0, k
+        ends[k].done = True
+    ch.decide()
+    assert not ch.auto and not ch.use_graph and ch.choice == dict(eager_ms=7.0, graph_ms=7.25, kept="eager")
+    assert _StubEvent.asked == 4
+    ch.decide()                                                 # decided once
+    assert _StubEvent.asked == 4
+    # the graph wins, rounding to 4 digits
+    ch, _ = _timed_chooser((7.123456, 8.0), (9.0, 6.98765))
+    ch.decide()
+    assert not ch.auto and ch.use_graph and ch.choice == dict(eager_ms=7.1235, graph_ms=6.9877, kept="graph")
+    # a tie keeps the graph
+    ch, _ = _timed_chooser((7.0, 8.0), (8.0, 7.0))
+    ch.decide()
+    assert ch.use_graph and ch.choice["kept"] == "graph"
+    # a pin before the decision wins: no choice is recorded, nothing is timed any more, either way round
+    for pinned in (False, True):
+        _StubEvent.asked = 0
+        ch, _ = _timed_chooser((9.0, 9.0), (1.0, 1.0)) if not pinned else _timed_chooser((1.0, 1.0), (9.0, 9.0))
+        ch.pin(pinned)
+        ch.decide()
+        assert not ch.auto and ch.use_graph == pinned and ch.choice is None and _StubEvent.asked == 0
+        assert not ch.wants("eager") and not ch.wants("graph")
+    # pinned from the start (DCAP_STEP_GRAPH=0/1): never times
+    ch = PathChooser(True, auto=False)
+    assert not ch.wants("eager") and not ch.wants("graph")
