@@ -115,6 +115,14 @@ class VocabTopkDesc(C.Structure):
                 ("bias", C.c_void_p), ("ids", C.c_void_p), ("probs", C.c_void_p)]
 
 
+class VocabTop1Bf16Desc(C.Structure):
+    _fields_ = VocabTop1Desc._fields_ + [("tile", C.c_int)]
+
+
+class VocabTopkBf16Desc(C.Structure):
+    _fields_ = VocabTopkDesc._fields_ + [("tile", C.c_int)]
+
+
 class BeamSelectDesc(C.Structure):
     _fields_ = [("R", C.c_int), ("k", C.c_int), ("nb", C.c_int), ("steps", C.c_int), ("j", C.c_int), ("log_score", C.c_int),
                 ("cand_ids", C.c_void_p), ("cand_probs", C.c_void_p), ("scores_in", C.c_void_p), ("scores_out", C.c_void_p),
@@ -239,6 +247,11 @@ SYMBOLS = {
     "dc_vocab_top1_f32": (C.c_int, [C.POINTER(VocabTop1Desc), C.c_void_p, C.c_size_t, C.c_void_p]),
     "dc_vocab_topk_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "dc_vocab_topk_f32": (C.c_int, [C.POINTER(VocabTopkDesc), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "dc_vocab_topk_bf16_tile": (C.c_int, [C.c_int, C.c_int, C.c_int]),
+    "dc_vocab_top1_bf16_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "dc_vocab_topk_bf16_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "dc_vocab_top1_bf16": (C.c_int, [C.POINTER(VocabTop1Bf16Desc), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "dc_vocab_topk_bf16": (C.c_int, [C.POINTER(VocabTopkBf16Desc), C.c_void_p, C.c_size_t, C.c_void_p]),
     "dc_beam_select_f32": (C.c_int, [C.POINTER(BeamSelectDesc), C.c_void_p]),
     "dc_beam_backtrace": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "dc_argmax_rows_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),

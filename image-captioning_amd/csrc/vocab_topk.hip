@@ -2,6 +2,13 @@
 //   dc_vocab_top1_f32   the vocabulary projection FUSED with the row top-1 (greedy decoding): the next token, its softmax probability
 //                       and the mask byte;
 //   dc_vocab_topk_f32   the vocabulary projection FUSED with the row top-k (k <= 8) and the softmax probabilities of those k words;
+//   dc_vocab_top1_bf16 / dc_vocab_topk_bf16   the same contract on bf16 operands and the bf16 matrix pipe (the arithmetic a bf16 model
+//                       trains its vocabulary layer in: dc_vocab_ce's bf16 branch), on one of two tiles.  128 x 128 (bgemm_core.h): the
+//                       main loop leaves the fp32 loop's accumulator layout, so the tile ends in the SAME epilogue.  256 x 256
+//                       (bgemm256_core.h): the 128 accumulator registers of a lane are never transposed through LDS; every wave
+//                       reduces its own 64-column slice in registers and writes its own cells (ceil(V/64) cells per row instead of
+//                       ceil(V/128); no cross-wave combine, no barrier after the main loop), and the row kernel, generic over the
+//                       number of cells per row, combines them unchanged.
 //   dc_beam_select_f32  per RoI, the k best of the k live beams' k proposals each (score + p or score + log p), with the parents'
 //                       word-LSTM rows gathered into the next state buffers;
 //   dc_beam_backtrace   the [steps,R,k] parent / token history -> [R,k,steps] sequences.
@@ -17,7 +24,7 @@
 // the order (value descending, column ascending), so no per-lane lists are needed.  A row kernel (one wave per row) runs the same
 // rounds over the row's tiles_n * k candidates in an order that does not depend on M.  The [M,V] logits are never written.  No
 // persistent grid, no cross-block spin: an ordinary grid plus one combine launch.
-#include "igemm_core.h"
+#include "bgemm256_core.h"
 #include <algorithm>
 #include <climits>
 
@@ -101,6 +108,105 @@ __global__ __launch_bounds__(256, 2) void vocab_topk_f32_kernel(TKA al, TKB bl, 
     f32x16 acc[2][2];
     igemm_mainloop<128, 128, TKA, TKB>(al, bl, smem, m0, n0, 0, K, acc, wm, wn);
     topk_epilogue(acc, smem, ta, m0, n0, wm, wn, tile_n);
+}
+
+__global__ __launch_bounds__(256, 2) void vocab_topk_bf16_kernel(BOperand a, BOperand b, TopkArgs ta, int K) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int wave = threadIdx.x >> 6;
+    const int lid = xcd_remap(blockIdx.x, gridDim.x);
+    const int tile_m = lid % ta.tiles_m, tile_n = lid / ta.tiles_m;
+    const int m0 = tile_m * 128, n0 = tile_n * 128;
+    const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
+    f32x16 acc[2][2];
+    bgemm_mainloop<true, false>(a, b, reinterpret_cast<char*>(smem), m0, n0, 0, K, acc, wm, wn);
+    topk_epilogue(acc, smem, ta, m0, n0, wm, wn, tile_n);
+}
+
+// Epilogue of one 256 x 256 bf16 tile, straight from the accumulators (layout: bgemm256_core.h, mainloop).  Lane l of wave (group,
+// wcol) holds, for each of its 8 rows (mt), 16 logits of the wave's 64-column slice: columns 32 (nt >> 1) + 16 (nt & 1) + 4 (l >> 4) + j;
+// the lanes l, l ^ 16, l ^ 32, l ^ 48 share a row.  A threshold round is 16 in-lane comparisons and two shuffles; the sum of exp is 16
+// in-lane terms in a fixed order and the same two shuffles.  The wave writes cell (row, n0 / 64 + wcol) in the 128-tile's cell format
+// (ta.tiles_n = cells per row = ceil(V / 64)); a slice that starts at or past V writes nothing (no cell of that index exists).
+__device__ __forceinline__ void topk_epilogue256(b256::f32x4 (&acc)[8][4], const TopkArgs& ta, int m0, int n0) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int group = wave >> 2, wcol = wave & 3, i = lane & 15, q = lane >> 4;
+    const int c0 = n0 + 64 * wcol;
+    if (c0 >= ta.V) return;                                    // wave-uniform; nothing after the main loop synchronises the block
+    const int cell = c0 >> 6;
+    int col[4];
+    float bias[4][4];
+    unsigned live = 0;                                         // bit 4 nt + j: the column lies inside V
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) {
+        col[nt] = c0 + 32 * (nt >> 1) + 16 * (nt & 1) + 4 * q;
+        float4 b4 = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (ta.bias && col[nt] + 3 < ta.V) b4 = *reinterpret_cast<const float4*>(ta.bias + col[nt]);
+        else if (ta.bias) {
+            if (col[nt] < ta.V) b4.x = ta.bias[col[nt]];
+            if (col[nt] + 1 < ta.V) b4.y = ta.bias[col[nt] + 1];
+            if (col[nt] + 2 < ta.V) b4.z = ta.bias[col[nt] + 2];
+        }
+        bias[nt][0] = b4.x; bias[nt][1] = b4.y; bias[nt][2] = b4.z; bias[nt][3] = b4.w;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (col[nt] + j < ta.V) live |= 1u << (4 * nt + j);
+    }
+#pragma unroll
+    for (int mt = 0; mt < 8; ++mt) {
+        const int row = m0 + 128 * group + 64 * (mt >> 2) + 16 * (mt & 3) + i;
+        const bool wr = row < ta.M && q == 0;
+        float2* out = ta.cells + ((long)row * ta.tiles_n + cell) * (ta.k + 1);
+        float z[4][4];
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) z[nt][j] = acc[mt][nt][j] + bias[nt][j];
+        float tv = INFINITY, mx = -INFINITY;
+        int tc = INT_MIN;
+        for (int r = 0; r < ta.k; ++r) {                       // round r: the slice's (r+1)-th best pair
+            float bm = -INFINITY;
+            int bi = INT_MAX;
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if ((live >> (4 * nt + j) & 1u) && tk_after(z[nt][j], col[nt] + j, tv, tc)) tk_take(bm, bi, z[nt][j], col[nt] + j);
+#pragma unroll
+            for (int o = 16; o <= 32; o <<= 1) {
+                const float om = __shfl_xor(bm, o, 64);
+                const int oi = __shfl_xor(bi, o, 64);
+                tk_take(bm, bi, om, oi);
+            }
+            if (r == 0) mx = bm;
+            if (wr) out[1 + r] = make_float2(bm, __int_as_float(bi));
+            tv = bm; tc = bi;                                  // (no pair left: (-inf, INT_MAX), after which nothing comes)
+        }
+        float s = 0.f;
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) s += (live >> (4 * nt + j) & 1u) ? expf(z[nt][j] - mx) : 0.f;
+        s += __shfl_xor(s, 16, 64);
+        s += __shfl_xor(s, 32, 64);
+        if (wr) out[0] = make_float2(mx, s);
+    }
+}
+
+// Tile ids walk down the row tiles of a column panel first (b256::tile_coords), so W streams from HBM about once.
+__global__ __launch_bounds__(b256::NTHREADS, 2) void vocab_topk_bf16_256_kernel(BOperand a, BOperand b, TopkArgs ta, int K, int tiles_m, int tiles_n) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    int tile_m, tile_n;
+    b256::tile_coords(xcd_remap(blockIdx.x, gridDim.x), tiles_m, tiles_n, tile_m, tile_n);
+    const int m0 = tile_m * b256::BM, n0 = tile_n * b256::BN;
+    b256::Load<true, true> la;
+    b256::Load<false, false> lb;
+    la.init(a, m0, lane, wave);
+    lb.init(b, n0, lane, wave);
+    b256::f32x4 acc[8][4];
+    b256::mainloop(la, lb, reinterpret_cast<char*>(smem), 0, K, acc);
+    topk_epilogue256(acc, ta, m0, n0);
 }
 
 // One wave per row.  k threshold rounds over the tiles_n * k candidates, each a scan strided over the tiles (a lane takes all k
@@ -240,6 +346,25 @@ static int vocab_f32_validate(const char* fn, const dc_vocab_topk_desc& d) {
     return DC_OK;
 }
 
+// bf16 operands: the rules of dc_vocab_ce's bf16 branch, but any V (W's rows readable up to V rounded up to 8).
+static int vocab_bf16_validate(const char* fn, const dc_vocab_topk_bf16_desc& d) {
+    DC_REQUIRE(d.tile == 0 || d.tile == 128 || d.tile == 256, DC_EINVAL, "%s: tile must be 0 (automatic), 128 or 256, got %d", fn, d.tile);
+    DC_REQUIRE((d.K & 7) == 0 && (d.ldx & 7) == 0 && (d.ldw & 7) == 0, DC_EALIGN, "%s: K, ldx, ldw must be multiples of 8", fn);
+    DC_REQUIRE(d.ldx >= d.K && d.ldw >= (d.V + 7) / 8 * 8, DC_EINVAL, "%s: ldx < K or ldw < V rounded up to 8", fn);
+    DC_REQUIRE(aligned16(d.X) && aligned16(d.W) && (!d.bias || aligned16(d.bias)), DC_EALIGN, "%s: X, W, bias must be 16-byte aligned", fn);
+    DC_REQUIRE((size_t)d.M * d.ldx * 2 < (size_t)0x7FFFFFF0u && (size_t)d.K * d.ldw * 2 < (size_t)0x7FFFFFF0u, DC_EINVAL,
+               "%s: operands must span < 2 GiB", fn);
+    return DC_OK;
+}
+
+// 0 (automatic) -> the tile dc_vocab_ce's bf16 branch would run this problem on (ce_big()); V counts rounded up to 8, as W is read
+static int tk_bf16_tile(int M, int V, int K, int tile) {
+    if (tile) return tile;
+    return b256::prefer(M, (V + 7) / 8 * 8, K, 1) ? 256 : 128;
+}
+// cells per row: one per 128-column tile, or one per 64-column wave slice of the 256-column tile
+static int tk_bf16_cells(int V, int tile) { return tile == 256 ? (V + 63) / 64 : (V + 127) / 128; }
+
 }  // namespace dcap
 
 using namespace dcap;
@@ -292,6 +417,71 @@ extern "C" int dc_vocab_top1_f32(const dc_vocab_top1_desc* d, void* workspace, s
     DC_REQUIRE((!d->ids || d->ld_ids >= 1) && (!d->probs || d->ld_probs >= 1), DC_EINVAL, "dc_vocab_top1: ld_ids / ld_probs must be >= 1");
     const dc_vocab_topk_desc tk{d->M, d->V, d->K, 1, d->X, d->ldx, d->W, d->ldw, d->bias, d->ids, d->probs};
     return vocab_topk_run("dc_vocab_top1", tk, d->ld_ids, d->ld_probs, d->tokens, d->mask, workspace, workspace_bytes, stream);
+}
+
+extern "C" int dc_vocab_topk_bf16_tile(int M, int V, int K) {
+    if (M <= 0 || V <= 0 || K <= 0) return 0;
+    return tk_bf16_tile(M, V, K, 0);
+}
+
+extern "C" size_t dc_vocab_topk_bf16_workspace_bytes(int M, int V, int K, int k, int tile) {
+    if (M <= 0 || V <= 0 || K <= 0 || k <= 0 || (tile != 0 && tile != 128 && tile != 256)) return 0;
+    return tk_align256((size_t)M * tk_bf16_cells(V, tk_bf16_tile(M, V, K, tile)) * (k + 1) * sizeof(float2));
+}
+
+extern "C" size_t dc_vocab_top1_bf16_workspace_bytes(int M, int V, int K, int tile) { return dc_vocab_topk_bf16_workspace_bytes(M, V, K, 1, tile); }
+
+// Both bf16 entry points: the tile kernel of the chosen shape, then the row kernel over that shape's cells.
+static int vocab_topk_bf16_run(const char* fn, const dc_vocab_topk_bf16_desc& d, long ld_ids, long ld_probs, int32_t* tokens, uint8_t* mask,
+                               void* workspace, size_t workspace_bytes, void* stream) {
+    int rc = vocab_bf16_validate(fn, d);
+    if (rc) return rc;
+    const size_t need = dc_vocab_topk_bf16_workspace_bytes(d.M, d.V, d.K, d.k, d.tile);
+    DC_REQUIRE(workspace && workspace_bytes >= need, DC_EWORKSPACE, "%s: needs %zu workspace bytes, got %zu", fn, need, workspace_bytes);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int T = tk_bf16_tile(d.M, d.V, d.K, d.tile);
+    TopkArgs ta{};
+    ta.M = d.M; ta.V = d.V; ta.k = d.k;
+    ta.tiles_m = (d.M + T - 1) / T;
+    ta.tiles_n = tk_bf16_cells(d.V, T);
+    ta.bias = d.bias;
+    ta.cells = static_cast<float2*>(workspace);
+    // the W loader reads whole 16-byte chunks of 8 columns: the columns V .. round8(V) - 1 lie inside the row (ldw >= round8(V)) and feed
+    // only guarded-off lanes; the buffer ranges end with the last element the rules above make readable
+    const int Vp = (d.V + 7) / 8 * 8;
+    BOperand a{static_cast<const unsigned short*>(d.X), d.ldx, d.M, nullptr, (unsigned)(((size_t)(d.M - 1) * d.ldx + d.K) * 2)};
+    BOperand b{static_cast<const unsigned short*>(d.W), d.ldw, Vp, nullptr, (unsigned)(((size_t)(d.K - 1) * d.ldw + Vp) * 2)};
+    if (T == 256) {
+        const int tiles_n = (d.V + 255) / 256;
+        DC_ENSURE_DYN_LDS((&vocab_topk_bf16_256_kernel), 160 * 1024);
+        hipLaunchKernelGGL(vocab_topk_bf16_256_kernel, dim3(ta.tiles_m * tiles_n), dim3(b256::NTHREADS), b256::LDS_BYTES, s, a, b, ta, d.K,
+                           ta.tiles_m, tiles_n);
+        rc = check_launch("vocab_topk_bf16_256_kernel");
+    } else {
+        DC_ENSURE_DYN_LDS((&vocab_topk_bf16_kernel), 160 * 1024);
+        hipLaunchKernelGGL(vocab_topk_bf16_kernel, dim3(ta.tiles_m * ta.tiles_n), dim3(256), bgemm_lds_bytes(), s, a, b, ta, d.K);
+        rc = check_launch("vocab_topk_bf16_kernel");
+    }
+    if (rc) return rc;
+    hipLaunchKernelGGL(vocab_topk_rows_kernel, dim3((d.M + 3) / 4), dim3(256), 0, s, d.M, ta.tiles_n, d.k, ta.cells, d.ids, ld_ids, d.probs,
+                       ld_probs, tokens, mask);
+    return check_launch("vocab_topk_rows_kernel");
+}
+
+extern "C" int dc_vocab_topk_bf16(const dc_vocab_topk_bf16_desc* d, void* workspace, size_t workspace_bytes, void* stream) {
+    DC_REQUIRE(d != nullptr, DC_EINVAL, "dc_vocab_topk_bf16: null descriptor");
+    DC_REQUIRE(d->M > 0 && d->V > 0 && d->K > 0 && d->X && d->W && d->ids && d->probs, DC_EINVAL, "dc_vocab_topk_bf16: bad arguments");
+    DC_REQUIRE(d->k >= 1 && d->k <= TK_MAX && d->V >= d->k, DC_EINVAL, "dc_vocab_topk_bf16: need 1 <= k <= 8 and V >= k (k = %d, V = %d)", d->k,
+               d->V);
+    return vocab_topk_bf16_run("dc_vocab_topk_bf16", *d, d->k, d->k, nullptr, nullptr, workspace, workspace_bytes, stream);
+}
+
+extern "C" int dc_vocab_top1_bf16(const dc_vocab_top1_bf16_desc* d, void* workspace, size_t workspace_bytes, void* stream) {
+    DC_REQUIRE(d != nullptr, DC_EINVAL, "dc_vocab_top1_bf16: null descriptor");
+    DC_REQUIRE(d->M > 0 && d->V > 0 && d->K > 0 && d->X && d->W && d->tokens, DC_EINVAL, "dc_vocab_top1_bf16: bad arguments");
+    DC_REQUIRE((!d->ids || d->ld_ids >= 1) && (!d->probs || d->ld_probs >= 1), DC_EINVAL, "dc_vocab_top1_bf16: ld_ids / ld_probs must be >= 1");
+    const dc_vocab_topk_bf16_desc tk{d->M, d->V, d->K, 1, d->X, d->ldx, d->W, d->ldw, d->bias, d->ids, d->probs, d->tile};
+    return vocab_topk_bf16_run("dc_vocab_top1_bf16", tk, d->ld_ids, d->ld_probs, d->tokens, d->mask, workspace, workspace_bytes, stream);
 }
 
 extern "C" int dc_beam_select_f32(const dc_beam_select_desc* d, void* stream) {

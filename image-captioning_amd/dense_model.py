@@ -1264,14 +1264,17 @@ class DenseImageCapRCNN(object):
             windows.append(window)
         return np.stack(molded), np.stack(metas), np.stack(windows)
 
-    def generate_captions(self, images, verbose=0, return_probabilities=True, decoder="prefix"):
+    def generate_captions(self, images, verbose=0, return_probabilities=True, decoder="prefix", vocab_math=None):
         """The inference graph (:1602-1622) + generate_captions (:1964-2003): RPN proposals (POST_NMS_ROIS_INFERENCE) ->
         RoI features -> greedy ROICaptionInferenceLayer -> GenerationMatchLayer -> boxes in the original image.
         Returns [{'rois': int32 [K,4], 'captions': f32 [K,T,V] word probabilities, 'ids': int32 [K,T]}]; with
         return_probabilities=False the [K,T,V] tensor (3 GB at 1000 RoIs x 15 x 50 000) stays on the GPU and is dropped.
         decoder='incremental' (needs return_probabilities=False): CaptionModelV1.decode_greedy -- one token per step with carried LSTM
-        state and the vocabulary argmax fused into its GEMM, the same ids and word scores; 'prefix' (default): the reference's loop."""
-        CaptionModelV1.check_decoder(decoder, return_probabilities)
+        state and the vocabulary argmax fused into its GEMM, the same ids and word scores; 'prefix' (default): the reference's loop.
+        vocab_math='bf16' (decoder='incremental' on a compute_dtype='bf16' model): the vocabulary layer scores words on the bf16 matrix
+        pipe from the bf16 activations and the weight's bf16 mirror, the arithmetic the model trains it in (CaptionModelV1.decode_greedy);
+        None / 'f32' (default): from the fp32 activations and the fp32 master weight."""
+        CaptionModelV1.check_decoder(decoder, return_probabilities, vocab_math, getattr(self, "compute_dtype", None) if vocab_math == "bf16" else None)
         assert self.mode == "inference", "Create model in inference mode."
         assert len(images) == self.config.BATCH_SIZE, "len(images) must be equal to BATCH_SIZE"
         molded, metas, windows = self.mold_inputs(images)
@@ -1282,7 +1285,8 @@ class DenseImageCapRCNN(object):
         feats = p.roi_features(boxes_norm=proposals)
         results = []
         for b in range(len(images)):
-            probs, ids, word_scores = self.caption_model.generate(feats[b], return_probabilities=return_probabilities, decoder=decoder)
+            probs, ids, word_scores = self.caption_model.generate(feats[b], return_probabilities=return_probabilities, decoder=decoder,
+                                                                  vocab_math=vocab_math)
             boxes, keep = refine_generations(proposals[b].cpu().numpy(), word_scores, windows[b], self.config)
             final, ok = unmold_generations(boxes, images[b].shape, windows[b])
             keep = keep[ok]

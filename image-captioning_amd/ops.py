@@ -12,7 +12,7 @@ import torch
 
 from . import _lib
 from ._lib import (PwChainDesc, ConvBf16Desc, AmsgradDesc, DetectionTargetsDesc, BnReluDesc, ConvDesc, ConvWgradBf16Desc, GemmBf16Desc, VocabCeDesc, ProposalDesc, RpnLossDesc, GemmDesc, LstmBwdDesc, LstmFwdDesc, RoiAlignDesc,
-                   SoftmaxCeDesc, VocabTop1Desc, VocabTopkDesc, BeamSelectDesc, LstmStepDesc, check)
+                   SoftmaxCeDesc, VocabTop1Desc, VocabTopkDesc, VocabTop1Bf16Desc, VocabTopkBf16Desc, BeamSelectDesc, LstmStepDesc, check)
 
 
 def _stream():
@@ -777,28 +777,31 @@ def _row_out(t, M, dtype, name):
 
 
 def _vocab_operands(X, W, bias):
-    """X [M,K], W [K,V], bias [V] as the fused vocabulary kernels read them: W rows readable in whole 16-byte column quads up to V
-    rounded up to 4, X rows and bias 16-byte aligned (a padded / aligned copy otherwise)."""
+    """X [M,K], W [K,V], bias [V] as the fused vocabulary kernels read them: W rows readable in whole 16-byte chunks (4 float32 / 8 bf16
+    columns) up to V rounded up to that, X rows and bias 16-byte aligned (a padded / aligned copy otherwise)."""
     M, K = X.shape
     V = W.shape[1]
-    Vp = (V + 3) // 4 * 4
+    q = 8 if W.dtype == BF16 else 4
+    Vp = (V + q - 1) // q * q
     esz = W.element_size()
-    w_ok = (W.stride(0) % 4 == 0 and W.stride(0) >= Vp and W.data_ptr() % 16 == 0 and
+    w_ok = (W.stride(0) % q == 0 and W.stride(0) >= Vp and W.data_ptr() % 16 == 0 and
             (W.storage_offset() + (K - 1) * W.stride(0) + Vp) * esz <= W.untyped_storage().nbytes())
-    if not w_ok:                                       # (the kernel reads whole 16-byte column quads of W's rows)
-        Wp = torch.zeros((K, Vp), dtype=torch.float32, device=W.device)
+    if not w_ok:                                       # (the kernel reads whole 16-byte chunks of W's rows)
+        Wp = torch.zeros((K, Vp), dtype=W.dtype, device=W.device)
         Wp[:, :V].copy_(W)
         W = Wp
-    if X.stride(0) % 4 or X.data_ptr() % 16:
-        X = torch.empty((M, K), dtype=torch.float32, device=X.device).copy_(X)
+    if X.stride(0) % q or X.data_ptr() % 16:
+        X = torch.empty((M, K), dtype=X.dtype, device=X.device).copy_(X)
     if bias is not None and (bias.data_ptr() % 16 or not bias.is_contiguous()):
         bias = torch.empty((V,), dtype=torch.float32, device=bias.device).copy_(bias)
     return X, W, bias
 
 
-def _vocab_args(fn, X, W, bias):
-    """The argument checks of vocab_top1 and vocab_topk (fn: the caller, for the messages) -> (lib, M, K, V)."""
-    _chk(X, name="X"), _chk(W, name="W")
+def _vocab_args(fn, X, W, bias, tile=None):
+    """The argument checks of vocab_top1 and vocab_topk (fn: the caller, for the messages) -> (lib, M, K, V, bf16 operands?)."""
+    bf = X.dtype == BF16 or W.dtype == BF16            # both or neither: a mix fails W's or X's dtype check
+    dt = BF16 if bf else torch.float32
+    _chk(X, dt, "X"), _chk(W, dt, "W")
     if bias is not None:
         _chk(bias, name="bias")
     lib = _lib.load()
@@ -806,19 +809,28 @@ def _vocab_args(fn, X, W, bias):
     V = W.shape[1]
     if W.shape[0] != K:
         raise _lib.DcapError("%s: inner dimensions differ (%d vs %d)" % (fn, K, W.shape[0]))
-    if K % 32:
-        raise _lib.DcapError("%s: K must be a multiple of 32, got %d" % (fn, K))
+    if K % (8 if bf else 32):
+        raise _lib.DcapError("%s: K must be a multiple of %d, got %d" % (fn, 8 if bf else 32, K))
     if bias is not None and tuple(bias.shape) != (V,):
         raise _lib.DcapError("%s: bias must be [V]" % fn)
-    return lib, M, K, V
+    if tile and not bf:
+        raise _lib.DcapError("%s: tile= chooses between the bf16 kernels; float32 operands have one tile shape" % fn)
+    return lib, M, K, V, bf
 
 
-def vocab_top1(X, W, bias=None, tokens=None, ids=None, probs=None, mask=None):
-    """Fused Dense(V) + greedy top-1 (dc_vocab_top1_f32): per row of X [M,K] (float32, K % 32 == 0) the argmax of X W + bias (lowest
-    index on ties) into tokens int32 [M] (contiguous), optionally also into ids / probs (int32 / float32 length-M vectors with any
+def vocab_topk_bf16_tile(M, V, K):
+    """The tile shape (128 or 256) vocab_top1 / vocab_topk run bf16 operands of this problem size on when tile is 0 / None."""
+    return int(_lib.load().dc_vocab_topk_bf16_tile(int(M), int(V), int(K)))
+
+
+def vocab_top1(X, W, bias=None, tokens=None, ids=None, probs=None, mask=None, tile=None):
+    """Fused Dense(V) + greedy top-1: per row of X [M,K] the argmax of X W + bias (lowest index on ties) into tokens int32 [M]
+    (contiguous), optionally also into ids / probs (int32 / float32 length-M vectors with any
     stride -- e.g. column j of [B,T] outputs; probs = the softmax probability of the chosen word) and mask uint8 [M] (id != 0).  The
-    [M,V] logits are never materialised.  Every V >= 1: a W whose rows are not 16-byte chunks is copied once into a padded buffer."""
-    lib, M, K, V = _vocab_args("vocab_top1", X, W, bias)
+    [M,V] logits are never materialised.  Every V >= 1: a W whose rows are not 16-byte chunks is copied once into a padded buffer.
+    X and W both float32 (dc_vocab_top1_f32: fp32 MFMA products, K % 32 == 0) or both bf16 (dc_vocab_top1_bf16: the bf16 matrix pipe,
+    fp32 accumulation, K % 8 == 0; tile = None / 0 (automatic), 128 or 256 picks its tile shape); bias float32 either way."""
+    lib, M, K, V, bf = _vocab_args("vocab_top1", X, W, bias, tile)
     if tokens is None:
         tokens = torch.empty((M,), dtype=torch.int32, device=X.device)
     if not _chk(tokens, torch.int32, "tokens").is_contiguous() or tokens.numel() != M:
@@ -830,13 +842,18 @@ def vocab_top1(X, W, bias=None, tokens=None, ids=None, probs=None, mask=None):
     if M == 0:
         return tokens
     X, W, bias = _vocab_operands(X, W, bias)
-    d = VocabTop1Desc()
+    d = VocabTop1Bf16Desc() if bf else VocabTop1Desc()
     d.M, d.V, d.K = M, V, K
     d.X, d.ldx, d.W, d.ldw = X.data_ptr(), X.stride(0), W.data_ptr(), W.stride(0)
     d.bias = _ptr(bias)
     d.tokens = tokens.data_ptr()
     d.ids, d.ld_ids, d.probs, d.ld_probs = ids_p, ld_ids, probs_p, ld_probs
     d.mask = _ptr(mask)
+    if bf:
+        d.tile = int(tile or 0)
+        ws, wsb = WORKSPACE.get(lib.dc_vocab_top1_bf16_workspace_bytes(M, V, K, d.tile), X.device)
+        check(lib.dc_vocab_top1_bf16(C.byref(d), _ptr(ws), wsb, _stream()), "dc_vocab_top1_bf16")
+        return tokens
     ws, wsb = WORKSPACE.get(lib.dc_vocab_top1_workspace_bytes(M, V), X.device)
     check(lib.dc_vocab_top1_f32(C.byref(d), _ptr(ws), wsb, _stream()), "dc_vocab_top1_f32")
     return tokens
@@ -845,12 +862,13 @@ def vocab_top1(X, W, bias=None, tokens=None, ids=None, probs=None, mask=None):
 TOPK_MAX = 8
 
 
-def vocab_topk(X, W, bias, k, ids=None, probs=None):
-    """Fused Dense(V) + row top-k (dc_vocab_topk_f32; beam search): per row of X [M,K] (float32, K % 32 == 0) the k best words of
+def vocab_topk(X, W, bias, k, ids=None, probs=None, tile=None):
+    """Fused Dense(V) + row top-k (beam search): per row of X [M,K] the k best words of
     X W + bias in the order logit descending, then index ascending, into ids int32 [M,k], and their softmax probabilities into probs
     float32 [M,k] (both contiguous; allocated when None).  1 <= k <= 8 and V >= k; any V (W padded as for vocab_top1).  The [M,V]
-    logits are never materialised.  k = 1 gives vocab_top1's ids and probabilities.  Returns (ids, probs)."""
-    lib, M, K, V = _vocab_args("vocab_topk", X, W, bias)
+    logits are never materialised.  k = 1 gives vocab_top1's ids and probabilities.  Operands as vocab_top1: float32 (dc_vocab_topk_f32,
+    K % 32 == 0) or bf16 (dc_vocab_topk_bf16, K % 8 == 0, tile=).  Returns (ids, probs)."""
+    lib, M, K, V, bf = _vocab_args("vocab_topk", X, W, bias, tile)
     k = int(k)
     if not 1 <= k <= TOPK_MAX or V < k:
         raise _lib.DcapError("vocab_topk: need 1 <= k <= %d and V >= k, got k = %d, V = %d" % (TOPK_MAX, k, V))
@@ -864,11 +882,16 @@ def vocab_topk(X, W, bias, k, ids=None, probs=None):
     if M == 0:
         return ids, probs
     X, W, bias = _vocab_operands(X, W, bias)
-    d = VocabTopkDesc()
+    d = VocabTopkBf16Desc() if bf else VocabTopkDesc()
     d.M, d.V, d.K, d.k = M, V, K, k
     d.X, d.ldx, d.W, d.ldw = X.data_ptr(), X.stride(0), W.data_ptr(), W.stride(0)
     d.bias = _ptr(bias)
     d.ids, d.probs = ids.data_ptr(), probs.data_ptr()
+    if bf:
+        d.tile = int(tile or 0)
+        ws, wsb = WORKSPACE.get(lib.dc_vocab_topk_bf16_workspace_bytes(M, V, K, k, d.tile), X.device)
+        check(lib.dc_vocab_topk_bf16(C.byref(d), _ptr(ws), wsb, _stream()), "dc_vocab_topk_bf16")
+        return ids, probs
     ws, wsb = WORKSPACE.get(lib.dc_vocab_topk_workspace_bytes(M, V, k), X.device)
     check(lib.dc_vocab_topk_f32(C.byref(d), _ptr(ws), wsb, _stream()), "dc_vocab_topk_f32")
     return ids, probs

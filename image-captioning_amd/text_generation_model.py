@@ -594,27 +594,55 @@ class CaptionModelV1(KerasLikeModel):
         return float(self.test_on_batch_device(inputs, targets).item())
 
     DECODERS = ("prefix", "incremental")
+    VOCAB_MATH = (None, "f32", "bf16")
 
     @classmethod
-    def check_decoder(cls, decoder, return_probabilities):
-        """decoder='incremental' never forms the per-step [B,V] probability rows: it needs return_probabilities=False."""
+    def check_decoder(cls, decoder, return_probabilities, vocab_math=None, compute_dtype=None):
+        """decoder='incremental' never forms the per-step [B,V] probability rows: it needs return_probabilities=False.
+        vocab_math: None / 'f32' (the vocabulary layer scores words from the fp32 activations and the fp32 master weight) or 'bf16' (from
+        their bf16 copies on the bf16 matrix pipe, the arithmetic a bf16 model trains that layer in): 'bf16' needs decoder='incremental'
+        and a model that computes in bf16 (compute_dtype: the model's; only a bf16 model keeps the weight's bf16 mirror)."""
         if decoder not in cls.DECODERS:
             raise ValueError("decoder must be one of %s, got %r" % (cls.DECODERS, decoder))
         if decoder == "incremental" and return_probabilities is not False:
             raise ValueError("decoder='incremental' returns no word probabilities: pass return_probabilities=False")
+        if vocab_math not in cls.VOCAB_MATH:
+            raise ValueError("vocab_math must be one of %s, got %r" % (cls.VOCAB_MATH, vocab_math))
+        if vocab_math == "bf16":
+            if decoder != "incremental":
+                raise ValueError("vocab_math='bf16' is the incremental decoder's fused vocabulary top-1: pass decoder='incremental' (got %r)" % (decoder,))
+            if compute_dtype != "bf16":
+                raise ValueError("vocab_math='bf16' needs a model built with compute_dtype='bf16' (its vocabulary weight's bf16 mirror), "
+                                 "this one computes in %r" % (compute_dtype,))
 
-    def decode_greedy(self, feat):
+    def decode_greedy(self, feat, vocab_math=None):
         """Greedy decoding of ROICaptionInferenceLayer (:192-232) ONE token per step, entirely on the device: the RoI head and the per-RoI
         halves of the first LSTM's and the Dense-1024's inputs once, then per token j the embedding-gather GEMM over the B rows, one
         carried-state step of each LSTM (a generated id 0 is masked, as Keras masks it in the reference's padded prefix: the state is
         carried over it), the Dense-1024 and the vocabulary layer fused with its argmax (ops.vocab_top1: no [B,V] logits).  The same
         results as the prefix decoder: under the mask carry, the last row of the prefix-j pass IS the state after feeding token j.
+        vocab_math='bf16' (bf16 models): the vocabulary layer reads the Dense-1024's bf16 output (written by that GEMM's epilogue) and
+        the weight's bf16 mirror, on the bf16 matrix pipe; None / 'f32': the fp32 activations and the fp32 master weight.
         Returns device tensors (ids int32 [B,T], word_scores float32 [B,T] = the softmax probability of each chosen word), two views
         of one [2,B,T] buffer (one copy brings both to the host).  No host synchronisation."""
-        out = self._decode_greedy(feat)
+        self.check_decoder("incremental", False, vocab_math, self.compute_dtype if vocab_math == "bf16" else None)
+        out = self._decode_greedy(feat, vocab_math)
         return out[0], out[1].view(torch.float32)
 
-    def _decode_greedy(self, feat):
+    def _vocab_mirror(self):
+        """The vocabulary weight's bf16 mirror as ops.vocab_top1 reads it; a mirror whose rows are not whole, aligned 16-byte chunks (V not a
+        multiple of 8, or a base the parameter bucket left 8-byte aligned) takes one zero-padded copy per decode call, not one per token."""
+        Wb = self.store.wb['imgcap_lstm_d2/kernel']
+        Wb = Wb.view(-1, Wb.shape[-1])
+        if self.V % 8 == 0 and Wb.data_ptr() % 16 == 0:
+            return Wb
+        Vp = (self.V + 7) // 8 * 8
+        pad = self._buf('dec_wvb', (Wb.shape[0], Vp), torch.bfloat16)
+        pad[:, self.V:].zero_()
+        pad[:, :self.V].copy_(Wb)
+        return pad[:, :self.V]
+
+    def _decode_greedy(self, feat, vocab_math=None):
         """decode_greedy into one int32 [2,B,T] device buffer: [0] the ids, [1] the word scores' float32 bits."""
         feat = self._dev_feat(feat)
         B, T, u, w = feat.shape[0], self.T, self.units, self.store.w
@@ -622,6 +650,7 @@ class CaptionModelV1(KerasLikeModel):
         ids, scores = out[0], out[1].view(torch.float32)
         if B == 0:
             return out
+        vb = vocab_math == "bf16"
         self._draw_rec_masks(B, training=False)
         f = self._head_forward(feat.reshape(B, -1))
         zf = self._mm(f, self._wview('imgcap_lstm1/kernel', (self.E, self.E + self.FEAT)), key='dec_zf').f
@@ -629,7 +658,7 @@ class CaptionModelV1(KerasLikeModel):
         U1, U2 = w['imgcap_lstm1/recurrent_kernel'], w['imgcap_lstm2/recurrent_kernel']
         pk = [ops.lstm_pack_urec(Ur, out=self._buf('dec_upk%d' % l, (u, 4 * u))) if u % 32 == 0 else None for l, Ur in enumerate((U1, U2))]
         emb_b = self._emb_bf16()
-        Wv, _ = self._wview('imgcap_lstm_d2/kernel')
+        Wv = self._vocab_mirror() if vb else self._wview('imgcap_lstm_d2/kernel')[0]
         tok = self._buf('dec_tok', (B,), torch.int32).fill_(1)          # start token (:203)
         live = self._buf('dec_live', (B,), torch.uint8)
         st = [[self._buf('dec_%s%d_%d' % (k, l, q), (B, u)) for q in range(2) for k in 'hc'] for l in range(2)]    # ping-pong (h, c, h', c')
@@ -649,19 +678,21 @@ class CaptionModelV1(KerasLikeModel):
             h2, c2 = ops.lstm_step(z2, U2, None if first else st[1][prev], None if first else st[1][prev + 1], mask,
                                    st[1][cur], st[1][cur + 1], U_packed=pk[1])
             a1 = self._mm(self._act('dec_h2', h2), self._wview('imgcap_lstm_d1/kernel', (0, u)), key='dec_a1', shift=w['imgcap_lstm_d1/bias'],
-                          residual=zdf, res_rows=B, relu=True)
-            ops.vocab_top1(a1.f, Wv, w['imgcap_lstm_d2/bias'], tokens=tok, ids=ids[:, j], probs=scores[:, j], mask=live)
+                          residual=zdf, res_rows=B, relu=True, want_b=vb)
+            # (a1.b: the bf16 copy the Dense-1024 GEMM's epilogue wrote; were that GEMM off the bf16 pipe, one cast of a1.f)
+            ops.vocab_top1(a1.b if vb else a1.f, Wv, w['imgcap_lstm_d2/bias'], tokens=tok, ids=ids[:, j], probs=scores[:, j], mask=live)
         return out
 
-    def generate(self, feat, return_probabilities=None, decoder="prefix"):
+    def generate(self, feat, return_probabilities=None, decoder="prefix", vocab_math=None):
         """ROICaptionInferenceLayer (:192-232): start token 1; step j feeds [prev..., 0...] through the word
         model and appends float(argmax).  Returns (probs [B,T,V], ids [B,T]); with return_probabilities given (the joint
         model) returns (probs or None, ids, word_scores [B,T] = the probability of each chosen word).
         decoder='incremental' (needs return_probabilities=False): decode_greedy -- one token per step on the device, no [B,V] rows --
-        returning (None, ids, word_scores) through one device-to-host copy; 'prefix' (default): the reference's T-prefix loop below."""
-        self.check_decoder(decoder, return_probabilities)
+        returning (None, ids, word_scores) through one device-to-host copy; 'prefix' (default): the reference's T-prefix loop below.
+        vocab_math='bf16' (incremental decoder of a bf16 model only): see decode_greedy; the default scores words in fp32."""
+        self.check_decoder(decoder, return_probabilities, vocab_math, getattr(self, "compute_dtype", None) if vocab_math == "bf16" else None)
         if decoder == "incremental":
-            host = self._decode_greedy(feat).cpu().numpy()
+            host = self._decode_greedy(feat, vocab_math).cpu().numpy()
             return None, host[0], host[1].view(np.float32)
         feat = self._dev_feat(feat)
         B, T = feat.shape[0], self.T

@@ -550,6 +550,50 @@ size_t dc_vocab_topk_workspace_bytes(int M, int V, int k);
 int    dc_vocab_topk_f32(const dc_vocab_topk_desc* d, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The two fused vocabulary reductions above on bf16 operands and the bf16 matrix pipe (fp32 accumulate): the arithmetic a bf16 model
+ * trains its vocabulary layer in (dc_vocab_ce, bf16 = 1), for decoding that model.  Outputs, tie rule, NaN rule, k range: as the
+ * fp32 entry points (the epilogue's rounds and the row kernel are the same code).
+ *   X [M][ldx], W [K][ldw]: bf16 bit patterns; bias fp32 [V] or NULL.  Operand rules of dc_vocab_ce's bf16 branch: K, ldx, ldw
+ *   multiples of 8, X, W, bias 16-byte aligned, operands < 2 GiB; any V >= k provided ldw >= V rounded up to 8 (the columns up to that
+ *   are read, never used).
+ *   tile: 0 = automatic, 128 or 256.  128: bgemm_core.h's 128 x 128 loop and the fp32 kernel's LDS epilogue, one cell per row and
+ *   128-column tile.  256: bgemm256_core.h's 256 x 256 loop; every wave reduces its 64-column slice of the tile in registers and
+ *   writes its own cell (ceil(V / 64) cells per row).  Automatic picks the tile dc_vocab_ce's bf16 branch picks for the same M, V, K
+ *   (dc_vocab_topk_bf16_tile tells which, without launching).
+ * Deterministic; with `tile` fixed the result of a row is the same at every M (automatic may pick another tile at another M).  The
+ * two tiles sum the K products of a logit in different orders: between them, and against a float64 reference, ids agree on every
+ * row whose adjacent top-(k+1) logit gaps exceed the fp32 dot-product bound 2 K 2^-24 max_v sum_k |x_k w_kv|.
+ * Workspace: dc_vocab_topk_bf16_workspace_bytes(M, V, K, k, tile) (8 (k + 1) bytes per row and cell); 0 for a tile that is none of the three.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct {
+    int M, V, K;
+    const void* X;   int ldx;
+    const void* W;   int ldw;
+    const float* bias;
+    int32_t* tokens;
+    int32_t* ids;    int ld_ids;
+    float* probs;    int ld_probs;
+    uint8_t* mask;
+    int tile;
+} dc_vocab_top1_bf16_desc;
+
+typedef struct {
+    int M, V, K, k;
+    const void* X;   int ldx;
+    const void* W;   int ldw;
+    const float* bias;
+    int32_t* ids;
+    float* probs;
+    int tile;
+} dc_vocab_topk_bf16_desc;
+
+int    dc_vocab_topk_bf16_tile(int M, int V, int K);
+size_t dc_vocab_top1_bf16_workspace_bytes(int M, int V, int K, int tile);
+size_t dc_vocab_topk_bf16_workspace_bytes(int M, int V, int K, int k, int tile);
+int    dc_vocab_top1_bf16(const dc_vocab_top1_bf16_desc* d, void* workspace, size_t workspace_bytes, void* stream);
+int    dc_vocab_topk_bf16(const dc_vocab_topk_bf16_desc* d, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * One beam-search step for R RoIs with k beams each (image captioning/test.py:33-56), one wave per RoI.  Rows of the per-beam
  * tensors are BEAM-MAJOR: beam b of RoI r is row b * R + r.
  *   cand_ids / cand_probs [k*R][k]: dc_vocab_topk_f32's output for every beam row;  nb: live beams (1 at the first step, then k);

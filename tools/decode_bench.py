@@ -2,6 +2,10 @@
 decoder='incremental' (decode_greedy: one token per step with carried LSTM state, ops.vocab_top1), on synthetic weights, plus
 ops.vocab_top1 alone as a fraction of the fp32 matrix peak.  Both decoders run with return_probabilities=False (the prefix path then
 still writes and reads its [T*B, V] logits every step, but copies no [B,V] rows to the host).
+A bf16 model gets a third leg, decoder='incremental' with vocab_math='bf16' (the vocabulary top-1 on the bf16 matrix pipe), timed
+ALTERNATING with the fp32-vocabulary incremental leg in this process (call by call, so both see the same clocks), the share of RoIs
+whose captions are identical between the two vocabulary arithmetics, and ops.vocab_top1 on bf16 operands alone at the step's shape on
+both tile shapes and the automatic choice, against the bf16 MFMA peak and the time to stream W once from HBM.
 
 Shapes: configs[4] inference (K = 1000 RoIs = POST_NMS_ROIS_INFERENCE, T = 15, V = 50 000, 512 units) and a configs[2]-style one
 (K = 200, V = 10 000).  Times: torch.cuda.Event around the whole call (host copies of the ids included), warm-up first, median of
@@ -20,6 +24,8 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 FP32_PEAK = 157e12          # MI355X dense fp32 matrix peak (TFLOP/s x 1e12)
+BF16_PEAK = 2.5e15          # MI355X dense bf16 matrix peak
+HBM_PEAK = 8.0e12           # HBM3E bytes / s (spec)
 
 
 def timed(fn, warm, reps):
@@ -35,6 +41,24 @@ def timed(fn, warm, reps):
         b.synchronize()
         ts.append(a.elapsed_time(b))
     return float(np.median(ts)), [round(t, 3) for t in ts]
+
+
+def timed_alternating(fns, warm, reps):
+    """The calls of `fns` in turn, `reps` rounds after `warm` rounds: [(median ms, [ms ...]) per fn]."""
+    for _ in range(warm):
+        for fn in fns:
+            fn()
+    torch.cuda.synchronize()
+    ts = [[] for _ in fns]
+    for _ in range(reps):
+        for i, fn in enumerate(fns):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            ts[i].append(a.elapsed_time(b))
+    return [(float(np.median(t)), [round(x, 3) for x in t]) for t in ts]
 
 
 def model_for(V, T, K, units, dtype, seed=0):
@@ -76,6 +100,25 @@ def main():
             rows.append(dict(what="decode_speedup", shape=sh["name"], dtype=dtype, speedup=round(p / i, 2), ids_identical=same,
                              max_rel_score_diff=rel))
             print(json.dumps(rows[-1]), flush=True)
+            if dtype == "bf16":
+                # the two vocabulary arithmetics of the incremental decoder, call by call in turn
+                legs = (("f32", lambda: model.generate(feat, return_probabilities=False, decoder="incremental", vocab_math="f32")),
+                        ("bf16", lambda: model.generate(feat, return_probabilities=False, decoder="incremental", vocab_math="bf16")))
+                out = [fn() for _, fn in legs]
+                res = timed_alternating([fn for _, fn in legs], max(args.warmup, 1), max(args.repeats, 5))
+                for (vm, _), (ms, all_ms) in zip(legs, res):
+                    rows.append(dict(what="decode_per_image", shape=sh["name"], dtype=dtype, decoder="incremental", vocab_math=vm, alternating=True,
+                                     K=sh["K"], T=sh["T"], V=sh["V"], units=sh["units"], ms=round(ms, 3), runs_ms=all_ms,
+                                     spread_ms=round(max(all_ms) - min(all_ms), 3)))
+                    print(json.dumps(rows[-1]), flush=True)
+                (m32, r32), (m16, r16) = res
+                spread = max(max(r32) - min(r32), max(r16) - min(r16))
+                same_rois = (out[0][1] == out[1][1]).all(axis=1)
+                first = np.where(same_rois, sh["T"], (out[0][1] != out[1][1]).argmax(axis=1))
+                rows.append(dict(what="vocab_math_bf16_vs_f32", shape=sh["name"], dtype=dtype, f32_ms=round(m32, 3), bf16_ms=round(m16, 3),
+                                 speedup=round(m32 / m16, 2), larger_spread_ms=round(spread, 3), gain_exceeds_spread=bool(m32 - m16 > spread),
+                                 identical_caption_share=round(float(same_rois.mean()), 4), mean_first_differing_step=round(float(first.mean()), 2)))
+                print(json.dumps(rows[-1]), flush=True)
             del model
             torch.cuda.empty_cache()
         # the fused vocabulary top-1 alone, at the decode step's shape (M = K live rows, 1024 inputs)
@@ -95,7 +138,22 @@ def main():
         rows.append(dict(what="unfused_gemm_same_shape", shape=sh["name"], M=M_, K=Kd, V=V, ms=round(ms_g, 4),
                          fraction_of_fp32_peak=round(flops / (ms_g * 1e-3) / FP32_PEAK, 3)))
         print(json.dumps(rows[-1]), flush=True)
-        del X, W, logits
+        # the same step on bf16 operands: both tile shapes forced and the automatic choice; the roof is the larger of the MFMA time at
+        # the bf16 peak and the time to stream W [K,V] bf16 once from HBM
+        Xb, Wb = X.to(torch.bfloat16), W.to(torch.bfloat16)
+        t_mfma, t_hbm = flops / BF16_PEAK * 1e3, Kd * V * 2.0 / HBM_PEAK * 1e3
+        auto = ops.vocab_topk_bf16_tile(M_, V, Kd)
+        res = timed_alternating([lambda t=t: ops.vocab_top1(Xb, Wb, b, tokens=tok, tile=t) for t in (128, 256, 0)], 3, 20)
+        for t, (ms, all_ms) in zip((128, 256, 0), res):
+            rows.append(dict(what="vocab_top1_bf16", shape=sh["name"], M=M_, K=Kd, V=V, tile=t, tile_run=t or auto, ms=round(ms, 4),
+                             tflops=round(flops / ms / 1e9, 1), fraction_of_bf16_peak=round(flops / (ms * 1e-3) / BF16_PEAK, 3),
+                             mfma_roof_ms=round(t_mfma, 4), hbm_w_once_roof_ms=round(t_hbm, 4), larger_roof="mfma" if t_mfma > t_hbm else "hbm",
+                             fraction_of_larger_roof=round(max(t_mfma, t_hbm) / ms, 3), runs_ms=all_ms))
+            print(json.dumps(rows[-1]), flush=True)
+        faster = 128 if res[0][0] <= res[1][0] else 256
+        rows.append(dict(what="vocab_top1_bf16_tile_choice", shape=sh["name"], automatic=auto, faster=faster, automatic_is_faster=bool(auto == faster)))
+        print(json.dumps(rows[-1]), flush=True)
+        del X, W, Xb, Wb, logits
         torch.cuda.empty_cache()
     if args.out:
         os.makedirs(os.path.dirname(args.out) or ".", exist_ok=True)
