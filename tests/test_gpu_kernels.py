@@ -709,7 +709,7 @@ def test_rpn_proposals_bit_exact_given_scores(ops, B, S):
 def test_rpn_topk_order_ties_and_sizes(ops, kind, pre):
     """The hand-written top-k (radix select + ordered compaction + bitonic sort) against a stable descending argsort of the
     device's own scores: massive ties (all scores equal; a handful of distinct values), k above the in-LDS sort's 8192, and
-    k = every anchor."""
+    k = every anchor.  The NMS survivors of every size are compared with the oracle as well."""
     S, B = 256, 2
     rng = np.random.default_rng(len(kind) + pre)
     strides, scales, ratios = [4, 8, 16, 32, 64], (32, 64, 128, 256, 512), [0.5, 1, 2]
@@ -728,11 +728,18 @@ def test_rpn_topk_order_ties_and_sizes(ops, kind, pre):
     A = anchors.shape[0]
     k = min(pre, A)
     props, (scores, order, keep) = ops.rpn_proposals([dev(h) for h in heads], dev(anchors), (S, S), 50, 0.7, pre_nms_limit=pre, debug=True)
-    scores, order = scores.cpu().numpy(), order.cpu().numpy()
+    scores, order, keep, props = scores.cpu().numpy(), order.cpu().numpy(), keep.cpu().numpy(), props.cpu().numpy()
     assert order.shape == (B, k)
+    box = np.concatenate([h[..., 6:].reshape(B, -1, 4) for h in heads], axis=1)
     for b in range(B):
         want = np.argsort(-scores[b].astype(np.float64), kind="stable")[:k]
         np.testing.assert_array_equal(order[b], want)
+        # the survivors too (k = 9000, 12000 and "all" go through the serial scan), and the padding behind them
+        want_props, ix, kp = O.proposal_layer(scores[b], box[b], anchors, (S, S), 50, 0.7, pre_nms_limit=pre)
+        np.testing.assert_array_equal(keep[b][:len(kp)], kp)
+        assert np.all(keep[b][len(kp):] == -1)
+        np.testing.assert_allclose(props[b], want_props, rtol=3e-7, atol=1e-7)
+        assert np.all(props[b][len(kp):] == 0)
 
 
 @pytest.mark.parametrize("case", [(2, 16, 16, 64, 64, 3, 1), (1, 32, 32, 128, 256, 3, 1), (2, 16, 16, 256, 64, 1, 1), (1, 32, 32, 64, 128, 1, 2)])
