@@ -73,6 +73,12 @@ class RoiAlignDesc(C.Structure):
                 ("out", C.c_void_p), ("levels_out", C.c_void_p)]
 
 
+class RoiGroupsDesc(C.Structure):
+    _fields_ = [("B", C.c_int), ("R", C.c_int), ("pool", C.c_int), ("Hs", C.c_int * 4), ("Ws", C.c_int * 4),
+                ("boxes", C.c_void_p), ("image_area", C.c_float),
+                ("marks", C.c_void_p), ("lists", C.c_void_p * 4), ("counts", C.c_void_p)]
+
+
 class LstmFwdDesc(C.Structure):
     _fields_ = [("B", C.c_int), ("T", C.c_int), ("U", C.c_int),
                 ("z", C.c_void_p), ("U_rec", C.c_void_p), ("mask", C.c_void_p),
@@ -231,6 +237,9 @@ SYMBOLS = {
     "dc_mold_image_rgbx_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                          C.c_float, C.c_float, C.c_float, C.c_void_p]),
     "dc_roi_align_pyramid_f32": (C.c_int, [C.POINTER(RoiAlignDesc), C.c_void_p]),
+    "dc_roi_tile_groups": (C.c_int, [C.POINTER(RoiGroupsDesc), C.c_void_p]),
+    "dc_conv2d_winograd_group_count": (C.c_int, [C.c_int, C.c_int]),
+    "dc_conv2d_winograd_groups_f32": (C.c_int, [C.POINTER(ConvDesc), C.c_void_p, C.c_void_p, C.c_void_p]),
     "dc_subsample2_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "dc_proposals_workspace_bytes": (C.c_size_t, [C.POINTER(ProposalDesc)]),
     "dc_proposals_f32": (C.c_int, [C.POINTER(ProposalDesc), C.c_void_p, C.c_size_t, C.c_void_p]),

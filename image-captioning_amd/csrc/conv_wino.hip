@@ -51,6 +51,10 @@ struct Args {
     int N, H, W, Cin, Cout, relu;
     int gy, gx, groups;       // tile groups per image (rows, columns), in all
     unsigned x_bytes, u_bytes;
+    // list-driven launches (wino32b_list_kernel): the tile groups to compute, as group indices of the dense walk (image-major, then group
+    // row, then group column), and how many there are -- both written on the device by an earlier launch of the stream
+    const int* glist;
+    const int* gcount;
 };
 
 // U in fragment order, K in chunks of 16: f4 index ((((xi * NTG + ntg) * KC16 + kc) * 2 + j) * 64 + lane), lane = 32 h + i,
@@ -167,7 +171,7 @@ __device__ __forceinline__ int patch_swizzle(int y, int x) { return ((x >> 2) & 
 // two blocks per CU -- for layers with too few tiles to give every CU a 64-tile item (stage 5, fpn_p5, one-image batches).
 template <int HALVES>
 struct Cfg {
-    static constexpr int NT = 256 * HALVES, TGY = 4 * HALVES, TGX = 8, PH = 2 * TGY + 2, NPIX = PH * PW, SLOTS = NPIX * 8;
+    static constexpr int NT = 256 * HALVES, TGY = kWinoTGY * HALVES, TGX = kWinoTGX, PH = 2 * TGY + 2, NPIX = PH * PW, SLOTS = NPIX * 8;
     static constexpr int BUF = 32768 * HALVES;           // one patch buffer (HALVES = 2: 41.5 KiB used); buffer 1 = buffer 0 ^ BUF
     static constexpr int LDS_BYTES = 2 * BUF;
     static_assert(NDMA * NT >= SLOTS && NDMA * NT * 16 <= BUF, "patch buffer; the kernel issues the pieces three per step");
@@ -198,9 +202,13 @@ __device__ __forceinline__ f32x16 mfma_b(const u32x4& a, const u32x4& b, const f
 // instead of 32 of 64 (the fp32 matrix pipe's floor per 32-channel pair 3.41 us -> 1.28); the patch staging, the transform, the
 // output transform and the persistent item walk are the fp32 kernel's.  A lane's fragment of a K = 16 MFMA is its 8 channels
 // 8 h .. 8 h + 7 of the chunk: the values of the fp32 kernel's steps j = 0 and j = 1 side by side.
-template <int HALVES, bool B3, int NCH = 1>
+// LIST = true (the split-bf16 32-tile kernel only): the item walk covers the a.gcount[0] tile groups of a.glist instead of all a.groups --
+// the FPN output convolutions computed only where RoIAlign reads (dc_conv2d_winograd_groups_f32).  setup() maps the compact group index
+// through the list; everything an item does from there on is the dense kernel's, so what is computed is bit-identical to it.
+template <int HALVES, bool B3, int NCH = 1, bool LIST = false>
 __device__ __forceinline__ void wino_body(const Args& a) {
     static_assert(NCH == 1 || (NCH == 2 && HALVES == 1 && B3), "64-channel items: the split-bf16 32-tile kernel only");
+    static_assert(!LIST || (HALVES == 1 && B3), "list-driven item walk: the split-bf16 32-tile kernel only");
     using namespace wp;
     typedef Cfg<HALVES> C;
     constexpr int NT64 = C::NT, SLOTS = C::SLOTS, BUF = C::BUF;
@@ -210,7 +218,9 @@ __device__ __forceinline__ void wino_body(const Args& a) {
     const int wa = wave & 3, th = wave >> 2;
     const int gpi = a.gy * a.gx;
     const int NTG = a.Cout >> 5, KC = a.Cin >> 4, KP = a.Cin >> 5;
-    const int total = a.groups * (NTG / NCH);              // work items (slice, tile group); this block takes blockIdx.x, + gridDim.x, ...
+    int groups = a.groups;                                 // tile groups this launch computes
+    if constexpr (LIST) groups = min(max(*a.gcount, 0), a.groups);          // (block-uniform; an empty list: every block leaves below)
+    const int total = groups * (NTG / NCH);                // work items (slice, tile group); this block takes blockIdx.x, + gridDim.x, ...
     const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.x), 0, (int)a.x_bytes, 0x00020000);
 
     // ---- per work item: coordinates, patch DMA sources (slot s = n * 512 + tid of the image <-> pixel s >> 3, image chunk
@@ -221,8 +231,9 @@ __device__ __forceinline__ void wino_body(const Args& a) {
     unsigned ubyte3;                                       // B3: byte offset of this wave row's fragments for the item (block-uniform)
     auto setup = [&](int item) {
         const int bid = xcd_remap(item, total);            // gridDim.x % 8 == 0: item % 8 is this block's XCD for every item it takes
-        nb = bid / a.groups;
-        const int g = bid - nb * a.groups;
+        nb = bid / groups;
+        int g = bid - nb * groups;
+        if constexpr (LIST) g = min(max(a.glist[g], 0), a.groups - 1);      // (a list entry never leaves the map)
         img = g / gpi;
         const int gr = g - img * gpi;
         gyi = gr / a.gx;
@@ -598,6 +609,11 @@ template <int NCH>
 __global__ __launch_bounds__(256, 2) void wino32b_kernel(Args a) { wino_body<1, true, NCH>(a); }
 template __global__ void wino32b_kernel<1>(Args);
 template __global__ void wino32b_kernel<2>(Args);
+// ... and its list-driven form
+template <int NCH>
+__global__ __launch_bounds__(256, 2) void wino32b_list_kernel(Args a) { wino_body<1, true, NCH, true>(a); }
+template __global__ void wino32b_list_kernel<1>(Args);
+template __global__ void wino32b_list_kernel<2>(Args);
 
 }  // namespace wino
 
@@ -666,26 +682,34 @@ static int conv_winograd_cout(const dc_conv_desc* d) {
     return items >= 2 * kNumCU ? 64 : 32;
 }
 
-int conv2d_winograd(const dc_conv_desc* d, hipStream_t s) {
-    wino::Args a;
+// the kernel arguments of layer `d` on 32-tile (big = false) or 64-tile items
+static int wino_args(const dc_conv_desc* d, bool b3, bool big, wino::Args& a) {
     a.x = d->x;
-    const bool b3 = wino_b3(d);
     a.u = b3 ? reinterpret_cast<const f4*>(d->w_wino_b3) : reinterpret_cast<const f4*>(d->w_wino);
     a.y = d->y;
     a.scale = d->scale;
     a.shift = d->shift;
     a.N = d->N; a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.Cout = d->Cout; a.relu = d->relu;
-    const int th = (d->H + 1) / 2, tw = (d->W + 1) / 2;
     const size_t x_bytes = (size_t)d->N * d->H * d->W * d->Cin * sizeof(float);
     // the kernels address the input through ONE buffer resource with 32-bit byte offsets (and a signed num_records): a P2-level input of
     // 32 or more 1024 x 1024 images does not fit -- split the batch
     DC_REQUIRE(x_bytes < (1ull << 31), DC_EINVAL, "dc_conv2d (winograd): the input tensor has %zu bytes, the kernel addresses < 2 GiB", x_bytes);
     a.x_bytes = (unsigned)x_bytes;
     a.u_bytes = (unsigned)((size_t)16 * d->Cin * d->Cout * (b3 ? 6 : 4));
-    const bool big = conv_winograd_tiles(d) == 64;
-    a.gy = (th + (big ? 8 : 4) - 1) / (big ? 8 : 4);
-    a.gx = (tw + 7) / 8;
+    a.gy = big ? (wino_groups_y(d->H) + 1) / 2 : wino_groups_y(d->H);     // (64-tile items: two 32-tile group rows each)
+    a.gx = wino_groups_x(d->W);
     a.groups = d->N * a.gy * a.gx;
+    a.glist = nullptr;
+    a.gcount = nullptr;
+    return DC_OK;
+}
+
+int conv2d_winograd(const dc_conv_desc* d, hipStream_t s) {
+    wino::Args a;
+    const bool b3 = wino_b3(d);
+    const bool big = conv_winograd_tiles(d) == 64;
+    const int rc = wino_args(d, b3, big, a);
+    if (rc) return rc;
     const bool wide = b3 && !big && conv_winograd_cout(d) == 64;
     const long items = (long)a.groups * (d->Cout / (wide ? 64 : 32));
     DC_REQUIRE(items < (1l << 31), DC_EINVAL, "dc_conv2d (winograd): grid too large");
@@ -717,9 +741,49 @@ int conv2d_winograd(const dc_conv_desc* d, hipStream_t s) {
     return check_launch("dc_conv2d (winograd)");
 }
 
+// The list-driven launch: 32-tile items on the split-bf16 kernel, the grid sized WITHOUT the count (the host never reads it): the blocks
+// that fit the chip, or as many as the layer has items when that is fewer; a block whose first item lies behind the list's end leaves at
+// once.  Output channels per item: 32 -- the lists are short (the benchmark's 64 RoIs touch 5 - 134 groups per level), and 64-channel
+// items halve an item count that already fills only one to three rounds of the 512 block slots (profiles/r08_fpn_rois.txt);
+// DCAP_WINO_COUT = 64 forces the wide items (tests).
+int conv2d_winograd_groups(const dc_conv_desc* d, const int* glist, const int* gcount, hipStream_t s) {
+    wino::Args a;
+    const int rc = wino_args(d, true, false, a);
+    if (rc) return rc;
+    a.glist = glist;
+    a.gcount = gcount;
+    const bool wide = wino_cout_force() == 64 && d->Cout % 64 == 0;
+    const long items = (long)a.groups * (d->Cout / (wide ? 64 : 32));
+    DC_REQUIRE(items < (1l << 31), DC_EINVAL, "dc_conv2d_winograd_groups: grid too large");
+    const long full = 2L * kNumCU;
+    const unsigned grid = items >= full ? (unsigned)full : (unsigned)std::max<long>(8, items / 8 * 8);
+    if (wide) {
+        DC_ENSURE_DYN_LDS((&wino::wino32b_list_kernel<2>), wino::wp::Cfg<1>::LDS_BYTES);
+        hipLaunchKernelGGL((wino::wino32b_list_kernel<2>), dim3(grid), dim3(wino::wp::Cfg<1>::NT), wino::wp::Cfg<1>::LDS_BYTES, s, a);
+    } else {
+        DC_ENSURE_DYN_LDS((&wino::wino32b_list_kernel<1>), wino::wp::Cfg<1>::LDS_BYTES);
+        hipLaunchKernelGGL((wino::wino32b_list_kernel<1>), dim3(grid), dim3(wino::wp::Cfg<1>::NT), wino::wp::Cfg<1>::LDS_BYTES, s, a);
+    }
+    return check_launch("dc_conv2d_winograd_groups_f32");
+}
+
 }  // namespace dcap
 
 using namespace dcap;
+
+extern "C" int dc_conv2d_winograd_groups_f32(const dc_conv_desc* d, const int32_t* groups, const int32_t* count, void* stream) {
+    DC_REQUIRE(d && d->x && d->y && groups && count, DC_EINVAL, "dc_conv2d_winograd_groups: null pointer");
+    DC_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0, DC_EINVAL, "dc_conv2d_winograd_groups: bad N/H/W");
+    DC_REQUIRE(wino_b3(d), DC_EINVAL,
+               "dc_conv2d_winograd_groups: the layer must be one the split-bf16 Winograd kernel takes (3x3, stride 1, pad 1, Cin and Cout "
+               "multiples of 32, no residual, fp32 math, w_wino_b3 given, 16-byte aligned operands, input below 2 GiB)");
+    return conv2d_winograd_groups(d, groups, count, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int dc_conv2d_winograd_group_count(int H, int W) {
+    if (H <= 0 || W <= 0) return 0;
+    return wino_groups_y(H) * wino_groups_x(W);
+}
 
 extern "C" size_t dc_conv2d_winograd_weight_bytes(int Cin, int Cout) {
     if (Cin <= 0 || Cout <= 0 || Cin % 32 || Cout % 32) return 0;

@@ -63,6 +63,13 @@ __device__ __forceinline__ int xcd_remap(int bid, int nblk) {
     return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + bid / kNumXCD;
 }
 
+// Tile-group geometry of the 32-tile Winograd work items (conv_wino.hip: wp::Cfg<1>; the RoI tile-group list of roialign.hip marks
+// the same groups): a group is kWinoTGY x kWinoTGX tiles of 2 x 2 output pixels, ragged at the bottom and right edges.
+constexpr int kWinoTGY = 4, kWinoTGX = 8;
+constexpr int kWinoGroupH = 2 * kWinoTGY, kWinoGroupW = 2 * kWinoTGX;      // output pixels per group: 8 x 16
+inline int wino_groups_y(int H) { return ((H + 1) / 2 + kWinoTGY - 1) / kWinoTGY; }
+inline int wino_groups_x(int W) { return ((W + 1) / 2 + kWinoTGX - 1) / kWinoTGX; }
+
 // Zero `bytes` bytes at `p` (both multiples of 4) with a KERNEL.  Used instead of hipMemsetAsync wherever a launch sequence may be
 // captured into a hipGraph: a captured memset becomes a memset NODE, and on this runtime the joint train step replayed as a graph
 // faulted on its second launch inside the top-k radix select (whose histograms a memset node was supposed to clear) while the same

@@ -31,6 +31,35 @@ __device__ __forceinline__ int roi_level(float y1, float x1, float y2, float x2,
     return min(5, max(2, 4 + r));
 }
 
+// Sample coordinates of bin row / column `p` of a box on a map of extent n (TF's operation order).
+__device__ __forceinline__ float roi_sample(float lo, float hi, int p, int n, int pool) {
+    if (pool > 1) {
+        const float step = div_rn(mul_rn(sub_rn(hi, lo), (float)(n - 1)), (float)(pool - 1));
+        return add_rn(mul_rn(lo, (float)(n - 1)), mul_rn((float)p, step));
+    }
+    return mul_rn(mul_rn(0.5f, add_rn(lo, hi)), (float)(n - 1));
+}
+
+// The one sample of bin (py, px) of box bx = (y1, x1, y2, x2) on an H x W map: its coordinates, whether it lies inside the map (outside:
+// the bin is zero and no pixel is read) and the rows / columns of its four corner pixels.  The forward kernel and the tile-group list
+// (roi_tile_groups_kernel) take every decision here, so the list can never disagree with what the forward reads.
+struct RoiBin {
+    float in_y, in_x;
+    bool ok;
+    int top, bot, left, right;
+};
+__device__ __forceinline__ RoiBin roi_bin(const float4& bx, int py, int px, int H, int W, int pool) {
+    RoiBin r;
+    r.in_y = roi_sample(bx.x, bx.z, py, H, pool);
+    r.in_x = roi_sample(bx.y, bx.w, px, W, pool);
+    r.ok = (r.in_y >= 0.f) && (r.in_y <= (float)(H - 1)) && (r.in_x >= 0.f) && (r.in_x <= (float)(W - 1));
+    r.top = (int)floorf(r.in_y);
+    r.bot = (int)ceilf(r.in_y);
+    r.left = (int)floorf(r.in_x);
+    r.right = (int)ceilf(r.in_x);
+    return r;
+}
+
 __global__ __launch_bounds__(256) void roi_align_kernel(dc_roialign_desc d) {
     const int wave = (blockIdx.x * 256 + threadIdx.x) >> 6, lane = threadIdx.x & 63;
     const int bins = d.pool * d.pool;
@@ -46,19 +75,13 @@ __global__ __launch_bounds__(256) void roi_align_kernel(dc_roialign_desc d) {
     const float* fm = d.maps[li] + (long)(box / d.R) * H * W * d.C;
     float4* out = reinterpret_cast<float4*>(d.out) + (long)wave * C4;
 
-    const float hs = (d.pool > 1) ? div_rn(mul_rn(sub_rn(bx.z, bx.x), (float)(H - 1)), (float)(d.pool - 1)) : 0.f;
-    const float ws = (d.pool > 1) ? div_rn(mul_rn(sub_rn(bx.w, bx.y), (float)(W - 1)), (float)(d.pool - 1)) : 0.f;
-    const float in_y = (d.pool > 1) ? add_rn(mul_rn(bx.x, (float)(H - 1)), mul_rn((float)py, hs))
-                                    : mul_rn(mul_rn(0.5f, add_rn(bx.x, bx.z)), (float)(H - 1));
-    const float in_x = (d.pool > 1) ? add_rn(mul_rn(bx.y, (float)(W - 1)), mul_rn((float)px, ws))
-                                    : mul_rn(mul_rn(0.5f, add_rn(bx.y, bx.w)), (float)(W - 1));
-    const bool ok = (in_y >= 0.f) && (in_y <= (float)(H - 1)) && (in_x >= 0.f) && (in_x <= (float)(W - 1));
-    if (!ok) {
+    const RoiBin sb = roi_bin(bx, py, px, H, W, d.pool);
+    if (!sb.ok) {
         for (int c = lane; c < C4; c += 64) out[c] = make_float4(0.f, 0.f, 0.f, 0.f);
         return;
     }
-    const int top = (int)floorf(in_y), bot = (int)ceilf(in_y), left = (int)floorf(in_x), right = (int)ceilf(in_x);
-    const float ly = in_y - (float)top, lx = in_x - (float)left;
+    const int top = sb.top, bot = sb.bot, left = sb.left, right = sb.right;
+    const float ly = sb.in_y - (float)top, lx = sb.in_x - (float)left;
     const float4* tl = reinterpret_cast<const float4*>(fm + ((long)top * W + left) * d.C);
     const float4* tr = reinterpret_cast<const float4*>(fm + ((long)top * W + right) * d.C);
     const float4* bl = reinterpret_cast<const float4*>(fm + ((long)bot * W + left) * d.C);
@@ -75,15 +98,6 @@ __global__ __launch_bounds__(256) void roi_align_kernel(dc_roialign_desc d) {
         DC_LERP(x) DC_LERP(y) DC_LERP(z) DC_LERP(w)
         out[c] = o;
     }
-}
-
-// Sample coordinates of bin row / column `p` of a box on a map of extent n (TF's operation order, as in the forward kernel).
-__device__ __forceinline__ float roi_sample(float lo, float hi, int p, int n, int pool) {
-    if (pool > 1) {
-        const float step = div_rn(mul_rn(sub_rn(hi, lo), (float)(n - 1)), (float)(pool - 1));
-        return add_rn(mul_rn(lo, (float)(n - 1)), mul_rn((float)p, step));
-    }
-    return mul_rn(mul_rn(0.5f, add_rn(lo, hi)), (float)(n - 1));
 }
 
 // backward, DETERMINISTIC (round 3): gather per destination pixel instead of an atomic scatter per bin.  One wave per pixel of
@@ -182,9 +196,109 @@ __global__ __launch_bounds__(256) void roi_align_bwd_gather_kernel(dc_roialign_d
         }
 }
 
+// ------------------------------------------------------------------------------------------------------------------------
+// The tile groups of the pyramid maps that roi_align_kernel reads for a set of boxes (dc_roi_tile_groups): the FPN output convolutions
+// then compute those groups only (conv_wino.hip, wino32b_list_kernel).  ONE block: (1) clear the marks, one per group, the four levels
+// end to end, (2) thread per (box, bin): the forward's own routing and sample (roi_level, roi_bin), a mark on the group of each of the
+// four corner pixels at the routed level -- a sample outside the map marks nothing, as the forward reads nothing there --, (3) one
+// ballot scan over all marks, RG_THREADS at a time: a marked group goes to its level's list at its rank among the level's marks, so
+// every list is in ascending group index (image-major, group row, group column: the dense item walk's index), and counts[level] is
+// the level's number of marks.  Plain stores only; the same lists in the same order on every run.  The marks live in LDS when they fit
+// (RG_LDS_MARKS: 1360 groups at two 1024 x 1024 images) -- the launch is then two global round trips deep, the boxes in and the lists
+// out -- and in the caller's scratch otherwise.
+// ------------------------------------------------------------------------------------------------------------------------
+constexpr int RG_THREADS = 1024, RG_WAVES = RG_THREADS / 64, RG_LDS_MARKS = 8192;
+struct RoiGroupsArgs {
+    dc_roi_groups_desc d;
+    int gy[4], gx[4], off[5];        // tile groups per image (rows, columns); the level's first mark, off[4] = all marks
+};
+
+__global__ __launch_bounds__(RG_THREADS) void roi_tile_groups_kernel(RoiGroupsArgs a) {
+    const dc_roi_groups_desc& d = a.d;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    __shared__ int lds_marks[RG_LDS_MARKS];
+    __shared__ int wsum[4][RG_WAVES];                    // per wave: marks of the chunk [0] in all, [l] below level l's first mark
+    const int nmarks = a.off[4];
+    int* marks = nmarks <= RG_LDS_MARKS ? lds_marks : d.marks;
+    for (int i = tid; i < nmarks; i += RG_THREADS) marks[i] = 0;
+    __syncthreads();
+    const int bins = d.pool * d.pool, samples = d.B * d.R * bins;
+    for (int s = tid; s < samples; s += RG_THREADS) {
+        const int box = s / bins, bin = s - box * bins;
+        const int py = bin / d.pool, px = bin - py * d.pool;
+        const float4 bx = reinterpret_cast<const float4*>(d.boxes)[box];
+        const int li = roi_level(bx.x, bx.y, bx.z, bx.w, d.image_area) - 2;
+        const RoiBin sb = roi_bin(bx, py, px, d.Hs[li], d.Ws[li], d.pool);
+        if (!sb.ok) continue;
+        int* m = marks + a.off[li] + (box / d.R) * a.gy[li] * a.gx[li];
+        const int gt = sb.top / kWinoGroupH * a.gx[li], gb = sb.bot / kWinoGroupH * a.gx[li];
+        const int gl = sb.left / kWinoGroupW, gr = sb.right / kWinoGroupW;
+        m[gt + gl] = 1;
+        m[gt + gr] = 1;
+        m[gb + gl] = 1;
+        m[gb + gr] = 1;
+    }
+    __syncthreads();
+    int below[4] = {0, 0, 0, 0};                         // marks seen so far: [0] in all, [l] below level l's first mark (block-uniform)
+    for (int c0 = 0; c0 < nmarks; c0 += RG_THREADS) {
+        const int i = c0 + tid;
+        const bool on = i < nmarks && marks[i] != 0;
+        const int l = i >= a.off[3] ? 3 : (i >= a.off[2] ? 2 : (i >= a.off[1] ? 1 : 0));
+        const int first = l == 3 ? a.off[3] : (l == 2 ? a.off[2] : (l == 1 ? a.off[1] : 0));       // (a.off[0] = 0)
+        const unsigned long long b = __ballot(on);
+        const unsigned long long b1 = __ballot(on && i < a.off[1]), b2 = __ballot(on && i < a.off[2]), b3 = __ballot(on && i < a.off[3]);
+        if (lane == 0) {
+            wsum[0][wave] = __popcll(b);
+            wsum[1][wave] = __popcll(b1);
+            wsum[2][wave] = __popcll(b2);
+            wsum[3][wave] = __popcll(b3);
+        }
+        __syncthreads();
+        int before = 0, add[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int w = 0; w < RG_WAVES; ++w) {
+            before += w < wave ? wsum[0][w] : 0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) add[k] += wsum[k][w];
+        }
+        // rank among ALL marks, less the marks below this level's first one: they all lie in this chunk or an earlier one
+        const int rank = below[0] + before + __popcll(b & ((1ull << lane) - 1ull));
+        const int lower = l == 3 ? below[3] + add[3] : (l == 2 ? below[2] + add[2] : (l == 1 ? below[1] + add[1] : 0));
+        if (on) d.lists[l][rank - lower] = i - first;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) below[k] += add[k];
+        __syncthreads();
+    }
+    if (tid < 4) {                                       // every mark below level l + 1's first one, less those below level l's
+        const int lo = tid == 3 ? below[3] : (tid == 2 ? below[2] : (tid == 1 ? below[1] : 0));
+        const int hi = tid == 3 ? below[0] : (tid == 2 ? below[3] : (tid == 1 ? below[2] : below[1]));
+        d.counts[tid] = hi - lo;
+    }
+}
+
 }  // namespace dcap
 
 using namespace dcap;
+
+extern "C" int dc_roi_tile_groups(const dc_roi_groups_desc* d, void* stream) {
+    DC_REQUIRE(d && d->boxes && d->marks && d->counts, DC_EINVAL, "dc_roi_tile_groups: null pointer");
+    DC_REQUIRE(d->B > 0 && d->R > 0 && d->pool > 0, DC_EINVAL, "dc_roi_tile_groups: bad B/R/pool");
+    DC_REQUIRE(aligned16(d->boxes), DC_EALIGN, "dc_roi_tile_groups: boxes not 16-byte aligned");
+    RoiGroupsArgs a;
+    a.d = *d;
+    long off = 0;
+    for (int l = 0; l < 4; ++l) {
+        DC_REQUIRE(d->lists[l] && d->Hs[l] > 0 && d->Ws[l] > 0, DC_EINVAL, "dc_roi_tile_groups: bad level %d", l);
+        a.gy[l] = wino_groups_y(d->Hs[l]);
+        a.gx[l] = wino_groups_x(d->Ws[l]);
+        a.off[l] = (int)off;
+        off += (long)d->B * a.gy[l] * a.gx[l];
+    }
+    a.off[4] = (int)off;
+    DC_REQUIRE(off < (1l << 30) && (long)d->B * d->R * d->pool * d->pool < (1l << 30), DC_EINVAL, "dc_roi_tile_groups: too many groups / samples");
+    hipLaunchKernelGGL(roi_tile_groups_kernel, dim3(1), dim3(RG_THREADS), 0, static_cast<hipStream_t>(stream), a);
+    return check_launch("roi_tile_groups_kernel");
+}
 
 extern "C" int dc_roi_align_pyramid_bwd_f32(const dc_roialign_desc* d, void* stream) {
     DC_REQUIRE(d && d->boxes && d->out, DC_EINVAL, "dc_roi_align_pyramid_bwd: null pointer");

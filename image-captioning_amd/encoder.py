@@ -359,12 +359,21 @@ class EncoderPlan:
         P2, P3 = self._buf(H // 4, W // 4, 256), self._buf(H // 8, W // 8, 256)
         P4, P5 = self._buf(H // 16, W // 16, 256), self._buf(H // 32, W // 32, 256)
         rp = self.rpn is not None                       # the RPN's shared convolution reads the pyramid maps
+        self._n_lateral = len(self._ops)                # ops [_n_lateral, _n_lateral + 4): fpn_p2..p5 (forward_rois)
         self._conv("fpn_p2", t2, P2, relu=False, bf16=rp)
         self._conv("fpn_p3", t3, P3, relu=False, bf16=rp)
         self._conv("fpn_p4", t4, P4, relu=False, bf16=rp)
         self._conv("fpn_p5", t5, P5, relu=False, bf16=rp)
         self.P = (P2, P3, P4, P5)
         self.pre = (t2, t3, t4, t5)                        # top-down sums: the inputs of fpn_p2..p5 (kept for the joint backward)
+        # forward_rois' fast path: the pyramid maps have RoIAlign as their only reader (no RPN), fpn_p2..p5 are the last four launches
+        # of the pass and all run the split-bf16 Winograd kernel on frozen weights, fp32 storage.  DCAP_SPARSE_FPN is the callers' switch.
+        pops = self._ops[self._n_lateral:]
+        self.sparse_rois = (self.rpn is None and not self.fast_bf16 and not self.train_stages and not self._external_bn and len(pops) == 4 and
+                            all(op[0] == "conv" and op[2] == "fpn_p%d" % (2 + i) and op[2] not in self._external and op[1].w_wino_b3
+                                for i, op in enumerate(pops)))
+        self._roi_groups = None                            # ops.RoiTileGroups, made by the first forward_rois()
+        self._roi_boxes = {}                               # {R: plan-owned [B,R,4] box buffer}
         if self.rpn is not None:
             from .utils import generate_pyramid_anchors
             P6 = self._buf(H // 64, W // 64, 256)
@@ -552,6 +561,54 @@ class EncoderPlan:
             cs = self._steps[part] = step_graph.CapturedStep()
         cs.run(body, warm_calls=1, propagate=True)
 
+    def _run_rois(self, boxes):
+        """forward_rois() between the FPN laterals and RoIAlign: the tile-group lists of `boxes`, fpn_p2..p5 on them."""
+        g = ops.roi_tile_groups(boxes, self._roi_groups, float(self.H * self.W), 7)
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        for l, op in enumerate(self._ops[self._n_lateral:]):
+            rc = self.lib.dc_conv2d_winograd_groups_f32(C.byref(op[1]), C.c_void_p(g.lists[l].data_ptr()), g.count_ptr(l), stream)
+            if rc:
+                check(rc, "dc_conv2d_winograd_groups_f32(%s)" % op[2])
+
+    def forward_rois(self, images_u8, boxes_norm, out=None, before_align=None):
+        """forward() + roi_features(boxes_norm=...) for boxes known BEFORE the pass (ground-truth boxes), with the FPN output
+        convolutions computed only on the tile groups (8 x 16 output pixels) RoIAlign reads: trunk, the four FPN laterals (dense), the
+        tile-group lists of the boxes (dc_roi_tile_groups), fpn_p2..p5 on the listed groups (dc_conv2d_winograd_groups_f32), RoIAlign
+        into `out`.  The features are bit-identical to the dense path's: every computed output sums the same products in the same order.
+
+        images_u8 as in forward(); boxes_norm [B,R,4] normalised (normalize_boxes), any device: copied into a plan-owned buffer first,
+        so nothing captured holds a caller's address, and the lists are rebuilt on the device for every call.  Two captured parts:
+        "lat" (trunk + laterals, whatever R is) and "rois<R>" (the list kernel, whose launch carries R, and the four list-driven ones).
+        before_align: optional callable run right in front of the RoIAlign launch, the only one that writes `out` (the training
+        pipeline waits there for the slot's last reader).
+
+        AFTER THIS CALL self.P HOLDS VALID VALUES ONLY INSIDE THE LISTED GROUPS: whatever else the maps hold is stale.  Call forward()
+        before roi_features() with other boxes, or before reading the maps whole.
+
+        Plans without the fast path (self.sparse_rois False: an RPN, which reads whole maps; trainable FPN / ResNet stages; bf16
+        storage; the direct or fp32-product kernels on the FPN outputs; Vgg16Plan) run the dense pass and roi_features() here."""
+        if not self.sparse_rois:
+            self.forward(images_u8)
+            if before_align is not None:
+                before_align()
+            return self.roi_features(boxes_norm=boxes_norm.to(self.device, torch.float32).contiguous(), out=out)
+        if images_u8 is not None:
+            self.images.copy_(images_u8, non_blocking=bool(images_u8.is_cuda or images_u8.is_pinned()))
+        B, R = int(boxes_norm.shape[0]), int(boxes_norm.shape[1])
+        if B != self.B or tuple(boxes_norm.shape[2:]) != (4,):
+            raise ValueError("forward_rois: boxes must be [%d,R,4], got %s" % (self.B, tuple(boxes_norm.shape)))
+        if self._roi_groups is None:
+            self._roi_groups = ops.RoiTileGroups(self.B, [(p.shape[1], p.shape[2]) for p in self.P], self.device)
+        boxes = self._roi_boxes.get(R)
+        if boxes is None:
+            boxes = self._roi_boxes[R] = torch.zeros((self.B, R, 4), dtype=torch.float32, device=self.device)
+        boxes.copy_(boxes_norm, non_blocking=bool(boxes_norm.is_cuda or boxes_norm.is_pinned()))
+        self._run_part("lat", lambda: self._run_ops(0, self._n_lateral))
+        self._run_part("rois%d" % R, lambda: self._run_rois(boxes))
+        if before_align is not None:
+            before_align()
+        return ops.roi_align_pyramid(list(self.P), boxes, float(self.H * self.W), 7, out=out)
+
     def forward_trunk(self, images_u8=None):
         if self._external_bn:
             raise RuntimeError("forward_trunk: this plan folds trainable BatchNorm layers inside the backbone pass; use forward()")
@@ -653,6 +710,7 @@ class Vgg16Plan(EncoderPlan):
         self.C = (x,)
         self.P = (x, x, x, x)            # every RoI reads the one stride-16 map, whatever level its size routes it to
         self.pre = None
+        self.sparse_rois = False         # (forward_rois: the dense pass)
         self._ws = torch.empty(max(self._ws_bytes, 16), dtype=torch.uint8, device=self.device)
 
     def _run_ops(self):

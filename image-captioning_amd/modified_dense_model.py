@@ -115,13 +115,17 @@ class DenseImageCapRCNN(object):
                                            self.config.MEAN_PIXEL, rpn=self._rpn_config(), math=self.conv_math)
         return self._plans[key]
 
-    def extract_features(self, images_u8, rois_px=None):
+    def extract_features(self, images_u8, rois_px=None, sparse=False):
         """Device-resident fast path: images [B,H,W,3] uint8 (numpy or torch, already the model's
         size), rois [B,R,4] pixels (or None with use_generated_rois: the RPN's proposals)
-        -> torch [B,R,7,7,256] on the GPU (no host round trip)."""
+        -> torch [B,R,7,7,256] on the GPU (no host round trip).
+        sparse=True (caller-given RoIs, a plan without the RPN): the FPN output convolutions run only where RoIAlign reads
+        (EncoderPlan.forward_rois) -- the same features bit for bit, but the plan's pyramid maps are then valid only there."""
         imgs = torch.as_tensor(images_u8)
         B, H, W, _ = imgs.shape
         p = self.plan(B, H, W)
+        if sparse and not self.use_generated_rois and p.sparse_rois:
+            return p.forward_rois(imgs, p.normalize_boxes(rois_px))
         p.forward(imgs)
         if self.use_generated_rois:
             self.last_proposals = p.proposals()
@@ -150,7 +154,7 @@ class DenseImageCapRCNN(object):
         assert len(images) == self.config.BATCH_SIZE, "len(images) must be equal to BATCH_SIZE"
         molded, metas, windows = self.mold_inputs(images)
         rois = None if self.use_generated_rois else np.asarray(rois, np.float32)
-        feats = self.extract_features(molded, rois)
+        feats = self.extract_features(molded, rois, sparse=True)      # (only the features leave this call: nothing reads the maps whole)
         feats = feats.clone() if device_features else feats.cpu().numpy()
         n = self.config.POST_NMS_ROIS_INFERENCE
         results = [{"features": feats[i][:n]} for i in range(len(images))]

@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import (PwChainDesc, ConvBf16Desc, AmsgradDesc, DetectionTargetsDesc, BnReluDesc, ConvDesc, ConvWgradBf16Desc, GemmBf16Desc, VocabCeDesc, ProposalDesc, RpnLossDesc, GemmDesc, LstmBwdDesc, LstmFwdDesc, RoiAlignDesc,
+from ._lib import (PwChainDesc, ConvBf16Desc, AmsgradDesc, DetectionTargetsDesc, BnReluDesc, ConvDesc, ConvWgradBf16Desc, GemmBf16Desc, VocabCeDesc, ProposalDesc, RpnLossDesc, GemmDesc, LstmBwdDesc, LstmFwdDesc, RoiAlignDesc, RoiGroupsDesc,
                    SoftmaxCeDesc, VocabTop1Desc, VocabTopkDesc, VocabTop1Bf16Desc, VocabTopkBf16Desc, BeamSelectDesc, LstmStepDesc, check)
 
 
@@ -553,6 +553,71 @@ def roi_align_pyramid(maps, boxes, image_area, pool=7, out=None, levels_out=None
     d.boxes, d.image_area, d.out = boxes.data_ptr(), float(image_area), out.data_ptr()
     d.levels_out = None if levels_out is None else _chk(levels_out, torch.int32, "levels").data_ptr()
     check(lib.dc_roi_align_pyramid_f32(C.byref(d), _stream()), "dc_roi_align_pyramid_f32")
+    return out
+
+
+class RoiTileGroups(object):
+    """Device buffers of dc_roi_tile_groups for a batch of B images whose pyramid levels have the extents `hw` [(H, W)] * 4: per level a
+    list of tile-group indices (int32, as long as the level has groups) and, in counts[level], how many of them the last
+    roi_tile_groups() call listed.  Nothing here is ever read by the host on the hot path."""
+
+    def __init__(self, B, hw, device):
+        lib = _lib.load()
+        self.B, self.hw = int(B), [(int(h), int(w)) for h, w in hw]
+        if len(self.hw) != 4:
+            raise _lib.DcapError("RoiTileGroups: four pyramid levels expected")
+        self.per_image = [lib.dc_conv2d_winograd_group_count(h, w) for h, w in self.hw]
+        self.lists = [torch.zeros(self.B * n, dtype=torch.int32, device=device) for n in self.per_image]
+        self.counts = torch.zeros(4, dtype=torch.int32, device=device)
+        self.marks = torch.zeros(self.B * sum(self.per_image), dtype=torch.int32, device=device)
+
+    def count_ptr(self, level):
+        return C.c_void_p(self.counts.data_ptr() + 4 * level)
+
+
+def roi_tile_groups(boxes, groups, image_area, pool=7):
+    """The tile groups of P2..P5 that roi_align_pyramid(maps, boxes, image_area, pool) reads, into `groups` (RoiTileGroups): the same
+    routing and sampling decisions, taken by the same device functions.  boxes [B,R,4] normalised float32."""
+    lib = _lib.load()
+    _chk(boxes, name="boxes")
+    B, R, _ = boxes.shape
+    if not boxes.is_contiguous() or B != groups.B:
+        raise _lib.DcapError("roi_tile_groups: boxes must be contiguous [B,R,4] with the B the group buffers were made for")
+    d = RoiGroupsDesc()
+    d.B, d.R, d.pool = B, R, pool
+    for i, (h, w) in enumerate(groups.hw):
+        d.Hs[i], d.Ws[i] = h, w
+        d.lists[i] = groups.lists[i].data_ptr()
+    d.boxes, d.image_area = boxes.data_ptr(), float(image_area)
+    d.marks, d.counts = groups.marks.data_ptr(), groups.counts.data_ptr()
+    check(lib.dc_roi_tile_groups(C.byref(d), _stream()), "dc_roi_tile_groups")
+    return groups
+
+
+def conv2d_winograd_groups(x, w_packed, w_wino_b3, group_list, count, out, scale=None, shift=None, relu=False):
+    """The 3x3 / stride 1 / 'same' layer of conv2d(..., w_wino_b3=...) on the tile groups of `group_list` only (int32 device tensor;
+    `count`: int32 device tensor whose first element is the list's length).  Listed groups of `out` get conv2d's values bit for bit,
+    nothing else of it is written.  dc_conv2d_winograd_groups_f32."""
+    lib = _lib.load()
+    _chk(x, name="x"), _chk(w_packed, name="w"), _chk(out, name="out")
+    _chk(group_list, torch.int32, "group_list"), _chk(count, torch.int32, "count")
+    N, H, W, Cin = x.shape
+    Cout = w_packed.shape[0]
+    if not x.is_contiguous() or not out.is_contiguous() or tuple(out.shape) != (N, H, W, Cout):
+        raise _lib.DcapError("conv2d_winograd_groups: x and out must be contiguous [N,H,W,C]")
+    if not w_wino_b3.is_contiguous() or w_wino_b3.numel() != 48 * Cin * Cout:
+        raise _lib.DcapError("conv2d_winograd_groups: w_wino_b3 must be the contiguous winograd_pack_b3() of this layer's kernel")
+    if group_list.numel() < N * lib.dc_conv2d_winograd_group_count(H, W) or count.numel() < 1:
+        raise _lib.DcapError("conv2d_winograd_groups: the list must have room for every tile group of the layer")
+    d = ConvDesc()
+    d.N, d.H, d.W, d.Cin = N, H, W, Cin
+    d.Cout, d.kh, d.kw, d.stride, d.pad_t, d.pad_l, d.Ho, d.Wo = Cout, 3, 3, 1, 1, 1, H, W
+    d.x, d.w, d.y = x.data_ptr(), w_packed.data_ptr(), out.data_ptr()
+    d.scale = None if scale is None else scale.data_ptr()
+    d.shift = None if shift is None else shift.data_ptr()
+    d.relu = int(relu)
+    d.w_wino_b3 = _chk(w_wino_b3, torch.int16, "w_wino_b3").data_ptr()
+    check(lib.dc_conv2d_winograd_groups_f32(C.byref(d), _ptr(group_list), _ptr(count), _stream()), "dc_conv2d_winograd_groups_f32")
     return out
 
 

@@ -33,6 +33,10 @@ class CaptionTrainPipeline(object):
         self.pending = None                                          # (slot, tables) awaiting its decoder pass
         self.n = 0
         self.late_wait = os.environ.get("DCAP_PIPE_LATE_WAIT", "1") != "0"      # the slot event gates the RoIAlign launch only (see _encode)
+        # the boxes are in hand before the encoder pass is enqueued: the FPN output convolutions run only on the tile groups RoIAlign reads
+        # (EncoderPlan.forward_rois: 0.64 ms of dense launches per pass become a list kernel and four short ones, same features bit for
+        # bit).  DCAP_SPARSE_FPN=0: the dense pass, for A/B runs.
+        self.sparse_fpn = os.environ.get("DCAP_SPARSE_FPN", "1") != "0" and bool(getattr(plan, "sparse_rois", False))
         # inputs of the steps in flight, each with the event recorded behind its decoder pass (which itself waits for its encoder
         # pass): their memory -- allocated on the PRODUCER's stream -- must not go back to the allocator, and from there into the next
         # upload, while a kernel that reads them is still queued.  Lifetime follows the GPU, not a host step count: an entry is
@@ -48,6 +52,12 @@ class CaptionTrainPipeline(object):
         with torch.cuda.stream(self.s_enc):
             if self.n >= 2 and not self.late_wait:
                 self.s_enc.wait_event(self.ev_free[slot])
+            if self.sparse_fpn:
+                # (the same late wait: forward_rois runs it directly in front of its RoIAlign launch, the only writer of the slot)
+                late = (lambda: self.s_enc.wait_event(self.ev_free[slot])) if self.n >= 2 and self.late_wait else None
+                self.plan.forward_rois(images, boxes, out=self.feat[slot], before_align=late)
+                self.ev_feat[slot].record(self.s_enc)
+                return
             self.plan.forward(images)
             # Only the RoIAlign launch writes the slot the decoder pass of two batches ago read: the ~100 convolution launches in front of it
             # wait for nothing but the previous encoder pass.  (Rounds 2 - 6 waited HERE, in front of the whole pass: the encoder stream then

@@ -314,6 +314,34 @@ typedef struct {
 
 int dc_roi_align_pyramid_f32(const dc_roialign_desc* d, void* stream);
 
+/* The FPN output convolutions computed only where PyramidROIAlign reads.  When the boxes are known before the encoder pass (ground-truth
+ * boxes: the caption-training flows), the pyramid maps P2..P5 have one consumer, the gather above, which reads at most pool * pool * 4
+ * pixels per box.  The split-bf16 Winograd kernel works on tile groups of 8 x 16 output pixels (ragged at the bottom / right edges);
+ * group index = (image * groups_y + group row) * groups_x + group column, groups_y * groups_x = dc_conv2d_winograd_group_count(H, W).
+ *
+ * dc_roi_tile_groups: for every box and bin the routing and the sample of dc_roi_align_pyramid_f32 (the same device functions), a mark
+ * on the group of each of the four corner pixels at the routed level (a sample outside the map marks nothing), then per level the
+ * marked groups in ascending index into lists[l] and their number into counts[l].  One small launch; the host never reads either.
+ *   boxes [B*R,4] as in dc_roialign_desc; Hs / Ws: the extents of P2..P5; marks: scratch, B * (sum of the four levels' group counts)
+ *   int32; lists[l]: B * dc_conv2d_winograd_group_count(Hs[l], Ws[l]) int32; counts: 4 int32.
+ * dc_conv2d_winograd_groups_f32: the layer `d` on the listed groups only -- every output element inside a listed group gets the value
+ * dc_conv2d_nhwc_f32 gives it, bit for bit; nothing else of d->y is written; count[0] == 0 is a no-op.  `groups` / `count` are device
+ * pointers (a level's list and its count).  The layer must be one the split-bf16 Winograd kernel takes (3x3, stride 1, pad 1, Cin and
+ * Cout multiples of 32, no residual, DC_MATH_F32, w_wino_b3 given): anything else is DC_EINVAL, there is no other path. */
+typedef struct {
+    int B, R, pool;
+    int Hs[4], Ws[4];
+    const float* boxes;
+    float image_area;
+    int32_t* marks;
+    int32_t* lists[4];
+    int32_t* counts;
+} dc_roi_groups_desc;
+
+int dc_roi_tile_groups(const dc_roi_groups_desc* d, void* stream);
+int dc_conv2d_winograd_group_count(int H, int W);
+int dc_conv2d_winograd_groups_f32(const dc_conv_desc* d, const int32_t* groups, const int32_t* count, void* stream);
+
 /* KL.MaxPooling2D(pool_size=(1,1), strides=2): P6 = every other pixel of P5 (dense_model.py:1423). */
 int dc_subsample2_f32(const float* x, float* y, int N, int H, int W, int C, void* stream);
 
