@@ -240,6 +240,9 @@ SYMBOLS = {
     "dc_roi_tile_groups": (C.c_int, [C.POINTER(RoiGroupsDesc), C.c_void_p]),
     "dc_conv2d_winograd_group_count": (C.c_int, [C.c_int, C.c_int]),
     "dc_conv2d_winograd_groups_f32": (C.c_int, [C.POINTER(ConvDesc), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dc_conv2d_winograd_levels_f32": (C.c_int, [C.POINTER(ConvDesc), C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p]),
+    "dc_roi_tile_groups_lateral": (C.c_int, [C.POINTER(RoiGroupsDesc), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dc_conv2d_nhwc_tiles_f32": (C.c_int, [C.POINTER(ConvDesc), C.c_void_p, C.c_void_p, C.c_void_p]),
     "dc_subsample2_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "dc_proposals_workspace_bytes": (C.c_size_t, [C.POINTER(ProposalDesc)]),
     "dc_proposals_f32": (C.c_int, [C.POINTER(ProposalDesc), C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -305,6 +305,24 @@ extern "C" int dc_conv2d_nhwc_f32(const dc_conv_desc* d, void* workspace, size_t
     return conv_dispatch(al, bl, ep, M, N, K, t, workspace, workspace_bytes, s);
 }
 
+extern "C" int dc_conv2d_nhwc_tiles_f32(const dc_conv_desc* d, const int32_t* tiles, const int32_t* count, void* stream) {
+    bool stem;
+    int rc = conv_validate(d, stem);
+    if (rc) return rc;
+    DC_REQUIRE(tiles && count, DC_EINVAL, "dc_conv2d_nhwc_tiles: null list / count");
+    int M, N, K;
+    conv_dims(d, stem, M, N, K);
+    const TileChoice t = conv_tile_bs(M, N, K, d->split_k);
+    const Epilogue ep = conv_epilogue(d);
+    DC_REQUIRE(!stem && conv_is_pointwise(d) && d->math == DC_MATH_BF16X3 && d->split_k <= 1 && t.bm == 128 && t.bn == 128 && t.split == 1 &&
+                   (d->res_mode == 0 || d->res_mode == 2) && !d->accumulate && ep.vec4,
+               DC_EINVAL,
+               "dc_conv2d_nhwc_tiles: the layer must be a 1x1 / stride 1 convolution in DC_MATH_BF16X3 that the dense launch runs on 128 x 128 "
+               "tiles without split-K (set split_k = 1 where the dense rule would split), res_mode 0 or 2, no accumulate, Cout %% 4 == 0 and "
+               "16-byte aligned operands: there is no other list-driven path");
+    return conv2d_bf16x3_tiles(d, ep, tiles, count, static_cast<hipStream_t>(stream));
+}
+
 static int wgrad_validate(const dc_conv_desc* d) {
     DC_REQUIRE(d && d->x && d->w && d->y, DC_EINVAL, "dc_conv2d_wgrad: x, dy (y) and dw (w) must be non-null");
     DC_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0 && d->Ho > 0 && d->Wo > 0 && d->kh >= 1 && d->kw >= 1 && d->kh <= 8 && d->kw <= 8 &&

@@ -54,6 +54,15 @@ int conv2d_bf16x3(const dc_conv_desc* d, bool stem, const Epilogue& ep, int M, i
     return dispatch_bs(al, bl, ep, M, N, K, bm, bn, split, workspace, workspace_bytes, s, pieces);
 }
 
+// The pointwise layer on the listed tile groups (dc_conv2d_nhwc_tiles_f32 has checked the layer): the 128 x 128 six-product kernel, the
+// weights walked by the dense launch's loader, K in the same order.
+int conv2d_bf16x3_tiles(const dc_conv_desc* d, const Epilogue& ep, const int* tiles, const int* count, hipStream_t s) {
+    const int gy = wino_groups_y(d->H), gx = wino_groups_x(d->W);
+    ConvWeightKC bl{d->w, d->Cin, d->Cout, 1, d->Cin};
+    TileListKC al{d->x, d->H, d->W, d->Cin, gy, gx, d->N * gy * gx, (unsigned)((size_t)d->N * d->H * d->W * d->Cin * sizeof(float)), tiles, count};
+    return launch_igemm_bs_list<128, 128, TileListKC, ConvWeightKC>(al, bl, ep, d->N * gy * gx, d->Cout, d->Cin, s);
+}
+
 }  // namespace dcap
 
 extern "C" int dc_split_bf16x3_f32(const float* x, uint16_t* out, size_t n, void* stream) {

@@ -57,6 +57,24 @@ struct Args {
     const int* gcount;
 };
 
+// Up to four layers of equal Cin, Cout and relu in ONE list-driven launch (wino32b_levels_kernel: fpn_p2..p5 on the groups RoIAlign
+// reads): per level what Args holds per layer, passed by value.
+struct LevelArgs {
+    const float* x;
+    const f4* u;
+    float* y;
+    const float* scale;
+    const float* shift;
+    int H, W, gy, gx, groups;
+    unsigned x_bytes, u_bytes;
+    const int* glist;
+    const int* gcount;
+};
+struct LevelsArgs {
+    LevelArgs lv[4];
+    int nlevels, N, Cin, Cout, relu;
+};
+
 // U in fragment order, K in chunks of 16: f4 index ((((xi * NTG + ntg) * KC16 + kc) * 2 + j) * 64 + lane), lane = 32 h + i,
 // component e   <->   cout = 32 ntg + i, cin = 16 kc + 8 h + 4 j + e     (MFMA step 4 j + e of a chunk contracts cin 8 h + 4 j + e)
 __global__ void wino_pack_kernel(const float* __restrict__ w, float* __restrict__ u, int Cin, int Cout) {
@@ -180,6 +198,10 @@ struct Cfg {
 
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
+// one of four VALUES (a conditional on the struct members themselves selects between their addresses and keeps the struct in memory)
+template <class T>
+__device__ __forceinline__ T sel4(int l, T v0, T v1, T v2, T v3) { return l == 0 ? v0 : (l == 1 ? v1 : (l == 2 ? v2 : v3)); }
+
 // eight fp32 values (channels 8 h + 0..3 in va, 8 h + 4..7 in vb) -> the three bf16x8 pieces of an MFMA operand fragment
 __device__ __forceinline__ void split8(const f4& va, const f4& vb, u32x4& p0, u32x4& p1, u32x4& p2) {
     unsigned a0, a1, a2, b0, b1, b2, c0, c1, c2, d0, d1, d2;
@@ -205,10 +227,29 @@ __device__ __forceinline__ f32x16 mfma_b(const u32x4& a, const u32x4& b, const f
 // LIST = true (the split-bf16 32-tile kernel only): the item walk covers the a.gcount[0] tile groups of a.glist instead of all a.groups --
 // the FPN output convolutions computed only where RoIAlign reads (dc_conv2d_winograd_groups_f32).  setup() maps the compact group index
 // through the list; everything an item does from there on is the dense kernel's, so what is computed is bit-identical to it.
-template <int HALVES, bool B3, int NCH = 1, bool LIST = false>
-__device__ __forceinline__ void wino_body(const Args& a) {
+// LIST = 2: the lists of up to four layers (LevelsArgs) in one launch -- the items are the levels' listed groups end to end, all of equal
+// cost (equal Cin and Cout); setup() finds the item's level with block-uniform scalar work, makes that level's fields the current Args
+// and rebuilds the two buffer resources; an empty level contributes nothing.  The item body is again the dense kernel's.
+template <int HALVES, bool B3, int NCH = 1, int LIST = 0, class KA = Args>
+__device__ __forceinline__ void wino_body(const KA& ka) {
     static_assert(NCH == 1 || (NCH == 2 && HALVES == 1 && B3), "64-channel items: the split-bf16 32-tile kernel only");
     static_assert(!LIST || (HALVES == 1 && B3), "list-driven item walk: the split-bf16 32-tile kernel only");
+    Args cur;                                              // LIST = 2: the current item's level (block-uniform: scalar registers)
+    const Args& a = [&]() -> const Args& {
+        if constexpr (LIST == 2) return cur;
+        else return ka;
+    }();
+    int cum[4] = {0, 0, 0, 0};                             // LIST = 2: listed groups below each level
+    if constexpr (LIST == 2) {
+        cur.N = ka.N; cur.Cin = ka.Cin; cur.Cout = ka.Cout; cur.relu = ka.relu;
+        // (written out level by level: an indexed walk would keep a copy of the arguments in scratch)
+#define DC_CNT(l) (l < ka.nlevels ? min(max(ka.lv[l].gcount[0], 0), ka.lv[l].groups) : 0)
+        cum[1] = DC_CNT(0);
+        cum[2] = cum[1] + DC_CNT(1);
+        cum[3] = cum[2] + DC_CNT(2);
+        cur.groups = cum[3] + DC_CNT(3);
+#undef DC_CNT
+    }
     using namespace wp;
     typedef Cfg<HALVES> C;
     constexpr int NT64 = C::NT, SLOTS = C::SLOTS, BUF = C::BUF;
@@ -216,12 +257,27 @@ __device__ __forceinline__ void wino_body(const Args& a) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wa = wave & 3, th = wave >> 2;
-    const int gpi = a.gy * a.gx;
+    int gpi = LIST == 2 ? 0 : a.gy * a.gx;
     const int NTG = a.Cout >> 5, KC = a.Cin >> 4, KP = a.Cin >> 5;
     int groups = a.groups;                                 // tile groups this launch computes
-    if constexpr (LIST) groups = min(max(*a.gcount, 0), a.groups);          // (block-uniform; an empty list: every block leaves below)
+    if constexpr (LIST == 1) groups = min(max(*a.gcount, 0), a.groups);     // (block-uniform; an empty list: every block leaves below)
     const int total = groups * (NTG / NCH);                // work items (slice, tile group); this block takes blockIdx.x, + gridDim.x, ...
-    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.x), 0, (int)a.x_bytes, 0x00020000);
+    __amdgpu_buffer_rsrc_t rsrc, rsrc_u;                   // the input; B3: U (below)
+    if constexpr (LIST != 2) rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.x), 0, (int)a.x_bytes, 0x00020000);
+    int lgroups = 0;                                       // LIST = 2: the current level's capacity (a list entry never leaves the map)
+    auto set_level = [&](int l) {                          // LIST = 2, l block-uniform: scalar selects, no indexed copy of the arguments
+#define DC_LV(f) sel4(l, ka.lv[0].f, ka.lv[1].f, ka.lv[2].f, ka.lv[3].f)
+        if constexpr (LIST == 2) {
+            cur.x = DC_LV(x); cur.u = DC_LV(u); cur.y = DC_LV(y); cur.scale = DC_LV(scale); cur.shift = DC_LV(shift);
+            cur.H = DC_LV(H); cur.W = DC_LV(W); cur.gy = DC_LV(gy); cur.gx = DC_LV(gx);
+            cur.x_bytes = DC_LV(x_bytes); cur.u_bytes = DC_LV(u_bytes); cur.glist = DC_LV(glist);
+            lgroups = DC_LV(groups);
+            gpi = cur.gy * cur.gx;
+            rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(cur.x), 0, (int)cur.x_bytes, 0x00020000);
+            rsrc_u = __builtin_amdgcn_make_buffer_rsrc(const_cast<f4*>(cur.u), 0, (int)cur.u_bytes, 0x00020000);
+        }
+#undef DC_LV
+    };
 
     // ---- per work item: coordinates, patch DMA sources (slot s = n * 512 + tid of the image <-> pixel s >> 3, image chunk
     // s & 7 = source chunk ^ swizzle), U fragment base
@@ -233,7 +289,13 @@ __device__ __forceinline__ void wino_body(const Args& a) {
         const int bid = xcd_remap(item, total);            // gridDim.x % 8 == 0: item % 8 is this block's XCD for every item it takes
         nb = bid / groups;
         int g = bid - nb * groups;
-        if constexpr (LIST) g = min(max(a.glist[g], 0), a.groups - 1);      // (a list entry never leaves the map)
+        if constexpr (LIST == 1) g = min(max(a.glist[g], 0), a.groups - 1);      // (a list entry never leaves the map)
+        if constexpr (LIST == 2) {
+            const int l = g >= cum[3] ? 3 : (g >= cum[2] ? 2 : (g >= cum[1] ? 1 : 0));      // (an empty level: cum[l + 1] == cum[l], never chosen)
+            g -= l == 3 ? cum[3] : (l == 2 ? cum[2] : (l == 1 ? cum[1] : 0));
+            set_level(l);
+            g = min(max(a.glist[g], 0), lgroups - 1);
+        }
         img = g / gpi;
         const int gr = g - img * gpi;
         gyi = gr / a.gx;
@@ -269,7 +331,7 @@ __device__ __forceinline__ void wino_body(const Args& a) {
     auto load_u = [&](f4 (&dst)[4][2], int kc) { load_u_part(dst, kc, 0, 4); };
     // B3: U through a buffer resource -- the lane's offset (16 lane) is a fixed VGPR, everything else (item, position, chunk, piece) one
     // block-uniform SGPR offset: no address VALU beside the loads
-    const __amdgpu_buffer_rsrc_t rsrc_u = __builtin_amdgcn_make_buffer_rsrc(const_cast<f4*>(a.u), 0, (int)a.u_bytes, 0x00020000);
+    if constexpr (LIST != 2) rsrc_u = __builtin_amdgcn_make_buffer_rsrc(const_cast<f4*>(a.u), 0, (int)a.u_bytes, 0x00020000);
     const unsigned ustep3 = (unsigned)NTG * KC * 3 * 1024u;                  // bytes: xi -> xi + 1
     auto load_u3 = [&](u32x4 (&dst)[3], int kc, int b, int hc) {                // hc: the 32-channel half of a 64-channel item
         const unsigned so = __builtin_amdgcn_readfirstlane(ubyte3 + (unsigned)b * ustep3 + (unsigned)(hc * KC + kc) * 3072u);
@@ -538,6 +600,8 @@ __device__ __forceinline__ void wino_body(const Args& a) {
 
         // ---- this item is summed.  Start the next item's first patch and U loads, then finish this one beside them.
         const int onb = nb, oimg = img, ogy = gyi, ogx = gxi;
+        const int oH = a.H, oW = a.W;                      // (LIST = 2: setup(next) may move on to another level)
+        float* const oy = a.y;
         const int next = item + (int)gridDim.x;
         // this item's epilogue operands, requested BEFORE anything of the next item: vmcnt retires in issue order, so waiting for them
         // later must not mean waiting for the next patch
@@ -590,8 +654,8 @@ __device__ __forceinline__ void wino_body(const Args& a) {
                     for (int pr = 0; pr < 2; ++pr) {
                         f4 val = o[pr] * sc[hc] + sh[hc];
                         if (a.relu) val = f4{fmaxf(val[0], 0.f), fmaxf(val[1], 0.f), fmaxf(val[2], 0.f), fmaxf(val[3], 0.f)};
-                        if (2 * ty + pr < a.H && 2 * tx + qx < a.W)
-                            *reinterpret_cast<f4*>(a.y + (((long)oimg * a.H + 2 * ty + pr) * a.W + 2 * tx + qx) * a.Cout + cout) = val;
+                        if (2 * ty + pr < oH && 2 * tx + qx < oW)
+                            *reinterpret_cast<f4*>(oy + (((long)oimg * oH + 2 * ty + pr) * oW + 2 * tx + qx) * a.Cout + cout) = val;
                     }
                 }
             }
@@ -611,9 +675,11 @@ template __global__ void wino32b_kernel<1>(Args);
 template __global__ void wino32b_kernel<2>(Args);
 // ... and its list-driven form
 template <int NCH>
-__global__ __launch_bounds__(256, 2) void wino32b_list_kernel(Args a) { wino_body<1, true, NCH, true>(a); }
+__global__ __launch_bounds__(256, 2) void wino32b_list_kernel(Args a) { wino_body<1, true, NCH, 1>(a); }
 template __global__ void wino32b_list_kernel<1>(Args);
 template __global__ void wino32b_list_kernel<2>(Args);
+// ... and the lists of up to four layers in one launch (32-channel items)
+__global__ __launch_bounds__(256, 2) void wino32b_levels_kernel(LevelsArgs m) { wino_body<1, true, 1, 2>(m); }
 
 }  // namespace wino
 
@@ -767,9 +833,45 @@ int conv2d_winograd_groups(const dc_conv_desc* d, const int* glist, const int* g
     return check_launch("dc_conv2d_winograd_groups_f32");
 }
 
+// One launch for the lists of `nlevels` layers of equal Cin, Cout and relu (fpn_p2..p5): 32-channel items, the levels' listed groups end to
+// end; the grid is sized without the counts, capped at the resident block slots.
+int conv2d_winograd_levels(const dc_conv_desc* d, int nlevels, const int* const* lists, const int* counts, hipStream_t s) {
+    wino::LevelsArgs m;
+    m.nlevels = nlevels;
+    m.N = d[0].N; m.Cin = d[0].Cin; m.Cout = d[0].Cout; m.relu = d[0].relu;
+    long items = 0;
+    for (int l = 0; l < 4; ++l) {
+        const int k = l < nlevels ? l : 0;                 // (unused levels repeat level 0: never selected, their count is never read)
+        wino::Args a;
+        const int rc = wino_args(&d[k], true, false, a);
+        if (rc) return rc;
+        m.lv[l] = wino::LevelArgs{a.x, a.u, a.y, a.scale, a.shift, a.H, a.W, a.gy, a.gx, a.groups, a.x_bytes, a.u_bytes, lists[k], counts + k};
+        if (l < nlevels) items += (long)a.groups * (d[0].Cout / 32);
+    }
+    DC_REQUIRE(items < (1l << 31), DC_EINVAL, "dc_conv2d_winograd_levels: grid too large");
+    const long full = 2L * kNumCU;
+    const unsigned grid = items >= full ? (unsigned)full : (unsigned)std::max<long>(8, items / 8 * 8);
+    DC_ENSURE_DYN_LDS(wino::wino32b_levels_kernel, wino::wp::Cfg<1>::LDS_BYTES);
+    hipLaunchKernelGGL(wino::wino32b_levels_kernel, dim3(grid), dim3(wino::wp::Cfg<1>::NT), wino::wp::Cfg<1>::LDS_BYTES, s, m);
+    return check_launch("dc_conv2d_winograd_levels_f32");
+}
+
 }  // namespace dcap
 
 using namespace dcap;
+
+extern "C" int dc_conv2d_winograd_levels_f32(const dc_conv_desc* d, int nlevels, const int32_t* const* lists, const int32_t* counts, void* stream) {
+    DC_REQUIRE(d && lists && counts && nlevels >= 1 && nlevels <= 4, DC_EINVAL, "dc_conv2d_winograd_levels: null pointer or nlevels outside 1..4");
+    for (int l = 0; l < nlevels; ++l) {
+        DC_REQUIRE(d[l].x && d[l].y && lists[l] && d[l].N > 0 && d[l].H > 0 && d[l].W > 0, DC_EINVAL, "dc_conv2d_winograd_levels: bad level %d", l);
+        DC_REQUIRE(wino_b3(&d[l]), DC_EINVAL,
+                   "dc_conv2d_winograd_levels: level %d must be a layer the split-bf16 Winograd kernel takes (3x3, stride 1, pad 1, Cin and Cout "
+                   "multiples of 32, no residual, fp32 math, w_wino_b3 given, 16-byte aligned operands, input below 2 GiB)", l);
+        DC_REQUIRE(d[l].N == d[0].N && d[l].Cin == d[0].Cin && d[l].Cout == d[0].Cout && (d[l].relu != 0) == (d[0].relu != 0), DC_EINVAL,
+                   "dc_conv2d_winograd_levels: level %d differs from level 0 in N, Cin, Cout or relu (equal-cost items only)", l);
+    }
+    return conv2d_winograd_levels(d, nlevels, lists, counts, static_cast<hipStream_t>(stream));
+}
 
 extern "C" int dc_conv2d_winograd_groups_f32(const dc_conv_desc* d, const int32_t* groups, const int32_t* count, void* stream) {
     DC_REQUIRE(d && d->x && d->y && groups && count, DC_EINVAL, "dc_conv2d_winograd_groups: null pointer");

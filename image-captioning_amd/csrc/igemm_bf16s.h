@@ -21,6 +21,7 @@
 // they knock out one phase of the loop so that its share of the K-tile time can be read off a timing difference.
 #pragma once
 #include "igemm_core.h"
+#include <algorithm>
 
 namespace dcap {
 
@@ -90,86 +91,129 @@ __global__ __launch_bounds__(256, 2) void igemm_bs_kernel(AL al, BL bl, Epilogue
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int tiles_n = (N + BN - 1) / BN;
-    const int lid = xcd_remap(blockIdx.x, gridDim.x);
-    const int m0 = (lid / tiles_n) * BM, n0 = (lid % tiles_n) * BN;
+    // LIST: a list-driven launch (TileListKC) -- the grid is sized without the list's length (the host never reads it): its blocks walk the
+    // entries x tiles_n items, a block whose first item lies behind the list's end leaves at once.  Per item everything is the dense
+    // block's, so a computed element is the dense launch's bit for bit.
+    constexpr bool LIST = is_tile_list<AL>::value;
+    int lid = xcd_remap(blockIdx.x, gridDim.x);
+    int items = 0;
+    if constexpr (LIST) {
+        items = al.entries() * tiles_n;
+        if (lid >= items) return;                          // (block-uniform)
+    }
     const int kbeg = blockIdx.z * klen;
     const int kend = min(K, kbeg + klen);
     const int wm = (wave >> 1) * (BM / 2), wn = (wave & 1) * (BN / 2);
     const int li = lane & 31, lh = lane >> 5;
+    for (;;) {
+        const int m0 = (lid / tiles_n) * BM, n0 = (lid % tiles_n) * BN;
 
-    typename AL::template State<BM> sa;
-    typename BL::template State<BN> sb;
-    al.template init<BM>(sa, m0, tid);
-    bl.template init<BN>(sb, n0, tid);
+        typename AL::template State<BM> sa;
+        typename BL::template State<BN> sb;
+        al.template init<BM>(sa, m0, tid);
+        bl.template init<BN>(sb, n0, tid);
 
-    f32x16 acc[TM][TN];
+        f32x16 acc[TM][TN];
 #pragma unroll
-    for (int tm = 0; tm < TM; ++tm)
+        for (int tm = 0; tm < TM; ++tm)
 #pragma unroll
-        for (int tn = 0; tn < TN; ++tn)
+            for (int tn = 0; tn < TN; ++tn)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc[tm][tn][r] = 0.f;
+                for (int r = 0; r < 16; ++r) acc[tm][tn][r] = 0.f;
 
-    // two K-tiles of staging registers: a tile's global loads are issued two MFMA phases before they are drained to LDS
-    // (one phase, ~0.6 us, is shorter than an L2/HBM round trip under load)
-    f4 ra[2][BM / 32], rb[2][BN / 32];
-    const int nkt = (kend - kbeg + BK - 1) / BK;
+        // two K-tiles of staging registers: a tile's global loads are issued two MFMA phases before they are drained to LDS
+        // (one phase, ~0.6 us, is shorter than an L2/HBM round trip under load)
+        f4 ra[2][BM / 32], rb[2][BN / 32];
+        const int nkt = (kend - kbeg + BK - 1) / BK;
 #pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int k0 = kbeg + j * BK;
-        al.template load<BM>(sa, ra[j], al.kclamp(k0, kend), kend, tid);
-        bl.template load<BN>(sb, rb[j], bl.kclamp(k0, kend), kend, tid);
-    }
-
-    const __bf16* afrag = As + (wm + li) * LDB + 8 * lh;
-    const __bf16* bfrag = Bs + (wn + li) * LDB + 8 * lh;
-
-    auto phase = [&](int kt, f4 (&qa)[BM / 32], f4 (&qb)[BN / 32]) {
-        // registers (tile kt) -> bf16 planes in LDS; every wave is past the previous tile's fragment reads (barrier below)
-        store_split_kc<BM, BM / 32, NP>(As, qa, tid);
-        store_split_kc<BN, BN / 32, NP>(Bs, qb, tid);
-        __syncthreads();
-        // refill the drained registers with tile kt+2: unconditional (clamped / range-checked)
-        {
-            const int k0 = kbeg + (kt + 2) * BK;
-            al.template load<BM>(sa, qa, al.kclamp(k0, kend), kend, tid);
-            bl.template load<BN>(sb, qb, bl.kclamp(k0, kend), kend, tid);
+        for (int j = 0; j < 2; ++j) {
+            const int k0 = kbeg + j * BK;
+            al.template load<BM>(sa, ra[j], al.kclamp(k0, kend), kend, tid);
+            bl.template load<BN>(sb, rb[j], bl.kclamp(k0, kend), kend, tid);
         }
-#pragma unroll
-        for (int s = 0; s < BK / 16; ++s) {
-            bf16x8 a[TM][NP], b[TN][NP];
-#pragma unroll
-            for (int p = 0; p < NP; ++p) {
-#pragma unroll
-                for (int tm = 0; tm < TM; ++tm) a[tm][p] = *reinterpret_cast<const bf16x8*>(afrag + (p * BM + tm * 32) * LDB + 16 * s);
-#pragma unroll
-                for (int tn = 0; tn < TN; ++tn) b[tn][p] = *reinterpret_cast<const bf16x8*>(bfrag + (p * BN + tn * 32) * LDB + 16 * s);
+
+        const __bf16* afrag = As + (wm + li) * LDB + 8 * lh;
+        const __bf16* bfrag = Bs + (wn + li) * LDB + 8 * lh;
+
+        auto phase = [&](int kt, f4 (&qa)[BM / 32], f4 (&qb)[BN / 32]) {
+            // registers (tile kt) -> bf16 planes in LDS; every wave is past the previous tile's fragment reads (barrier below)
+            store_split_kc<BM, BM / 32, NP>(As, qa, tid);
+            store_split_kc<BN, BN / 32, NP>(Bs, qb, tid);
+            __syncthreads();
+            // refill the drained registers with tile kt+2: unconditional (clamped / range-checked)
+            {
+                const int k0 = kbeg + (kt + 2) * BK;
+                al.template load<BM>(sa, qa, al.kclamp(k0, kend), kend, tid);
+                bl.template load<BN>(sb, qb, bl.kclamp(k0, kend), kend, tid);
             }
 #pragma unroll
-            for (int tm = 0; tm < TM; ++tm)
+            for (int s = 0; s < BK / 16; ++s) {
+                bf16x8 a[TM][NP], b[TN][NP];
 #pragma unroll
-                for (int tn = 0; tn < TN; ++tn) {
-                    f32x16 c = acc[tm][tn];
-                    if constexpr (NP == 3) {
-                        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[tm][2], b[tn][0], c, 0, 0, 0);
-                        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[tm][1], b[tn][1], c, 0, 0, 0);
-                        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[tm][0], b[tn][2], c, 0, 0, 0);
-                    }
-                    if constexpr (NP >= 2) {
-                        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[tm][1], b[tn][0], c, 0, 0, 0);
-                        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[tm][0], b[tn][1], c, 0, 0, 0);
-                    }
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[tm][0], b[tn][0], c, 0, 0, 0);
-                    acc[tm][tn] = c;
+                for (int p = 0; p < NP; ++p) {
+#pragma unroll
+                    for (int tm = 0; tm < TM; ++tm) a[tm][p] = *reinterpret_cast<const bf16x8*>(afrag + (p * BM + tm * 32) * LDB + 16 * s);
+#pragma unroll
+                    for (int tn = 0; tn < TN; ++tn) b[tn][p] = *reinterpret_cast<const bf16x8*>(bfrag + (p * BN + tn * 32) * LDB + 16 * s);
                 }
+#pragma unroll
+                for (int tm = 0; tm < TM; ++tm)
+#pragma unroll
+                    for (int tn = 0; tn < TN; ++tn) {
+                        f32x16 c = acc[tm][tn];
+                        if constexpr (NP == 3) {
+                            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[tm][2], b[tn][0], c, 0, 0, 0);
+                            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[tm][1], b[tn][1], c, 0, 0, 0);
+                            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[tm][0], b[tn][2], c, 0, 0, 0);
+                        }
+                        if constexpr (NP >= 2) {
+                            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[tm][1], b[tn][0], c, 0, 0, 0);
+                            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[tm][0], b[tn][1], c, 0, 0, 0);
+                        }
+                        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[tm][0], b[tn][0], c, 0, 0, 0);
+                        acc[tm][tn] = c;
+                    }
+            }
+            __syncthreads();                 // fragment reads done: the LDS image may be overwritten
+        };
+        for (int kt = 0; kt < nkt; kt += 2) {
+            phase(kt, ra[0], rb[0]);
+            if (kt + 1 < nkt) phase(kt + 1, ra[1], rb[1]);
         }
-        __syncthreads();                 // fragment reads done: the LDS image may be overwritten
-    };
-    for (int kt = 0; kt < nkt; kt += 2) {
-        phase(kt, ra[0], rb[0]);
-        if (kt + 1 < nkt) phase(kt + 1, ra[1], rb[1]);
+        if constexpr (LIST) {
+            int img, y0, x0;
+            al.origin(lid / tiles_n, img, y0, x0);
+            store_tile_list<BM, BN>(acc, smem, ep, N, img, y0, x0, al.H, al.W, n0, wm, wn);
+            lid += gridDim.x;                                  // (gridDim.x % 8 == 0: the block's items stay on its XCD)
+            if (lid >= items) break;
+            __syncthreads();                                   // the tile image has been read: the next item may stage its operands
+        } else {
+            store_tile<BM, BN>(acc, smem, ep, partial, M, N, m0, n0, wm, wn);
+            break;
+        }
     }
-    store_tile<BM, BN>(acc, smem, ep, partial, M, N, m0, n0, wm, wn);
+}
+
+// The list-driven launch: `entries` = the list's capacity (all tile groups of the map).  No split-K.
+template <int BM, int BN, class AL, class BL, int NP = 3>
+int launch_igemm_bs_list(const AL& al, const BL& bl, const Epilogue& ep, int entries, int N, int K, hipStream_t stream) {
+    const long items = (long)entries * ((N + BN - 1) / BN);
+    DC_REQUIRE(items > 0 && items * BM < (1l << 31), DC_EINVAL, "igemm (tile list): bad item count %ld", items);
+    const int klen = ((K + BK - 1) / BK) * BK;
+    constexpr size_t lds = igemm_bs_lds_bytes<BM, BN, NP>();
+    DC_ENSURE_DYN_LDS((&igemm_bs_kernel<BM, BN, AL, BL, NP>), 160 * 1024);
+    // the blocks that fit the chip (two per CU), or as many as the map has items when that is fewer; a multiple of 8
+    // (DCAP_EXP_LIST_GRID_ALL, an ablation switch like the ones above: one block per item of the whole map, the blocks behind the list's
+    // end leaving at once -- 4096 blocks for 356 items at the benchmark's size; profiles/r09_fpn_lateral.txt has both)
+#ifdef DCAP_EXP_LIST_GRID_ALL
+    const long full = items;
+#else
+    const long full = 2L * kNumCU;
+#endif
+    const unsigned grid = items >= full ? (unsigned)((full + 7) / 8 * 8) : (unsigned)std::max<long>(8, items / 8 * 8);
+    hipLaunchKernelGGL((igemm_bs_kernel<BM, BN, AL, BL, NP>), dim3(grid), dim3(256), lds, stream, al, bl, ep, (int)(entries * BM), N, K, klen,
+                       static_cast<float*>(nullptr));
+    return check_launch("igemm_bs_kernel (tile list)");
 }
 
 template <int BM, int BN, class AL, class BL, int NP = 3>

@@ -355,6 +355,58 @@ struct Im2colKCT {
 using Im2colKC = Im2colKCT<false>;
 using Im2colKCcm = Im2colKCT<true>;
 
+// The A operand of a LIST-DRIVEN pointwise (1x1 / stride 1) convolution: M tile e of the launch is tile group list[e] of the NHWC map --
+// the 8 x 16-pixel groups of the split-bf16 Winograd kernel (dcap_internal.h), group index (image * gy + group row) * gx + group column,
+// 128 rows per tile: row r is pixel (8 group row + r / 16, 16 group column + r % 16).  Rows outside a ragged map carry the out-of-range
+// offset: the hardware returns zeros, nothing is read (and the epilogue, store_tile_list, stores nothing for them).  K = Cin, walked
+// in storage order like the dense loaders; list and count are written on the device by an earlier launch of the stream.
+struct TileListKC {
+    static constexpr bool KC = true;
+    static constexpr int ROWS = kWinoGroupH * kWinoGroupW;
+    __device__ __forceinline__ int kclamp(int k0, int kend) const { return min(k0, kend - BK); }
+    const float* x;
+    int H, W, Cin, gy, gx, groups;      // groups = images * gy * gx: the list's capacity
+    unsigned x_bytes;
+    const int* list;
+    const int* count;
+    __device__ __forceinline__ int entries() const { return min(max(count[0], 0), groups); }
+    // image and first pixel of list entry e (an entry never leaves the map)
+    __device__ __forceinline__ void origin(int e, int& img, int& y0, int& x0) const {
+        const int g = min(max(list[e], 0), groups - 1);
+        img = g / (gy * gx);
+        const int gr = g - img * (gy * gx), gyi = gr / gx;
+        y0 = gyi * kWinoGroupH;
+        x0 = (gr - gyi * gx) * kWinoGroupW;
+    }
+    template <int BT>
+    struct State {
+        __amdgpu_buffer_rsrc_t rsrc;
+        unsigned boff[BT / 32];
+    };
+    template <int BT>
+    __device__ __forceinline__ void init(State<BT>& s, int row0, int tid) const {
+        static_assert(BT == ROWS, "one M tile is one 8 x 16 tile group");
+        s.rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(x), 0, (int)x_bytes, 0x00020000);
+        int img, y0, x0;
+        origin(row0 / BT, img, y0, x0);
+        const int rr = tid >> 3;
+#pragma unroll
+        for (int i = 0; i < BT / 32; ++i) {
+            const int r = rr + 32 * i, y = y0 + r / kWinoGroupW, xx = x0 + r % kWinoGroupW;
+            s.boff[i] = (y < H && xx < W) ? (unsigned)(((((long)img * H + y) * W + xx) * Cin + 4 * (tid & 7)) * 4) : kOobOffset;
+        }
+    }
+    template <int BT>
+    __device__ __forceinline__ void load(State<BT>& s, f4 (&r)[BT / 32], int k0, int, int) const {
+#pragma unroll
+        for (int i = 0; i < BT / 32; ++i) r[i] = buf_f4s(s.rsrc, s.boff[i], (unsigned)k0 * 4u);          // k0 block-uniform
+    }
+};
+template <class AL>
+struct is_tile_list { static constexpr bool value = false; };
+template <>
+struct is_tile_list<TileListKC> { static constexpr bool value = true; };
+
 // wgrad's B operand: the im2col matrix K-major.  K rows = output pixels (all images), columns
 // n = tap*Cin + ci; a column tile of BT lies inside one tap (Cin % BT == 0), so a K row is a contiguous run of
 // channels of ONE (shifted) input pixel.  Each thread walks its pixels incrementally (32 pixels per K-tile:
@@ -712,6 +764,62 @@ __device__ __forceinline__ void store_tile(f32x16 (&acc)[TM][TN], float* smem, c
     }
 }
 
+// The epilogue of a list-driven launch (TileListKC): store_tile's vectorised path with tile row lr written to pixel
+// (y0 + lr / 16, x0 + lr % 16) of image img, the upsample-add operand (res_mode 2) taken from that pixel's parent.  Same expression per
+// element as store_tile, so a stored value is the dense launch's bit for bit; rows outside a ragged map are not stored.  Host-checked:
+// vec4 operands, N % 4 == 0, res_mode 0 or 2, no accumulate, no bf16 copy.
+template <int BM, int BN, int TM = BM / 64, int TN = BN / 64>
+__device__ __forceinline__ void store_tile_list(f32x16 (&acc)[TM][TN], float* smem, const Epilogue& ep, int N, int img, int y0, int x0,
+                                                int H, int W, int n0, int wm, int wn) {
+    const int tid = threadIdx.x, lane = tid & 63;
+    constexpr int LDC = BN + 4;
+    constexpr int CPR = BN / 4, RPP = 256 / CPR;
+    constexpr int PASSES = BM / RPP, G = PASSES < 8 ? PASSES : 8;
+    const int c4 = tid % CPR, rp = tid / CPR;
+    const int col = n0 + 4 * c4;
+    const bool pre_res = ep.res_mode == 2;
+    f4 qres[G];
+    auto prefetch = [&](int p0) {
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            const int lr = (p0 + g) * RPP + rp;
+            const int y = min(y0 + lr / kWinoGroupW, H - 1), xx = min(x0 + lr % kWinoGroupW, W - 1);      // clamped: rows outside the map are never stored
+            if (pre_res) qres[g] = *reinterpret_cast<const f4*>(ep.res + (((long)img * (H >> 1) + (y >> 1)) * (W >> 1) + (xx >> 1)) * ep.ldr + min(col, N - 4));
+        }
+    };
+    prefetch(0);
+    float* Cs = smem;
+    {
+        const int i = lane & 31, h = lane >> 5;
+#pragma unroll
+        for (int tm = 0; tm < TM; ++tm)
+#pragma unroll
+            for (int tn = 0; tn < TN; ++tn)
+#pragma unroll
+                for (int r = 0; r < 16; ++r)
+                    Cs[(wm + tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * h) * LDC + wn + tn * 32 + i] = acc[tm][tn][r];
+    }
+    __syncthreads();
+    if (col >= N) return;
+    float4 sc = make_float4(1.f, 1.f, 1.f, 1.f), sh = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (ep.scale) sc = *reinterpret_cast<const float4*>(ep.scale + col);
+    if (ep.shift) sh = *reinterpret_cast<const float4*>(ep.shift + col);
+#pragma unroll
+    for (int p0 = 0; p0 < PASSES; p0 += G) {
+        if (p0 > 0) prefetch(p0);
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            const int lr = (p0 + g) * RPP + rp;
+            const int y = y0 + lr / kWinoGroupW, xx = x0 + lr % kWinoGroupW;
+            float4 v = *reinterpret_cast<const float4*>(&Cs[lr * LDC + 4 * c4]);
+            v.x = v.x * sc.x + sh.x; v.y = v.y * sc.y + sh.y; v.z = v.z * sc.z + sh.z; v.w = v.w * sc.w + sh.w;
+            if (pre_res) { v.x += qres[g][0]; v.y += qres[g][1]; v.z += qres[g][2]; v.w += qres[g][3]; }
+            if (ep.relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+            if (y < H && xx < W) *reinterpret_cast<float4*>(ep.C + (((long)img * H + y) * W + xx) * ep.ldc + col) = v;
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // The kernel.  grid.x = tiles_m*tiles_n (XCD-remapped so consecutive tiles along N, which share the
 // A panel, run on one XCD), grid.z = split-K slices.  With split-K the raw partial sums go to the
@@ -905,6 +1013,8 @@ inline int splitk_reduce_blocks(long total) { return (int)((total + 1023) / 1024
 // conv forward on the split-bf16 main loop (conv_bs.hip)
 int conv2d_bf16x3(const dc_conv_desc* d, bool stem, const Epilogue& ep, int M, int N, int K, int bm, int bn, int split, void* workspace,
                   size_t workspace_bytes, hipStream_t s);
+// ... its pointwise 128 x 128 form on the listed 8 x 16-pixel tile groups only (conv_bs.hip)
+int conv2d_bf16x3_tiles(const dc_conv_desc* d, const Epilogue& ep, const int* tiles, const int* count, hipStream_t s);
 
 // short-K pointwise convolutions on the streaming kernel (conv_pw.hip)
 bool conv_pw_stream_supported(const dc_conv_desc* d, const Epilogue& ep);

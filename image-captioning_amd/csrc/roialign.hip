@@ -206,11 +206,17 @@ __global__ __launch_bounds__(256) void roi_align_bwd_gather_kernel(dc_roialign_d
 // the level's number of marks.  Plain stores only; the same lists in the same order on every run.  The marks live in LDS when they fit
 // (RG_LDS_MARKS: 1360 groups at two 1024 x 1024 images) -- the launch is then two global round trips deep, the boxes in and the lists
 // out -- and in the caller's scratch otherwise.
+// (4) dc_roi_tile_groups_lateral only: the tiles of the level-2 LATERAL map (t2, the input of fpn_p2) that the list-driven fpn_p2 reads --
+// every listed level-2 group plus whatever lies within one pixel of it: the group itself and its up to eight neighbours in the group
+// grid of the SAME image (no wrap across a group row, none from one image into the next).  A second ballot scan over the level-2
+// groups, each thread OR-ing the up to nine marks around its group; ascending list, device-side count, plain stores.
 // ------------------------------------------------------------------------------------------------------------------------
 constexpr int RG_THREADS = 1024, RG_WAVES = RG_THREADS / 64, RG_LDS_MARKS = 8192;
 struct RoiGroupsArgs {
     dc_roi_groups_desc d;
     int gy[4], gx[4], off[5];        // tile groups per image (rows, columns); the level's first mark, off[4] = all marks
+    int* lat_list;                   // optional: the level-2 lateral tile list (off[1] entries of room) and its count
+    int* lat_count;
 };
 
 __global__ __launch_bounds__(RG_THREADS) void roi_tile_groups_kernel(RoiGroupsArgs a) {
@@ -274,18 +280,47 @@ __global__ __launch_bounds__(RG_THREADS) void roi_tile_groups_kernel(RoiGroupsAr
         const int hi = tid == 3 ? below[0] : (tid == 2 ? below[3] : (tid == 1 ? below[2] : below[1]));
         d.counts[tid] = hi - lo;
     }
+    if (a.lat_list == nullptr) return;                   // (block-uniform)
+    // the main scan's last barrier is behind every thread: wsum[0] is free, the marks are final
+    const int n0 = a.off[1], gy0 = a.gy[0], gx0 = a.gx[0], gpi0 = gy0 * gx0;
+    int listed = 0;                                      // lateral tiles so far (block-uniform)
+    for (int c0 = 0; c0 < n0; c0 += RG_THREADS) {
+        const int i = c0 + tid;
+        bool on = false;
+        if (i < n0) {
+            const int img = i / gpi0, gr = i - img * gpi0, y = gr / gx0, x = gr - y * gx0;
+            const int* m = marks + img * gpi0;
+            for (int yy = max(y - 1, 0); yy <= min(y + 1, gy0 - 1); ++yy)
+                for (int xx = max(x - 1, 0); xx <= min(x + 1, gx0 - 1); ++xx) on = on || m[yy * gx0 + xx] != 0;
+        }
+        const unsigned long long b = __ballot(on);
+        if (lane == 0) wsum[0][wave] = __popcll(b);
+        __syncthreads();
+        int before = 0, all = 0;
+#pragma unroll
+        for (int w = 0; w < RG_WAVES; ++w) {
+            before += w < wave ? wsum[0][w] : 0;
+            all += wsum[0][w];
+        }
+        if (on) a.lat_list[listed + before + __popcll(b & ((1ull << lane) - 1ull))] = i;
+        listed += all;
+        __syncthreads();
+    }
+    if (tid == 0) a.lat_count[0] = listed;
 }
 
 }  // namespace dcap
 
 using namespace dcap;
 
-extern "C" int dc_roi_tile_groups(const dc_roi_groups_desc* d, void* stream) {
+static int roi_tile_groups_launch(const dc_roi_groups_desc* d, int32_t* lat_list, int32_t* lat_count, void* stream) {
     DC_REQUIRE(d && d->boxes && d->marks && d->counts, DC_EINVAL, "dc_roi_tile_groups: null pointer");
     DC_REQUIRE(d->B > 0 && d->R > 0 && d->pool > 0, DC_EINVAL, "dc_roi_tile_groups: bad B/R/pool");
     DC_REQUIRE(aligned16(d->boxes), DC_EALIGN, "dc_roi_tile_groups: boxes not 16-byte aligned");
     RoiGroupsArgs a;
     a.d = *d;
+    a.lat_list = lat_list;
+    a.lat_count = lat_count;
     long off = 0;
     for (int l = 0; l < 4; ++l) {
         DC_REQUIRE(d->lists[l] && d->Hs[l] > 0 && d->Ws[l] > 0, DC_EINVAL, "dc_roi_tile_groups: bad level %d", l);
@@ -298,6 +333,13 @@ extern "C" int dc_roi_tile_groups(const dc_roi_groups_desc* d, void* stream) {
     DC_REQUIRE(off < (1l << 30) && (long)d->B * d->R * d->pool * d->pool < (1l << 30), DC_EINVAL, "dc_roi_tile_groups: too many groups / samples");
     hipLaunchKernelGGL(roi_tile_groups_kernel, dim3(1), dim3(RG_THREADS), 0, static_cast<hipStream_t>(stream), a);
     return check_launch("roi_tile_groups_kernel");
+}
+
+extern "C" int dc_roi_tile_groups(const dc_roi_groups_desc* d, void* stream) { return roi_tile_groups_launch(d, nullptr, nullptr, stream); }
+
+extern "C" int dc_roi_tile_groups_lateral(const dc_roi_groups_desc* d, int32_t* lat_list, int32_t* lat_count, void* stream) {
+    DC_REQUIRE(lat_list && lat_count, DC_EINVAL, "dc_roi_tile_groups_lateral: null lateral list / count");
+    return roi_tile_groups_launch(d, lat_list, lat_count, stream);
 }
 
 extern "C" int dc_roi_align_pyramid_bwd_f32(const dc_roialign_desc* d, void* stream) {

@@ -372,7 +372,18 @@ class EncoderPlan:
         self.sparse_rois = (self.rpn is None and not self.fast_bf16 and not self.train_stages and not self._external_bn and len(pops) == 4 and
                             all(op[0] == "conv" and op[2] == "fpn_p%d" % (2 + i) and op[2] not in self._external and op[1].w_wino_b3
                                 for i, op in enumerate(pops)))
+        # ... and fpn_c2p2, the last launch in front of them, has the list-driven fpn_p2 as its only reader there: it then runs on the
+        # tiles that launch reads (dc_conv2d_nhwc_tiles_f32).  Only where the dense launch is the kernel the list-driven form repeats bit
+        # for bit -- split-bf16 arithmetic on 128 x 128 tiles without split-K: P2 maps of 32 768 pixels or more (two 512 x 512 images);
+        # smaller plans keep the dense lateral.  The other laterals stay dense: their maps are listed almost whole.
+        self._lat_tiles = False
+        lat = self._ops[self._n_lateral - 1]
+        if self.sparse_rois and lat[0] == "conv" and lat[2] == "fpn_c2p2" and lat[1].math == _lib.MATH_BF16X3:
+            bm, bn, sk = C.c_int(), C.c_int(), C.c_int()
+            check(self.lib.dc_conv2d_tile_config(C.byref(lat[1]), C.byref(bm), C.byref(bn), C.byref(sk)), "dc_conv2d_tile_config")
+            self._lat_tiles = (bm.value, bn.value, sk.value) == (128, 128, 1)
         self._roi_groups = None                            # ops.RoiTileGroups, made by the first forward_rois()
+        self._roi_levels = None                            # (ConvDesc * 4, list pointers) of the one fpn_p2..p5 launch
         self._roi_boxes = {}                               # {R: plan-owned [B,R,4] box buffer}
         if self.rpn is not None:
             from .utils import generate_pyramid_anchors
@@ -562,28 +573,44 @@ class EncoderPlan:
         cs.run(body, warm_calls=1, propagate=True)
 
     def _run_rois(self, boxes):
-        """forward_rois() between the FPN laterals and RoIAlign: the tile-group lists of `boxes`, fpn_p2..p5 on them."""
-        g = ops.roi_tile_groups(boxes, self._roi_groups, float(self.H * self.W), 7)
+        """forward_rois() between the dense FPN laterals and RoIAlign: the tile-group lists of `boxes`, fpn_c2p2 on the tiles the
+        list-driven fpn_p2 reads (plans with _lat_tiles; the others ran it dense with the laterals), fpn_p2..p5 on the listed groups."""
+        g = ops.roi_tile_groups(boxes, self._roi_groups, float(self.H * self.W), 7, lateral=self._lat_tiles)
         stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        for l, op in enumerate(self._ops[self._n_lateral:]):
-            rc = self.lib.dc_conv2d_winograd_groups_f32(C.byref(op[1]), C.c_void_p(g.lists[l].data_ptr()), g.count_ptr(l), stream)
+        if self._lat_tiles:
+            op = self._ops[self._n_lateral - 1]
+            rc = self.lib.dc_conv2d_nhwc_tiles_f32(C.byref(op[1]), C.c_void_p(g.lat_list.data_ptr()), C.c_void_p(g.lat_count.data_ptr()), stream)
             if rc:
-                check(rc, "dc_conv2d_winograd_groups_f32(%s)" % op[2])
+                check(rc, "dc_conv2d_nhwc_tiles_f32(%s)" % op[2])
+        if self._roi_levels is None:                       # the four output layers' descriptors side by side, their lists' addresses
+            descs, ptrs = (ConvDesc * 4)(), (C.c_void_p * 4)()
+            for l, op in enumerate(self._ops[self._n_lateral:]):
+                descs[l] = op[1]
+                ptrs[l] = g.lists[l].data_ptr()
+            self._roi_levels = (descs, ptrs)
+        descs, ptrs = self._roi_levels
+        rc = self.lib.dc_conv2d_winograd_levels_f32(descs, 4, ptrs, C.c_void_p(g.counts.data_ptr()), stream)
+        if rc:
+            check(rc, "dc_conv2d_winograd_levels_f32(fpn_p2..p5)")
 
     def forward_rois(self, images_u8, boxes_norm, out=None, before_align=None):
         """forward() + roi_features(boxes_norm=...) for boxes known BEFORE the pass (ground-truth boxes), with the FPN output
-        convolutions computed only on the tile groups (8 x 16 output pixels) RoIAlign reads: trunk, the four FPN laterals (dense), the
-        tile-group lists of the boxes (dc_roi_tile_groups), fpn_p2..p5 on the listed groups (dc_conv2d_winograd_groups_f32), RoIAlign
-        into `out`.  The features are bit-identical to the dense path's: every computed output sums the same products in the same order.
+        convolutions computed only on the tile groups (8 x 16 output pixels) RoIAlign reads: trunk, the FPN laterals of P5..P3 (dense), the
+        tile-group lists of the boxes (dc_roi_tile_groups_lateral), the P2 lateral fpn_c2p2 on the listed level-2 groups and their
+        neighbours -- what fpn_p2 reads of it -- (dc_conv2d_nhwc_tiles_f32; plans whose dense fpn_c2p2 is not the 128 x 128 split-bf16
+        kernel without split-K, P2 maps below 32 768 pixels, run it dense with the other laterals), fpn_p2..p5 on the listed groups in
+        one launch (dc_conv2d_winograd_levels_f32), RoIAlign into `out`.  The features are bit-identical to the dense path's: every
+        computed output sums the same products in the same order.
 
         images_u8 as in forward(); boxes_norm [B,R,4] normalised (normalize_boxes), any device: copied into a plan-owned buffer first,
         so nothing captured holds a caller's address, and the lists are rebuilt on the device for every call.  Two captured parts:
-        "lat" (trunk + laterals, whatever R is) and "rois<R>" (the list kernel, whose launch carries R, and the four list-driven ones).
+        "lat" (trunk + dense laterals, whatever R is) and "rois<R>" (the list kernel, whose launch carries R, and the list-driven ones).
         before_align: optional callable run right in front of the RoIAlign launch, the only one that writes `out` (the training
         pipeline waits there for the slot's last reader).
 
-        AFTER THIS CALL self.P HOLDS VALID VALUES ONLY INSIDE THE LISTED GROUPS: whatever else the maps hold is stale.  Call forward()
-        before roi_features() with other boxes, or before reading the maps whole.
+        AFTER THIS CALL self.P HOLDS VALID VALUES ONLY INSIDE THE LISTED GROUPS, AND self.pre[0] (t2, the input of fpn_p2) ONLY INSIDE THE
+        LISTED LEVEL-2 GROUPS AND THEIR NEIGHBOURS (plans with _lat_tiles): whatever else the maps hold is stale.  Call forward() before
+        roi_features() with other boxes, or before reading the maps whole.
 
         Plans without the fast path (self.sparse_rois False: an RPN, which reads whole maps; trainable FPN / ResNet stages; bf16
         storage; the direct or fp32-product kernels on the FPN outputs; Vgg16Plan) run the dense pass and roi_features() here."""
@@ -603,7 +630,7 @@ class EncoderPlan:
         if boxes is None:
             boxes = self._roi_boxes[R] = torch.zeros((self.B, R, 4), dtype=torch.float32, device=self.device)
         boxes.copy_(boxes_norm, non_blocking=bool(boxes_norm.is_cuda or boxes_norm.is_pinned()))
-        self._run_part("lat", lambda: self._run_ops(0, self._n_lateral))
+        self._run_part("lat", lambda: self._run_ops(0, self._n_lateral - (1 if self._lat_tiles else 0)))
         self._run_part("rois%d" % R, lambda: self._run_rois(boxes))
         if before_align is not None:
             before_align()

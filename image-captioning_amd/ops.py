@@ -559,7 +559,9 @@ def roi_align_pyramid(maps, boxes, image_area, pool=7, out=None, levels_out=None
 class RoiTileGroups(object):
     """Device buffers of dc_roi_tile_groups for a batch of B images whose pyramid levels have the extents `hw` [(H, W)] * 4: per level a
     list of tile-group indices (int32, as long as the level has groups) and, in counts[level], how many of them the last
-    roi_tile_groups() call listed.  Nothing here is ever read by the host on the hot path."""
+    roi_tile_groups() call listed.  lat_list / lat_count: the tiles of the level-2 lateral map the list-driven fpn_p2 reads (the listed
+    level-2 groups and their neighbours in the group grid), written by roi_tile_groups(..., lateral=True) only.  Nothing here is ever
+    read by the host on the hot path."""
 
     def __init__(self, B, hw, device):
         lib = _lib.load()
@@ -570,14 +572,17 @@ class RoiTileGroups(object):
         self.lists = [torch.zeros(self.B * n, dtype=torch.int32, device=device) for n in self.per_image]
         self.counts = torch.zeros(4, dtype=torch.int32, device=device)
         self.marks = torch.zeros(self.B * sum(self.per_image), dtype=torch.int32, device=device)
+        self.lat_list = torch.zeros(self.B * self.per_image[0], dtype=torch.int32, device=device)
+        self.lat_count = torch.zeros(1, dtype=torch.int32, device=device)
 
     def count_ptr(self, level):
         return C.c_void_p(self.counts.data_ptr() + 4 * level)
 
 
-def roi_tile_groups(boxes, groups, image_area, pool=7):
+def roi_tile_groups(boxes, groups, image_area, pool=7, lateral=False):
     """The tile groups of P2..P5 that roi_align_pyramid(maps, boxes, image_area, pool) reads, into `groups` (RoiTileGroups): the same
-    routing and sampling decisions, taken by the same device functions.  boxes [B,R,4] normalised float32."""
+    routing and sampling decisions, taken by the same device functions.  boxes [B,R,4] normalised float32.  lateral: the same launch
+    also lists, in groups.lat_list / lat_count, the level-2 tiles within one pixel of a listed level-2 group (dc_roi_tile_groups_lateral)."""
     lib = _lib.load()
     _chk(boxes, name="boxes")
     B, R, _ = boxes.shape
@@ -590,8 +595,41 @@ def roi_tile_groups(boxes, groups, image_area, pool=7):
         d.lists[i] = groups.lists[i].data_ptr()
     d.boxes, d.image_area = boxes.data_ptr(), float(image_area)
     d.marks, d.counts = groups.marks.data_ptr(), groups.counts.data_ptr()
-    check(lib.dc_roi_tile_groups(C.byref(d), _stream()), "dc_roi_tile_groups")
+    if lateral:
+        check(lib.dc_roi_tile_groups_lateral(C.byref(d), _ptr(groups.lat_list), _ptr(groups.lat_count), _stream()), "dc_roi_tile_groups_lateral")
+    else:
+        check(lib.dc_roi_tile_groups(C.byref(d), _stream()), "dc_roi_tile_groups")
     return groups
+
+
+def conv2d_tiles(x, w_packed, tile_list, count, out, scale=None, shift=None, residual=None, res_mode=0, relu=False, split_k=1,
+                 math=_lib.MATH_BF16X3):
+    """The 1x1 / stride 1 layer of conv2d(x, w_packed, 1, 1, 1, 0, 0, H, W, ..., split_k=1, math=1) on the 8 x 16-pixel tile groups of
+    `tile_list` only (int32 device tensor of group indices; `count`: int32 device tensor whose first element is the list's length).
+    Listed tiles of `out` get conv2d's values bit for bit, nothing else of it is written.  dc_conv2d_nhwc_tiles_f32."""
+    lib = _lib.load()
+    _chk(x, name="x"), _chk(w_packed, name="w"), _chk(out, name="out")
+    _chk(tile_list, torch.int32, "tile_list"), _chk(count, torch.int32, "count")
+    N, H, W, Cin = x.shape
+    Cout = w_packed.shape[0]
+    if not x.is_contiguous() or not w_packed.is_contiguous() or not out.is_contiguous() or tuple(out.shape) != (N, H, W, Cout):
+        raise _lib.DcapError("conv2d_tiles: x, w and out must be contiguous, out [N,H,W,Cout]")
+    if tuple(w_packed.shape) != (Cout, Cin):
+        raise _lib.DcapError("conv2d_tiles: w must be the packed kernel of a 1x1 layer, [Cout][Cin]")
+    if tile_list.numel() < N * lib.dc_conv2d_winograd_group_count(H, W) or count.numel() < 1:
+        raise _lib.DcapError("conv2d_tiles: the list must have room for every tile group of the map")
+    if residual is not None and (not _chk(residual, name="residual").is_contiguous() or tuple(residual.shape) != (N, H // 2, W // 2, Cout)):
+        raise _lib.DcapError("conv2d_tiles: the upsample-add operand must be contiguous [N,H/2,W/2,Cout]")
+    d = ConvDesc()
+    d.N, d.H, d.W, d.Cin = N, H, W, Cin
+    d.Cout, d.kh, d.kw, d.stride, d.pad_t, d.pad_l, d.Ho, d.Wo = Cout, 1, 1, 1, 0, 0, H, W
+    d.x, d.w, d.y = x.data_ptr(), w_packed.data_ptr(), out.data_ptr()
+    d.scale = None if scale is None else _chk(scale, name="scale").data_ptr()
+    d.shift = None if shift is None else _chk(shift, name="shift").data_ptr()
+    d.residual = None if residual is None else residual.data_ptr()
+    d.res_mode, d.relu, d.split_k, d.math = int(res_mode), int(relu), int(split_k), int(math)
+    check(lib.dc_conv2d_nhwc_tiles_f32(C.byref(d), _ptr(tile_list), _ptr(count), _stream()), "dc_conv2d_nhwc_tiles_f32")
+    return out
 
 
 def conv2d_winograd_groups(x, w_packed, w_wino_b3, group_list, count, out, scale=None, shift=None, relu=False):
@@ -619,6 +657,42 @@ def conv2d_winograd_groups(x, w_packed, w_wino_b3, group_list, count, out, scale
     d.w_wino_b3 = _chk(w_wino_b3, torch.int16, "w_wino_b3").data_ptr()
     check(lib.dc_conv2d_winograd_groups_f32(C.byref(d), _ptr(group_list), _ptr(count), _stream()), "dc_conv2d_winograd_groups_f32")
     return out
+
+
+def conv2d_winograd_levels(xs, ws_packed, ws_wino_b3, lists, counts, outs, scales=None, shifts=None, relu=False):
+    """conv2d_winograd_groups for up to four layers of equal Cin, Cout and relu in ONE launch: per level l the input xs[l], the packed
+    kernel, its winograd_pack_b3, the group list lists[l] and the output outs[l]; counts: int32 device tensor, level l's count at
+    counts[l].  dc_conv2d_winograd_levels_f32."""
+    lib = _lib.load()
+    n = len(xs)
+    if not 1 <= n <= 4 or any(len(v) != n for v in (ws_packed, ws_wino_b3, lists, outs)):
+        raise _lib.DcapError("conv2d_winograd_levels: one to four levels, every argument one entry per level")
+    _chk(counts, torch.int32, "counts")
+    if counts.numel() < n:
+        raise _lib.DcapError("conv2d_winograd_levels: counts must hold one entry per level")
+    descs, ptrs = (ConvDesc * n)(), (C.c_void_p * n)()
+    for l in range(n):
+        x, w, u, out = xs[l], ws_packed[l], ws_wino_b3[l], outs[l]
+        _chk(x, name="x"), _chk(w, name="w"), _chk(out, name="out"), _chk(lists[l], torch.int32, "list")
+        N, H, W, Cin = x.shape
+        Cout = w.shape[0]
+        if not x.is_contiguous() or not out.is_contiguous() or tuple(out.shape) != (N, H, W, Cout):
+            raise _lib.DcapError("conv2d_winograd_levels: x and out must be contiguous [N,H,W,C]")
+        if not u.is_contiguous() or u.numel() != 48 * Cin * Cout:
+            raise _lib.DcapError("conv2d_winograd_levels: w_wino_b3 must be the contiguous winograd_pack_b3() of the layer's kernel")
+        if lists[l].numel() < N * lib.dc_conv2d_winograd_group_count(H, W):
+            raise _lib.DcapError("conv2d_winograd_levels: a list must have room for every tile group of its layer")
+        d = descs[l]
+        d.N, d.H, d.W, d.Cin = N, H, W, Cin
+        d.Cout, d.kh, d.kw, d.stride, d.pad_t, d.pad_l, d.Ho, d.Wo = Cout, 3, 3, 1, 1, 1, H, W
+        d.x, d.w, d.y = x.data_ptr(), w.data_ptr(), out.data_ptr()
+        d.scale = None if scales is None or scales[l] is None else _chk(scales[l], name="scale").data_ptr()
+        d.shift = None if shifts is None or shifts[l] is None else _chk(shifts[l], name="shift").data_ptr()
+        d.relu = int(relu[l] if isinstance(relu, (list, tuple)) else relu)
+        d.w_wino_b3 = _chk(u, torch.int16, "w_wino_b3").data_ptr()
+        ptrs[l] = lists[l].data_ptr()
+    check(lib.dc_conv2d_winograd_levels_f32(descs, n, ptrs, _ptr(counts), _stream()), "dc_conv2d_winograd_levels_f32")
+    return outs
 
 
 def subsample2(x, out=None):

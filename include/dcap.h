@@ -342,6 +342,27 @@ int dc_roi_tile_groups(const dc_roi_groups_desc* d, void* stream);
 int dc_conv2d_winograd_group_count(int H, int W);
 int dc_conv2d_winograd_groups_f32(const dc_conv_desc* d, const int32_t* groups, const int32_t* count, void* stream);
 
+/* The lateral 1x1 in front of fpn_p2 computed only where the list-driven fpn_p2 reads it (the other laterals stay dense: their maps
+ * are listed almost whole).
+ *
+ * dc_roi_tile_groups_lateral: dc_roi_tile_groups, and in the same launch the tiles of the level-2 map that hold a pixel of a listed
+ * level-2 group or of its one-pixel ring (the halo the 3x3 convolution reads): every listed group and its up to eight neighbours in the
+ * group grid of the same image, in ascending group index into lat_list (B * dc_conv2d_winograd_group_count of level 2, int32), their
+ * number into lat_count[0].  The descriptor is dc_roi_tile_groups' own, unchanged.
+ * dc_conv2d_nhwc_tiles_f32: the pointwise layer `d` on the listed 8 x 16-pixel tile groups only (`tiles` / `count`: device pointers) --
+ * every output element inside a listed tile gets the value dc_conv2d_nhwc_f32 gives it, bit for bit (the upsample-add operand of
+ * res_mode 2 included); nothing else of d->y is written; count[0] == 0 is a no-op.  The layer must be a 1x1 / stride 1 / unpadded
+ * convolution in DC_MATH_BF16X3 that dc_conv2d_nhwc_f32 runs on 128 x 128 tiles without split-K (dc_conv2d_tile_config; split_k = 1
+ * pins that where the dense rule would split), res_mode 0 or 2, Cout % 4 == 0: anything else is DC_EINVAL, there is no other path. */
+/* dc_conv2d_winograd_levels_f32: dc_conv2d_winograd_groups_f32 for `nlevels` (1..4) layers in ONE launch -- d: an array of nlevels
+ * descriptors, lists: a host array of nlevels device pointers (level l's group list), counts: device pointer to nlevels int32 (level
+ * l's count at counts[l]).  The work items of all levels cost the same, so the layers must agree in N, Cin, Cout and relu (DC_EINVAL
+ * otherwise); each must be a layer dc_conv2d_winograd_groups_f32 takes.  Every listed group of every level gets the dense values bit
+ * for bit, nothing else is written, an empty level contributes nothing. */
+int dc_conv2d_winograd_levels_f32(const dc_conv_desc* d, int nlevels, const int32_t* const* lists, const int32_t* counts, void* stream);
+int dc_roi_tile_groups_lateral(const dc_roi_groups_desc* d, int32_t* lat_list, int32_t* lat_count, void* stream);
+int dc_conv2d_nhwc_tiles_f32(const dc_conv_desc* d, const int32_t* tiles, const int32_t* count, void* stream);
+
 /* KL.MaxPooling2D(pool_size=(1,1), strides=2): P6 = every other pixel of P5 (dense_model.py:1423). */
 int dc_subsample2_f32(const float* x, float* y, int N, int H, int W, int C, void* stream);
 
