@@ -136,6 +136,17 @@ class BeamSelectDesc(C.Structure):
                 ("U", C.c_int), ("h_in", C.c_void_p), ("c_in", C.c_void_p), ("h_out", C.c_void_p), ("c_out", C.c_void_p)]
 
 
+BEAM_MAX_SETS = 4
+
+
+class BeamStepDesc(C.Structure):
+    _fields_ = [("R", C.c_int), ("k", C.c_int), ("nb", C.c_int), ("steps", C.c_int), ("j", C.c_int), ("log_score", C.c_int),
+                ("cand_ids", C.c_void_p), ("cand_probs", C.c_void_p), ("scores_in", C.c_void_p), ("scores_out", C.c_void_p),
+                ("parents", C.c_void_p), ("tokens_hist", C.c_void_p), ("tokens", C.c_void_p), ("mask", C.c_void_p),
+                ("end_id", C.c_int), ("finished_in", C.c_void_p), ("finished_out", C.c_void_p),
+                ("n_sets", C.c_int), ("U", C.c_int * BEAM_MAX_SETS), ("src", C.c_void_p * BEAM_MAX_SETS), ("dst", C.c_void_p * BEAM_MAX_SETS)]
+
+
 class LstmStepDesc(C.Structure):
     _fields_ = [("B", C.c_int), ("U", C.c_int),
                 ("z", C.c_void_p), ("U_rec", C.c_void_p), ("U_packed", C.c_void_p),
@@ -265,6 +276,7 @@ SYMBOLS = {
     "dc_vocab_top1_bf16": (C.c_int, [C.POINTER(VocabTop1Bf16Desc), C.c_void_p, C.c_size_t, C.c_void_p]),
     "dc_vocab_topk_bf16": (C.c_int, [C.POINTER(VocabTopkBf16Desc), C.c_void_p, C.c_size_t, C.c_void_p]),
     "dc_beam_select_f32": (C.c_int, [C.POINTER(BeamSelectDesc), C.c_void_p]),
+    "dc_beam_step_f32": (C.c_int, [C.POINTER(BeamStepDesc), C.c_void_p]),
     "dc_beam_backtrace": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "dc_argmax_rows_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "dc_gather_rows_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),

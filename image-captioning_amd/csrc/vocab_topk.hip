@@ -9,8 +9,9 @@
 //                       reduces its own 64-column slice in registers and writes its own cells (ceil(V/64) cells per row instead of
 //                       ceil(V/128); no cross-wave combine, no barrier after the main loop), and the row kernel, generic over the
 //                       number of cells per row, combines them unchanged.
-//   dc_beam_select_f32  per RoI, the k best of the k live beams' k proposals each (score + p or score + log p), with the parents'
-//                       word-LSTM rows gathered into the next state buffers;
+//   dc_beam_step_f32    per RoI, the k best of the k beams' proposals (score + p or score + log p; a beam that has produced the end
+//                       token proposes only itself, with token 0), with the parents' rows of up to four state tensors gathered into
+//                       the next state buffers;  dc_beam_select_f32: the same kernel with one (h, c) pair and no end token;
 //   dc_beam_backtrace   the [steps,R,k] parent / token history -> [R,k,steps] sequences.
 //
 // Replaces, per decoded token, Dense(V, activation='softmax') + tf.argmax + the chosen word's probability of the reference's
@@ -264,29 +265,38 @@ __global__ __launch_bounds__(256) void vocab_topk_rows_kernel(int M, int tiles_n
 }
 
 // ------------------------------------------------------------------------------------------------ beam selection
-// One wave per RoI.  Lane l < nb * k holds candidate (beam b = l / k, rank i = l % k) of the beam-major candidate rows b * R + roi:
-// score = scores_in[roi][b] + (p or log p).  k threshold rounds in the order (score descending, parent ascending, word id ascending)
-// give the new beams best first; round q writes beam q's score, history entries and next token, then the whole wave copies the
-// parent's h / c rows into row q * R + roi of the next state buffers.
+// One block of four waves per RoI.  Every wave repeats the decision: lane l < nb * k holds candidate (beam b = l / k, rank i = l % k)
+// of the beam-major candidate rows b * R + roi: score = scores_in[roi][b] + (p or log p).  A beam that finished_in marks proposes ONE
+// candidate, in its rank-0 lane: token 0 at its own score, nothing added; its candidate rows are not read.  k threshold rounds in the
+// order (score descending, parent ascending, word id ascending) give the new beams best first; wave 0 writes beam q's score, history
+// entries, next token, mask and finished byte.  After the first step there are always at least k candidates (a live beam brings k, and
+// at worst k finished beams bring one each), so the "no candidate left" fallback (beam 0, token 0) is met only with NaN probabilities,
+// as before.  Then the block copies the parents' rows of every row set into rows q * R + roi of the set's destination, the float4
+// chunks of all k rows spread over the 256 threads (lane q of every wave keeps beam q's parent; four loads in flight per thread).
 __device__ __forceinline__ bool bs_before(float s, int b, int t, float os, int ob, int ot) {
     return s > os || (s == os && (b < ob || (b == ob && t < ot)));
 }
 
-__global__ __launch_bounds__(256) void beam_select_kernel(dc_beam_select_desc d) {
-    const int roi = (blockIdx.x * 256 + threadIdx.x) >> 6, lane = threadIdx.x & 63;
-    if (roi >= d.R) return;
+__global__ __launch_bounds__(256) void beam_step_kernel(dc_beam_step_desc d) {
+    const int roi = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
     const int k = d.k, R = d.R;
     float s = -INFINITY;
-    int b = INT_MAX, t = INT_MAX;
+    int b = INT_MAX, t = INT_MAX, fin = 0;
     if (lane < d.nb * k) {
-        b = lane / k;
-        const long c = ((long)b * R + roi) * k + lane % k;
-        t = d.cand_ids[c];
-        const float p = d.cand_probs[c];
-        s = (d.scores_in ? d.scores_in[roi * k + b] : 0.f) + (d.log_score ? logf(p) : p);
+        const int lb = lane / k, i = lane - lb * k;
+        fin = d.finished_in && d.finished_in[(long)lb * R + roi] ? 1 : 0;
+        if (fin) {
+            if (i == 0) { b = lb; t = 0; s = d.scores_in ? d.scores_in[roi * k + lb] : 0.f; }
+        } else {
+            const long c = ((long)lb * R + roi) * k + i;
+            b = lb;
+            t = d.cand_ids[c];
+            const float p = d.cand_probs[c];
+            s = (d.scores_in ? d.scores_in[roi * k + lb] : 0.f) + (d.log_score ? logf(p) : p);
+        }
     }
     float ts = INFINITY;
-    int tb = INT_MIN, tt = INT_MIN;
+    int tb = INT_MIN, tt = INT_MIN, par = 0;                   // par: lane q < k keeps new beam q's parent
     for (int q = 0; q < k; ++q) {
         const bool ok = bs_before(ts, tb, tt, s, b, t);       // this lane's candidate comes after the previous winner
         float bs = ok ? s : -INFINITY;
@@ -299,22 +309,41 @@ __global__ __launch_bounds__(256) void beam_select_kernel(dc_beam_select_desc d)
         }
         ts = bs; tb = bb; tt = bt;
         if (bb == INT_MAX) { bb = 0; bt = 0; }                // (no candidate left, only with NaN probabilities: beam 0, token 0)
-        const long dst = (long)q * R + roi;
-        if (lane == 0) {
-            const long hix = ((long)d.j * R + roi) * k + q;
+        const int pfin = __shfl(fin, bb * k, 64);             // the parent's finished flag sits in its rank-0 lane
+        if (lane == q) par = bb;
+        if (tid == 0) {
+            const long dst = (long)q * R + roi, hix = ((long)d.j * R + roi) * k + q;
             d.scores_out[roi * k + q] = bs;
             d.parents[hix] = bb;
             d.tokens_hist[hix] = bt;
             if (d.tokens) d.tokens[dst] = bt;
             if (d.mask) d.mask[dst] = bt != 0 ? 1 : 0;
+            if (d.finished_out) d.finished_out[dst] = pfin || bt == d.end_id ? 1 : 0;
         }
-        if (d.h_in) {
-            const long src = (long)bb * R + roi;
-            const float4* hs = reinterpret_cast<const float4*>(d.h_in + src * d.U);
-            const float4* cs = reinterpret_cast<const float4*>(d.c_in + src * d.U);
-            float4* hd = reinterpret_cast<float4*>(d.h_out + dst * d.U);
-            float4* cdst = reinterpret_cast<float4*>(d.c_out + dst * d.U);
-            for (int u = lane; u < d.U / 4; u += 64) { hd[u] = hs[u]; cdst[u] = cs[u]; }
+    }
+#pragma unroll
+    for (int si = 0; si < DC_BEAM_MAX_SETS; ++si) {
+        if (si >= d.n_sets) break;
+        const int n4 = d.U[si] >> 2, items = k * n4;
+        const float4* __restrict__ src = reinterpret_cast<const float4*>(d.src[si]);
+        float4* __restrict__ dst = reinterpret_cast<float4*>(d.dst[si]);
+        // chunk i of the set's k * n4: row q = i / n4 of the new beams, from the row of q's parent (named registers, not arrays: an
+        // indexed private array here is placed in LDS)
+        auto load = [&](int i, float4& v) -> long {
+            const int q = i < items ? i / n4 : 0;
+            const int p = __shfl(par, q, 64);
+            const int u = i - q * n4;
+            if (i >= items) return -1;
+            v = src[((long)p * R + roi) * n4 + u];
+            return ((long)q * R + roi) * n4 + u;
+        };
+        for (int base = tid; base - tid < items; base += 1024) {
+            float4 v0, v1, v2, v3;
+            const long o0 = load(base, v0), o1 = load(base + 256, v1), o2 = load(base + 512, v2), o3 = load(base + 768, v3);
+            if (o0 >= 0) dst[o0] = v0;
+            if (o1 >= 0) dst[o1] = v1;
+            if (o2 >= 0) dst[o2] = v2;
+            if (o3 >= 0) dst[o3] = v3;
         }
     }
 }
@@ -484,21 +513,55 @@ extern "C" int dc_vocab_top1_bf16(const dc_vocab_top1_bf16_desc* d, void* worksp
     return vocab_topk_bf16_run("dc_vocab_top1_bf16", tk, d->ld_ids, d->ld_probs, d->tokens, d->mask, workspace, workspace_bytes, stream);
 }
 
+static bool bs_overlap(const void* a, const void* b, size_t bytes_a, size_t bytes_b) {
+    const char* x = static_cast<const char*>(a);
+    const char* y = static_cast<const char*>(b);
+    return x < y + bytes_b && y < x + bytes_a;
+}
+
+// The checks and the launch of both beam entry points; fn names the entry point in the messages.
+static int beam_step_run(const char* fn, const dc_beam_step_desc& d, void* stream) {
+    DC_REQUIRE(d.R > 0 && d.k >= 1 && d.k <= TK_MAX && d.nb >= 1 && d.nb <= d.k && d.j >= 0 && d.j < d.steps, DC_EINVAL,
+               "%s: need R > 0, 1 <= nb <= k <= 8, 0 <= j < steps", fn);
+    DC_REQUIRE(d.cand_ids && d.cand_probs && d.scores_out && d.parents && d.tokens_hist, DC_EINVAL, "%s: null pointer", fn);
+    DC_REQUIRE(d.scores_out != d.scores_in, DC_EINVAL, "%s: scores_out must not alias scores_in", fn);
+    DC_REQUIRE(d.end_id >= -1, DC_EINVAL, "%s: end_id is a word id or -1 (none), got %d", fn, d.end_id);
+    DC_REQUIRE(d.end_id < 0 || d.finished_out, DC_EINVAL, "%s: an end token needs finished_out", fn);
+    DC_REQUIRE(!d.finished_out || d.finished_out != d.finished_in, DC_EINVAL, "%s: finished_out must not alias finished_in", fn);
+    DC_REQUIRE(d.n_sets >= 0 && d.n_sets <= DC_BEAM_MAX_SETS, DC_EINVAL, "%s: 0 to %d row sets, got %d", fn, DC_BEAM_MAX_SETS, d.n_sets);
+    const size_t rows = (size_t)d.k * d.R * sizeof(float);
+    for (int i = 0; i < d.n_sets; ++i) {
+        DC_REQUIRE(d.src[i] && d.dst[i] && d.U[i] > 0 && (d.U[i] & 3) == 0, DC_EINVAL, "%s: row set %d needs src, dst and U %% 4 == 0", fn, i);
+        DC_REQUIRE(aligned16(d.src[i]) && aligned16(d.dst[i]), DC_EALIGN, "%s: row set %d must be 16-byte aligned", fn, i);
+        for (int o = 0; o < d.n_sets; ++o)
+            DC_REQUIRE(!bs_overlap(d.dst[i], d.src[o], rows * d.U[i], rows * d.U[o]) &&
+                           (o == i || !bs_overlap(d.dst[i], d.dst[o], rows * d.U[i], rows * d.U[o])),
+                       DC_EINVAL, "%s: dst of row set %d must not alias a src or another dst (set %d)", fn, i, o);
+    }
+    hipLaunchKernelGGL(beam_step_kernel, dim3(d.R), dim3(256), 0, static_cast<hipStream_t>(stream), d);
+    return check_launch("beam_step_kernel");
+}
+
+extern "C" int dc_beam_step_f32(const dc_beam_step_desc* d, void* stream) {
+    DC_REQUIRE(d != nullptr, DC_EINVAL, "dc_beam_step: null descriptor");
+    return beam_step_run("dc_beam_step", *d, stream);
+}
+
+// The earlier entry point: its h / c pair is two row sets of one width, and there is no end token.
 extern "C" int dc_beam_select_f32(const dc_beam_select_desc* d, void* stream) {
     DC_REQUIRE(d != nullptr, DC_EINVAL, "dc_beam_select: null descriptor");
-    DC_REQUIRE(d->R > 0 && d->k >= 1 && d->k <= TK_MAX && d->nb >= 1 && d->nb <= d->k && d->j >= 0 && d->j < d->steps, DC_EINVAL,
-               "dc_beam_select: need R > 0, 1 <= nb <= k <= 8, 0 <= j < steps");
-    DC_REQUIRE(d->cand_ids && d->cand_probs && d->scores_out && d->parents && d->tokens_hist, DC_EINVAL, "dc_beam_select: null pointer");
-    DC_REQUIRE(d->scores_out != d->scores_in, DC_EINVAL, "dc_beam_select: scores_out must not alias scores_in");
+    dc_beam_step_desc s{};
+    s.R = d->R, s.k = d->k, s.nb = d->nb, s.steps = d->steps, s.j = d->j, s.log_score = d->log_score;
+    s.cand_ids = d->cand_ids, s.cand_probs = d->cand_probs, s.scores_in = d->scores_in, s.scores_out = d->scores_out;
+    s.parents = d->parents, s.tokens_hist = d->tokens_hist, s.tokens = d->tokens, s.mask = d->mask;
+    s.end_id = -1;
     if (d->h_in) {
         DC_REQUIRE(d->c_in && d->h_out && d->c_out && d->U > 0 && (d->U & 3) == 0, DC_EINVAL, "dc_beam_select: h/c rows need U %% 4 == 0 and four buffers");
-        DC_REQUIRE(aligned16(d->h_in) && aligned16(d->c_in) && aligned16(d->h_out) && aligned16(d->c_out), DC_EALIGN,
-                   "dc_beam_select: h/c buffers must be 16-byte aligned");
-        DC_REQUIRE(d->h_out != d->h_in && d->c_out != d->c_in && d->h_out != d->c_out, DC_EINVAL,
-                   "dc_beam_select: h_out / c_out must not alias h_in / c_in / each other");
+        s.n_sets = 2;
+        s.U[0] = s.U[1] = d->U;
+        s.src[0] = d->h_in, s.dst[0] = d->h_out, s.src[1] = d->c_in, s.dst[1] = d->c_out;
     }
-    hipLaunchKernelGGL(beam_select_kernel, dim3((d->R + 3) / 4), dim3(256), 0, static_cast<hipStream_t>(stream), *d);
-    return check_launch("beam_select_kernel");
+    return beam_step_run("dc_beam_select", s, stream);
 }
 
 extern "C" int dc_beam_backtrace(const int32_t* parents, const int32_t* tokens_hist, int steps, int R, int k, int32_t* seq, void* stream) {

@@ -156,14 +156,18 @@ def clip_to_window(window, boxes):
     return boxes
 
 
-def refine_generations(rois, word_scores, window, config):
+def refine_generations(rois, word_scores, window, config, caption_scores=None):
     """GenerationMatchLayer for one image (:593-630): caption score = sum over positions of log(max word probability)
-    (word_scores [N,T] holds those maxima); boxes to pixels of the molded image, clipped to the window, rounded;
+    (word_scores [N,T] holds those maxima), or caption_scores [N] when given (the beam decoder's own scores: word_scores is then
+    unused and may be None); boxes to pixels of the molded image, clipped to the window, rounded;
     NMS(DETECTION_NMS_THRESHOLD) on the clipped boxes by caption score; the best DETECTION_MAX_INSTANCES survive.
     (The reference then indexes `keep` by its own leading values, which raises for most inputs; the evident intent --
     the leading entries of `keep` -- is what runs here.)  Returns (int32 boxes [K,4], kept indices [K])."""
-    with np.errstate(divide="ignore"):
-        scores = np.log(np.asarray(word_scores, np.float64)).sum(axis=1)
+    if caption_scores is not None:
+        scores = np.asarray(caption_scores, np.float64)
+    else:
+        with np.errstate(divide="ignore"):
+            scores = np.log(np.asarray(word_scores, np.float64)).sum(axis=1)
     h, w = config.IMAGE_SHAPE[:2]
     boxes = clip_to_window(window, np.asarray(rois, np.float64) * np.array([h, w, h, w], np.float64))
     keep = non_max_suppression(boxes, scores, config.DETECTION_NMS_THRESHOLD)[:config.DETECTION_MAX_INSTANCES]
@@ -1264,7 +1268,8 @@ class DenseImageCapRCNN(object):
             windows.append(window)
         return np.stack(molded), np.stack(metas), np.stack(windows)
 
-    def generate_captions(self, images, verbose=0, return_probabilities=True, decoder="prefix", vocab_math=None):
+    def generate_captions(self, images, verbose=0, return_probabilities=True, decoder="prefix", vocab_math=None, beam_size=None, score="logprob",
+                          end_id=None):
         """The inference graph (:1602-1622) + generate_captions (:1964-2003): RPN proposals (POST_NMS_ROIS_INFERENCE) ->
         RoI features -> greedy ROICaptionInferenceLayer -> GenerationMatchLayer -> boxes in the original image.
         Returns [{'rois': int32 [K,4], 'captions': f32 [K,T,V] word probabilities, 'ids': int32 [K,T]}]; with
@@ -1273,8 +1278,13 @@ class DenseImageCapRCNN(object):
         state and the vocabulary argmax fused into its GEMM, the same ids and word scores; 'prefix' (default): the reference's loop.
         vocab_math='bf16' (decoder='incremental' on a compute_dtype='bf16' model): the vocabulary layer scores words on the bf16 matrix
         pipe from the bf16 activations and the weight's bf16 mirror, the arithmetic the model trains it in (CaptionModelV1.decode_greedy);
-        None / 'f32' (default): from the fp32 activations and the fp32 master weight."""
-        CaptionModelV1.check_decoder(decoder, return_probabilities, vocab_math, getattr(self, "compute_dtype", None) if vocab_math == "bf16" else None)
+        None / 'f32' (default): from the fp32 activations and the fp32 master weight.
+        decoder='beam' (needs return_probabilities=False and beam_size=k; score='logprob' or 'prob', end_id=None or the end word's id,
+        vocab_math as above): CaptionModelV1.decode_beam.  Each RoI's caption is its best beam and the caption score that orders the NMS
+        is that beam's score (with end_id: the sum up to and including the end word).  Each result holds 'rois', 'ids' [K,T] (the best
+        beam), 'beam_ids' [K,k,T] and 'beam_scores' [K,k] (best first)."""
+        CaptionModelV1.check_decoder(decoder, return_probabilities, vocab_math, getattr(self, "compute_dtype", None) if vocab_math == "bf16" else None,
+                                     beam_size=beam_size, score=score, end_id=end_id)
         assert self.mode == "inference", "Create model in inference mode."
         assert len(images) == self.config.BATCH_SIZE, "len(images) must be equal to BATCH_SIZE"
         molded, metas, windows = self.mold_inputs(images)
@@ -1285,6 +1295,14 @@ class DenseImageCapRCNN(object):
         feats = p.roi_features(boxes_norm=proposals)
         results = []
         for b in range(len(images)):
+            if decoder == "beam":
+                _, beam_ids, beam_scores = self.caption_model.generate(feats[b], return_probabilities=False, decoder="beam", vocab_math=vocab_math,
+                                                                       beam_size=beam_size, score=score, end_id=end_id)
+                boxes, keep = refine_generations(proposals[b].cpu().numpy(), None, windows[b], self.config, caption_scores=beam_scores[:, 0])
+                final, ok = unmold_generations(boxes, images[b].shape, windows[b])
+                keep = keep[ok]
+                results.append({"rois": final[ok], "ids": beam_ids[keep, 0], "beam_ids": beam_ids[keep], "beam_scores": beam_scores[keep]})
+                continue
             probs, ids, word_scores = self.caption_model.generate(feats[b], return_probabilities=return_probabilities, decoder=decoder,
                                                                   vocab_math=vocab_math)
             boxes, keep = refine_generations(proposals[b].cpu().numpy(), word_scores, windows[b], self.config)

@@ -12,7 +12,7 @@ import torch
 
 from . import _lib
 from ._lib import (PwChainDesc, ConvBf16Desc, AmsgradDesc, DetectionTargetsDesc, BnReluDesc, ConvDesc, ConvWgradBf16Desc, GemmBf16Desc, VocabCeDesc, ProposalDesc, RpnLossDesc, GemmDesc, LstmBwdDesc, LstmFwdDesc, RoiAlignDesc, RoiGroupsDesc,
-                   SoftmaxCeDesc, VocabTop1Desc, VocabTopkDesc, VocabTop1Bf16Desc, VocabTopkBf16Desc, BeamSelectDesc, LstmStepDesc, check)
+                   SoftmaxCeDesc, VocabTop1Desc, VocabTopkDesc, VocabTop1Bf16Desc, VocabTopkBf16Desc, BeamSelectDesc, BeamStepDesc, LstmStepDesc, check)
 
 
 def _stream():
@@ -1073,6 +1073,69 @@ def beam_select(cand_ids, cand_probs, scores_in, scores_out, parents, tokens_his
     d.parents, d.tokens_hist, d.tokens, d.mask = parents.data_ptr(), tokens_hist.data_ptr(), _ptr(tokens), _ptr(mask)
     d.U, d.h_in, d.c_in, d.h_out, d.c_out = U, _ptr(h_in), _ptr(c_in), _ptr(h_out), _ptr(c_out)
     check(lib.dc_beam_select_f32(C.byref(d), _stream()), "dc_beam_select_f32")
+    return scores_out
+
+
+def beam_step(cand_ids, cand_probs, scores_in, scores_out, parents, tokens_hist, j, nb, log_score=False, tokens=None, mask=None,
+              rows=(), end_id=None, finished_in=None, finished_out=None):
+    """One beam-search step (dc_beam_step_f32): beam_select's step -- the same rows, order (score descending, parent beam ascending, word
+    id ascending) and outputs -- with row sets and an end token.  rows: up to 4 (src, dst) pairs of float32 [k*R,U] tensors (U % 4 == 0,
+    widths may differ, 16-byte aligned, no dst overlapping a src or another dst): row q*R + r of dst receives row parent*R + r of src.
+    end_id (None: no end token): a beam whose finished_in byte (uint8 [k*R]; None: nobody is finished) is set proposes one candidate,
+    token 0 at its unchanged score, and its cand_ids / cand_probs rows are not read; finished_out (uint8 [k*R], required with end_id,
+    not finished_in) marks the new beams whose parent was finished or whose token is end_id.  A finished beam's token 0 writes mask 0."""
+    rows = tuple(rows)
+    if len(rows) > _lib.BEAM_MAX_SETS:
+        raise _lib.DcapError("beam_step: at most %d row sets, got %d" % (_lib.BEAM_MAX_SETS, len(rows)))
+    if end_id is not None and (isinstance(end_id, bool) or int(end_id) != end_id or end_id < 0):
+        raise _lib.DcapError("beam_step: end_id must be a word id or None, got %r" % (end_id,))
+    if end_id is not None and finished_out is None:
+        raise _lib.DcapError("beam_step: end_id needs finished_out")
+    if finished_out is not None and finished_in is not None and finished_out.data_ptr() == finished_in.data_ptr():
+        raise _lib.DcapError("beam_step: finished_out must not alias finished_in")
+    R, k = scores_out.shape
+    spans = []
+    for i, pair in enumerate(rows):
+        if len(pair) != 2:
+            raise _lib.DcapError("beam_step: row set %d must be a (src, dst) pair" % i)
+        src, dst = pair
+        for name, t in (("src", src), ("dst", dst)):
+            if t.dtype != torch.float32 or t.dim() != 2 or not t.is_contiguous() or tuple(t.shape) != (k * R, src.shape[-1]):
+                raise _lib.DcapError("beam_step: row set %d: %s must be a contiguous float32 [k*R,U] tensor" % (i, name))
+            if t.shape[1] % 4 or t.data_ptr() % 16:
+                raise _lib.DcapError("beam_step: row set %d: %s needs U %% 4 == 0 and a 16-byte aligned base" % (i, name))
+        spans.append(((src.data_ptr(), src.data_ptr() + src.numel() * 4), (dst.data_ptr(), dst.data_ptr() + dst.numel() * 4)))
+    for i, (_, d0) in enumerate(spans):
+        for o, (s1, d1) in enumerate(spans):
+            if any(a[0] < b[1] and b[0] < a[1] for a, b in ((d0, s1),) + (((d0, d1),) if o != i else ())):
+                raise _lib.DcapError("beam_step: dst of row set %d must not alias a src or another dst (set %d)" % (i, o))
+    lib = _lib.load()
+    _chk(scores_out, name="scores_out")
+    for name, t, dt, shape in (("cand_ids", cand_ids, torch.int32, (k * R, k)), ("cand_probs", cand_probs, torch.float32, (k * R, k)),
+                               ("scores_in", scores_in, torch.float32, (R, k)), ("tokens", tokens, torch.int32, (k * R,)),
+                               ("mask", mask, torch.uint8, (k * R,)), ("finished_in", finished_in, torch.uint8, (k * R,)),
+                               ("finished_out", finished_out, torch.uint8, (k * R,))):
+        if t is not None and (not _chk(t, dt, name).is_contiguous() or tuple(t.shape) != shape):
+            raise _lib.DcapError("beam_step: %s must be a contiguous %s %s tensor" % (name, dt, shape))
+    steps = parents.shape[0]
+    for name, t in (("parents", parents), ("tokens_hist", tokens_hist)):
+        if not _chk(t, torch.int32, name).is_contiguous() or tuple(t.shape) != (steps, R, k):
+            raise _lib.DcapError("beam_step: %s must be a contiguous int32 [steps,R,k] tensor" % name)
+    if not scores_out.is_contiguous() or not 1 <= k <= TOPK_MAX or not 1 <= nb <= k or not 0 <= j < steps:
+        raise _lib.DcapError("beam_step: need contiguous scores_out, 1 <= nb <= k <= %d, 0 <= j < steps" % TOPK_MAX)
+    for i, (src, dst) in enumerate(rows):
+        _chk(src, name="rows[%d] src" % i), _chk(dst, name="rows[%d] dst" % i)
+    if R == 0:
+        return scores_out
+    d = BeamStepDesc()
+    d.R, d.k, d.nb, d.steps, d.j, d.log_score = R, k, int(nb), steps, int(j), int(bool(log_score))
+    d.cand_ids, d.cand_probs, d.scores_in, d.scores_out = cand_ids.data_ptr(), cand_probs.data_ptr(), _ptr(scores_in), scores_out.data_ptr()
+    d.parents, d.tokens_hist, d.tokens, d.mask = parents.data_ptr(), tokens_hist.data_ptr(), _ptr(tokens), _ptr(mask)
+    d.end_id, d.finished_in, d.finished_out = -1 if end_id is None else int(end_id), _ptr(finished_in), _ptr(finished_out)
+    d.n_sets = len(rows)
+    for i, (src, dst) in enumerate(rows):
+        d.U[i], d.src[i], d.dst[i] = src.shape[1], src.data_ptr(), dst.data_ptr()
+    check(lib.dc_beam_step_f32(C.byref(d), _stream()), "dc_beam_step_f32")
     return scores_out
 
 

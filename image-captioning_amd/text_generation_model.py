@@ -593,24 +593,39 @@ class CaptionModelV1(KerasLikeModel):
     def test_on_batch(self, inputs, targets):
         return float(self.test_on_batch_device(inputs, targets).item())
 
-    DECODERS = ("prefix", "incremental")
+    DECODERS = ("prefix", "incremental", "beam")
     VOCAB_MATH = (None, "f32", "bf16")
+    SCORES = ("prob", "logprob")
 
     @classmethod
-    def check_decoder(cls, decoder, return_probabilities, vocab_math=None, compute_dtype=None):
-        """decoder='incremental' never forms the per-step [B,V] probability rows: it needs return_probabilities=False.
+    def check_decoder(cls, decoder, return_probabilities, vocab_math=None, compute_dtype=None, beam_size=None, score="logprob", end_id=None):
+        """decoder='incremental' and 'beam' never form the per-step [B,V] probability rows: they need return_probabilities=False.
+        decoder='beam' needs beam_size in 1..ops.TOPK_MAX (an integer, not a bool); score is 'logprob' (the sum of log p, the caption score
+        of GenerationMatchLayer; the default) or 'prob' (the sum of p); end_id is None (fixed length T) or the end word's id >= 1.
+        beam_size and end_id belong to 'beam' alone.
         vocab_math: None / 'f32' (the vocabulary layer scores words from the fp32 activations and the fp32 master weight) or 'bf16' (from
         their bf16 copies on the bf16 matrix pipe, the arithmetic a bf16 model trains that layer in): 'bf16' needs decoder='incremental'
-        and a model that computes in bf16 (compute_dtype: the model's; only a bf16 model keeps the weight's bf16 mirror)."""
+        or 'beam' and a model that computes in bf16 (compute_dtype: the model's; only a bf16 model keeps the weight's bf16 mirror)."""
         if decoder not in cls.DECODERS:
             raise ValueError("decoder must be one of %s, got %r" % (cls.DECODERS, decoder))
-        if decoder == "incremental" and return_probabilities is not False:
-            raise ValueError("decoder='incremental' returns no word probabilities: pass return_probabilities=False")
+        if decoder == "beam":
+            if beam_size is None or isinstance(beam_size, bool) or int(beam_size) != beam_size or not 1 <= beam_size <= ops.TOPK_MAX:
+                raise ValueError("decoder='beam' needs beam_size in 1..%d, got %r" % (ops.TOPK_MAX, beam_size))
+        elif beam_size is not None or end_id is not None:
+            raise ValueError("beam_size and end_id are only for decoder='beam' (got decoder=%r)" % (decoder,))
+        if decoder != "prefix" and return_probabilities is not False:
+            raise ValueError("decoder=%r returns no word probabilities: pass return_probabilities=False" % (decoder,))
+        if decoder == "beam":
+            if score not in cls.SCORES:
+                raise ValueError("score must be one of %s, got %r" % (cls.SCORES, score))
+            if end_id is not None and (isinstance(end_id, bool) or int(end_id) != end_id or end_id < 1):
+                raise ValueError("end_id must be None or the end word's id, an integer in [1, V), got %r" % (end_id,))
         if vocab_math not in cls.VOCAB_MATH:
             raise ValueError("vocab_math must be one of %s, got %r" % (cls.VOCAB_MATH, vocab_math))
         if vocab_math == "bf16":
-            if decoder != "incremental":
-                raise ValueError("vocab_math='bf16' is the incremental decoder's fused vocabulary top-1: pass decoder='incremental' (got %r)" % (decoder,))
+            if decoder == "prefix":
+                raise ValueError("vocab_math='bf16' is the device decoders' fused vocabulary top-k: pass decoder='incremental' or 'beam' "
+                                 "(got %r)" % (decoder,))
             if compute_dtype != "bf16":
                 raise ValueError("vocab_math='bf16' needs a model built with compute_dtype='bf16' (its vocabulary weight's bf16 mirror), "
                                  "this one computes in %r" % (compute_dtype,))
@@ -683,14 +698,89 @@ class CaptionModelV1(KerasLikeModel):
             ops.vocab_top1(a1.b if vb else a1.f, Wv, w['imgcap_lstm_d2/bias'], tokens=tok, ids=ids[:, j], probs=scores[:, j], mask=live)
         return out
 
-    def generate(self, feat, return_probabilities=None, decoder="prefix", vocab_math=None):
+    def decode_beam(self, feat, beam_size, score="logprob", end_id=None, vocab_math=None):
+        """Beam search over ROICaptionInferenceLayer's decoder for every RoI at once, on the device.  Every beam starts from token 1; each
+        of the T steps runs, over the k*B beam-major rows (beam b of RoI r = row b*B + r), the embedding-gather GEMM, one carried-state
+        step of each LSTM, the Dense-1024 and the vocabulary layer fused with its row top-k (ops.vocab_topk: every beam's k = beam_size
+        most probable words), then ops.beam_step: a candidate scores its beam's score + log p (score='logprob', Model 3's own caption
+        score) or + p ('prob'); the k best survive in the order score descending, parent beam ascending, word id ascending, and the four
+        LSTM state tensors follow their parents.  A chosen 0 is masked (the state carries over it), as in decode_greedy.
+        end_id (None: every caption runs T steps): a beam that has chosen this word is finished -- it stays a candidate at its score, adds
+        nothing more, and its later tokens are 0; so a returned score is the sum up to and including the end word.
+        vocab_math='bf16' (bf16 models): the vocabulary layer on the bf16 matrix pipe, as decode_greedy.
+        Returns device tensors (tokens int32 [B,k,T], scores float32 [B,k]), best first, views of one buffer.  No host synchronisation."""
+        B, k, T, out = self._decode_beam(feat, beam_size, score, end_id, vocab_math)
+        return out[:B * k * T].view(B, k, T), out[B * k * T:].view(torch.float32).view(B, k)
+
+    def _decode_beam(self, feat, beam_size, score, end_id, vocab_math):
+        """decode_beam into one flat int32 device buffer: the [B,k,T] tokens, then the [B,k] scores' float32 bits."""
+        self.check_decoder("beam", False, vocab_math, getattr(self, "compute_dtype", None) if vocab_math == "bf16" else None, beam_size=beam_size,
+                           score=score, end_id=end_id)
+        k = int(beam_size)
+        if k > self.V:
+            raise ValueError("beam_size %d exceeds the vocabulary (%d words)" % (k, self.V))
+        if end_id is not None and end_id >= self.V:
+            raise ValueError("end_id %d is outside the vocabulary (%d words)" % (end_id, self.V))
+        feat = self._dev_feat(feat)
+        B, T, u, w = feat.shape[0], self.T, self.units, self.store.w
+        out = torch.empty((B * k * (T + 1),), dtype=torch.int32, device=self.device)
+        if B == 0:
+            return B, k, T, out
+        n = k * B
+        tokens, final = out[:n * T].view(B, k, T), out[n * T:].view(torch.float32).view(B, k)
+        vb = vocab_math == "bf16"
+        self._draw_rec_masks(B, training=False)
+        f = self._head_forward(feat.reshape(B, -1))
+        zf = self._mm(f, self._wview('imgcap_lstm1/kernel', (self.E, self.E + self.FEAT)), key='dec_zf').f        # per RoI: res_rows=B below
+        zdf = self._mm(f, self._wview('imgcap_lstm_d1/kernel', (u, u + self.FEAT)), key='dec_zdf').f
+        U1, U2 = w['imgcap_lstm1/recurrent_kernel'], w['imgcap_lstm2/recurrent_kernel']
+        pk = [ops.lstm_pack_urec(Ur, out=self._buf('dec_upk%d' % l, (u, 4 * u))) if u % 32 == 0 else None for l, Ur in enumerate((U1, U2))]
+        emb_b = self._emb_bf16()
+        Wv = self._vocab_mirror() if vb else self._wview('imgcap_lstm_d2/kernel')[0]
+        tok = self._buf('bm_tok', (n,), torch.int32).fill_(1)           # start token (:203) on every beam row
+        live = self._buf('bm_live', (n,), torch.uint8)
+        # two state sets (h1, c1, h2, c2): the LSTM steps write S, beam_step gathers the parents' rows of S into G, the next steps read G
+        S, G = ([self._buf('bm_%s%d_%d' % (x, l, q), (n, u)) for l in range(2) for x in 'hc'] for q in range(2))
+        parents, hist = self._buf('bm_par', (T, B, k), torch.int32), self._buf('bm_hist', (T, B, k), torch.int32)
+        sc = [self._buf('bm_sc%d' % q, (B, k)) for q in range(2)]
+        fin = [self._buf('bm_fin%d' % q, (n,), torch.uint8) for q in range(2)] if end_id is not None else None
+        cids, cprobs = self._buf('bm_cid', (n, k), torch.int32), self._buf('bm_cp', (n, k))
+        for j in range(T):
+            if emb_b is not None:
+                z1 = ops.gemm_bf16(emb_b, self.store.wb['imgcap_lstm1/kernel'][:emb_b.shape[1]], gather=tok, shift=w['imgcap_lstm1/bias'],
+                                   residual=zf, res_rows=B, out=self._buf('bm_z1', (n, 4 * u)))
+            else:
+                z1 = ops.gemm(w['imgcap_embedding_layer/embeddings'], w['imgcap_lstm1/kernel'][:self.E], gather=tok, shift=w['imgcap_lstm1/bias'],
+                              residual=zf, res_rows=B, out=self._buf('bm_z1', (n, 4 * u)))
+            first, last = j == 0, j + 1 == T
+            mask = None if first else live                               # token 1 is never masked; then id != 0 of the step before
+            h1, c1 = ops.lstm_step(z1, U1, None if first else G[0], None if first else G[1], mask, S[0], S[1], U_packed=pk[0])
+            z2 = self._mm(self._act('bm_h1', h1), self._wview('imgcap_lstm2/kernel'), key='bm_z2', shift=w['imgcap_lstm2/bias']).f
+            h2, c2 = ops.lstm_step(z2, U2, None if first else G[2], None if first else G[3], mask, S[2], S[3], U_packed=pk[1])
+            a1 = self._mm(self._act('bm_h2', h2), self._wview('imgcap_lstm_d1/kernel', (0, u)), key='bm_a1', shift=w['imgcap_lstm_d1/bias'],
+                          residual=zdf, res_rows=B, relu=True, want_b=vb)
+            ops.vocab_topk(a1.b if vb else a1.f, Wv, w['imgcap_lstm_d2/bias'], k, ids=cids, probs=cprobs)
+            end = {} if fin is None else dict(end_id=int(end_id), finished_in=None if first else fin[j % 2], finished_out=fin[(j + 1) % 2])
+            ops.beam_step(cids, cprobs, None if first else sc[j % 2], final if last else sc[(j + 1) % 2], parents, hist, j, 1 if first else k,
+                          score == "logprob", tokens=tok, mask=live, rows=() if last else tuple(zip(S, G)), **end)
+        ops.beam_backtrace(parents, hist, out=tokens)
+        return B, k, T, out
+
+    def generate(self, feat, return_probabilities=None, decoder="prefix", vocab_math=None, beam_size=None, score="logprob", end_id=None):
         """ROICaptionInferenceLayer (:192-232): start token 1; step j feeds [prev..., 0...] through the word
         model and appends float(argmax).  Returns (probs [B,T,V], ids [B,T]); with return_probabilities given (the joint
         model) returns (probs or None, ids, word_scores [B,T] = the probability of each chosen word).
         decoder='incremental' (needs return_probabilities=False): decode_greedy -- one token per step on the device, no [B,V] rows --
         returning (None, ids, word_scores) through one device-to-host copy; 'prefix' (default): the reference's T-prefix loop below.
-        vocab_math='bf16' (incremental decoder of a bf16 model only): see decode_greedy; the default scores words in fp32."""
-        self.check_decoder(decoder, return_probabilities, vocab_math, getattr(self, "compute_dtype", None) if vocab_math == "bf16" else None)
+        decoder='beam' (needs return_probabilities=False and beam_size=k; score=, end_id=: see decode_beam) returns
+        (None, tokens int32 [B,k,T], scores float32 [B,k]), best beam first, through one device-to-host copy.
+        vocab_math='bf16' (the device decoders of a bf16 model only): see decode_greedy; the default scores words in fp32."""
+        self.check_decoder(decoder, return_probabilities, vocab_math, getattr(self, "compute_dtype", None) if vocab_math == "bf16" else None,
+                           beam_size=beam_size, score=score, end_id=end_id)
+        if decoder == "beam":
+            B, k, T, out = self._decode_beam(feat, beam_size, score, end_id, vocab_math)
+            host = out.cpu().numpy()
+            return None, host[:B * k * T].reshape(B, k, T), host[B * k * T:].view(np.float32).reshape(B, k)
         if decoder == "incremental":
             host = self._decode_greedy(feat, vocab_math).cpu().numpy()
             return None, host[0], host[1].view(np.float32)

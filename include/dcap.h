@@ -643,7 +643,7 @@ int    dc_vocab_top1_bf16(const dc_vocab_top1_bf16_desc* d, void* workspace, siz
 int    dc_vocab_topk_bf16(const dc_vocab_topk_bf16_desc* d, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
- * One beam-search step for R RoIs with k beams each (image captioning/test.py:33-56), one wave per RoI.  Rows of the per-beam
+ * One beam-search step for R RoIs with k beams each (image captioning/test.py:33-56).  Rows of the per-beam
  * tensors are BEAM-MAJOR: beam b of RoI r is row b * R + r.
  *   cand_ids / cand_probs [k*R][k]: dc_vocab_topk_f32's output for every beam row;  nb: live beams (1 at the first step, then k);
  *   scores_in [R][k] (NULL: zeros).  Candidate (b, i) scores scores_in[r][b] + p (log_score 0, the reference's rule) or + log p.
@@ -651,6 +651,16 @@ int    dc_vocab_topk_bf16(const dc_vocab_topk_bf16_desc* d, void* workspace, siz
  *   scores_out [R][k], parents / tokens_hist [steps][R][k] at step j, tokens [k*R] (optional: the next embedding-gather rows),
  *   mask [k*R] (optional: token != 0).  h_in / c_in -> h_out / c_out [k*R][U] (optional, U % 4 == 0, 16-byte aligned): row q * R + r
  *   receives row parent * R + r (the word LSTM's state follows its beam).
+ * dc_beam_step_f32: the same step (same rows, order and fallback; dc_beam_select_f32 runs its kernel) with two additions.
+ *   Row sets: n_sets <= DC_BEAM_MAX_SETS entries (src, dst, U), each [k*R][U] with U % 4 == 0 and 16-byte aligned bases; widths may
+ *   differ.  Row q * R + r of dst receives row parent * R + r of src.  No dst may overlap a src or another dst.  n_sets = 0: no copy.
+ *   End token: end_id (-1: none), finished_in uint8 [k*R] (NULL: nobody is finished), finished_out uint8 [k*R] (required when
+ *   end_id >= 0; must not alias finished_in).  A finished beam proposes exactly ONE candidate: token 0 at its scores_in entry, nothing
+ *   added under either score rule, its parent itself; its cand_ids / cand_probs rows are not read.  A live beam proposes its k words.
+ *   New beam q is finished when its parent was or its token is end_id.  A finished beam's token 0 writes mask 0, so the next LSTM
+ *   steps carry its state (the carry a generated 0 gets anyway).  After the first step there are always at least k candidates: a live
+ *   beam brings k, and at worst k finished beams bring one each.
+ *   One block of four waves per RoI: every wave repeats the k selection rounds, the row copies are spread over the block.
  * dc_beam_backtrace: parents / tokens_hist [steps][R][k] -> seq [R][k][steps], the beams' token sequences.
  * ------------------------------------------------------------------------------------------------ */
 typedef struct {
@@ -670,7 +680,29 @@ typedef struct {
     float* c_out;
 } dc_beam_select_desc;
 
+#define DC_BEAM_MAX_SETS 4
+
+typedef struct {
+    int R, k, nb, steps, j, log_score;
+    const int32_t* cand_ids;
+    const float* cand_probs;
+    const float* scores_in;
+    float* scores_out;
+    int32_t* parents;
+    int32_t* tokens_hist;
+    int32_t* tokens;
+    uint8_t* mask;
+    int end_id;
+    const uint8_t* finished_in;
+    uint8_t* finished_out;
+    int n_sets;
+    int U[DC_BEAM_MAX_SETS];
+    const float* src[DC_BEAM_MAX_SETS];
+    float* dst[DC_BEAM_MAX_SETS];
+} dc_beam_step_desc;
+
 int    dc_beam_select_f32(const dc_beam_select_desc* d, void* stream);
+int    dc_beam_step_f32(const dc_beam_step_desc* d, void* stream);
 int    dc_beam_backtrace(const int32_t* parents, const int32_t* tokens_hist, int steps, int R, int k, int32_t* seq, void* stream);
 
 /* tf.argmax over the last axis, lowest index wins ties (text_generation_model.py:222-225). */

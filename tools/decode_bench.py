@@ -12,6 +12,14 @@ Shapes: configs[4] inference (K = 1000 RoIs = POST_NMS_ROIS_INFERENCE, T = 15, V
 --repeats.  Prints one JSON line per measurement and, with --out, writes them all to that JSON file (profiles/decode_bench.json).
 
     python tools/decode_bench.py [--repeats 5] [--out decode_bench.json]
+
+--what beam: the beam decoder instead (profiles/decode_bench_beam_v1.json).  Per shape and dtype, generate(decoder='beam') at beam_size 3
+and 5, each without an end token and with end_id=2, timed ALTERNATING with the incremental leg of the same vocabulary arithmetic (fp32 model:
+fp32; bf16 model: vocab_math='bf16') in one process; then ops.beam_step alone at R = 1000, k = 5 with four row sets of U = 512 (Model 3's
+step), alternating with the sequence it replaces: ops.beam_select without rows plus four torch.index_select copies of the same bytes
+(their row index made outside the timed region).  Device events, medians of --repeats (at least 5).
+
+    python tools/decode_bench.py --what beam --out profiles/decode_bench_beam_v1.json
 """
 import argparse
 import json
@@ -69,6 +77,75 @@ def model_for(V, T, K, units, dtype, seed=0):
     return CaptionModelV1([7, 7, 256], cfg, units, 'inference', seed=seed, compute_dtype=dtype)
 
 
+def beam_legs(args, shapes, rows):
+    """--what beam: the beam decoder against the incremental one, then ops.beam_step alone against beam_select + index_select."""
+    from image_captioning_amd import ops
+    reps, warm = max(args.repeats, 5), max(args.warmup, 1)
+    for key in args.shapes.split(","):
+        sh = shapes[key]
+        for dtype in args.dtypes.split(","):
+            model = model_for(sh["V"], sh["T"], sh["K"], sh["units"], dtype)
+            feat = torch.tensor(np.random.default_rng(1).standard_normal((sh["K"], 7, 7, 256)).astype(np.float32), device="cuda:0")
+            vm = "bf16" if dtype == "bf16" else None
+            legs = [(dict(decoder="incremental"), lambda: model.generate(feat, return_probabilities=False, decoder="incremental", vocab_math=vm))]
+            for k in (3, 5):
+                for end_id in (None, 2):
+                    legs.append((dict(decoder="beam", beam_size=k, end_id=end_id),
+                                 lambda k=k, e=end_id: model.generate(feat, return_probabilities=False, decoder="beam", beam_size=k, end_id=e, vocab_math=vm)))
+            res = timed_alternating([fn for _, fn in legs], warm, reps)
+            inc = res[0][0]
+            for (kw, _), (ms, all_ms) in zip(legs, res):
+                rows.append(dict(what="decode_per_image", shape=sh["name"], dtype=dtype, vocab_math=vm or "f32", alternating=True, K=sh["K"], T=sh["T"],
+                                 V=sh["V"], units=sh["units"], ms=round(ms, 3), runs_ms=all_ms, spread_ms=round(max(all_ms) - min(all_ms), 3),
+                                 times_incremental=round(ms / inc, 2), timing="device events around the call, median of %d, legs alternating" % reps, **kw))
+                print(json.dumps(rows[-1]), flush=True)
+            del model
+            torch.cuda.empty_cache()
+    # the step kernel alone: Model 3's step at configs[4] (four state tensors of 512 units follow their beams)
+    R, k, U, nsets = 1000, 5, 512, 4
+    rng = np.random.default_rng(3)
+    dev = lambda a, dt: torch.tensor(a, dtype=dt, device="cuda:0")
+    cid = dev(np.stack([rng.permutation(50000)[:k] for _ in range(k * R)]), torch.int32)
+    cp = dev(rng.uniform(1e-4, 0.2, (k * R, k)), torch.float32)
+    sin = dev(-rng.uniform(0, 10, (R, k)), torch.float32)
+    so = torch.empty((R, k), device="cuda:0")
+    par, hist = (torch.zeros((2, R, k), dtype=torch.int32, device="cuda:0") for _ in range(2))
+    tok, mask = torch.empty((k * R,), dtype=torch.int32, device="cuda:0"), torch.empty((k * R,), dtype=torch.uint8, device="cuda:0")
+    src = [dev(rng.standard_normal((k * R, U)), torch.float32) for _ in range(nsets)]
+    dst = [torch.empty((k * R, U), device="cuda:0") for _ in range(nsets)]
+    ops.beam_select(cid, cp, sin, so, par, hist, 1, k, True, tokens=tok, mask=mask)
+    index = (par[1].t().contiguous().view(-1).long() * R + torch.arange(R, device="cuda:0").repeat(k))       # source row of row q * R + r
+
+    def fused():
+        ops.beam_step(cid, cp, sin, so, par, hist, 1, k, True, tokens=tok, mask=mask, rows=list(zip(src, dst)))
+
+    def unfused():
+        ops.beam_select(cid, cp, sin, so, par, hist, 1, k, True, tokens=tok, mask=mask)
+        for s_, d_ in zip(src, dst):
+            torch.index_select(s_, 0, index, out=d_)
+
+    def select_only():
+        ops.beam_step(cid, cp, sin, so, par, hist, 1, k, True, tokens=tok, mask=mask)
+
+    fused()
+    want = [d_.clone() for d_ in dst]
+    unfused()
+    same = all(bool(torch.equal(a, b)) for a, b in zip(want, dst))
+    res = timed_alternating([fused, unfused, select_only], 3, 20)
+    moved = 2.0 * nsets * k * R * U * 4
+    for name, (ms, all_ms) in zip(("beam_step, 4 row sets", "beam_select + 4 x index_select", "beam_step, no row sets"), res):
+        rows.append(dict(what="beam_step_alone", leg=name, R=R, k=k, U=U, sets=nsets, ms=round(ms, 4), min_ms=min(all_ms), max_ms=max(all_ms),
+                         spread_ms=round(max(all_ms) - min(all_ms), 4), copy_bytes=int(moved),
+                         copy_tb_per_s=None if name.endswith("no row sets") else round(moved / (ms * 1e-3) / 1e12, 2),
+                         timing="device events around the call, median of 20, legs alternating", runs_ms=all_ms))
+        print(json.dumps(rows[-1]), flush=True)
+    (mf, rf), (mu, ru), _ = res
+    spread = max(max(rf) - min(rf), max(ru) - min(ru))
+    rows.append(dict(what="beam_step_vs_unfused", fused_ms=round(mf, 4), unfused_ms=round(mu, 4), ratio=round(mu / mf, 2), larger_spread_ms=round(spread, 4),
+                     fused_not_slower_beyond_spread=bool(mf <= mu + spread), rows_identical=same))
+    print(json.dumps(rows[-1]), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=5)
@@ -76,13 +153,16 @@ def main():
     ap.add_argument("--out", default=None, help="JSON file for all rows (default: print only)")
     ap.add_argument("--shapes", default="c4,c2")
     ap.add_argument("--dtypes", default="f32,bf16")
+    ap.add_argument("--what", default="greedy", choices=("greedy", "beam"), help="greedy: prefix / incremental (default); beam: the beam decoder")
     args = ap.parse_args()
     from image_captioning_amd import ops
     torch.cuda.set_device(0)
     rows = []
     shapes = {"c4": dict(name="configs[4] inference", K=1000, T=15, V=50000, units=512),
               "c2": dict(name="configs[2]-style", K=200, T=15, V=10000, units=512)}
-    for key in args.shapes.split(","):
+    if args.what == "beam":
+        beam_legs(args, shapes, rows)
+    for key in args.shapes.split(",") if args.what == "greedy" else ():
         sh = shapes[key]
         for dtype in args.dtypes.split(","):
             model = model_for(sh["V"], sh["T"], sh["K"], sh["units"], dtype)
