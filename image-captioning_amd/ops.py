@@ -1036,26 +1036,37 @@ def vocab_topk(X, W, bias, k, ids=None, probs=None, tile=None):
     return ids, probs
 
 
+def _beam_args(fn, d, cand_ids, cand_probs, scores_in, scores_out, parents, tokens_hist, j, nb, log_score, tokens, mask, more=()):
+    """beam_select's and beam_step's (fn: which, for the messages) common checks -- more: further (name, tensor, dtype, shape) entries like
+    tokens / mask -- and the fields their descriptors share, into d.  Returns (lib, R, k)."""
+    lib = _lib.load()
+    R, k = scores_out.shape
+    _chk(scores_out, name="scores_out")
+    for name, t, dt, shape in (("cand_ids", cand_ids, torch.int32, (k * R, k)), ("cand_probs", cand_probs, torch.float32, (k * R, k)),
+                               ("scores_in", scores_in, torch.float32, (R, k)), ("tokens", tokens, torch.int32, (k * R,)),
+                               ("mask", mask, torch.uint8, (k * R,))) + tuple(more):
+        if t is not None and (not _chk(t, dt, name).is_contiguous() or tuple(t.shape) != shape):
+            raise _lib.DcapError("%s: %s must be a contiguous %s %s tensor" % (fn, name, dt, shape))
+    steps = parents.shape[0]
+    for name, t in (("parents", parents), ("tokens_hist", tokens_hist)):
+        if not _chk(t, torch.int32, name).is_contiguous() or tuple(t.shape) != (steps, R, k):
+            raise _lib.DcapError("%s: %s must be a contiguous int32 [steps,R,k] tensor" % (fn, name))
+    if not scores_out.is_contiguous() or not 1 <= k <= TOPK_MAX or not 1 <= nb <= k or not 0 <= j < steps:
+        raise _lib.DcapError("%s: need contiguous scores_out, 1 <= nb <= k <= %d, 0 <= j < steps" % (fn, TOPK_MAX))
+    d.R, d.k, d.nb, d.steps, d.j, d.log_score = R, k, int(nb), steps, int(j), int(bool(log_score))
+    d.cand_ids, d.cand_probs, d.scores_in, d.scores_out = cand_ids.data_ptr(), cand_probs.data_ptr(), _ptr(scores_in), scores_out.data_ptr()
+    d.parents, d.tokens_hist, d.tokens, d.mask = parents.data_ptr(), tokens_hist.data_ptr(), _ptr(tokens), _ptr(mask)
+    return lib, R, k
+
+
 def beam_select(cand_ids, cand_probs, scores_in, scores_out, parents, tokens_hist, j, nb, log_score=False, tokens=None, mask=None,
                 h_in=None, c_in=None, h_out=None, c_out=None):
     """One beam-search step (dc_beam_select_f32) for R RoIs x k beams, beam-major rows (beam b of RoI r = row b * R + r):
     cand_ids / cand_probs [k*R,k] (vocab_topk's output), scores_in [R,k] (None: zeros, the first step) -> the k best of the first nb
     beams' candidates (score + p, or + log p with log_score), best first: scores_out [R,k], parents / tokens_hist [steps,R,k] at step j,
     tokens int32 [k*R] and mask uint8 [k*R] (token != 0) when given, and h_in / c_in [k*R,U] gathered by parent into h_out / c_out."""
-    lib = _lib.load()
-    R, k = scores_out.shape
-    _chk(scores_out, name="scores_out")
-    for name, t, dt, shape in (("cand_ids", cand_ids, torch.int32, (k * R, k)), ("cand_probs", cand_probs, torch.float32, (k * R, k)),
-                               ("scores_in", scores_in, torch.float32, (R, k)), ("tokens", tokens, torch.int32, (k * R,)),
-                               ("mask", mask, torch.uint8, (k * R,))):
-        if t is not None and (not _chk(t, dt, name).is_contiguous() or tuple(t.shape) != shape):
-            raise _lib.DcapError("beam_select: %s must be a contiguous %s %s tensor" % (name, dt, shape))
-    steps = parents.shape[0]
-    for name, t in (("parents", parents), ("tokens_hist", tokens_hist)):
-        if not _chk(t, torch.int32, name).is_contiguous() or tuple(t.shape) != (steps, R, k):
-            raise _lib.DcapError("beam_select: %s must be a contiguous int32 [steps,R,k] tensor" % name)
-    if not scores_out.is_contiguous() or not 1 <= k <= TOPK_MAX or not 1 <= nb <= k or not 0 <= j < steps:
-        raise _lib.DcapError("beam_select: need contiguous scores_out, 1 <= nb <= k <= %d, 0 <= j < steps" % TOPK_MAX)
+    d = BeamSelectDesc()
+    lib, R, k = _beam_args("beam_select", d, cand_ids, cand_probs, scores_in, scores_out, parents, tokens_hist, j, nb, log_score, tokens, mask)
     rows = (h_in, c_in, h_out, c_out)
     U = 0
     if any(t is not None for t in rows):
@@ -1067,10 +1078,6 @@ def beam_select(cand_ids, cand_probs, scores_in, scores_out, parents, tokens_his
                 raise _lib.DcapError("beam_select: %s must be a contiguous float32 [k*R,U] tensor" % name)
     if R == 0:
         return scores_out
-    d = BeamSelectDesc()
-    d.R, d.k, d.nb, d.steps, d.j, d.log_score = R, k, int(nb), steps, int(j), int(bool(log_score))
-    d.cand_ids, d.cand_probs, d.scores_in, d.scores_out = cand_ids.data_ptr(), cand_probs.data_ptr(), _ptr(scores_in), scores_out.data_ptr()
-    d.parents, d.tokens_hist, d.tokens, d.mask = parents.data_ptr(), tokens_hist.data_ptr(), _ptr(tokens), _ptr(mask)
     d.U, d.h_in, d.c_in, d.h_out, d.c_out = U, _ptr(h_in), _ptr(c_in), _ptr(h_out), _ptr(c_out)
     check(lib.dc_beam_select_f32(C.byref(d), _stream()), "dc_beam_select_f32")
     return scores_out
@@ -1109,28 +1116,13 @@ def beam_step(cand_ids, cand_probs, scores_in, scores_out, parents, tokens_hist,
         for o, (s1, d1) in enumerate(spans):
             if any(a[0] < b[1] and b[0] < a[1] for a, b in ((d0, s1),) + (((d0, d1),) if o != i else ())):
                 raise _lib.DcapError("beam_step: dst of row set %d must not alias a src or another dst (set %d)" % (i, o))
-    lib = _lib.load()
-    _chk(scores_out, name="scores_out")
-    for name, t, dt, shape in (("cand_ids", cand_ids, torch.int32, (k * R, k)), ("cand_probs", cand_probs, torch.float32, (k * R, k)),
-                               ("scores_in", scores_in, torch.float32, (R, k)), ("tokens", tokens, torch.int32, (k * R,)),
-                               ("mask", mask, torch.uint8, (k * R,)), ("finished_in", finished_in, torch.uint8, (k * R,)),
-                               ("finished_out", finished_out, torch.uint8, (k * R,))):
-        if t is not None and (not _chk(t, dt, name).is_contiguous() or tuple(t.shape) != shape):
-            raise _lib.DcapError("beam_step: %s must be a contiguous %s %s tensor" % (name, dt, shape))
-    steps = parents.shape[0]
-    for name, t in (("parents", parents), ("tokens_hist", tokens_hist)):
-        if not _chk(t, torch.int32, name).is_contiguous() or tuple(t.shape) != (steps, R, k):
-            raise _lib.DcapError("beam_step: %s must be a contiguous int32 [steps,R,k] tensor" % name)
-    if not scores_out.is_contiguous() or not 1 <= k <= TOPK_MAX or not 1 <= nb <= k or not 0 <= j < steps:
-        raise _lib.DcapError("beam_step: need contiguous scores_out, 1 <= nb <= k <= %d, 0 <= j < steps" % TOPK_MAX)
+    d = BeamStepDesc()
+    lib, R, k = _beam_args("beam_step", d, cand_ids, cand_probs, scores_in, scores_out, parents, tokens_hist, j, nb, log_score, tokens, mask,
+                           more=(("finished_in", finished_in, torch.uint8, (k * R,)), ("finished_out", finished_out, torch.uint8, (k * R,))))
     for i, (src, dst) in enumerate(rows):
         _chk(src, name="rows[%d] src" % i), _chk(dst, name="rows[%d] dst" % i)
     if R == 0:
         return scores_out
-    d = BeamStepDesc()
-    d.R, d.k, d.nb, d.steps, d.j, d.log_score = R, k, int(nb), steps, int(j), int(bool(log_score))
-    d.cand_ids, d.cand_probs, d.scores_in, d.scores_out = cand_ids.data_ptr(), cand_probs.data_ptr(), _ptr(scores_in), scores_out.data_ptr()
-    d.parents, d.tokens_hist, d.tokens, d.mask = parents.data_ptr(), tokens_hist.data_ptr(), _ptr(tokens), _ptr(mask)
     d.end_id, d.finished_in, d.finished_out = -1 if end_id is None else int(end_id), _ptr(finished_in), _ptr(finished_out)
     d.n_sets = len(rows)
     for i, (src, dst) in enumerate(rows):

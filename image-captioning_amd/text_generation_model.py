@@ -12,13 +12,14 @@ one-hot f64[B,T,V]) and return what the T-prefix graph returns (parity: tests/te
 the as-written oracle), at 1/T of the LSTM work.  recurrent_dropout=0.2 of the reference is applied in the training
 phase (device-side masks; `recurrent_dropout`, `dropout_rows` below); parity runs set it to 0 or replay the masks in the oracle.
 """
+import functools
 import json
 import os
 
 import numpy as np
 import torch
 
-from . import ops, step_graph, synth
+from . import decoding, ops, step_graph, synth
 from .config import Config
 from .keras_like import KerasLikeModel, ModelCheckpoint, CSVLogger  # noqa: F401
 from .params import ParamStore, Adam  # noqa: F401
@@ -314,15 +315,7 @@ class CaptionModelV1(KerasLikeModel):
         w, u = self.store.w, self.units
         Bl = B if Bl is None else Bl
         zf = self._mm(f, self._wview('imgcap_lstm1/kernel', (self.E, self.E + self.FEAT)), key='zf').f        # per-RoI half of x.W
-        emb_b = self._emb_bf16()
-        if emb_b is not None:
-            # bf16 model: the embedding half of x.W on the bf16 pipe like the other half.  The table's bf16 copy is zero-padded to a multiple of
-            # 8 columns (E = 300 -> 304): the kernel rows 300 .. 303 it then also reads (the feature half's first rows) meet zeros
-            z1 = ops.gemm_bf16(emb_b, self.store.wb['imgcap_lstm1/kernel'][:emb_b.shape[1]], gather=ids_tm, shift=w['imgcap_lstm1/bias'],
-                               residual=zf, res_rows=B, out=self._buf('z1', (T * Bl, 4 * u)))
-        else:
-            z1 = ops.gemm(w['imgcap_embedding_layer/embeddings'], w['imgcap_lstm1/kernel'][:self.E], gather=ids_tm, shift=w['imgcap_lstm1/bias'],
-                          residual=zf, res_rows=B, out=self._buf('z1', (T * Bl, 4 * u)))
+        z1 = self._embed_z1(ids_tm, zf, B, self._buf('z1', (T * Bl, 4 * u)))
         h1, c1 = ops.lstm_seq_fwd(z1, w['imgcap_lstm1/recurrent_kernel'], mask, Bl, T, self._buf('h1', (T * Bl, u)),
                                   self._buf('c1', (T * Bl, u)), rec_masks=self._rec_masks[0])
         self._h1 = self._act('h1', h1)
@@ -334,6 +327,19 @@ class CaptionModelV1(KerasLikeModel):
         zdf = self._mm(f, self._wview('imgcap_lstm_d1/kernel', (u, u + self.FEAT)), key='zdf').f
         return self._mm(self._h2_out, self._wview('imgcap_lstm_d1/kernel', (0, u)), key='a1', shift=w['imgcap_lstm_d1/bias'], residual=zdf,
                         res_rows=B, relu=True, want_b=True)
+
+    def _embed_z1(self, ids, zf, B, out):
+        """The first LSTM's input x.W + bias for the rows' token ids: the embedding half as a gather GEMM, the per-RoI half zf [B, 4u] as
+        its residual (row i takes zf's row i % B), into out."""
+        w = self.store.w
+        emb_b = self._emb_bf16()
+        if emb_b is not None:
+            # bf16 model: the embedding half of x.W on the bf16 pipe like the other half.  The table's bf16 copy is zero-padded to a multiple of
+            # 8 columns (E = 300 -> 304): the kernel rows 300 .. 303 it then also reads (the feature half's first rows) meet zeros
+            return ops.gemm_bf16(emb_b, self.store.wb['imgcap_lstm1/kernel'][:emb_b.shape[1]], gather=ids, shift=w['imgcap_lstm1/bias'],
+                                 residual=zf, res_rows=B, out=out)
+        return ops.gemm(w['imgcap_embedding_layer/embeddings'], w['imgcap_lstm1/kernel'][:self.E], gather=ids, shift=w['imgcap_lstm1/bias'],
+                        residual=zf, res_rows=B, out=out)
 
     def _emb_bf16(self):
         """bf16 copy of the (frozen) embedding table, zero-padded to a multiple of 8 columns -- the bf16 GEMMs' operand granularity -- or None
@@ -593,9 +599,8 @@ class CaptionModelV1(KerasLikeModel):
     def test_on_batch(self, inputs, targets):
         return float(self.test_on_batch_device(inputs, targets).item())
 
-    DECODERS = ("prefix", "incremental", "beam")
+    DECODERS = decoding.DECODERS
     VOCAB_MATH = (None, "f32", "bf16")
-    SCORES = ("prob", "logprob")
 
     @classmethod
     def check_decoder(cls, decoder, return_probabilities, vocab_math=None, compute_dtype=None, beam_size=None, score="logprob", end_id=None):
@@ -606,20 +611,10 @@ class CaptionModelV1(KerasLikeModel):
         vocab_math: None / 'f32' (the vocabulary layer scores words from the fp32 activations and the fp32 master weight) or 'bf16' (from
         their bf16 copies on the bf16 matrix pipe, the arithmetic a bf16 model trains that layer in): 'bf16' needs decoder='incremental'
         or 'beam' and a model that computes in bf16 (compute_dtype: the model's; only a bf16 model keeps the weight's bf16 mirror)."""
-        if decoder not in cls.DECODERS:
-            raise ValueError("decoder must be one of %s, got %r" % (cls.DECODERS, decoder))
-        if decoder == "beam":
-            if beam_size is None or isinstance(beam_size, bool) or int(beam_size) != beam_size or not 1 <= beam_size <= ops.TOPK_MAX:
-                raise ValueError("decoder='beam' needs beam_size in 1..%d, got %r" % (ops.TOPK_MAX, beam_size))
-        elif beam_size is not None or end_id is not None:
-            raise ValueError("beam_size and end_id are only for decoder='beam' (got decoder=%r)" % (decoder,))
-        if decoder != "prefix" and return_probabilities is not False:
-            raise ValueError("decoder=%r returns no word probabilities: pass return_probabilities=False" % (decoder,))
-        if decoder == "beam":
-            if score not in cls.SCORES:
-                raise ValueError("score must be one of %s, got %r" % (cls.SCORES, score))
-            if end_id is not None and (isinstance(end_id, bool) or int(end_id) != end_id or end_id < 1):
-                raise ValueError("end_id must be None or the end word's id, an integer in [1, V), got %r" % (end_id,))
+        decoding.check_decoder(decoder, beam_size, score, dict(end_id=end_id), score_for_beam_only=True, own=None if decoder == "prefix" or
+                               return_probabilities is False else "decoder=%r returns no word probabilities: pass return_probabilities=False" % (decoder,))
+        if decoder == "beam" and end_id is not None and (isinstance(end_id, bool) or int(end_id) != end_id or end_id < 1):
+            raise ValueError("end_id must be None or the end word's id, an integer in [1, V), got %r" % (end_id,))
         if vocab_math not in cls.VOCAB_MATH:
             raise ValueError("vocab_math must be one of %s, got %r" % (cls.VOCAB_MATH, vocab_math))
         if vocab_math == "bf16":
@@ -641,8 +636,7 @@ class CaptionModelV1(KerasLikeModel):
         Returns device tensors (ids int32 [B,T], word_scores float32 [B,T] = the softmax probability of each chosen word), two views
         of one [2,B,T] buffer (one copy brings both to the host).  No host synchronisation."""
         self.check_decoder("incremental", False, vocab_math, self.compute_dtype if vocab_math == "bf16" else None)
-        out = self._decode_greedy(feat, vocab_math)
-        return out[0], out[1].view(torch.float32)
+        return decoding.greedy_views(self._decode_greedy(feat, vocab_math))
 
     def _vocab_mirror(self):
         """The vocabulary weight's bf16 mirror as ops.vocab_top1 reads it; a mirror whose rows are not whole, aligned 16-byte chunks (V not a
@@ -657,46 +651,44 @@ class CaptionModelV1(KerasLikeModel):
         pad[:, :self.V].copy_(Wb)
         return pad[:, :self.V]
 
-    def _decode_greedy(self, feat, vocab_math=None):
-        """decode_greedy into one int32 [2,B,T] device buffer: [0] the ids, [1] the word scores' float32 bits."""
-        feat = self._dev_feat(feat)
-        B, T, u, w = feat.shape[0], self.T, self.units, self.store.w
-        out = torch.empty((2, B, T), dtype=torch.int32, device=self.device)
-        ids, scores = out[0], out[1].view(torch.float32)
-        if B == 0:
-            return out
+    def _decode_setup(self, feat, n, prefix, vocab_math):
+        """Once per decode call, for n rows (row i belongs to RoI i % B) whose scratch buffers carry `prefix`: the RoI head, the per-RoI
+        halves of the first LSTM's and the Dense-1024's inputs, the two packed recurrent kernels, the vocabulary operand, the start token
+        and the two state sets (h1, c1, h2, c2) -> the decoding.Decode of this call."""
+        B, u, w = feat.shape[0], self.units, self.store.w
         vb = vocab_math == "bf16"
         self._draw_rec_masks(B, training=False)
         f = self._head_forward(feat.reshape(B, -1))
-        zf = self._mm(f, self._wview('imgcap_lstm1/kernel', (self.E, self.E + self.FEAT)), key='dec_zf').f
-        zdf = self._mm(f, self._wview('imgcap_lstm_d1/kernel', (u, u + self.FEAT)), key='dec_zdf').f
-        U1, U2 = w['imgcap_lstm1/recurrent_kernel'], w['imgcap_lstm2/recurrent_kernel']
-        pk = [ops.lstm_pack_urec(Ur, out=self._buf('dec_upk%d' % l, (u, 4 * u))) if u % 32 == 0 else None for l, Ur in enumerate((U1, U2))]
-        emb_b = self._emb_bf16()
+        ctx = dict(prefix=prefix, B=B, vb=vb, U=(w['imgcap_lstm1/recurrent_kernel'], w['imgcap_lstm2/recurrent_kernel']),
+                   zf=self._mm(f, self._wview('imgcap_lstm1/kernel', (self.E, self.E + self.FEAT)), key='dec_zf').f,        # per RoI: res_rows=B
+                   zdf=self._mm(f, self._wview('imgcap_lstm_d1/kernel', (u, u + self.FEAT)), key='dec_zdf').f)
+        ctx['Upk'] = [ops.lstm_pack_urec(Ur, out=self._buf('dec_upk%d' % l, (u, 4 * u))) if u % 32 == 0 else None for l, Ur in enumerate(ctx['U'])]
         Wv = self._vocab_mirror() if vb else self._wview('imgcap_lstm_d2/kernel')[0]
-        tok = self._buf('dec_tok', (B,), torch.int32).fill_(1)          # start token (:203)
-        live = self._buf('dec_live', (B,), torch.uint8)
-        st = [[self._buf('dec_%s%d_%d' % (k, l, q), (B, u)) for q in range(2) for k in 'hc'] for l in range(2)]    # ping-pong (h, c, h', c')
-        for j in range(T):
-            if emb_b is not None:
-                z1 = ops.gemm_bf16(emb_b, self.store.wb['imgcap_lstm1/kernel'][:emb_b.shape[1]], gather=tok, shift=w['imgcap_lstm1/bias'],
-                                   residual=zf, res_rows=B, out=self._buf('dec_z1', (B, 4 * u)))
-            else:
-                z1 = ops.gemm(w['imgcap_embedding_layer/embeddings'], w['imgcap_lstm1/kernel'][:self.E], gather=tok, shift=w['imgcap_lstm1/bias'],
-                              residual=zf, res_rows=B, out=self._buf('dec_z1', (B, 4 * u)))
-            mask = live if j else None                                   # token 1 is never masked; then id != 0 of the step before
-            cur, prev = (0, 2) if j % 2 == 0 else (2, 0)
-            first = j == 0
-            h1, c1 = ops.lstm_step(z1, U1, None if first else st[0][prev], None if first else st[0][prev + 1], mask,
-                                   st[0][cur], st[0][cur + 1], U_packed=pk[0])
-            z2 = self._mm(self._act('dec_h1', h1), self._wview('imgcap_lstm2/kernel'), key='dec_z2', shift=w['imgcap_lstm2/bias']).f
-            h2, c2 = ops.lstm_step(z2, U2, None if first else st[1][prev], None if first else st[1][prev + 1], mask,
-                                   st[1][cur], st[1][cur + 1], U_packed=pk[1])
-            a1 = self._mm(self._act('dec_h2', h2), self._wview('imgcap_lstm_d1/kernel', (0, u)), key='dec_a1', shift=w['imgcap_lstm_d1/bias'],
-                          residual=zdf, res_rows=B, relu=True, want_b=vb)
-            # (a1.b: the bf16 copy the Dense-1024 GEMM's epilogue wrote; were that GEMM off the bf16 pipe, one cast of a1.f)
-            ops.vocab_top1(a1.b if vb else a1.f, Wv, w['imgcap_lstm_d2/bias'], tokens=tok, ids=ids[:, j], probs=scores[:, j], mask=live)
-        return out
+        tok = self._buf(prefix + 'tok', (n,), torch.int32).fill_(1)          # start token (:203) on every row; never masked (mask0 = None)
+        live = self._buf(prefix + 'live', (n,), torch.uint8)
+        states = [[self._buf('%s%s%d_%d' % (prefix, x, l, q), (n, u)) for l in range(2) for x in 'hc'] for q in range(2)]
+        return decoding.Decode(self._buf, prefix, tok, live, None, states, functools.partial(self._decode_step, ctx), (Wv, w['imgcap_lstm_d2/bias']))
+
+    def _decode_step(self, ctx, tok, mask, prev, cur):
+        """One token per row: the embedding-gather GEMM, one carried-state step of each LSTM (prev -> cur; prev None: zero states) and the
+        Dense-1024; returns the vocabulary layer's input."""
+        p, n, u, w = ctx['prefix'], tok.shape[0], self.units, self.store.w
+        (U1, U2), (pk1, pk2) = ctx['U'], ctx['Upk']
+        h1p, c1p, h2p, c2p = prev or (None,) * 4
+        z1 = self._embed_z1(tok, ctx['zf'], ctx['B'], self._buf(p + 'z1', (n, 4 * u)))
+        h1, _ = ops.lstm_step(z1, U1, h1p, c1p, mask, cur[0], cur[1], U_packed=pk1)
+        z2 = self._mm(self._act(p + 'h1', h1), self._wview('imgcap_lstm2/kernel'), key=p + 'z2', shift=w['imgcap_lstm2/bias']).f
+        h2, _ = ops.lstm_step(z2, U2, h2p, c2p, mask, cur[2], cur[3], U_packed=pk2)
+        a1 = self._mm(self._act(p + 'h2', h2), self._wview('imgcap_lstm_d1/kernel', (0, u)), key=p + 'a1', shift=w['imgcap_lstm_d1/bias'],
+                      residual=ctx['zdf'], res_rows=ctx['B'], relu=True, want_b=ctx['vb'])
+        # (a1.b: the bf16 copy the Dense-1024 GEMM's epilogue wrote; were that GEMM off the bf16 pipe, one cast of a1.f)
+        return a1.b if ctx['vb'] else a1.f
+
+    def _decode_greedy(self, feat, vocab_math=None):
+        """decode_greedy into one int32 [2,B,T] device buffer: [0] the ids, [1] the word scores' float32 bits."""
+        feat = self._dev_feat(feat)
+        B = feat.shape[0]
+        return decoding.greedy(B, self.T, self.device, lambda: self._decode_setup(feat, B, 'dec_', vocab_math))
 
     def decode_beam(self, feat, beam_size, score="logprob", end_id=None, vocab_math=None):
         """Beam search over ROICaptionInferenceLayer's decoder for every RoI at once, on the device.  Every beam starts from token 1; each
@@ -710,7 +702,7 @@ class CaptionModelV1(KerasLikeModel):
         vocab_math='bf16' (bf16 models): the vocabulary layer on the bf16 matrix pipe, as decode_greedy.
         Returns device tensors (tokens int32 [B,k,T], scores float32 [B,k]), best first, views of one buffer.  No host synchronisation."""
         B, k, T, out = self._decode_beam(feat, beam_size, score, end_id, vocab_math)
-        return out[:B * k * T].view(B, k, T), out[B * k * T:].view(torch.float32).view(B, k)
+        return decoding.beam_views(out, B, k, T)
 
     def _decode_beam(self, feat, beam_size, score, end_id, vocab_math):
         """decode_beam into one flat int32 device buffer: the [B,k,T] tokens, then the [B,k] scores' float32 bits."""
@@ -722,49 +714,8 @@ class CaptionModelV1(KerasLikeModel):
         if end_id is not None and end_id >= self.V:
             raise ValueError("end_id %d is outside the vocabulary (%d words)" % (end_id, self.V))
         feat = self._dev_feat(feat)
-        B, T, u, w = feat.shape[0], self.T, self.units, self.store.w
-        out = torch.empty((B * k * (T + 1),), dtype=torch.int32, device=self.device)
-        if B == 0:
-            return B, k, T, out
-        n = k * B
-        tokens, final = out[:n * T].view(B, k, T), out[n * T:].view(torch.float32).view(B, k)
-        vb = vocab_math == "bf16"
-        self._draw_rec_masks(B, training=False)
-        f = self._head_forward(feat.reshape(B, -1))
-        zf = self._mm(f, self._wview('imgcap_lstm1/kernel', (self.E, self.E + self.FEAT)), key='dec_zf').f        # per RoI: res_rows=B below
-        zdf = self._mm(f, self._wview('imgcap_lstm_d1/kernel', (u, u + self.FEAT)), key='dec_zdf').f
-        U1, U2 = w['imgcap_lstm1/recurrent_kernel'], w['imgcap_lstm2/recurrent_kernel']
-        pk = [ops.lstm_pack_urec(Ur, out=self._buf('dec_upk%d' % l, (u, 4 * u))) if u % 32 == 0 else None for l, Ur in enumerate((U1, U2))]
-        emb_b = self._emb_bf16()
-        Wv = self._vocab_mirror() if vb else self._wview('imgcap_lstm_d2/kernel')[0]
-        tok = self._buf('bm_tok', (n,), torch.int32).fill_(1)           # start token (:203) on every beam row
-        live = self._buf('bm_live', (n,), torch.uint8)
-        # two state sets (h1, c1, h2, c2): the LSTM steps write S, beam_step gathers the parents' rows of S into G, the next steps read G
-        S, G = ([self._buf('bm_%s%d_%d' % (x, l, q), (n, u)) for l in range(2) for x in 'hc'] for q in range(2))
-        parents, hist = self._buf('bm_par', (T, B, k), torch.int32), self._buf('bm_hist', (T, B, k), torch.int32)
-        sc = [self._buf('bm_sc%d' % q, (B, k)) for q in range(2)]
-        fin = [self._buf('bm_fin%d' % q, (n,), torch.uint8) for q in range(2)] if end_id is not None else None
-        cids, cprobs = self._buf('bm_cid', (n, k), torch.int32), self._buf('bm_cp', (n, k))
-        for j in range(T):
-            if emb_b is not None:
-                z1 = ops.gemm_bf16(emb_b, self.store.wb['imgcap_lstm1/kernel'][:emb_b.shape[1]], gather=tok, shift=w['imgcap_lstm1/bias'],
-                                   residual=zf, res_rows=B, out=self._buf('bm_z1', (n, 4 * u)))
-            else:
-                z1 = ops.gemm(w['imgcap_embedding_layer/embeddings'], w['imgcap_lstm1/kernel'][:self.E], gather=tok, shift=w['imgcap_lstm1/bias'],
-                              residual=zf, res_rows=B, out=self._buf('bm_z1', (n, 4 * u)))
-            first, last = j == 0, j + 1 == T
-            mask = None if first else live                               # token 1 is never masked; then id != 0 of the step before
-            h1, c1 = ops.lstm_step(z1, U1, None if first else G[0], None if first else G[1], mask, S[0], S[1], U_packed=pk[0])
-            z2 = self._mm(self._act('bm_h1', h1), self._wview('imgcap_lstm2/kernel'), key='bm_z2', shift=w['imgcap_lstm2/bias']).f
-            h2, c2 = ops.lstm_step(z2, U2, None if first else G[2], None if first else G[3], mask, S[2], S[3], U_packed=pk[1])
-            a1 = self._mm(self._act('bm_h2', h2), self._wview('imgcap_lstm_d1/kernel', (0, u)), key='bm_a1', shift=w['imgcap_lstm_d1/bias'],
-                          residual=zdf, res_rows=B, relu=True, want_b=vb)
-            ops.vocab_topk(a1.b if vb else a1.f, Wv, w['imgcap_lstm_d2/bias'], k, ids=cids, probs=cprobs)
-            end = {} if fin is None else dict(end_id=int(end_id), finished_in=None if first else fin[j % 2], finished_out=fin[(j + 1) % 2])
-            ops.beam_step(cids, cprobs, None if first else sc[j % 2], final if last else sc[(j + 1) % 2], parents, hist, j, 1 if first else k,
-                          score == "logprob", tokens=tok, mask=live, rows=() if last else tuple(zip(S, G)), **end)
-        ops.beam_backtrace(parents, hist, out=tokens)
-        return B, k, T, out
+        B, T = feat.shape[0], self.T
+        return B, k, T, decoding.beam(B, k, T, self.device, lambda: self._decode_setup(feat, k * B, 'bm_', vocab_math), score == "logprob", end_id)
 
     def generate(self, feat, return_probabilities=None, decoder="prefix", vocab_math=None, beam_size=None, score="logprob", end_id=None):
         """ROICaptionInferenceLayer (:192-232): start token 1; step j feeds [prev..., 0...] through the word
@@ -779,11 +730,9 @@ class CaptionModelV1(KerasLikeModel):
                            beam_size=beam_size, score=score, end_id=end_id)
         if decoder == "beam":
             B, k, T, out = self._decode_beam(feat, beam_size, score, end_id, vocab_math)
-            host = out.cpu().numpy()
-            return None, host[:B * k * T].reshape(B, k, T), host[B * k * T:].view(np.float32).reshape(B, k)
+            return (None,) + decoding.beam_views(out.cpu().numpy(), B, k, T)
         if decoder == "incremental":
-            host = self._decode_greedy(feat, vocab_math).cpu().numpy()
-            return None, host[0], host[1].view(np.float32)
+            return (None,) + decoding.greedy_views(self._decode_greedy(feat, vocab_math).cpu().numpy())
         feat = self._dev_feat(feat)
         B, T = feat.shape[0], self.T
         self._draw_rec_masks(B, training=False)

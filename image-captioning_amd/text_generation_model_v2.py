@@ -15,7 +15,7 @@ import os
 import numpy as np
 import torch
 
-from . import ops, step_graph, synth, utils
+from . import decoding, ops, step_graph, synth, utils
 from .config import Config
 from .keras_like import KerasLikeModel, ModelCheckpoint, CSVLogger  # noqa: F401  (re-exported for scripts)
 from .layers import V2_WORD_LSTM
@@ -573,24 +573,12 @@ class CaptionModelV2(KerasLikeModel):
         return np.array(ids[1:], np.int32), np.array(rows)
 
     # ---------------------------------------------------------------------------------- on-device decoding
-    DECODERS = ("prefix", "incremental", "beam")
-    SCORES = ("prob", "logprob")
-
     @classmethod
     def check_decoder(cls, decoder, beam_size=None, start_ids=None, score="prob"):
         """generate()'s argument rules (no GPU needed): a known decoder, beam_size in 1..8 with decoder='beam' only, no start_ids for
         'prefix' (greedy_decode always starts from 0) and a known score rule."""
-        if decoder not in cls.DECODERS:
-            raise ValueError("decoder must be one of %s, got %r" % (cls.DECODERS, decoder))
-        if decoder == "beam":
-            if beam_size is None or isinstance(beam_size, bool) or int(beam_size) != beam_size or not 1 <= beam_size <= ops.TOPK_MAX:
-                raise ValueError("decoder='beam' needs beam_size in 1..%d, got %r" % (ops.TOPK_MAX, beam_size))
-        elif beam_size is not None:
-            raise ValueError("beam_size is only for decoder='beam' (got decoder=%r)" % (decoder,))
-        if decoder == "prefix" and start_ids is not None:
-            raise ValueError("decoder='prefix' (greedy_decode) always starts from id 0: start_ids needs 'incremental' or 'beam'")
-        if score not in cls.SCORES:
-            raise ValueError("score must be one of %s, got %r" % (cls.SCORES, score))
+        decoding.check_decoder(decoder, beam_size, score, own=None if decoder != "prefix" or start_ids is None else
+                               "decoder='prefix' (greedy_decode) always starts from id 0: start_ids needs 'incremental' or 'beam'")
 
     def _decode_steps(self, steps):
         """steps <= Tw: a carried state is the prefix path's state only while pad_sequences has truncated nothing."""
@@ -659,9 +647,19 @@ class CaptionModelV2(KerasLikeModel):
         ops.gather_rows(h_word, ctx['rows'], ctx['cat'][:, self.FEAT:])
         return ctx['cat']
 
-    def _decode_state(self, n):
-        U = self.WORD_UNITS
-        return [self._buf('dec_%s%d' % (x, q), (n, U)) for q in range(2) for x in 'hc']           # (h, c, h', c')
+    def _decode_call(self, feat, k, start_ids):
+        """The decoding.Decode of one call over the n = k*R beam-major rows: the start ids (masked where 0, from the first step on), the
+        setup, and the word LSTM's two (h, c) state sets; a step is _decode_word then _decode_top."""
+        R, U, w = feat.shape[0], self.WORD_UNITS, self.store.w
+        tok, live = self._start_tokens(start_ids, R, k)
+        ctx = self._decode_setup(feat, k * R)
+        states = [[self._buf('dec_%s%d' % (x, q), (k * R, U)) for x in 'hc'] for q in range(2)]
+
+        def step(tok, mask, prev, cur):
+            h, _ = self._decode_word(ctx, tok, *(prev or (None, None)), mask, *cur)
+            return self._decode_top(ctx, h)
+
+        return decoding.Decode(self._buf, 'dec_', tok, live, live, states, step, (w['imgcap_d1/kernel'], w['imgcap_d1/bias']))
 
     def decode_greedy(self, feat, steps=None, start_ids=None):
         """Greedy decoding of the reference's test / eval loops (_v2.py:328-346; eval_text_generation_model_v2.py:164-189) for every
@@ -671,40 +669,23 @@ class CaptionModelV2(KerasLikeModel):
         The first id fed is start_ids (int [R]; default 0, as the test loop).  steps <= Tw (default Tw - 1).
         Returns device tensors: ids int32 [R,steps] and word_scores float32 [R,steps] (each chosen word's softmax probability), two
         views of one [2,R,steps] buffer.  No host synchronisation."""
-        out = self._decode_greedy(feat, steps, start_ids)
-        return out[0], out[1].view(torch.float32)
+        return decoding.greedy_views(self._decode_greedy(feat, steps, start_ids))
 
     def _decode_greedy(self, feat, steps, start_ids):
         steps = self._decode_steps(steps)
         feat = self._dev_feat(feat)
-        R = feat.shape[0]
-        out = torch.empty((2, R, steps), dtype=torch.int32, device=self.device)
-        if R == 0:
-            return out
-        ids, scores = out[0], out[1].view(torch.float32)
-        tok, live = self._start_tokens(start_ids, R, 1)
-        ctx = self._decode_setup(feat, R)
-        st = self._decode_state(R)
-        w = self.store.w
-        h, c = self._decode_word(ctx, tok, None, None, live, st[0], st[1])
-        for j in range(steps):
-            ops.vocab_top1(self._decode_top(ctx, h), w['imgcap_d1/kernel'], w['imgcap_d1/bias'], tokens=tok, ids=ids[:, j],
-                           probs=scores[:, j], mask=live)
-            if j + 1 < steps:
-                q = 2 * ((j + 1) % 2)
-                h, c = self._decode_word(ctx, tok, h, c, live, st[q], st[q + 1])
-        return out
+        return decoding.greedy(feat.shape[0], steps, self.device, lambda: self._decode_call(feat, 1, start_ids))
 
     def decode_beam(self, feat, beam_size, steps=None, start_ids=None, score="prob"):
         """Beam search of the authors' captioner (image captioning/test.py:23-64) over the v2 decoders, for every RoI at once on the
         device.  From one beam (start_ids, default 0), each step every beam proposes its k = beam_size most probable next words
         (ops.vocab_topk over the k*R beam rows); a candidate scores the beam's score + p (score='prob', the reference's rule) or + log p
-        ('logprob'); the k best of the k*k survive (ops.beam_select: score descending, then parent beam, then word id ascending), the
+        ('logprob'); the k best of the k*k survive (ops.beam_step: score descending, then parent beam, then word id ascending), the
         word LSTM's state follows its parent and then takes the chosen word (0 is masked: the state carries over it).  Fixed length
         steps <= Tw (default Tw - 1), no end token.  Returns device tensors: tokens int32 [R,k,steps] and scores float32 [R,k], best
         first.  No host synchronisation."""
         R, k, steps, out = self._decode_beam(feat, beam_size, steps, start_ids, score)
-        return out[:R * k * steps].view(R, k, steps), out[R * k * steps:].view(torch.float32).view(R, k)
+        return decoding.beam_views(out, R, k, steps)
 
     def _decode_beam(self, feat, beam_size, steps, start_ids, score):
         """decode_beam into one flat int32 device buffer: the [R,k,steps] tokens, then the [R,k] scores' float32 bits."""
@@ -715,29 +696,7 @@ class CaptionModelV2(KerasLikeModel):
         steps = self._decode_steps(steps)
         feat = self._dev_feat(feat)
         R = feat.shape[0]
-        out = torch.empty((R * k * (steps + 1),), dtype=torch.int32, device=self.device)
-        if R == 0:
-            return R, k, steps, out
-        n = k * R
-        tokens, final = out[:n * steps].view(R, k, steps), out[n * steps:].view(torch.float32).view(R, k)
-        tok, live = self._start_tokens(start_ids, R, k)
-        ctx = self._decode_setup(feat, n)
-        st = self._decode_state(n)
-        w = self.store.w
-        parents, hist = self._buf('dec_par', (steps, R, k), torch.int32), self._buf('dec_hist', (steps, R, k), torch.int32)
-        sc = [self._buf('dec_sc%d' % q, (R, k)) for q in range(2)]
-        cids, cprobs = self._buf('dec_cid', (n, k), torch.int32), self._buf('dec_cp', (n, k))
-        self._decode_word(ctx, tok, None, None, live, st[0], st[1])
-        for j in range(steps):
-            ops.vocab_topk(self._decode_top(ctx, st[0]), w['imgcap_d1/kernel'], w['imgcap_d1/bias'], k, ids=cids, probs=cprobs)
-            last = j + 1 == steps
-            gather = {} if last else dict(h_in=st[0], c_in=st[1], h_out=st[2], c_out=st[3])
-            ops.beam_select(cids, cprobs, None if j == 0 else sc[j % 2], final if last else sc[(j + 1) % 2], parents, hist, j,
-                            1 if j == 0 else k, score == "logprob", tokens=tok, mask=live, **gather)
-            if not last:                  # the parents' states (gathered into st[2:]) take the chosen words, back into st[:2]
-                self._decode_word(ctx, tok, st[2], st[3], live, st[0], st[1])
-        ops.beam_backtrace(parents, hist, out=tokens)
-        return R, k, steps, out
+        return R, k, steps, decoding.beam(R, k, steps, self.device, lambda: self._decode_call(feat, k, start_ids), score == "logprob")
 
     def generate(self, feat, steps=None, decoder="prefix", beam_size=None, start_ids=None, score="prob"):
         """Caption every RoI of feat [R,7,7,256].  decoder='prefix': greedy_decode per RoI (the reference's loop: the whole model on
@@ -746,12 +705,10 @@ class CaptionModelV2(KerasLikeModel):
         one device-to-host copy."""
         self.check_decoder(decoder, beam_size, start_ids, score)
         if decoder == "incremental":
-            host = self._decode_greedy(feat, steps, start_ids).cpu().numpy()
-            return host[0], host[1].view(np.float32)
+            return decoding.greedy_views(self._decode_greedy(feat, steps, start_ids).cpu().numpy())
         if decoder == "beam":
             R, k, steps, out = self._decode_beam(feat, beam_size, steps, start_ids, score)
-            host = out.cpu().numpy()
-            return host[:R * k * steps].reshape(R, k, steps), host[R * k * steps:].view(np.float32).reshape(R, k)
+            return decoding.beam_views(out.cpu().numpy(), R, k, steps)
         Tw = self.word_shape[0]
         n_steps = Tw - 1 if steps is None else int(steps)
         R = len(feat)

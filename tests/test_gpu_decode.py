@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+from _decode_cases import _dev, _exact_operands, joint_model, record_host_syncs, v1_model
 from oracle import np_models as M
 from oracle import np_oracle as O
 
@@ -20,10 +21,6 @@ def gpu():
     return torch.device("cuda:0")
 
 
-def _dev(a, dt=torch.float32):
-    return torch.tensor(np.ascontiguousarray(a), dtype=dt, device="cuda:0")
-
-
 def _ref_top1(X, W, b):
     z = X.astype(np.float64) @ W.astype(np.float64) + b.astype(np.float64)
     ids = z.argmax(1)
@@ -31,16 +28,6 @@ def _ref_top1(X, W, b):
     p = 1.0 / np.exp(z - m).sum(1)
     top2 = np.sort(z, axis=1)[:, -2:] if z.shape[1] > 1 else np.concatenate([z - 1.0, z], axis=1)
     return ids, p, top2[:, 1] - top2[:, 0]
-
-
-def _exact_operands(rng, Mr, K, V):
-    """X, W, bias on coarse binary grids (X in 1/8, W in 1/256, bias in 1/2048 steps): every product and every partial sum of X W + bias
-    is exact in fp32 at these sizes, so the logits are exact whatever the summation order and a comparison with float64 measures the
-    kernel's own reduction (max / argmax / sum of exp), not GEMM rounding (~1e-6 relative at K = 256 on N(0,1) data)."""
-    X = (rng.integers(-8, 9, (Mr, K)) / 8.0).astype(np.float32)
-    W = (rng.integers(-16, 17, (K, V)) / 256.0).astype(np.float32)
-    b = (rng.integers(-1024, 1025, V) / 2048.0).astype(np.float32)
-    return X, W, b
 
 
 def _top1(X, W, b, M_):
@@ -172,11 +159,7 @@ def test_lstm_step_matches_sequence(gpu, U, packed):
 
 # ---------------------------------------------------------------------------------------------- v1 decoder
 def _v1(V, T, B, seed=30, units=512):
-    from image_captioning_amd import synth
-    from image_captioning_amd.text_generation_model import DenseCapConfig, build_lstm_model
-    cfg = DenseCapConfig(V, synth.embedding_matrix(33, V), B)
-    cfg.PADDING_SIZE = T
-    return build_lstm_model([7, 7, 256], cfg, units, 'inference', seed=seed)
+    return v1_model(V, T, B, seed, units)
 
 
 @pytest.mark.gpu
@@ -243,10 +226,7 @@ def test_decode_greedy_never_syncs_with_the_host(gpu, monkeypatch):
     model = _v1(1000, 6, 5, seed=50)
     feat = torch.tensor(np.random.default_rng(51).standard_normal((5, 7, 7, 256)).astype(np.float32), device="cuda:0")
     model.decode_greedy(feat)                              # warm: buffers and workspaces
-    calls = []
-    for name in ("cpu", "item", "numpy", "tolist"):
-        orig = getattr(torch.Tensor, name)
-        monkeypatch.setattr(torch.Tensor, name, (lambda o, n: lambda self, *a, **k: (calls.append(n), o(self, *a, **k))[1])(orig, name))
+    calls = record_host_syncs(monkeypatch)
     ids, scores = model.decode_greedy(feat)
     monkeypatch.undo()
     assert calls == []
@@ -271,38 +251,6 @@ def test_degenerate_batches(gpu):
 
 
 # ---------------------------------------------------------------------------------------------- joint model
-def _make_joint(S=128, V=24, T=5, blocks=1):
-    from image_captioning_amd import synth
-    from image_captioning_amd.config import Config
-    from image_captioning_amd.dense_model import DenseImageCapRCNN
-
-    class Cfg(Config):
-        NAME = "joint"
-        IMAGES_PER_GPU = 1
-        IMAGE_MIN_DIM = S
-        IMAGE_MAX_DIM = S
-        POST_NMS_ROIS_TRAINING = 60
-        TRAIN_ROIS_PER_IMAGE = 12
-        PADDING_SIZE = T
-        VOCABULARY_SIZE = V
-        EMBEDDING_SIZE = 300
-        RECURRENT_DROPOUT = 0.0
-    cfg = Cfg()
-    Wt = dict(synth.encoder_weights(0, blocks), **synth.rpn_weights(4))
-    Wt['rpn_conv_shared/kernel'] = Wt['rpn_conv_shared/kernel'] * np.float32(0.05)
-    Wt['rpn_bbox_pred/kernel'] = Wt['rpn_bbox_pred/kernel'] * np.float32(0.3)
-    Wt.update(synth.head_weights(1))
-    Wt['mrcnn_class_conv1/kernel'] = Wt['mrcnn_class_conv1/kernel'] * np.float32(0.05)
-    Wt.update(synth.v1_weights(2, V))
-    Wt['imgcap_embedding_layer/embeddings'] = synth.embedding_matrix(3, V)
-    cfg.EMBEDDING_WEIGHTS = Wt['imgcap_embedding_layer/embeddings']
-    cfg.POST_NMS_ROIS_INFERENCE = 40
-    cfg.DETECTION_MAX_INSTANCES = 10
-    model = DenseImageCapRCNN("inference", cfg, "logs", stage4_blocks=blocks)
-    model.set_weights(Wt)
-    return model, cfg, Wt
-
-
 @pytest.mark.gpu
 def test_joint_model_incremental_captions(gpu, monkeypatch):
     """generate_captions(decoder='incremental') at the shape of test_joint_model_inference_captions: the same rois and ids as the prefix
@@ -310,7 +258,7 @@ def test_joint_model_incremental_captions(gpu, monkeypatch):
     oracle's features."""
     from image_captioning_amd import synth, dense_model
     S, V, T = 128, 24, 5
-    model, cfg, Wt = _make_joint(S, V, T)
+    model, cfg, Wt = joint_model(S, V, T)
     img = synth.images(7, 1, S, S)
     seen = []
     orig = dense_model.refine_generations

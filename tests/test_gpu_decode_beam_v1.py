@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+from _decode_cases import _dev, _feat, joint_model, record_host_syncs, v1_model
 from oracle import np_models as M
 
 
@@ -18,10 +19,6 @@ def gpu():
     from image_captioning_amd import _lib
     _lib.load()
     return torch.device("cuda:0")
-
-
-def _dev(a, dt=torch.float32):
-    return torch.tensor(np.ascontiguousarray(a), dtype=dt, device="cuda:0")
 
 
 # ---------------------------------------------------------------------------------------------- the kernel
@@ -205,19 +202,9 @@ def _v1(V, T, scale=1.0, dtype="f32", seed=70):
     distributions: clearer decisions).  One model per configuration for the whole module; returns (model, float64 weights)."""
     key = (V, T, scale, dtype, seed)
     if key not in _MODELS:
-        from image_captioning_amd import synth
-        from image_captioning_amd.text_generation_model import DenseCapConfig, CaptionModelV1
-        cfg = DenseCapConfig(V, synth.embedding_matrix(33, V), 32)
-        cfg.PADDING_SIZE = T
-        model = CaptionModelV1([7, 7, 256], cfg, 512, 'inference', seed=seed, compute_dtype=dtype)
-        if scale != 1.0:
-            model.load_weights({'imgcap_lstm_d2/kernel': model.get_weights_dict()['imgcap_lstm_d2/kernel'] * np.float32(scale)})
+        model = v1_model(V, T, 32, seed, compute_dtype=dtype, scale=scale)
         _MODELS[key] = (model, {k: v.astype(np.float64) for k, v in model.get_weights_dict().items()})
     return _MODELS[key]
-
-
-def _feat(seed, R):
-    return np.random.default_rng(seed).standard_normal((R, 7, 7, 256)).astype(np.float32)
 
 
 def _post_pad(seqs, T):
@@ -426,10 +413,7 @@ def test_decode_beam_never_syncs_with_the_host(gpu, monkeypatch):
     model, _ = _v1(1000, 6)
     feat = torch.tensor(_feat(51, 5), device="cuda:0")
     model.decode_beam(feat, 3, end_id=2)                    # warm: buffers and workspaces
-    calls = []
-    for name in ("cpu", "item", "numpy", "tolist"):
-        orig = getattr(torch.Tensor, name)
-        monkeypatch.setattr(torch.Tensor, name, (lambda o, n: lambda self, *a, **k: (calls.append(n), o(self, *a, **k))[1])(orig, name))
+    calls = record_host_syncs(monkeypatch)
     toks, sc = model.decode_beam(feat, 3, end_id=2)
     toks_p, sc_p = model.decode_beam(feat, 3, score="prob")
     monkeypatch.undo()
@@ -442,39 +426,6 @@ def test_decode_beam_never_syncs_with_the_host(gpu, monkeypatch):
 
 
 # ---------------------------------------------------------------------------------------------- joint model
-def _make_joint(S=128, V=24, T=5, blocks=1):
-    """The joint model of tests/test_gpu_decode._make_joint."""
-    from image_captioning_amd import synth
-    from image_captioning_amd.config import Config
-    from image_captioning_amd.dense_model import DenseImageCapRCNN
-
-    class Cfg(Config):
-        NAME = "joint"
-        IMAGES_PER_GPU = 1
-        IMAGE_MIN_DIM = S
-        IMAGE_MAX_DIM = S
-        POST_NMS_ROIS_TRAINING = 60
-        TRAIN_ROIS_PER_IMAGE = 12
-        PADDING_SIZE = T
-        VOCABULARY_SIZE = V
-        EMBEDDING_SIZE = 300
-        RECURRENT_DROPOUT = 0.0
-    cfg = Cfg()
-    Wt = dict(synth.encoder_weights(0, blocks), **synth.rpn_weights(4))
-    Wt['rpn_conv_shared/kernel'] = Wt['rpn_conv_shared/kernel'] * np.float32(0.05)
-    Wt['rpn_bbox_pred/kernel'] = Wt['rpn_bbox_pred/kernel'] * np.float32(0.3)
-    Wt.update(synth.head_weights(1))
-    Wt['mrcnn_class_conv1/kernel'] = Wt['mrcnn_class_conv1/kernel'] * np.float32(0.05)
-    Wt.update(synth.v1_weights(2, V))
-    Wt['imgcap_embedding_layer/embeddings'] = synth.embedding_matrix(3, V)
-    cfg.EMBEDDING_WEIGHTS = Wt['imgcap_embedding_layer/embeddings']
-    cfg.POST_NMS_ROIS_INFERENCE = 40
-    cfg.DETECTION_MAX_INSTANCES = 10
-    model = DenseImageCapRCNN("inference", cfg, "logs", stage4_blocks=blocks)
-    model.set_weights(Wt)
-    return model, cfg
-
-
 @pytest.mark.gpu
 def test_joint_model_beam_captions(gpu):
     """generate_captions(decoder='beam', beam_size=3, end_id=2): well-formed results whose rois and ids are what refine_generations gives
@@ -482,7 +433,7 @@ def test_joint_model_beam_captions(gpu):
     decoder's captions (the caption scores that order the NMS well apart)."""
     from image_captioning_amd import synth, dense_model
     S, V, T, k = 128, 24, 5, 3
-    model, cfg = _make_joint(S, V, T)
+    model, cfg, _ = joint_model(S, V, T)
     img = synth.images(7, 1, S, S)[0]
     res = model.generate_captions([img], return_probabilities=False, decoder="beam", beam_size=k, end_id=2)
     assert len(res) == 1 and sorted(res[0]) == ["beam_ids", "beam_scores", "ids", "rois"]

@@ -15,6 +15,8 @@ import numpy as np
 import pytest
 import torch
 
+from _decode_cases import _dev, _exact_operands, joint_model, record_host_syncs, v1_model
+
 MEAN = [123.7, 116.8, 103.9]
 TILES = (128, 256, 0)
 BF16 = torch.bfloat16
@@ -29,10 +31,6 @@ def gpu():
     return torch.device("cuda:0")
 
 
-def _dev(a, dt=torch.float32):
-    return torch.tensor(np.ascontiguousarray(a), dtype=dt, device="cuda:0")
-
-
 def _bf(a):
     """float32 host array -> bf16 device tensor, rounded to nearest even by the library's cast."""
     return _dev(a).to(BF16)
@@ -41,15 +39,6 @@ def _bf(a):
 def _f64(t):
     """device tensor (bf16 or float32) -> float64 host array of exactly its values."""
     return t.detach().to(torch.float32).cpu().numpy().astype(np.float64)
-
-
-def _exact_operands(rng, Mr, K, V):
-    """The grids of tests/test_gpu_decode.py::_exact_operands: X in steps of 1/8 within +-1, W in steps of 1/256 within +-1/16, bias in
-    steps of 1/2048.  At most 5 significant bits each: exact in bf16."""
-    X = (rng.integers(-8, 9, (Mr, K)) / 8.0).astype(np.float32)
-    W = (rng.integers(-16, 17, (K, V)) / 256.0).astype(np.float32)
-    b = (rng.integers(-1024, 1025, V) / 2048.0).astype(np.float32)
-    return X, W, b
 
 
 def _ref_topk(z, k):
@@ -342,11 +331,7 @@ def test_argument_refusals(gpu):
 
 # ---------------------------------------------------------------------------------------------- models
 def _v1_bf16(V, T, B, seed=30, units=512):
-    from image_captioning_amd import synth
-    from image_captioning_amd.text_generation_model import DenseCapConfig, CaptionModelV1
-    cfg = DenseCapConfig(V, synth.embedding_matrix(33, V), B)
-    cfg.PADDING_SIZE = T
-    return CaptionModelV1([7, 7, 256], cfg, units, 'inference', seed=seed, compute_dtype="bf16")
+    return v1_model(V, T, B, seed, units, compute_dtype="bf16")
 
 
 class _Recorder(object):
@@ -451,45 +436,13 @@ def test_every_disagreement_with_the_fp32_vocabulary_is_operand_rounding(gpu, mo
           % (V, B, differ.size, B, 100.0 * (1 - differ.size / B), worst))
 
 
-def _make_joint_bf16(S=128, V=24, T=5, blocks=1):
-    from image_captioning_amd import synth
-    from image_captioning_amd.config import Config
-    from image_captioning_amd.dense_model import DenseImageCapRCNN
-
-    class Cfg(Config):
-        NAME = "joint"
-        IMAGES_PER_GPU = 1
-        IMAGE_MIN_DIM = S
-        IMAGE_MAX_DIM = S
-        POST_NMS_ROIS_TRAINING = 60
-        TRAIN_ROIS_PER_IMAGE = 12
-        PADDING_SIZE = T
-        VOCABULARY_SIZE = V
-        EMBEDDING_SIZE = 300
-        RECURRENT_DROPOUT = 0.0
-    cfg = Cfg()
-    Wt = dict(synth.encoder_weights(0, blocks), **synth.rpn_weights(4))
-    Wt['rpn_conv_shared/kernel'] = Wt['rpn_conv_shared/kernel'] * np.float32(0.05)
-    Wt['rpn_bbox_pred/kernel'] = Wt['rpn_bbox_pred/kernel'] * np.float32(0.3)
-    Wt.update(synth.head_weights(1))
-    Wt['mrcnn_class_conv1/kernel'] = Wt['mrcnn_class_conv1/kernel'] * np.float32(0.05)
-    Wt.update(synth.v1_weights(2, V))
-    Wt['imgcap_embedding_layer/embeddings'] = synth.embedding_matrix(3, V)
-    cfg.EMBEDDING_WEIGHTS = Wt['imgcap_embedding_layer/embeddings']
-    cfg.POST_NMS_ROIS_INFERENCE = 40
-    cfg.DETECTION_MAX_INSTANCES = 10
-    model = DenseImageCapRCNN("inference", cfg, "logs", stage4_blocks=blocks, compute_dtype="bf16")
-    model.set_weights(Wt)
-    return model, cfg
-
-
 @pytest.mark.gpu
 def test_joint_bf16_model_captions_with_the_bf16_vocabulary(gpu, monkeypatch):
     """generate_captions(decoder='incremental', vocab_math='bf16') on a compute_dtype='bf16' joint model: well-formed results, the word
     scores that order the NMS are the recorded outputs of the bf16 vocabulary steps, and vocab_math=None is the call without the keyword."""
     from image_captioning_amd import synth, dense_model
     S, V, T = 128, 24, 5
-    model, cfg = _make_joint_bf16(S, V, T)
+    model, cfg, _ = joint_model(S, V, T, compute_dtype="bf16")
     img = synth.images(7, 1, S, S)
     seen = []
     orig = dense_model.refine_generations
@@ -523,10 +476,7 @@ def test_decode_greedy_bf16_never_syncs_with_the_host(gpu, monkeypatch):
     model = _v1_bf16(1000, 6, 5, seed=50)
     feat = torch.tensor(np.random.default_rng(51).standard_normal((5, 7, 7, 256)).astype(np.float32), device="cuda:0")
     model.decode_greedy(feat, vocab_math="bf16")           # warm: buffers and workspaces
-    calls = []
-    for name in ("cpu", "item", "numpy", "tolist"):
-        orig = getattr(torch.Tensor, name)
-        monkeypatch.setattr(torch.Tensor, name, (lambda o, n: lambda self, *a, **k: (calls.append(n), o(self, *a, **k))[1])(orig, name))
+    calls = record_host_syncs(monkeypatch)
     ids, scores = model.decode_greedy(feat, vocab_math="bf16")
     monkeypatch.undo()
     assert calls == []

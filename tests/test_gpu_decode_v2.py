@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+from _decode_cases import _dev, _exact_operands, _feat, record_host_syncs
 from oracle import np_models as M
 
 
@@ -17,20 +18,6 @@ def gpu():
     from image_captioning_amd import _lib
     _lib.load()
     return torch.device("cuda:0")
-
-
-def _dev(a, dt=torch.float32):
-    return torch.tensor(np.ascontiguousarray(a), dtype=dt, device="cuda:0")
-
-
-def _exact_operands(rng, Mr, K, V):
-    """X, W, bias on coarse binary grids (X in 1/8, W in 1/256, bias in 1/2048 steps), as in test_gpu_decode.py: every product and
-    partial sum of X W + bias is exact in fp32 at these sizes, so the logits are exact (exact ties included) whatever the summation
-    order, and a comparison with float64 measures the kernel's own reductions."""
-    X = (rng.integers(-8, 9, (Mr, K)) / 8.0).astype(np.float32)
-    W = (rng.integers(-16, 17, (K, V)) / 256.0).astype(np.float32)
-    b = (rng.integers(-1024, 1025, V) / 2048.0).astype(np.float32)
-    return X, W, b
 
 
 def _ref_topk(X, W, b, k):
@@ -126,10 +113,6 @@ def _make_v2(V, inject, Tw, seed=0, scale=1.0):
     if scale != 1.0:
         model.load_weights({'imgcap_d1/kernel': model.get_weights_dict()['imgcap_d1/kernel'] * np.float32(scale)})
     return model, {k: v.astype(np.float64) for k, v in model.get_weights_dict().items()}
-
-
-def _feat(seed, R):
-    return np.random.default_rng(seed).standard_normal((R, 7, 7, 256)).astype(np.float32)
 
 
 def _oracle_greedy(Wt, feat, Tw, steps, inject, start=None):
@@ -387,10 +370,7 @@ def test_device_decoders_never_sync_with_the_host(gpu, monkeypatch, inject):
     feat = torch.tensor(_feat(72, 5), device="cuda:0")
     model.decode_greedy(feat)                              # warm: buffers and workspaces
     model.decode_beam(feat, 3)
-    calls = []
-    for name in ("cpu", "item", "numpy", "tolist"):
-        orig = getattr(torch.Tensor, name)
-        monkeypatch.setattr(torch.Tensor, name, (lambda o, n: lambda self, *a, **k: (calls.append(n), o(self, *a, **k))[1])(orig, name))
+    calls = record_host_syncs(monkeypatch)
     ids, scores = model.decode_greedy(feat)
     toks, bsc = model.decode_beam(feat, 3, score="logprob")
     monkeypatch.undo()

@@ -1,7 +1,7 @@
 """Caption decoding of the v2 decoders (inject and merge) per call: CaptionModelV2.generate(decoder='prefix') -- greedy_decode per RoI,
 the reference's test loop (the whole model on the pre-padded prefix per token, a [V] row to the host per token) -- against
 decoder='incremental' (decode_greedy: one token per step with carried word-LSTM state, ops.vocab_top1) and decoder='beam' with k = 3
-and 5 (decode_beam: ops.vocab_topk + ops.beam_select over the k*R beam rows), on synthetic weights; plus ops.vocab_topk alone as a
+and 5 (decode_beam: ops.vocab_topk + ops.beam_step over the k*R beam rows), on synthetic weights; plus ops.vocab_topk alone as a
 fraction of the fp32 matrix peak.
 
 Shapes (Tw = 10, 9 tokens, 256 inject units): configs[1] (R = 64, V = 10 000), one image's ground-truth RoIs (R = 50, V = 10 000) and
