@@ -35,6 +35,7 @@ from .text_generation_model import CaptionModelV1, caption_targets
 
 FPN_CONVS = (("fpn_c5p5", 1, 2048), ("fpn_c4p4", 1, 1024), ("fpn_c3p3", 1, 512), ("fpn_c2p2", 1, 256),
              ("fpn_p2", 3, 256), ("fpn_p3", 3, 256), ("fpn_p4", 3, 256), ("fpn_p5", 3, 256))
+RPN_LAYERS = ("rpn_conv_shared", "rpn_head")
 HEAD_PAD = 20            # 2A + 4A = 18 RPN head channels padded to a multiple of 4 (A = 3 anchors per location)
 
 
@@ -255,6 +256,65 @@ class StepInputs(step_graph.PackedInputs):
                                                          ("gtc", n_gt * T * B), ("scalars", 4)])
 
 
+class _EarlyRanges(object):
+    """One step's bookkeeping of the gradient ranges that travel before the step ends.  Active (data parallel: a multi-rank exchange
+    with .ready is attached): a layer's range gets its L2 term and the trainable mask right when its backward is done, then its
+    all-reduce starts, and finish() regularises what did not go early.  Inactive, ready() does nothing: the single-GPU step keeps
+    the one fused regulariser pass over the whole bucket.  Lives for one _after_encoder call."""
+
+    def __init__(self, model, backward):
+        sync = model.grad_sync
+        active = backward and sync is not None and hasattr(sync, "ready") and getattr(sync, "world", 1) > 1
+        self.store, self.sync, self.done = model.store, sync if active else None, []      # done: [lo, hi) regularised
+        self.coef, self.mask = model._masks() if active else (None, None)
+
+    def _reg(self, lo, hi):
+        ops.l2_reg(self.store.flat[lo:hi], self.coef[lo:hi], self.store.flat_grad[lo:hi], mask=None if self.mask is None else self.mask[lo:hi])
+
+    def ready(self, *layers):
+        """These layers' gradients are final: the regulariser's gradient and the mask on each one's range, then it may travel."""
+        for layer in layers if self.sync is not None else ():
+            lo, hi = self.store.layer_range(layer)
+            self._reg(lo, hi)
+            self.done.append((lo, hi))
+            self.sync.ready(self.store.flat_grad, lo, hi)
+
+    def finish(self, loss):
+        """The ranges that did not go early (anything no layer announced), then the loss term alone (weights only) into `loss`."""
+        n, pos = self.store.flat.numel(), 0
+        for lo, hi in sorted(self.done) + [(n, n)]:
+            if lo > pos:
+                self._reg(pos, lo)
+            pos = max(pos, hi)
+        ops.l2_reg(self.store.flat, self.coef, None, loss=loss)
+
+
+class _RpnBranch(object):
+    """The RPN branch's backward of one step (DenseImageCapRCNN._rpn_backward), in place -- run() -- or forked onto the model's side
+    stream -- fork(), then join() where the current stream needs its results.  dP: the gradient maps dP2..dP6 it created.
+    Data parallel (round 6): the RPN ranges' regulariser pass and their all-reduce are issued from INSIDE the side stream's context
+    right behind the RPN backward -- torch.distributed orders a collective behind the stream that is current when it is issued -- so
+    the exchange of the RPN gradients starts while the main stream still runs proposals -> targets -> decoder."""
+
+    def __init__(self, model, *args):
+        self.model, self.args, self.dP = model, args, None
+
+    def run(self):
+        self.dP = self.model._rpn_backward(*self.args)
+
+    def fork(self, early):
+        m = self.model
+        if m._side_stream is None:
+            m._side_stream = torch.cuda.Stream(device=m.device)
+        m._side_stream.wait_stream(torch.cuda.current_stream(m.device))
+        with torch.cuda.stream(m._side_stream):
+            self.run()
+            early.ready(*RPN_LAYERS)
+
+    def join(self):
+        torch.cuda.current_stream(self.model.device).wait_stream(self.model._side_stream)
+
+
 class DenseImageCapRCNN(object):
     LOSS_NAMES = ("rpn_class_loss", "rpn_bbox_loss", "imgcap_loss")
     LAYER_REGEX = {                       # dense_img_cap/dense_model.py:1829-1845
@@ -302,6 +362,7 @@ class DenseImageCapRCNN(object):
         self._dt_rank = 0                                    # ParallelModel sets the tower's rank: towers shuffle their proposals independently
         self._last_targets = None
         self._step_in = None
+        self._pins = {}                                      # page-locked host buffers (_pinned)
         self.optimizer = None
         self.grad_sync = None
         self.is_chief = True               # ParallelModel clears it on ranks > 0: one rank prints and writes checkpoints
@@ -379,11 +440,6 @@ class DenseImageCapRCNN(object):
         extra.append(("rpn_head/bias", hb, True))
         self.caption_model = CaptionModelV1([cfg.POOL_SIZE, cfg.POOL_SIZE, 256], cfg, self.units, 'training', dev, seed,
                                             extra_params=extra, compute_dtype=self.compute_dtype)
-        # data parallel: a decoder layer's gradient range gets its L2 term and trainable mask right when its backward is done, then
-        # its all-reduce starts (forward_backward installs the hook when a gradient exchange is attached); the single-GPU step keeps
-        # the one fused regulariser pass over the whole bucket
-        self.caption_model.overlap_sync = False
-        self._reg_done = []
         self.caption_model.recurrent_dropout = float(getattr(cfg, "RECURRENT_DROPOUT", 0.2))    # dense_img_cap/dense_model.py:769-770: recurrent_dropout=0.2
         self.caption_model.dropout_rows = str(getattr(cfg, "DROPOUT_ROWS", "roi"))
         self.store = self.caption_model.store
@@ -734,12 +790,9 @@ class DenseImageCapRCNN(object):
 
     def _pinned(self, key, shape, dtype=torch.float32):
         """A page-locked host buffer owned by the model (asynchronous device -> host copies land here)."""
-        b = self._pins.get(key) if hasattr(self, "_pins") else None
+        b = self._pins.get(key)
         if b is None or tuple(b.shape) != tuple(shape) or b.dtype != dtype:
-            if not hasattr(self, "_pins"):
-                self._pins = {}
-            b = torch.empty(shape, dtype=dtype, pin_memory=True)
-            self._pins[key] = b
+            b = self._pins[key] = torch.empty(shape, dtype=dtype, pin_memory=True)
         return b
 
     def _step_uploads(self, p, rpn_match, rpn_bbox, gt_norm, gt_caps, training):
@@ -788,10 +841,15 @@ class DenseImageCapRCNN(object):
                     deltas=si.view("deltas", torch.float32).view(si.cap, 4), gt=si.view("gt", torch.float32).view(si.B, si.n_gt, 4),
                     gtc=si.view("gtc").view(si.B, si.n_gt, si.T), cap=si.cap, lr_t=sc[0:1].view(torch.float32), drop_offset=sc[1:2], dt_offset=sc[2:3])
 
+    def _rpn_losses(self, p, rpn_up, dheads, losses):
+        """RPN losses (dense_model.py:1008-1075) into losses[0:2], their gradients into the zeroed `dheads` (selection and counts: StepInputs views)."""
+        ops.rpn_loss_grad(p.rpn_heads, dheads, rpn_up["lvl"], rpn_up["idx"], rpn_up["mt"], rpn_up["deltas"], rpn_up["cap"], losses[0:2],
+                          anchors_per_loc=self.A, counts_dev=rpn_up["counts"], batched=True)
+
     def _rpn_backward(self, p, rpn_up, losses):
-        """RPN losses (dense_model.py:1008-1075) and the backward of the RPN branch: gradients of the fused head and of the shared
-        3x3 convolution (accumulated over the five pyramid levels) and the data gradients into dP2..dP6, which this call creates
-        (zeroed) and returns together with the pyramid maps.  Independent of the detection targets."""
+        """RPN losses and the backward of the RPN branch: gradients of the fused head and of the shared 3x3 convolution (accumulated
+        over the five pyramid levels) and the data gradients into dP2..dP6, which this call creates (zeroed) and returns.
+        Independent of the detection targets."""
         st = self.store
         w, g = st.w, st.grad
         maps = list(p.P) + [p.P6]
@@ -806,10 +864,7 @@ class DenseImageCapRCNN(object):
             cuts.append(pool[off:off + int(np.prod(sh))].view(sh))
             off += n
         dP, dheads = cuts[:len(maps)], cuts[len(maps):]
-        # ---- RPN losses and their gradients w.r.t. the fused head outputs (selection and counts: this step's StepInputs views)
-        ops.rpn_loss_grad(p.rpn_heads, dheads, rpn_up["lvl"], rpn_up["idx"], rpn_up["mt"], rpn_up["deltas"], rpn_up["cap"], losses[0:2],
-                          anchors_per_loc=self.A, counts_dev=rpn_up["counts"], batched=True)
-
+        self._rpn_losses(p, rpn_up, dheads, losses)
         # ---- RPN backward (shared weights over the five levels: gradients accumulate)
         wd_shared = ops.conv_weight_dgrad_pack(w["rpn_conv_shared/kernel"], 3, 3, 256, out=self._buf("wd_shared", (256, 9 * 512)))
         for i, (pm, sh, dh) in enumerate(zip(maps, p.rpn_shared, dheads)):
@@ -824,21 +879,27 @@ class DenseImageCapRCNN(object):
             self._wgrad(pm, dsh, 3, 1, g["rpn_conv_shared/kernel"], accumulate=acc, key="P%d" % i, dy_key="dsh%d" % i)
             ops.colsum(dsh.view(-1, 512), out=g["rpn_conv_shared/bias"], accumulate=acc)
             self._dgrad(dsh, wd_shared, 3, dP[i], residual=dP[i], key="rpn_shared", dy_key="dsh%d" % i)     # dP += dgrad
-        return maps, dP
+        return dP
 
     # ---- backward through trainable ResNet stages (train(layers = "5+" | "4+" | "3+" | "all")) ------------------------
-    def _bn_conv_backward(self, conv, bn, dz, bn_out, bn_sub, x, k, stride, key):
-        """Backward of y_bn = BN_frozen_stats(conv(x)) given dz = d(loss)/d(y_bn) and y_bn = bn_out - bn_sub (bn_sub may be None):
-        writes the gradients of kernel, bias, gamma, beta into the bucket and returns dacc = d(loss)/d(conv output)."""
-        p, w, g = self.plan(), self.store.w, self.store.grad
-        scale = p._w[conv][1]                                # gamma / sqrt(var + eps), folded by this step's forward
+    def _bn_backward(self, conv, bn, dz, bn_out, bn_sub, dacc, dzn):
+        """Backward of the frozen-statistics BatchNorm behind `conv`, y_bn = bn_out - bn_sub (bn_sub may be None), given dz = d(loss)/d(y_bn):
+        the gradients of gamma, beta and the convolution's bias into the bucket, d(loss)/d(conv output) into `dacc` (returned); dzn: scratch."""
+        w, g = self.store.w, self.store.grad
+        scale = self.plan()._w[conv][1]                      # gamma / sqrt(var + eps), folded by this step's forward
         cout = dz.shape[-1]
-        dacc = self._buf(("tb_dacc", key, tuple(dz.shape)), tuple(dz.shape))
-        dzn = self._buf(("tb_dzn", tuple(dz.shape)), tuple(dz.shape))
         ops.bn_bwd(dz, bn_out, bn_sub, w[bn + "/gamma"], w[bn + "/beta"], scale, dacc, dzn)
         ops.colsum(dz.view(-1, cout), out=g[bn + "/beta"])
         ops.colsum(dzn.view(-1, cout), out=g[bn + "/gamma"])
         ops.mul(scale, g[bn + "/beta"], g[conv + "/bias"])   # sum(dz * scale) over the pixels = scale * dbeta
+        return dacc
+
+    def _bn_conv_backward(self, conv, bn, dz, bn_out, bn_sub, x, k, stride, key):
+        """Backward of y_bn = BN_frozen_stats(conv(x)) given dz = d(loss)/d(y_bn) and y_bn = bn_out - bn_sub (bn_sub may be None):
+        writes the gradients of kernel, bias, gamma, beta into the bucket and returns dacc = d(loss)/d(conv output)."""
+        g = self.store.grad
+        dacc = self._bn_backward(conv, bn, dz, bn_out, bn_sub, self._buf(("tb_dacc", key, tuple(dz.shape)), tuple(dz.shape)),
+                                 self._buf(("tb_dzn", tuple(dz.shape)), tuple(dz.shape)))
         pad = (k - 1) // 2
         if stride == 1:
             self._wgrad(x, dacc, k, pad, g[conv + "/kernel"])
@@ -901,13 +962,7 @@ class DenseImageCapRCNN(object):
             c1, pooled = sv["c1"], sv["pooled"]
             dc1 = ops.maxpool3x3s2_same_bwd(c1, pooled, d_c, out=self._buf("tb_dc1", tuple(c1.shape)))
             dz = ops.relu_bwd(dc1.view(-1, 64), c1.view(-1, 64), dc1.view(-1, 64)).view(c1.shape)
-            scale = p._w["conv1"][1]
-            dacc = self._buf("tb_dacc_stem", tuple(c1.shape))
-            dzn = self._buf("tb_dzn_stem", tuple(c1.shape))
-            ops.bn_bwd(dz, c1, None, w["bn_conv1/gamma"], w["bn_conv1/beta"], scale, dacc, dzn)
-            ops.colsum(dz.view(-1, 64), out=g["bn_conv1/beta"])
-            ops.colsum(dzn.view(-1, 64), out=g["bn_conv1/gamma"])
-            ops.mul(scale, g["bn_conv1/beta"], g["conv1/bias"])
+            dacc = self._bn_backward("conv1", "bn_conv1", dz, c1, None, self._buf("tb_dacc_stem", tuple(c1.shape)), self._buf("tb_dzn_stem", tuple(c1.shape)))
             x64 = ops.mold_image_padded(p.images, p.mean_pixel, self._buf("tb_x64", tuple(p.images.shape[:3]) + (64,)))   # Cin % 64 == 0 for the wgrad kernel
             gw = ops.conv2d_wgrad(x64, dacc, 7, 7, 2, 3, 3, out=self._buf("tb_gw_stem", (64, 49 * 64)))
             gk = g["conv1/kernel"].view(64, 7, 8, 4)                       # the stem's packed layout (pads stay zero)
@@ -936,201 +991,160 @@ class DenseImageCapRCNN(object):
         evaluation between two train steps does not change the training run.
         targets = (rois [R,4] normalised, caps [R,T]): the DetectionTargetLayer's sample handed in by the caller instead of drawn (one
         image per step; parity tests check a second model against the oracle result of a sample another model drew)."""
-        images, _meta, rpn_match, rpn_bbox, gt_caps, gt_boxes = inputs[:6]
-        self._targets_given = None if targets is None else (np.asarray(targets[0], np.float32), np.asarray(targets[1]))
-        p = self.plan()
-        gt_norm = self._check_batch(p, images, gt_boxes)
-        # ---- this step's host inputs go to the device FIRST (GT boxes, GT captions, the RPN selection, the step scalars: one asynchronous
-        # copy, StepInputs): nothing the host contributes may sit in the middle of the step
-        rpn_up = self._step_uploads(p, rpn_match, rpn_bbox, gt_norm, gt_caps, backward)
+        p, rpn_up, images, gt_caps, gt_norm = self._begin_step(inputs, backward)
+        self._encoder_pass(p, images, trunk_done)
+        return self._after_encoder(p, rpn_up, shuffle, backward, gt_caps, gt_norm,
+                                   given=None if targets is None else (np.asarray(targets[0], np.float32), np.asarray(targets[1])))
 
-        # ---- forward: backbone + FPN + RPN (the plan's hipGraph), then everything behind the encoder
-        if trunk_done:                                       # the backbone pass of these images has run on this plan (JointTrainPipeline)
+    def _begin_step(self, inputs, training):
+        """The head of every step: this step's host inputs go to the device FIRST (GT boxes, GT captions, the RPN selection, the step scalars: one
+        asynchronous copy, StepInputs) -- nothing the host contributes may sit in the middle of the step.  Returns (plan, the StepInputs views,
+        images, gt_caps, the GT boxes normalised by the molded image's size [B,G,4])."""
+        images, _meta, rpn_match, rpn_bbox, gt_caps, gt_boxes = inputs[:6]
+        p, B = self.plan(), self.images_per_gpu
+        if len(images) != B:                                 # (static graph, like the reference's KL.Input batch)
+            raise ValueError("%d image(s) handed to a model built for IMAGES_PER_GPU = %d" % (len(images), B))
+        gt_norm = (np.asarray(gt_boxes, np.float32).reshape(B, -1, 4) / np.array([p.H, p.W, p.H, p.W], np.float32)).astype(np.float32)
+        return p, self._step_uploads(p, rpn_match, rpn_bbox, gt_norm, gt_caps, training), images, gt_caps, gt_norm
+
+    def _encoder_pass(self, p, images, trunk_done):
+        """backbone + FPN + RPN (the plan's hipGraph); trunk_done: the backbone pass of these images has run on this plan (JointTrainPipeline)."""
+        if trunk_done:
             p.forward_top()
         else:
             p.forward(self._images_u8(images))
-        return self._after_encoder(p, rpn_up, shuffle, backward, gt_caps, gt_norm)
 
-    def _check_batch(self, p, images, gt_boxes):
-        """The step takes exactly IMAGES_PER_GPU images (static graph, like the reference's KL.Input batch); returns the GT boxes
-        normalised by the molded image's size, float32 [B, G, 4]."""
-        if len(images) != self.images_per_gpu:
-            raise ValueError("%d image(s) handed to a model built for IMAGES_PER_GPU = %d" % (len(images), self.images_per_gpu))
-        return (np.asarray(gt_boxes, np.float32).reshape(self.images_per_gpu, -1, 4) / np.array([p.H, p.W, p.H, p.W], np.float32)).astype(np.float32)
-
-    def _after_encoder(self, p, rpn_up, shuffle, backward, gt_caps, gt_norm, fuse_reg=False):
+    def _after_encoder(self, p, rpn_up, shuffle, backward, gt_caps, gt_norm, fuse_reg=False, given=None):
         """The step behind the encoder pass: proposals, detection targets, RoIAlign, head + decoder, the four losses and (backward)
         every gradient into the flat bucket.  With device-side targets (shuffle None / "rng") nothing in here depends on a host value
         that changes from step to step -- counts, stream positions and lr_t are device words of StepInputs -- so train_on_batch_device
-        captures it (plus the optimizer) as ONE hipGraph."""
-        cfg, st, cm = self.config, self.store, self.caption_model
-        w, g = st.w, st.grad
-        dev = self.device
-        H, W = p.H, p.W
-        up = lambda a, dt=torch.float32: torch.tensor(np.ascontiguousarray(a), dtype=dt, device=dev)
-        given = getattr(self, "_targets_given", None)
-        self._targets_given = None
+        captures it (plus the optimizer) as ONE hipGraph.  given: forward_backward's `targets`, as arrays."""
         device_targets = (shuffle is None or shuffle == "rng") and given is None
-        gt_dev, gtc_dev = rpn_up["gt"], rpn_up["gtc"]
-        B = self.images_per_gpu
         self._bf16_cache = {}
         losses = self._buf("losses", (4,))
+        early = _EarlyRanges(self, backward)
+        rpn = _RpnBranch(self, p, rpn_up, losses) if backward else None
         # The RPN branch's backward (RPN losses, head / shared-convolution weight gradients, data gradients into dP2..dP6: ~1.2 ms of
         # large kernels) needs only the encoder's outputs and the step's RPN targets, while the chain proposals -> top-k -> NMS scan ->
         # detection targets -> RoIAlign -> head + LSTM forward is a string of small, latency-bound launches (the NMS scan alone is one
         # wave for 0.28 ms).  They run side by side: the RPN backward on a second stream, forked here and joined before the RoIAlign
         # backward adds into dP.  (Captured: two branches of the step's hipGraph.)
-        overlap_dp = self.grad_sync is not None and hasattr(self.grad_sync, "ready") and getattr(self.grad_sync, "world", 1) > 1
-        # Data parallel (round 6): the same fork.  The RPN ranges' regulariser pass and their all-reduce are issued from INSIDE the side
-        # stream's context right behind the RPN backward -- torch.distributed orders a collective behind the stream that is current when
-        # it is issued -- so the exchange of the RPN gradients starts while the main stream still runs proposals -> targets -> decoder.
         fork = backward and device_targets and self.use_side_stream
-        self._reg_done = []
-        early = None
-        if backward and overlap_dp:
-            coef_, mask_ = self._masks()
-
-            def early(lo, hi):                              # regulariser gradient + mask of one layer range, then it may travel
-                ops.l2_reg(st.flat[lo:hi], coef_[lo:hi], st.flat_grad[lo:hi], mask=None if mask_ is None else mask_[lo:hi])
-                self._reg_done.append((lo, hi))
-
-        def rpn_ranges_travel():
-            for layer in ("rpn_conv_shared", "rpn_head"):
-                lo, hi = st.layer_range(layer)
-                early(lo, hi)
-                self.grad_sync.ready(st.flat_grad, lo, hi)
-        maps = dP = None
         if fork:
-            if self._side_stream is None:
-                self._side_stream = torch.cuda.Stream(device=dev)
-            cur = torch.cuda.current_stream(dev)
-            self._side_stream.wait_stream(cur)
-            with torch.cuda.stream(self._side_stream):
-                maps, dP = self._rpn_backward(p, rpn_up, losses)
-                if overlap_dp:
-                    rpn_ranges_travel()
+            rpn.fork(early)
         proposals = p.proposals()
-        R = cfg.TRAIN_ROIS_PER_IMAGE
         if device_targets:
-            # DetectionTargetLayer on the device (dc_detection_targets_f32): IoU, the >= 0.5 / < 0.5 split, the shuffle (Philox keys drawn
-            # from (model seed, step): reproducible, where tf.random_shuffle is not), the 1:2 sample and the caption gather.  Nothing
-            # comes back to the host: counts travel as device words, every shape downstream is static (TRAIN_ROIS_PER_IMAGE rows).
-            seed = None if shuffle is None else ((self._seed + (0 if backward else 1)) * 2654435761 + 12345 + self._dt_rank * 0x9E3779B9) & 0xFFFFFFFF
-            T = int(np.asarray(gt_caps).shape[-1])
-            # one launch per image (the reference's utils.batch_slice over DetectionTargetLayer, dense_model.py:531-572), each image with
-            # its own Philox key; the sampled RoIs, captions and counts of the batch are rows of ONE set of buffers
-            rois_d, caps_d, counts_d = self._buf("dt_rois", (B, R, 4)), self._buf("dt_caps", (B, R, T), torch.int32), self._buf("dt_counts", (B, 2), torch.int32)
-            for b in range(B):
-                ops.detection_targets(proposals[b], gt_dev[b], gtc_dev[b], R, cfg.ROI_POSITIVE_RATIO,
-                                      seed=None if seed is None else (seed + b * 0x85EBCA6B) & 0xFFFFFFFF, offset=0, offset_dev=rpn_up["dt_offset"],
-                                      out=(rois_d[b], caps_d[b], counts_d[b]))
-            self._last_targets = (rois_d, caps_d, counts_d)
-            boxes = rois_d
-            feats = p.roi_features(boxes_norm=boxes, out=self._buf("feats", (B, R, cfg.POOL_SIZE, cfg.POOL_SIZE, 256)))
-            feats = feats.view(B * R, cfg.POOL_SIZE, cfg.POOL_SIZE, 256)
-            # the caption loss is the mean over every live position of the BATCH (imgcap_caption_loss_graph gathers over all images,
-            # dense_model.py:936-946): the tables' row weights are 1 / (live positions of all B * R captions)
-            R_all = B * R
-            tables = ops.caption_tables(caps_d.view(R_all, T), out=(self._buf("ct_ids", (T * R_all,), torch.int32), self._buf("ct_mask", (T * R_all,), torch.uint8),
-                                                                    self._buf("ct_tg", (T * R_all,), torch.int32), self._buf("ct_rw", (T * R_all,))))
-            if cm._prefix_rows(backward):
-                # DROPOUT_ROWS = 'prefix' (one mask per (RoI, prefix) row, as the reference's TimeDistributed graph draws them): the T-fold
-                # prefix tables are built on the host, so this non-default mode reads the sampled captions back (one synchronisation)
-                cm._drop_offset_dev = None
-                caps_h = caps_d.view(R_all, T).cpu().numpy()
-                tg_h = caption_targets(caps_h)
-                live = (tg_h > 0).astype(np.float32)
-                loss_rows, _ = cm._forward_train(feats, caps_h, tg_h, want_grad=backward, row_weights=live / max(float(live.sum()), 1.0),
-                                                 keras_sparse=True)
-            else:
-                cm._drop_offset_dev = rpn_up["drop_offset"]
-                try:
-                    loss_rows, _ = cm._forward_train(feats, None, want_grad=backward, keras_sparse=True, device_tables=tables + (R_all, T))
-                finally:
-                    cm._drop_offset_dev = None                  # a later standalone step of the shared caption model draws from ITS counter
+            boxes, loss_rows = self._device_sample(p, rpn_up, proposals, shuffle, backward, gt_caps)
             if backward and not fork:
-                maps, dP = self._rpn_backward(p, rpn_up, losses)
+                rpn.run()
         else:
-            # a caller-supplied permutation (shuffle = callable): the sample is drawn on the host, as until round 3.  The proposals start
-            # their way to the host first; the RPN branch's backward is enqueued behind that copy, so the GPU works while the host samples.
-            mix = shuffle
-            if B != 1:
-                raise ValueError("a caller-supplied shuffle samples on the host: one image per step only (use shuffle=None or 'rng')")
-            if given is not None:
-                props_np = None
-                if backward:
-                    maps, dP = self._rpn_backward(p, rpn_up, losses)
-            elif backward:
+            boxes, loss_rows = self._host_sample(p, proposals, shuffle, given, rpn, gt_caps, gt_norm)
+        ops.mean(loss_rows, out=losses[2:3])                 # x rows below: the weights already carry 1/count
+        self._loss_scale = float(loss_rows.numel())
+        if not backward:
+            return self._validation_tail(p, rpn_up, losses)
+        if not fork:                                         # serial order: the RPN's gradients are final here, they travel first
+            early.ready(*RPN_LAYERS)
+        # (tried and measured without gain, round 4: the decoder's weight-gradient GEMMs on the side stream beside its LSTM backward
+        # chain -- 8.77 ms against 8.68 captured, 8.57 against 8.58 eager)
+        dX = self.caption_model._backward(want_dx=True, ready=early.ready)
+        if fork:
+            rpn.join()                                       # dP, the RPN gradients and losses[0:2] are complete
+            # (a SECOND fork was tried and removed, round 4: the decoder's / head's share of the regulariser pass -- HBM-bound, 290 of the
+            # bucket's 308 MB -- on the side stream beside the RoIAlign / FPN backward: 8.59 ms against 8.58 eager, 9.07 against 8.68
+            # captured -- every extra branch costs the graph replay more than the overlap returns)
+        self._fpn_backward(p, rpn.dP, boxes, dX, early.ready)
+        self._regulariser_tail(losses, early, fuse_reg)
+        return losses
+
+    def _device_sample(self, p, rpn_up, proposals, shuffle, backward, gt_caps):
+        """DetectionTargetLayer on the device (dc_detection_targets_f32): IoU, the >= 0.5 / < 0.5 split, the shuffle (Philox keys drawn
+        from (model seed, step): reproducible, where tf.random_shuffle is not), the 1:2 sample and the caption gather.  Nothing comes
+        back to the host: counts travel as device words, every shape downstream is static (TRAIN_ROIS_PER_IMAGE rows).
+        Enqueues detection_targets per image, RoIAlign, caption_tables and the decoder's forward; returns (boxes [B,R,4], loss_rows)."""
+        cfg, cm, B, R, T = self.config, self.caption_model, self.images_per_gpu, self.config.TRAIN_ROIS_PER_IMAGE, int(np.asarray(gt_caps).shape[-1])
+        seed = None if shuffle is None else ((self._seed + (0 if backward else 1)) * 2654435761 + 12345 + self._dt_rank * 0x9E3779B9) & 0xFFFFFFFF
+        # one launch per image (the reference's utils.batch_slice over DetectionTargetLayer, dense_model.py:531-572), each image with
+        # its own Philox key; the sampled RoIs, captions and counts of the batch are rows of ONE set of buffers
+        rois_d, caps_d, counts_d = self._buf("dt_rois", (B, R, 4)), self._buf("dt_caps", (B, R, T), torch.int32), self._buf("dt_counts", (B, 2), torch.int32)
+        for b in range(B):
+            ops.detection_targets(proposals[b], rpn_up["gt"][b], rpn_up["gtc"][b], R, cfg.ROI_POSITIVE_RATIO,
+                                  seed=None if seed is None else (seed + b * 0x85EBCA6B) & 0xFFFFFFFF, offset=0, offset_dev=rpn_up["dt_offset"],
+                                  out=(rois_d[b], caps_d[b], counts_d[b]))
+        self._last_targets = (rois_d, caps_d, counts_d)
+        feats = p.roi_features(boxes_norm=rois_d, out=self._buf("feats", (B, R, cfg.POOL_SIZE, cfg.POOL_SIZE, 256))).view(B * R, cfg.POOL_SIZE, cfg.POOL_SIZE, 256)
+        # the caption loss is the mean over every live position of the BATCH (imgcap_caption_loss_graph gathers over all images,
+        # dense_model.py:936-946): the tables' row weights are 1 / (live positions of all B * R captions)
+        R_all = B * R
+        tables = ops.caption_tables(caps_d.view(R_all, T), out=(self._buf("ct_ids", (T * R_all,), torch.int32), self._buf("ct_mask", (T * R_all,), torch.uint8),
+                                                                self._buf("ct_tg", (T * R_all,), torch.int32), self._buf("ct_rw", (T * R_all,))))
+        if cm._prefix_rows(backward):
+            # DROPOUT_ROWS = 'prefix' (one mask per (RoI, prefix) row, as the reference's TimeDistributed graph draws them): the T-fold
+            # prefix tables are built on the host, so this non-default mode reads the sampled captions back (one synchronisation)
+            caps_h = caps_d.view(R_all, T).cpu().numpy()
+            tg_h = caption_targets(caps_h)
+            live = (tg_h > 0).astype(np.float32)
+            return rois_d, cm._forward_train(feats, caps_h, tg_h, want_grad=backward, row_weights=live / max(float(live.sum()), 1.0), keras_sparse=True)[0]
+        return rois_d, cm._forward_train(feats, None, want_grad=backward, keras_sparse=True, device_tables=tables + (R_all, T),
+                                         drop_offset_dev=rpn_up["drop_offset"])[0]
+
+    def _host_sample(self, p, proposals, shuffle, given, rpn, gt_caps, gt_norm):
+        """A caller-supplied permutation (shuffle = callable) or sample (given): drawn on the host, as until round 3.  The proposals start their
+        way to the host first (a pinned, asynchronous copy); the RPN branch's backward (rpn.run(); rpn is None in a forward-only pass) is enqueued
+        behind that copy, so the GPU works while the host samples.  Then the sample's upload, RoIAlign, the decoder's forward; returns (boxes [1,R,4], loss_rows)."""
+        cfg = self.config
+        if self.images_per_gpu != 1:
+            raise ValueError("a caller-supplied shuffle samples on the host: one image per step only (use shuffle=None or 'rng')")
+        if given is not None:
+            if rpn is not None:
+                rpn.run()
+            rois, caps = given
+            npos = int((np.asarray(caps)[:, 1:] > 0).any(axis=1).sum())
+            nneg = int((np.abs(rois).sum(axis=1) > 0).sum()) - npos
+        else:
+            if rpn is not None:
                 host_props = self._pinned("props", tuple(proposals[0].shape))
                 host_props.copy_(proposals[0], non_blocking=True)
                 ev = torch.cuda.Event()
                 ev.record()
-                maps, dP = self._rpn_backward(p, rpn_up, losses)
+                rpn.run()
                 ev.synchronize()
                 props_np = host_props.numpy()
             else:
                 props_np = proposals[0].cpu().numpy()
-            cm._drop_offset_dev = None
-            if given is not None:
-                rois, caps = given
-                npos = int((np.asarray(caps)[:, 1:] > 0).any(axis=1).sum())
-                nneg = int((np.abs(rois).sum(axis=1) > 0).sum()) - npos
-            else:
-                rois, caps, npos, nneg = detection_targets(props_np, gt_caps[0], gt_norm[0], cfg, mix)
-            self._last_targets = dict(rois=rois, caps=caps, npos=npos, nneg=nneg)
-            boxes = up(rois[None])
-            feats = p.roi_features(boxes_norm=boxes, out=self._buf("feats", (1, R, cfg.POOL_SIZE, cfg.POOL_SIZE, 256)))
-            tg = caption_targets(caps)
-            live = (tg > 0).astype(np.float32)
-            count = float(live.sum())
-            loss_rows, _ = cm._forward_train(feats[0], caps, tg, want_grad=backward, row_weights=live / max(count, 1.0), keras_sparse=True)
-        ops.mean(loss_rows, out=losses[2:3])                 # x rows below: the weights already carry 1/count
-        self._loss_scale = float(loss_rows.numel())
-        if not backward:
-            # RPN losses need the heads only (their gradient goes to scratch), the regulariser the weights only
-            scratch = [self._buf("dhead%d" % i, tuple(h.shape)) for i, h in enumerate(p.rpn_heads)]
-            for t in scratch:
-                ops.zero_fill(t)
-            ops.rpn_loss_grad(p.rpn_heads, scratch, rpn_up["lvl"], rpn_up["idx"], rpn_up["mt"], rpn_up["deltas"], rpn_up["cap"], losses[0:2],
-                              anchors_per_loc=self.A, counts_dev=rpn_up["counts"], batched=True)
-            coef, _ = self._masks()
-            ops.l2_reg(st.flat, coef, None, loss=losses[3:4])
-            return losses
+            rois, caps, npos, nneg = detection_targets(props_np, gt_caps[0], gt_norm[0], cfg, shuffle)
+        self._last_targets = dict(rois=rois, caps=caps, npos=npos, nneg=nneg)
+        boxes = torch.tensor(np.ascontiguousarray(rois[None]), dtype=torch.float32, device=self.device)
+        feats = p.roi_features(boxes_norm=boxes, out=self._buf("feats", (1, cfg.TRAIN_ROIS_PER_IMAGE, cfg.POOL_SIZE, cfg.POOL_SIZE, 256)))
+        tg = caption_targets(caps)
+        live = (tg > 0).astype(np.float32)
+        return boxes, self.caption_model._forward_train(feats[0], caps, tg, want_grad=rpn is not None, row_weights=live / max(float(live.sum()), 1.0),
+                                                        keras_sparse=True)[0]
 
-        # ---- backward: decoder + head -> RoI features -> pyramid
-        overlap = overlap_dp
-        if overlap:
-            cm.before_sync, cm.grad_sync, cm.overlap_sync = early, self.grad_sync, True
-        else:
-            cm.before_sync, cm.overlap_sync = None, False
-        if overlap and not fork:                             # serial order: the RPN's gradients are final here, they travel first
-            rpn_ranges_travel()
-        # (tried and measured without gain, round 4: the decoder's weight-gradient GEMMs on the side stream beside its LSTM backward
-        # chain -- 8.77 ms against 8.68 captured, 8.57 against 8.58 eager)
-        dX = cm._backward(want_dx=True)
-        if fork:
-            torch.cuda.current_stream(dev).wait_stream(self._side_stream)      # join: dP, the RPN gradients and losses[0:2] are complete
-            # (a SECOND fork was tried and removed, round 4: the decoder's / head's share of the regulariser pass -- HBM-bound, 290 of the
-            # bucket's 308 MB -- on the side stream beside the RoIAlign / FPN backward: 8.59 ms against 8.58 eager, 9.07 against 8.68
-            # captured -- every extra branch costs the graph replay more than the overlap returns)
+    def _validation_tail(self, p, rpn_up, losses):
+        """Forward-only pass: the RPN losses need the heads only (their gradient goes to zeroed scratch), the regulariser loss the weights only."""
+        scratch = [self._buf("dhead%d" % i, tuple(h.shape)) for i, h in enumerate(p.rpn_heads)]
+        for t in scratch:
+            ops.zero_fill(t)
+        self._rpn_losses(p, rpn_up, scratch, losses)
+        ops.l2_reg(self.store.flat, self._masks()[0], None, loss=losses[3:4])
+        return losses
+
+    def _fpn_backward(self, p, dP, boxes, dX, ready):
+        """RoI features -> pyramid -> FPN (-> trainable ResNet stages): the RoIAlign scatter into dP, the P6 scatter, the four fpn_p* output layers,
+        the top-down sums, the four laterals, then _trunk_backward.  ready(layer): its gradient range is complete (data parallel: it may travel)."""
+        cfg, w, g = self.config, self.store.w, self.store.grad
         # dP already holds the RPN branch's data gradients; the RoI features' gradient is added on top (a fixed-order gather per pyramid pixel: reproducible)
-        ops.roi_align_pyramid_bwd(dP[:4], boxes, float(H * W), dX.view(B, R, cfg.POOL_SIZE, cfg.POOL_SIZE, 256), cfg.POOL_SIZE)
+        ops.roi_align_pyramid_bwd(dP[:4], boxes, float(p.H * p.W), dX.view(self.images_per_gpu, cfg.TRAIN_ROIS_PER_IMAGE, cfg.POOL_SIZE, cfg.POOL_SIZE, 256),
+                                  cfg.POOL_SIZE)
         ops.scatter2_add(dP[4], dP[3])                       # P6 = MaxPooling2D(1, strides=2)(P5)
-
-        # ---- FPN backward (data parallel: every layer's gradient range starts its all-reduce as soon as it is complete)
-        def announce(layer):
-            if overlap:
-                lo, hi = st.layer_range(layer)
-                early(lo, hi)
-                self.grad_sync.ready(st.flat_grad, lo, hi)
         dpre = []
         for i in range(4):
             name = "fpn_p%d" % (i + 2)
             wd = ops.conv_weight_dgrad_pack(w[name + "/kernel"], 3, 3, 256, out=self._buf("wd_" + name, (256, 9 * 256)))
-            _, h_, w_, _ = dP[i].shape
             self._wgrad(p.pre[i], dP[i], 3, 1, g[name + "/kernel"], dy_key="dP%d" % i)
             ops.colsum(dP[i].view(-1, 256), out=g[name + "/bias"])
-            announce(name)
+            ready(name)
             # (dpre[0] is final here: its bf16 copy comes out of the same epilogue; the coarser ones still receive the top-down sums below)
             dpre.append(self._dgrad(dP[i], wd, 3, self._buf("dpre%d" % i, tuple(dP[i].shape)), key=name, dy_key="dP%d" % i,
                                     out_key="dpre0" if i == 0 else None))
@@ -1140,26 +1154,18 @@ class DenseImageCapRCNN(object):
             name = "fpn_c%dp%d" % (i + 2, i + 2)
             self._wgrad(cmap, dpre[i], 1, 0, g[name + "/kernel"], dy_key="dpre%d" % i)
             ops.colsum(dpre[i].view(-1, 256), out=g[name + "/bias"])
-            announce(name)
+            ready(name)
         if self.backbone_from is not None:
             self._trunk_backward(p, dpre)
-        if fuse_reg and not self._reg_done:
-            # single-GPU train step: the regulariser's gradient, the trainable mask, the clip norm and losses[3] are the optimizer's
-            # passes (Adam.apply(reg=...)): flat_grad keeps the plain loss gradient and is not rewritten here
-            self._loss_scale = float(loss_rows.numel())
-            return losses
-        coef, mask = self._masks()
-        if self._reg_done:                                  # the ranges that did not go early (FPN / RPN, anything the decoder skipped)
-            n, pos = st.flat.numel(), 0
-            for lo, hi in sorted(self._reg_done) + [(n, n)]:
-                if lo > pos:
-                    ops.l2_reg(st.flat[pos:lo], coef[pos:lo], st.flat_grad[pos:lo], mask=None if mask is None else mask[pos:lo])
-                pos = max(pos, hi)
-            ops.l2_reg(st.flat, coef, None, loss=losses[3:4])      # the loss term alone (weights only)
-        else:
-            ops.l2_reg(st.flat, coef, st.flat_grad, loss=losses[3:4], mask=mask)          # one pass: trainable subset, regulariser gradient, loss term
-        self._loss_scale = float(loss_rows.numel())
-        return losses
+
+    def _regulariser_tail(self, losses, early, fuse_reg):
+        """L2(w)/size(w), gradient + trainable mask into flat_grad and loss into losses[3]: the gaps between the ranges that went early (data
+        parallel); nothing when the optimizer fuses it (fuse_reg: Adam.apply(reg=...), flat_grad keeps the plain loss gradient); else one pass."""
+        if early.done:
+            early.finish(losses[3:4])
+        elif not fuse_reg:
+            coef, mask = self._masks()
+            ops.l2_reg(self.store.flat, coef, self.store.flat_grad, loss=losses[3:4], mask=mask)       # one pass: trainable subset, regulariser gradient, loss term
 
     def _loss_list(self, losses):
         """losses: the step's raw loss terms [rpn_class, rpn_bbox, imgcap (unscaled), reg], a device tensor or its host copy."""
@@ -1189,20 +1195,13 @@ class DenseImageCapRCNN(object):
             self.optimizer.apply(self.store, grad_scale=scale)
             return losses
         # ---- single GPU: [one async upload] -> [encoder hipGraph] -> [step hipGraph: proposals .. losses .. gradients .. AMSGrad]
-        images, _meta, rpn_match, rpn_bbox, gt_caps, gt_boxes = inputs[:6]
-        p = self.plan()
-        dev = self.device
-        gt_norm = self._check_batch(p, images, gt_boxes)
-        rpn_up = self._step_uploads(p, rpn_match, rpn_bbox, gt_norm, gt_caps, True)
+        p, rpn_up, images, gt_caps, gt_norm = self._begin_step(inputs, True)
         path = self._path
         self._choose_step_path()
         if path.auto and path.use_graph:                     # (this step may be one of the timed ones)
             e0 = torch.cuda.Event(enable_timing=True)
             e0.record()
-        if trunk_done:
-            p.forward_top()
-        else:
-            p.forward(self._images_u8(images))
+        self._encoder_pass(p, images, trunk_done)
         opt = self.optimizer
 
         def body():

@@ -46,7 +46,8 @@ class CSVLogger(object):
 
 
 class KerasLikeModel(object):
-    """Sub-classes provide: self.store (ParamStore), self.device, self._bufs, self.grad_sync, _forward_train(), _backward(), train_step() and predict()."""
+    """Sub-classes provide: self.store (ParamStore), self.device, self._bufs, self.grad_sync, _forward_train(), _backward(), train_step() and predict().
+    _backward() announces finished layer ranges to self.grad_sync.ready (when the exchange has one); nothing per-step is stored on the model for it."""
 
     optimizer = None
     loss = None

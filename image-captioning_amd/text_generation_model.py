@@ -163,8 +163,6 @@ class CaptionModelV1(KerasLikeModel):
     FEAT = 1024
     D1 = 1024
     HEAD = (("mrcnn_class_conv1", "mrcnn_class_bn1"), ("mrcnn_class_conv2", "mrcnn_class_bn2"))
-    overlap_sync = True        # data parallel: all-reduce a layer group's gradients as soon as its backward is enqueued
-    before_sync = None         # optional hook(lo, hi): last touch of a gradient range before its all-reduce starts
     # Keras recurrent_dropout of imgcap_lstm1 / imgcap_lstm2 (:141-142; dense_img_cap/dense_model.py:769-770).  Default = the
     # reference's 0.2: every train step (train_on_batch / fit_generator / train()) draws four inverted-dropout masks [B, units]
     # per LSTM (one per gate i,f,c,o), fixed over the timesteps, from a seeded counter-based generator ON THE DEVICE
@@ -215,7 +213,6 @@ class CaptionModelV1(KerasLikeModel):
         self._bufs = {}
         self._steps = {}                          # captured train steps by batch shape (step_graph.CapturedStep)
         self._drop_seed, self._drop_step = (seed + 77) & 0xFFFFFFFF, 0
-        self._drop_offset_dev = None
         self._rec_masks = (None, None)           # device masks of the current train step (lstm1, lstm2) or None
 
     @property
@@ -230,30 +227,30 @@ class CaptionModelV1(KerasLikeModel):
             raise ValueError("dropout_rows must be 'roi' or 'prefix'")
         return bool(training) and self.dropout_rows == "prefix" and float(self.recurrent_dropout or 0.0) > 0.0
 
-    def _draw_rec_masks(self, B, training):
+    def _draw_rec_masks(self, B, training, drop_offset_dev=None):
         """Keras LSTMCell._generate_recurrent_dropout_mask for both LSTMs: K.dropout(ones, rate) x 4 in the training phase.
-        B = rows the LSTMs run over (RoIs, or RoIs x prefixes with dropout_rows='prefix': row j*B_roi + b = prefix j of RoI b)."""
+        B = rows the LSTMs run over (RoIs, or RoIs x prefixes with dropout_rows='prefix': row j*B_roi + b = prefix j of RoI b).
+        drop_offset_dev: the stream position as a device word (captured steps); None draws from the host counter."""
         rate = float(self.recurrent_dropout or 0.0)
         if not training or rate <= 0.0:
             self._rec_masks = (None, None)
             return
         self._drop_step += 1
-        if self._drop_offset_dev is not None:
+        if drop_offset_dev is not None:
             # the stream position comes from a device word (= 2 * _drop_step, written by the caller before the step): the launch is the
             # same every step, so a captured hipGraph draws fresh masks on every replay
             self._rec_masks = tuple(ops.dropout_mask(self._buf('rec_mask%d' % l, (4, B, self.units)), rate, self._drop_seed, l,
-                                                     offset_dev=self._drop_offset_dev) for l in range(2))
+                                                     offset_dev=drop_offset_dev) for l in range(2))
             return
         self._rec_masks = tuple(ops.dropout_mask(self._buf('rec_mask%d' % l, (4, B, self.units)), rate, self._drop_seed, 2 * self._drop_step + l)
                                 for l in range(2))
 
     def _grads_ready(self, *layers):
-        """Data parallel: these layers' gradients are final -- start their all-reduce while the backward goes on."""
-        if self.overlap_sync and self.grad_sync is not None and hasattr(self.grad_sync, 'ready'):
+        """Data parallel: these layers' gradients are final -- start their all-reduce while the backward goes on (what _backward
+        announces to when its caller hands it no `ready` of its own)."""
+        if self.grad_sync is not None and hasattr(self.grad_sync, 'ready'):
             for layer in layers:
                 lo, hi = self.store.layer_range(layer)
-                if self.before_sync is not None:        # the joint model adds its regulariser's gradient to the range first
-                    self.before_sync(lo, hi)
                 self.grad_sync.ready(self.store.flat_grad, lo, hi)
 
     # ---------------------------------------------------------------------------------- engine
@@ -378,12 +375,12 @@ class CaptionModelV1(KerasLikeModel):
         return up(ids.T.reshape(-1), torch.int32), up((ids != 0).T.reshape(-1), torch.uint8), B, T
 
     def _forward_train(self, feat, caps, targets=None, want_probs=False, want_grad=False, row_weights=None, keras_sparse=False,
-                       device_tables=None):
+                       device_tables=None, drop_offset_dev=None):
         """row_weights [B,T] + keras_sparse: the joint model's masked K.sparse_categorical_crossentropy
         (dense_img_cap/dense_model.py:936-946); loss rows and dlogits are then weighted per row instead of 1/N.
         device_tables = (ids_tm, mask, targets_tm, row_weights_tm, B, T): the index tables already on the device
         (ops.caption_tables from device-resident captions: the joint model's step never builds them on the host); caps / targets /
-        row_weights are then ignored."""
+        row_weights are then ignored.  drop_offset_dev: handed to _draw_rec_masks."""
         pr = self._prefix_rows(want_grad)
         if device_tables is not None:
             if pr:
@@ -392,7 +389,7 @@ class CaptionModelV1(KerasLikeModel):
         else:
             ids_tm, mask, B, T = self._tables(caps, prefix_rows=pr)
         Bl = T * B if pr else B
-        self._draw_rec_masks(Bl, training=want_grad)
+        self._draw_rec_masks(Bl, training=want_grad, drop_offset_dev=drop_offset_dev)
         X = feat.reshape(B, -1)
         f = self._head_forward(X)
         a1 = self._hidden(f, ids_tm, mask, B, T, Bl)
@@ -432,9 +429,12 @@ class CaptionModelV1(KerasLikeModel):
         self._ctx = (X, f, a1, dl, ids_tm, mask, B, T, Bl)
         return loss_rows, probs
 
-    def _backward(self, want_dx=False):
+    def _backward(self, want_dx=False, ready=None):
         """Gradients of every trainable weight into the flat bucket; with want_dx also returns the gradient w.r.t.
-        the flattened RoI features [B, pool*pool*C] (the joint model backpropagates it through RoIAlign)."""
+        the flattened RoI features [B, pool*pool*C] (the joint model backpropagates it through RoIAlign).
+        ready(*layers): called as soon as those layers' gradients are final; None = this model's own _grads_ready (its grad_sync's
+        early all-reduce).  The joint model hands in its step's (regulariser first, then the exchange) or a no-op."""
+        ready = self._grads_ready if ready is None else ready
         w, g, u = self.store.w, self.store.grad, self.units
         X, f, a1, dl, ids_tm, mask, B, T, Bl = self._ctx
         bf = self._bufs
@@ -447,14 +447,14 @@ class CaptionModelV1(KerasLikeModel):
         else:
             ops.gemm(a1.f, dl.f, a_trans=True, out=g['imgcap_lstm_d2/kernel'])
             da1 = ops.gemm(dl.f, w['imgcap_lstm_d2/kernel'], b_trans=True, out=self._buf('da1', (N, self.D1)))
-        self._grads_ready('imgcap_lstm_d2')
+        ready('imgcap_lstm_d2')
         dz_d1 = self._act('dz_d1', ops.relu_bwd(da1, a1.f, da1))
         gWd1 = g['imgcap_lstm_d1/kernel']
         self._mm(h2, dz_d1, a_trans=True, out=gWd1[:u])
         ops.colsum(dz_d1.f, out=g['imgcap_lstm_d1/bias'])
         dzd_f = self._act('dzd_f', ops.fold_time(dz_d1.f, T, B, self._buf('dzd_f', (B, self.D1))))
         self._mm(f, dzd_f, a_trans=True, out=gWd1[u:])
-        self._grads_ready('imgcap_lstm_d1')
+        ready('imgcap_lstm_d1')
         df = self._mm(dzd_f, self._wview('imgcap_lstm_d1/kernel', (u, u + self.FEAT)), key='df', b_trans=True).f
         dh2 = self._mm(dz_d1, self._wview('imgcap_lstm_d1/kernel', (0, u)), key='dh2', b_trans=True).f
         # lstm2
@@ -474,7 +474,7 @@ class CaptionModelV1(KerasLikeModel):
             dU_bf16(self._h2, dz2, 'imgcap_lstm2/recurrent_kernel')
         self._mm(h1, dz2, a_trans=True, out=g['imgcap_lstm2/kernel'])
         ops.colsum(dz2.f, out=g['imgcap_lstm2/bias'])
-        self._grads_ready('imgcap_lstm2')
+        ready('imgcap_lstm2')
         dh1 = self._mm(dz2, self._wview('imgcap_lstm2/kernel'), key='dh1', b_trans=True).f
         # lstm1
         dz1, _ = ops.lstm_seq_bwd(bf['z1'], w['imgcap_lstm1/recurrent_kernel'], mask, h1.f, bf['c1'], Bl, T, dh_seq=dh1,
@@ -492,7 +492,7 @@ class CaptionModelV1(KerasLikeModel):
         ops.colsum(dz1, out=g['imgcap_lstm1/bias'])
         dzf = self._act('dzf', ops.fold_time(dz1, NL // B, B, self._buf('dzf', (B, 4 * u))))      # rows (t*Bl + j*B + b) -> RoI b
         self._mm(f, dzf, a_trans=True, out=gW1[self.E:])
-        self._grads_ready('imgcap_lstm1')
+        ready('imgcap_lstm1')
         self._mm(dzf, self._wview('imgcap_lstm1/kernel', (self.E, self.E + self.FEAT)), out=df, b_trans=True, accumulate=True)
         # trainable head (kernels, biases, BN gamma/beta; statistics frozen)
         dy = df
@@ -504,7 +504,7 @@ class CaptionModelV1(KerasLikeModel):
             dacc = self._act('dacc%d' % li, dacc)
             gk = g[conv + '/kernel']
             self._mm(self._head_in[li], dacc, a_trans=True, out=gk.view(-1, gk.shape[-1]))
-            self._grads_ready(conv, bn)
+            ready(conv, bn)
             if li == 1:
                 dy = self._mm(dacc, self._wview(conv + '/kernel'), key='dhact0', b_trans=True).f
             elif want_dx:
@@ -540,11 +540,7 @@ class CaptionModelV1(KerasLikeModel):
         dropout = float(self.recurrent_dropout or 0.0) > 0.0
 
         def body():
-            self._drop_offset_dev = drop_dev if dropout else None
-            try:
-                loss_rows, _ = self._forward_train(cs.feat, None, want_grad=True, device_tables=tables)
-            finally:
-                self._drop_offset_dev = None              # a later eager step draws from the host counter again
+            loss_rows, _ = self._forward_train(cs.feat, None, want_grad=True, device_tables=tables, drop_offset_dev=drop_dev if dropout else None)
             loss = ops.mean(loss_rows, out=self._buf('loss', (1,)))
             self._backward()
             opt.apply(self.store, grad_scale=1.0, lr_t_dev=lr_dev)

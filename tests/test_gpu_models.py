@@ -10,6 +10,8 @@ import torch
 from oracle import np_models as M
 from oracle import np_oracle as O
 
+from _joint_cases import joint_inputs, make_joint  # noqa: F401  (tests/_dp_joint_worker.py reads them from here)
+
 pytestmark = pytest.mark.gpu
 MEAN = [123.7, 116.8, 103.9]
 
@@ -452,51 +454,6 @@ def test_image_level_features_with_rpn_proposals(gpu, conv_math):
 # ---------------------------------------------------------------------------------------------
 # joint model (configs[4]): dense_img_cap/dense_model.py
 # ---------------------------------------------------------------------------------------------
-
-def make_joint(S=128, V=24, T=5, blocks=1, rois=12, compute_dtype="f32", conv_math=None):
-    from image_captioning_amd import synth
-    from image_captioning_amd.config import Config
-    from image_captioning_amd.dense_model import DenseImageCapRCNN
-
-    class Cfg(Config):
-        NAME = "joint"
-        IMAGES_PER_GPU = 1
-        IMAGE_MIN_DIM = S
-        IMAGE_MAX_DIM = S
-        POST_NMS_ROIS_TRAINING = 60
-        TRAIN_ROIS_PER_IMAGE = rois
-        PADDING_SIZE = T
-        VOCABULARY_SIZE = V
-        EMBEDDING_SIZE = 300
-        RECURRENT_DROPOUT = 0.0          # parity against the deterministic oracle graph (the training default is the reference's 0.2)
-    cfg = Cfg()
-    Wt = dict(synth.encoder_weights(0, blocks), **synth.rpn_weights(4))
-    Wt['rpn_conv_shared/kernel'] = Wt['rpn_conv_shared/kernel'] * np.float32(0.05)
-    Wt['rpn_bbox_pred/kernel'] = Wt['rpn_bbox_pred/kernel'] * np.float32(0.3)
-    Wt.update(synth.head_weights(1))
-    Wt['mrcnn_class_conv1/kernel'] = Wt['mrcnn_class_conv1/kernel'] * np.float32(0.05)   # random FPN maps are O(10): keep the
-    Wt.update(synth.v1_weights(2, V))                                                    # vocabulary softmax out of saturation
-    Wt['imgcap_embedding_layer/embeddings'] = synth.embedding_matrix(3, V)
-    cfg.EMBEDDING_WEIGHTS = Wt['imgcap_embedding_layer/embeddings']
-    model = DenseImageCapRCNN("training", cfg, "logs", stage4_blocks=blocks, compute_dtype=compute_dtype, conv_math=conv_math)
-    model.set_weights(Wt)
-    return model, cfg, Wt
-
-
-def joint_inputs(S, V, T, seed=8):
-    from image_captioning_amd import synth
-    rng = np.random.default_rng(seed)
-    img = synth.images(7, 1, S, S)
-    gt_boxes = np.zeros((1, 6, 4), np.float32)
-    gt_boxes[0, :3] = np.array([[10, 12, 70, 90], [40, 30, 120, 128], [0, 0, 50, 40]], np.float32) * (S / 128.0)
-    gt_caps = np.zeros((1, 6, T), np.int32)
-    gt_caps[0, :3] = synth.captions_v1(9, 3, T, V, lmin=1, lmax=3)
-    n_anchor = sum((S // s) ** 2 for s in (4, 8, 16, 32, 64)) * 3
-    match = np.zeros((1, n_anchor, 1), np.int32)
-    match[0, rng.choice(n_anchor, 40, replace=False), 0] = np.where(rng.random(40) < 0.4, 1, -1)
-    tdelta = rng.standard_normal((1, 64, 4))
-    return [img, np.zeros((1, 12)), match, tdelta, gt_caps, gt_boxes]
-
 
 def joint_oracle(Wt, cfg, inputs, targets, blocks, backbone_from=None):
     img, _, match, tdelta, gt_caps, gt_boxes = inputs
