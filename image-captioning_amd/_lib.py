@@ -169,6 +169,17 @@ class ProposalDesc(C.Structure):
                 ("proposals", C.c_void_p), ("scores_out", C.c_void_p), ("order_out", C.c_void_p), ("keep_out", C.c_void_p)]
 
 
+REFINE_CONSTS = 10        # DC_REFINE_CONSTS: float64 words per image of RefineDesc.image_consts
+REFINE_MAX_ROIS = 8192    # DC_REFINE_MAX_ROIS
+
+
+class RefineDesc(C.Structure):
+    _fields_ = [("B", C.c_int), ("N", C.c_int), ("T", C.c_int),
+                ("rois", C.c_void_p), ("word_scores", C.c_void_p), ("caption_scores", C.c_void_p), ("caption_stride", C.c_int),
+                ("image_consts", C.c_void_p), ("threshold", C.c_double), ("max_instances", C.c_int),
+                ("boxes_out", C.c_void_p), ("keep_out", C.c_void_p), ("count_out", C.c_void_p), ("scores_out", C.c_void_p)]
+
+
 class RpnLossDesc(C.Structure):
     _fields_ = [("levels", C.c_int), ("anchors_per_loc", C.c_int), ("head_stride", C.c_int),
                 ("heads", C.c_void_p * 5), ("dheads", C.c_void_p * 5), ("Hs", C.c_int * 5), ("Ws", C.c_int * 5),
@@ -257,6 +268,8 @@ SYMBOLS = {
     "dc_subsample2_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "dc_proposals_workspace_bytes": (C.c_size_t, [C.POINTER(ProposalDesc)]),
     "dc_proposals_f32": (C.c_int, [C.POINTER(ProposalDesc), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "dc_refine_generations_workspace_bytes": (C.c_size_t, [C.POINTER(RefineDesc)]),
+    "dc_refine_generations_f64": (C.c_int, [C.POINTER(RefineDesc), C.c_void_p, C.c_size_t, C.c_void_p]),
     "dc_lstm_seq_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "dc_lstm_seq_fwd_f32": (C.c_int, [C.POINTER(LstmFwdDesc), C.c_void_p, C.c_size_t, C.c_void_p]),
     "dc_lstm_seq_bwd_f32": (C.c_int, [C.POINTER(LstmBwdDesc), C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -82,23 +82,33 @@ __device__ __forceinline__ bool iou_exceeds(const float4 a, const float4 b, floa
     return div_rn(inter, sub_rn(add_rn(area_a, area_b), inter)) > thr;
 }
 
+// The overlap test of tf.image.non_max_suppression on float32 boxes (the ProposalLayer's), and the box type it reads.
+struct IouTF {
+    typedef float4 box;
+    typedef float thr;
+    static __device__ __forceinline__ box zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
+    static __device__ __forceinline__ bool exceeds(const box a, const box b, thr t) { return iou_exceeds(a, b, t); }
+};
+
 // mask[b][i][w] bit j: candidate 64*w + j (ranked after i) overlaps candidate i by more than the threshold
-__global__ __launch_bounds__(64) void nms_mask_kernel(const float4* __restrict__ boxes, unsigned long long* __restrict__ mask, int k, int words,
-                                                      float thr) {
-    __shared__ float4 cb[64];
+template <class P>
+__global__ __launch_bounds__(64) void nms_mask_kernel(const typename P::box* __restrict__ boxes, unsigned long long* __restrict__ mask, int k,
+                                                      int words, typename P::thr thr) {
+    typedef typename P::box box;
+    __shared__ box cb[64];
     const int b = blockIdx.z, rowb = blockIdx.y, colb = blockIdx.x;
     if (colb < rowb) return;
-    const float4* bx = boxes + (long)b * k;
+    const box* bx = boxes + (long)b * k;
     const int cj = colb * 64 + threadIdx.x;
-    cb[threadIdx.x] = cj < k ? bx[cj] : make_float4(0.f, 0.f, 0.f, 0.f);
+    cb[threadIdx.x] = cj < k ? bx[cj] : P::zero();
     __syncthreads();
     const int i = rowb * 64 + threadIdx.x;
     if (i >= k) return;
-    const float4 me = bx[i];
+    const box me = bx[i];
     unsigned long long bits = 0;
     const int ncol = min(64, k - colb * 64);
     for (int j = (rowb == colb) ? threadIdx.x + 1 : 0; j < ncol; ++j)
-        if (iou_exceeds(me, cb[j], thr)) bits |= 1ull << j;
+        if (P::exceeds(me, cb[j], thr)) bits |= 1ull << j;
     mask[((long)b * k + i) * words + colb] = bits;
 }
 
@@ -169,9 +179,10 @@ __device__ __forceinline__ unsigned long long wave_or64(unsigned long long v) {
 //     group by wave i % 4, NMS_ROWS rows in flight per wave); every wave keeps its own partial removed-set in registers for the whole
 //     scan, and only the G words the next group starts from are combined through LDS.
 // 12 round trips instead of 94, four waves' worth of loads in flight.  Same greedy order, same result bit for bit.
-__global__ __launch_bounds__(NMS_WAVES * 64) void nms_scan_wave_kernel(const float4* __restrict__ boxes, const unsigned long long* __restrict__ mask,
-                                                                    int k, int words, int count, float4* __restrict__ proposals,
-                                                                    int* __restrict__ keep_out) {
+template <class P>
+__global__ __launch_bounds__(NMS_WAVES * 64) void nms_scan_wave_kernel(const typename P::box* __restrict__ boxes,
+                                                                    const unsigned long long* __restrict__ mask, int k, int words, int count,
+                                                                    typename P::box* __restrict__ proposals, int* __restrict__ keep_out) {
     constexpr int G = NMS_G;
     __shared__ unsigned long long s_keep[G];
     __shared__ unsigned long long s_rem[NMS_WAVES][G];
@@ -288,7 +299,7 @@ __global__ __launch_bounds__(NMS_WAVES * 64) void nms_scan_wave_kernel(const flo
     if (wave == 0) {
         kept = __builtin_amdgcn_readfirstlane(kept);
         for (int r = kept + lane; r < count; r += 64) {
-            proposals[(long)b * count + r] = make_float4(0.f, 0.f, 0.f, 0.f);
+            proposals[(long)b * count + r] = P::zero();
             if (keep_out) keep_out[(long)b * count + r] = -1;
         }
     }
@@ -707,9 +718,9 @@ extern "C" int dc_proposals_f32(const dc_proposal_desc* d, void* workspace, size
                      reinterpret_cast<unsigned long long*>(ws + L.tk_cand), vals, keys, s);
     if (rc) return rc;
     hipLaunchKernelGGL(decode_kernel, dim3((d->B * k + 255) / 256), dim3(256), 0, s, *d, vals, deltas, boxes, k);
-    hipLaunchKernelGGL(nms_mask_kernel, dim3(words, words, d->B), dim3(64), 0, s, boxes, mask, k, words, d->nms_threshold);
+    hipLaunchKernelGGL(nms_mask_kernel<IouTF>, dim3(words, words, d->B), dim3(64), 0, s, boxes, mask, k, words, d->nms_threshold);
     if (words <= 128)
-        hipLaunchKernelGGL(nms_scan_wave_kernel, dim3(d->B), dim3(NMS_WAVES * 64), 0, s, boxes, mask, k, words, d->proposal_count,
+        hipLaunchKernelGGL(nms_scan_wave_kernel<IouTF>, dim3(d->B), dim3(NMS_WAVES * 64), 0, s, boxes, mask, k, words, d->proposal_count,
                            reinterpret_cast<float4*>(d->proposals), d->keep_out);
     else
         hipLaunchKernelGGL(nms_scan_kernel, dim3(d->B), dim3(64), (size_t)words * 8, s, boxes, mask, k, words, d->proposal_count,
@@ -725,6 +736,195 @@ extern "C" int dc_proposals_f32(const dc_proposal_desc* d, void* workspace, size
         DC_REQUIRE(e == hipSuccess, DC_ELAUNCH, "dc_proposals: copy failed");
     }
     return DC_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// GenerationMatchLayer + unmold_generations on the device (dense_img_cap/dense_model.py:593-630, :1925-1962; the product's host
+// functions refine_generations / unmold_generations): the caption scores, their order, the boxes in pixels of the molded image clipped
+// to the window, the NumPy NMS and the boxes in the original image's pixels.  Every decision is taken in float64 by the host path's
+// operations in the host path's order (this file compiles without fma contraction), so the results are the host path's, bit for bit;
+// the only float32 values are inputs, widened exactly.  Five launches: scores and sort keys, a rank sort that scatters the clipped
+// boxes, the suppression mask and the wave scan of the ProposalLayer (instantiated for double boxes and NumPy's overlap test), and
+// one wave per image that rounds, unmolds and compacts the survivors.
+// ------------------------------------------------------------------------------------------------
+namespace dcap {
+
+__device__ __forceinline__ double dmul_rn(double a, double b) { return a * b; }
+__device__ __forceinline__ double dadd_rn(double a, double b) { return a + b; }
+__device__ __forceinline__ double dsub_rn(double a, double b) { return a - b; }
+__device__ __forceinline__ double ddiv_rn(double a, double b) { return a / b; }
+
+// utils.non_max_suppression's overlap test on float64 boxes as they are: no corner canonicalisation, no early exit on an empty box;
+// the 0/0 of two empty boxes is a NaN, which exceeds nothing (the zero-padded proposals all survive, as on the host)
+struct IouNP {
+    typedef double4 box;
+    typedef double thr;
+    static __device__ __forceinline__ box zero() { return make_double4(0., 0., 0., 0.); }
+    static __device__ __forceinline__ bool exceeds(const box a, const box b, thr t) {
+        const double area_a = dmul_rn(dsub_rn(a.z, a.x), dsub_rn(a.w, a.y)), area_b = dmul_rn(dsub_rn(b.z, b.x), dsub_rn(b.w, b.y));
+        const double ih = fmax(dsub_rn(fmin(a.z, b.z), fmax(a.x, b.x)), 0.);
+        const double iw = fmax(dsub_rn(fmin(a.w, b.w), fmax(a.y, b.y)), 0.);
+        const double inter = dmul_rn(ih, iw);
+        return ddiv_rn(inter, dsub_rn(dadd_rn(area_a, area_b), inter)) > t;
+    }
+};
+
+// larger key = earlier in np.argsort(scores, kind="stable")[::-1] among different scores: NaN above everything (NumPy sorts it last,
+// the reversal brings it first), -0 and +0 alike (NumPy compares them equal), -inf an ordinary value
+__device__ __forceinline__ unsigned long long refine_key(double s) {
+    if (s != s) return ~0ull;
+    if (s == 0.) s = 0.;
+    const unsigned long long b = (unsigned long long)__double_as_longlong(s);
+    return b ^ ((b >> 63) ? ~0ull : 0x8000000000000000ull);
+}
+
+// caption score of RoI n of image b -> scores_out (RoI order) and its sort key
+__global__ __launch_bounds__(256) void refine_score_kernel(dc_refine_desc d, unsigned long long* __restrict__ keys) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long)d.B * d.N) return;
+    double s;
+    if (d.word_scores) {
+        const float* p = d.word_scores + idx * d.T;
+        s = 0.;
+        for (int t = 0; t < d.T; ++t) s = dadd_rn(s, log((double)p[t]));
+    } else {
+        s = (double)d.caption_scores[idx * d.caption_stride];
+    }
+    d.scores_out[idx] = s;
+    keys[idx] = refine_key(s);
+}
+
+__device__ __forceinline__ double clip_np(double x, double lo, double hi) {       // np.clip: minimum(maximum(x, lo), hi), a NaN stays
+    x = x < lo ? lo : x;
+    return x > hi ? hi : x;
+}
+
+// rank of RoI i = the RoIs that precede it: a larger key, or the same key and a HIGHER index (the reversal of a stable ascending
+// sort).  Writes the RoI's index and its clipped pixel box at its rank.  256 RoIs per workgroup, the image's keys through LDS.
+__global__ __launch_bounds__(256) void refine_rank_kernel(dc_refine_desc d, const unsigned long long* __restrict__ keys, int* __restrict__ order,
+                                                          double4* __restrict__ boxes) {
+    __shared__ unsigned long long sk[256];
+    const int b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x, N = d.N;
+    const unsigned long long* kb = keys + (long)b * N;
+    const unsigned long long mine = i < N ? kb[i] : 0ull;
+    int rank = 0;
+    for (int j0 = 0; j0 < N; j0 += 256) {
+        const int n = min(256, N - j0);
+        __syncthreads();
+        if ((int)threadIdx.x < n) sk[threadIdx.x] = kb[j0 + threadIdx.x];
+        __syncthreads();
+        for (int j = 0; j < n; ++j) {
+            const unsigned long long o = sk[j];
+            rank += (o > mine) || (o == mine && j0 + j > i);
+        }
+    }
+    if (i >= N) return;
+    const double* c = d.image_consts + (long)b * DC_REFINE_CONSTS;
+    const float* r = d.rois + ((long)b * N + i) * 4;
+    const double h = c[4], w = c[5];
+    const double y1 = clip_np(dmul_rn((double)r[0], h), c[0], c[2]), x1 = clip_np(dmul_rn((double)r[1], w), c[1], c[3]);
+    const double y2 = clip_np(dmul_rn((double)r[2], h), c[0], c[2]), x2 = clip_np(dmul_rn((double)r[3], w), c[1], c[3]);
+    order[(long)b * N + rank] = i;
+    boxes[(long)b * N + rank] = make_double4(y1, x1, y2, x2);
+}
+
+// One wave per image over the scan's survivors (slot order = score order): np.rint, (box - shift) * scale truncated to int32, the
+// non-empty boxes kept in order (ballot + popcount), the tail filled with -1 / zeros.
+__global__ __launch_bounds__(64) void refine_finish_kernel(dc_refine_desc d, const double4* __restrict__ kept_boxes, const int* __restrict__ kept_rank,
+                                                           const int* __restrict__ order) {
+    const int b = blockIdx.x, lane = threadIdx.x, M = d.max_instances;
+    const double* c = d.image_consts + (long)b * DC_REFINE_CONSTS;
+    const double sy = c[6], sx = c[7], scale = c[8];
+    int total = 0;
+    for (int s0 = 0; s0 < M; s0 += 64) {
+        const int s = s0 + lane;
+        const int r = s < M ? kept_rank[(long)b * M + s] : -1;
+        int y1 = 0, x1 = 0, y2 = 0, x2 = 0;
+        bool ok = false;
+        if (r >= 0) {
+            const double4 q = kept_boxes[(long)b * M + s];
+            y1 = (int)dmul_rn(dsub_rn(rint(q.x), sy), scale);
+            x1 = (int)dmul_rn(dsub_rn(rint(q.y), sx), scale);
+            y2 = (int)dmul_rn(dsub_rn(rint(q.z), sy), scale);
+            x2 = (int)dmul_rn(dsub_rn(rint(q.w), sx), scale);
+            ok = (int)((unsigned)(y2 - y1) * (unsigned)(x2 - x1)) > 0;
+        }
+        const unsigned long long live = __ballot(ok);
+        if (ok) {
+            const int pos = total + __builtin_popcountll(live & ((1ull << lane) - 1ull));
+            d.keep_out[(long)b * M + pos] = order[(long)b * d.N + r];
+            reinterpret_cast<int4*>(d.boxes_out)[(long)b * M + pos] = make_int4(y1, x1, y2, x2);
+        }
+        total += __builtin_popcountll(live);
+    }
+    for (int s = total + lane; s < M; s += 64) {
+        d.keep_out[(long)b * M + s] = -1;
+        reinterpret_cast<int4*>(d.boxes_out)[(long)b * M + s] = make_int4(0, 0, 0, 0);
+    }
+    if (lane == 0) d.count_out[b] = total;
+}
+
+struct RefineWs {
+    size_t keys, order, boxes, mask, kept_boxes, kept_rank, total;
+};
+
+static RefineWs refine_layout(const dc_refine_desc* d) {
+    RefineWs w{};
+    const size_t n = (size_t)d->B * d->N, words = (size_t)(d->N + 63) / 64, m = (size_t)d->B * d->max_instances;
+    size_t o = 0;
+    w.keys = o;       o += up256(n * 8);
+    w.order = o;      o += up256(n * 4);
+    w.boxes = o;      o += up256(n * 32);
+    w.mask = o;       o += up256(n * words * 8);
+    w.kept_boxes = o; o += up256(m * 32);
+    w.kept_rank = o;  o += up256(m * 4);
+    w.total = o;
+    return w;
+}
+
+static int refine_validate(const dc_refine_desc* d) {
+    DC_REQUIRE(d && d->rois && d->image_consts && d->boxes_out && d->keep_out && d->count_out && d->scores_out, DC_EINVAL,
+               "dc_refine_generations: null pointer");
+    DC_REQUIRE(d->B > 0 && d->N > 0 && d->max_instances > 0, DC_EINVAL, "dc_refine_generations: bad sizes");
+    DC_REQUIRE(d->N <= DC_REFINE_MAX_ROIS, DC_EINVAL, "dc_refine_generations: N = %d exceeds the NMS scan's limit of %d", d->N, DC_REFINE_MAX_ROIS);
+    DC_REQUIRE((d->word_scores != nullptr) != (d->caption_scores != nullptr), DC_EINVAL,
+               "dc_refine_generations: exactly one of word_scores and caption_scores");
+    DC_REQUIRE(d->word_scores ? d->T > 0 : d->caption_stride > 0, DC_EINVAL, "dc_refine_generations: T / caption_stride must be positive");
+    DC_REQUIRE(aligned16(d->boxes_out) && (reinterpret_cast<uintptr_t>(d->scores_out) & 7u) == 0 &&
+                   (reinterpret_cast<uintptr_t>(d->image_consts) & 7u) == 0,
+               DC_EALIGN, "dc_refine_generations: boxes_out must be 16-byte, scores_out / image_consts 8-byte aligned");
+    return DC_OK;
+}
+
+}  // namespace dcap
+
+extern "C" size_t dc_refine_generations_workspace_bytes(const dc_refine_desc* d) {
+    if (refine_validate(d)) return 0;
+    return refine_layout(d).total;
+}
+
+extern "C" int dc_refine_generations_f64(const dc_refine_desc* d, void* workspace, size_t workspace_bytes, void* stream) {
+    int rc = refine_validate(d);
+    if (rc) return rc;
+    const RefineWs L = refine_layout(d);
+    DC_REQUIRE(workspace && workspace_bytes >= L.total && (reinterpret_cast<uintptr_t>(workspace) & 31u) == 0, DC_EWORKSPACE,
+               "dc_refine_generations: needs %zu workspace bytes (32-byte aligned), got %zu", L.total, workspace_bytes);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    char* ws = static_cast<char*>(workspace);
+    unsigned long long* keys = reinterpret_cast<unsigned long long*>(ws + L.keys);
+    int* order = reinterpret_cast<int*>(ws + L.order);
+    double4* boxes = reinterpret_cast<double4*>(ws + L.boxes);
+    unsigned long long* mask = reinterpret_cast<unsigned long long*>(ws + L.mask);
+    double4* kept_boxes = reinterpret_cast<double4*>(ws + L.kept_boxes);
+    int* kept_rank = reinterpret_cast<int*>(ws + L.kept_rank);
+    const int N = d->N, words = (N + 63) / 64;          // words <= 128: the wave scan's limit (DC_REFINE_MAX_ROIS)
+    hipLaunchKernelGGL(refine_score_kernel, dim3((unsigned)(((long)d->B * N + 255) / 256)), dim3(256), 0, s, *d, keys);
+    hipLaunchKernelGGL(refine_rank_kernel, dim3((N + 255) / 256, d->B), dim3(256), 0, s, *d, keys, order, boxes);
+    hipLaunchKernelGGL(nms_mask_kernel<IouNP>, dim3(words, words, d->B), dim3(64), 0, s, boxes, mask, N, words, d->threshold);
+    hipLaunchKernelGGL(nms_scan_wave_kernel<IouNP>, dim3(d->B), dim3(NMS_WAVES * 64), 0, s, boxes, mask, N, words, d->max_instances, kept_boxes,
+                       kept_rank);
+    hipLaunchKernelGGL(refine_finish_kernel, dim3(d->B), dim3(64), 0, s, *d, kept_boxes, kept_rank, order);
+    return check_launch("refine_generations kernels");
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -25,7 +25,7 @@ import re
 import numpy as np
 import torch
 
-from . import ops, step_graph, synth, utils
+from . import decoding, ops, step_graph, synth, utils
 from .encoder import EncoderPlan, fuse_rpn_head
 from .layers import resnet_fpn_convs
 from .modified_dense_model import load_weight_file, save_weight_file
@@ -181,6 +181,14 @@ def unmold_generations(boxes, image_shape, window):
     shift = np.array([window[0], window[1], window[0], window[1]])
     out = ((np.asarray(boxes) - shift) * scale).astype(np.int32)
     return out, (out[:, 2] - out[:, 0]) * (out[:, 3] - out[:, 1]) > 0
+
+
+def refine_constants(window, config, image_shape):
+    """One image's row of ops.refine_generations' image_consts (float64 [_lib.REFINE_CONSTS]): the window, IMAGE_SHAPE's h and w,
+    and unmold_generations' shift (y, x) and scale, computed as that function computes them."""
+    h, w = config.IMAGE_SHAPE[:2]
+    scale = min(image_shape[0] / (window[2] - window[0]), image_shape[1] / (window[3] - window[1]))
+    return np.array([window[0], window[1], window[2], window[3], h, w, window[0], window[1], scale, 0.0], np.float64)
 
 
 def load_image_gt(dataset, config, image_id, augment=False, rng=np.random):
@@ -1268,7 +1276,7 @@ class DenseImageCapRCNN(object):
         return np.stack(molded), np.stack(metas), np.stack(windows)
 
     def generate_captions(self, images, verbose=0, return_probabilities=True, decoder="prefix", vocab_math=None, beam_size=None, score="logprob",
-                          end_id=None):
+                          end_id=None, postprocess="host"):
         """The inference graph (:1602-1622) + generate_captions (:1964-2003): RPN proposals (POST_NMS_ROIS_INFERENCE) ->
         RoI features -> greedy ROICaptionInferenceLayer -> GenerationMatchLayer -> boxes in the original image.
         Returns [{'rois': int32 [K,4], 'captions': f32 [K,T,V] word probabilities, 'ids': int32 [K,T]}]; with
@@ -1281,13 +1289,21 @@ class DenseImageCapRCNN(object):
         decoder='beam' (needs return_probabilities=False and beam_size=k; score='logprob' or 'prob', end_id=None or the end word's id,
         vocab_math as above): CaptionModelV1.decode_beam.  Each RoI's caption is its best beam and the caption score that orders the NMS
         is that beam's score (with end_id: the sum up to and including the end word).  Each result holds 'rois', 'ids' [K,T] (the best
-        beam), 'beam_ids' [K,k,T] and 'beam_scores' [K,k] (best first)."""
+        beam), 'beam_ids' [K,k,T] and 'beam_scores' [K,k] (best first).
+        postprocess='host' (default): GenerationMatchLayer and unmold_generations in NumPy, image by image, after each image's decoder
+        results have come to the host.  'device' (needs return_probabilities=False and decoder='incremental' or 'beam'): the images'
+        decode calls one after another without waiting, ONE ops.refine_generations for the batch on the decoder's device buffers, a
+        device gather of the survivors' captions and ONE device-to-host copy for the batch; nothing synchronises between the image upload and that copy.  The same
+        results, bit for bit (the float64 operations of the host path in its order; equal caption scores are ordered as
+        np.argsort(kind='stable')[::-1] orders them, where NumPy's default sort promises no order)."""
         CaptionModelV1.check_decoder(decoder, return_probabilities, vocab_math, getattr(self, "compute_dtype", None) if vocab_math == "bf16" else None,
-                                     beam_size=beam_size, score=score, end_id=end_id)
+                                     beam_size=beam_size, score=score, end_id=end_id, postprocess=postprocess)
         assert self.mode == "inference", "Create model in inference mode."
         assert len(images) == self.config.BATCH_SIZE, "len(images) must be equal to BATCH_SIZE"
         molded, metas, windows = self.mold_inputs(images)
         p = self.plan()
+        if postprocess == "device":
+            return self._generate_captions_device(p, images, molded, windows, decoder, vocab_math, beam_size, score, end_id)
         p.forward(torch.as_tensor(molded))
         proposals = p.proposals()
         self.last_proposals = proposals
@@ -1312,6 +1328,46 @@ class DenseImageCapRCNN(object):
                 out["captions"] = probs[keep]
             results.append(out)
         return results
+
+    def _generate_captions_device(self, p, images, molded, windows, decoder, vocab_math, beam_size, score, end_id):
+        """generate_captions(postprocess='device'): see there.  The packed int32 result buffer holds, for the batch, the survivor
+        counts [B], the boxes [B,M,4], the survivors' ids [B,M,T] (greedy) or beam tokens [B,M,k,T] and beam scores' bits [B,M,k]."""
+        cfg, cm, B = self.config, self.caption_model, len(images)
+        consts = np.stack([refine_constants(windows[b], cfg, images[b].shape) for b in range(B)])
+        consts = torch.as_tensor(consts).to(p.device)       # before the image upload: the stream is idle, nothing waits on this copy
+        p.forward(torch.as_tensor(molded))
+        proposals = p.proposals()
+        self.last_proposals = proposals
+        feats = p.roi_features(boxes_norm=proposals)
+        K, M = proposals.shape[1], int(cfg.DETECTION_MAX_INSTANCES)
+        # One decode call per image, each into its own output buffer, none of them waited for.  The per-image calls are the host
+        # path's, so the scores are its scores bit for bit: one call over the B * K rows chooses the same words, but its GEMMs run at
+        # another M and round the beam scores differently in the last bits.
+        if decoder == "beam":
+            outs = [cm._decode_beam(feats[b], beam_size, score, end_id, vocab_math) for b in range(B)]
+            k, T = outs[0][1], outs[0][2]
+            views = [decoding.beam_views(o[3], K, k, T) for o in outs]
+            toks, sc = (views[0] if B == 1 else tuple(torch.cat([v[i] for v in views]) for i in range(2)))
+            parts = [toks, sc]
+            boxes, keep, count, _ = ops.refine_generations(proposals, consts, cfg.DETECTION_NMS_THRESHOLD, M, caption_scores=sc[:, 0])
+        else:
+            views = [decoding.greedy_views(cm._decode_greedy(feats[b], vocab_math)) for b in range(B)]
+            ids, word_scores = (views[0] if B == 1 else tuple(torch.cat([v[i] for v in views]) for i in range(2)))
+            T, parts = ids.shape[1], [ids]
+            boxes, keep, count, _ = ops.refine_generations(proposals, consts, cfg.DETECTION_NMS_THRESHOLD, M, word_scores=word_scores)
+        rows = (keep.clamp(min=0).long() + torch.arange(B, device=keep.device).unsqueeze(1) * K).reshape(-1)
+        packed = torch.cat([count, boxes.reshape(-1)] + [t.index_select(0, rows).view(torch.int32).reshape(-1) for t in parts])
+        host = packed.cpu().numpy()                          # the one device-to-host copy
+        n, cut = host[:B], B
+        rois = host[cut:cut + B * M * 4].reshape(B, M, 4)
+        cut += B * M * 4
+        if decoder == "beam":
+            beam_ids = host[cut:cut + B * M * k * T].reshape(B, M, k, T)
+            beam_scores = host[cut + B * M * k * T:].view(np.float32).reshape(B, M, k)
+            return [{"rois": rois[b, :n[b]].copy(), "ids": beam_ids[b, :n[b], 0].copy(), "beam_ids": beam_ids[b, :n[b]].copy(),
+                     "beam_scores": beam_scores[b, :n[b]].copy()} for b in range(B)]
+        ids = host[cut:].reshape(B, M, T)
+        return [{"rois": rois[b, :n[b]].copy(), "ids": ids[b, :n[b]].copy()} for b in range(B)]
 
     # ---- training loop ----------------------------------------------------------------------
     def train(self, train_dataset, val_dataset, learning_rate, epochs, layers):

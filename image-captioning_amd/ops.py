@@ -12,7 +12,7 @@ import torch
 
 from . import _lib
 from ._lib import (PwChainDesc, ConvBf16Desc, AmsgradDesc, DetectionTargetsDesc, BnReluDesc, ConvDesc, ConvWgradBf16Desc, GemmBf16Desc, VocabCeDesc, ProposalDesc, RpnLossDesc, GemmDesc, LstmBwdDesc, LstmFwdDesc, RoiAlignDesc, RoiGroupsDesc,
-                   SoftmaxCeDesc, VocabTop1Desc, VocabTopkDesc, VocabTop1Bf16Desc, VocabTopkBf16Desc, BeamSelectDesc, BeamStepDesc, LstmStepDesc, check)
+                   SoftmaxCeDesc, VocabTop1Desc, VocabTopkDesc, VocabTop1Bf16Desc, VocabTopkBf16Desc, BeamSelectDesc, BeamStepDesc, LstmStepDesc, RefineDesc, check)
 
 
 def _stream():
@@ -738,6 +738,54 @@ def rpn_proposals(heads, anchors, image_hw, proposal_count, nms_threshold, std_d
     ws, wsb = WORKSPACE.get(lib.dc_proposals_workspace_bytes(C.byref(d)), dev)
     check(lib.dc_proposals_f32(C.byref(d), _ptr(ws), wsb, _stream()), "dc_proposals_f32")
     return (out, extra) if debug else out
+
+
+def refine_generations(rois, image_consts, threshold, max_instances, word_scores=None, caption_scores=None):
+    """GenerationMatchLayer + unmold_generations for B images x N RoIs on the device (dc_refine_generations_f64), in float64 by the host
+    path's operations: rois float32 [B,N,4] normalised; exactly one of word_scores float32 [B*N,T] (caption score = sum of log p in index
+    order) and caption_scores float32 [B*N] with any element stride (column 0 of the beam decoder's [B*N,k] scores); image_consts
+    float64 [B,_lib.REFINE_CONSTS] (per image: window y1 x1 y2 x2, IMAGE_SHAPE h w, unmold_generations' shift y x and scale, one unused
+    word).  Returns device tensors (boxes int32 [B,max_instances,4] in the original image's pixels, keep int32 [B,max_instances]: each
+    survivor's RoI index in score order, -1 after the last, count int32 [B], scores float64 [B,N]).  N <= _lib.REFINE_MAX_ROIS.  No host
+    synchronisation; B = 0 or N = 0 returns the empty result without a launch."""
+    lib = _lib.load()
+    if not _chk(rois, name="rois").is_contiguous() or rois.dim() != 3 or rois.shape[2] != 4:
+        raise _lib.DcapError("refine_generations: rois must be a contiguous float32 [B,N,4] tensor")
+    B, N = rois.shape[0], rois.shape[1]
+    if (word_scores is None) == (caption_scores is None):
+        raise _lib.DcapError("refine_generations: exactly one of word_scores and caption_scores")
+    if isinstance(max_instances, bool) or int(max_instances) != max_instances or max_instances < 1:
+        raise _lib.DcapError("refine_generations: max_instances must be a positive integer, got %r" % (max_instances,))
+    if N > _lib.REFINE_MAX_ROIS:
+        raise _lib.DcapError("refine_generations: N = %d exceeds the NMS scan's limit of %d RoIs per image" % (N, _lib.REFINE_MAX_ROIS))
+    d = RefineDesc()
+    if word_scores is not None:
+        if not _chk(word_scores, name="word_scores").is_contiguous() or word_scores.dim() != 2 or word_scores.shape[0] != B * N or (
+                word_scores.shape[1] < 1 and B * N > 0):
+            raise _lib.DcapError("refine_generations: word_scores must be a contiguous float32 [B*N,T] tensor, T >= 1")
+        d.T, d.word_scores = word_scores.shape[1], word_scores.data_ptr()
+    else:
+        c = caption_scores
+        if not c.is_cuda:
+            raise _lib.DcapError("caption_scores must live on the GPU (no CPU path exists)")
+        if c.dtype != torch.float32 or c.dim() != 1 or c.shape[0] != B * N or (B * N > 1 and c.stride(0) < 1):
+            raise _lib.DcapError("refine_generations: caption_scores must be a float32 [B*N] tensor (any positive element stride)")
+        d.caption_stride, d.caption_scores = (c.stride(0) if B * N > 1 else 1), c.data_ptr()
+    if not _chk(image_consts, torch.float64, "image_consts").is_contiguous() or tuple(image_consts.shape) != (B, _lib.REFINE_CONSTS):
+        raise _lib.DcapError("refine_generations: image_consts must be a contiguous float64 [B,%d] tensor" % _lib.REFINE_CONSTS)
+    M, dev = int(max_instances), rois.device
+    scores = torch.empty((B, N), dtype=torch.float64, device=dev)
+    if B == 0 or N == 0:
+        return (torch.zeros((B, M, 4), dtype=torch.int32, device=dev), torch.full((B, M), -1, dtype=torch.int32, device=dev),
+                torch.zeros((B,), dtype=torch.int32, device=dev), scores)
+    boxes = torch.empty((B, M, 4), dtype=torch.int32, device=dev)
+    keep = torch.empty((B, M), dtype=torch.int32, device=dev)
+    count = torch.empty((B,), dtype=torch.int32, device=dev)
+    d.B, d.N, d.rois, d.image_consts, d.threshold, d.max_instances = B, N, rois.data_ptr(), image_consts.data_ptr(), float(threshold), M
+    d.boxes_out, d.keep_out, d.count_out, d.scores_out = boxes.data_ptr(), keep.data_ptr(), count.data_ptr(), scores.data_ptr()
+    ws, wsb = WORKSPACE.get(lib.dc_refine_generations_workspace_bytes(C.byref(d)), dev)
+    check(lib.dc_refine_generations_f64(C.byref(d), _ptr(ws), wsb, _stream()), "dc_refine_generations_f64")
+    return boxes, keep, count, scores
 
 
 def _rec_masks(rec_masks, B, U):

@@ -597,16 +597,20 @@ class CaptionModelV1(KerasLikeModel):
 
     DECODERS = decoding.DECODERS
     VOCAB_MATH = (None, "f32", "bf16")
+    POSTPROCESS = ("host", "device")
 
     @classmethod
-    def check_decoder(cls, decoder, return_probabilities, vocab_math=None, compute_dtype=None, beam_size=None, score="logprob", end_id=None):
+    def check_decoder(cls, decoder, return_probabilities, vocab_math=None, compute_dtype=None, beam_size=None, score="logprob", end_id=None,
+                      postprocess="host"):
         """decoder='incremental' and 'beam' never form the per-step [B,V] probability rows: they need return_probabilities=False.
         decoder='beam' needs beam_size in 1..ops.TOPK_MAX (an integer, not a bool); score is 'logprob' (the sum of log p, the caption score
         of GenerationMatchLayer; the default) or 'prob' (the sum of p); end_id is None (fixed length T) or the end word's id >= 1.
         beam_size and end_id belong to 'beam' alone.
         vocab_math: None / 'f32' (the vocabulary layer scores words from the fp32 activations and the fp32 master weight) or 'bf16' (from
         their bf16 copies on the bf16 matrix pipe, the arithmetic a bf16 model trains that layer in): 'bf16' needs decoder='incremental'
-        or 'beam' and a model that computes in bf16 (compute_dtype: the model's; only a bf16 model keeps the weight's bf16 mirror)."""
+        or 'beam' and a model that computes in bf16 (compute_dtype: the model's; only a bf16 model keeps the weight's bf16 mirror).
+        postprocess (the joint model's generate_captions): 'host' or 'device'; 'device' works on the device decoders' buffers, so it needs
+        decoder='incremental' or 'beam' and return_probabilities=False."""
         decoding.check_decoder(decoder, beam_size, score, dict(end_id=end_id), score_for_beam_only=True, own=None if decoder == "prefix" or
                                return_probabilities is False else "decoder=%r returns no word probabilities: pass return_probabilities=False" % (decoder,))
         if decoder == "beam" and end_id is not None and (isinstance(end_id, bool) or int(end_id) != end_id or end_id < 1):
@@ -620,6 +624,11 @@ class CaptionModelV1(KerasLikeModel):
             if compute_dtype != "bf16":
                 raise ValueError("vocab_math='bf16' needs a model built with compute_dtype='bf16' (its vocabulary weight's bf16 mirror), "
                                  "this one computes in %r" % (compute_dtype,))
+        if postprocess not in cls.POSTPROCESS:
+            raise ValueError("postprocess must be one of %s, got %r" % (cls.POSTPROCESS, postprocess))
+        if postprocess == "device" and (decoder == "prefix" or return_probabilities is not False):
+            raise ValueError("postprocess='device' reads the device decoders' buffers: pass decoder='incremental' or 'beam' and "
+                             "return_probabilities=False (got decoder=%r, return_probabilities=%r)" % (decoder, return_probabilities))
 
     def decode_greedy(self, feat, vocab_math=None):
         """Greedy decoding of ROICaptionInferenceLayer (:192-232) ONE token per step, entirely on the device: the RoI head and the per-RoI

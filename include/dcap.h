@@ -398,6 +398,48 @@ typedef struct {
 size_t dc_proposals_workspace_bytes(const dc_proposal_desc* d);
 int    dc_proposals_f32(const dc_proposal_desc* d, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * GenerationMatchLayer + unmold_generations (dense_img_cap/dense_model.py:593-630, :1925-1962) for B images with N RoIs each, in
+ * float64 by the operations of the NumPy host path, in its order: the results are that path's bit for bit.
+ *   rois [B][N][4] float32, normalised (y1,x1,y2,x2).  Scores, exactly one of: word_scores [B*N][T] float32 (the greedy decoder's
+ *   word probabilities; caption score = sum over t = 0..T-1, in index order, of log((double) p)) or caption_scores float32, RoI i of
+ *   image b at element (b*N + i) * caption_stride (column 0 of the beam decoder's [B*N][k] scores: caption_stride = k).
+ *   image_consts [B][DC_REFINE_CONSTS] float64 in DEVICE memory, per image: the window y1, x1, y2, x2; IMAGE_SHAPE h, w;
+ *   unmold_generations' shift y, x and scale (computed by the host as that function computes it); one unused word.
+ *   Order: np.argsort(scores, kind="stable")[::-1] -- score descending, the HIGHER RoI index first among equal scores (-0 equals +0),
+ *   NaN before everything, -inf (a word probability of 0) an ordinary value.  Boxes: (double) roi * (h,w,h,w), y clipped to the
+ *   window's [y1,y2], x to [x1,x2].  NMS: greedy in that order, box j is suppressed by a kept box i when
+ *   ih*iw / (area_i + area_j - ih*iw) > threshold with ih = max(min(y2_i,y2_j) - max(y1_i,y1_j), 0), iw alike -- the corners as they
+ *   are, and a 0/0 NaN suppresses nothing (all-zero padding RoIs all survive); the first max_instances survivors go on.  Each is
+ *   rounded half to even, (box - shift) * scale is truncated toward zero to int32, and boxes with (y2-y1)*(x2-x1) <= 0 are dropped,
+ *   the others keeping their order.
+ * Outputs (fixed size): boxes_out int32 [B][max_instances][4] (16-byte aligned; zeros after the last survivor), keep_out int32
+ * [B][max_instances] (each survivor's index into the image's N RoIs, in score order; -1 after the last), count_out int32 [B],
+ * scores_out float64 [B][N] (the caption scores in RoI order).
+ * Limit: N <= DC_REFINE_MAX_ROIS (the one-workgroup NMS scan holds 128 mask words per row); larger N is DC_EINVAL.  Five launches on
+ * `stream`, workspace 32-byte aligned; no allocation, no synchronisation, capturable.
+ * ------------------------------------------------------------------------------------------------ */
+#define DC_REFINE_CONSTS 10
+#define DC_REFINE_MAX_ROIS 8192
+
+typedef struct {
+    int B, N, T;
+    const float* rois;
+    const float* word_scores;
+    const float* caption_scores;
+    int caption_stride;
+    const double* image_consts;
+    double threshold;
+    int max_instances;
+    int32_t* boxes_out;
+    int32_t* keep_out;
+    int32_t* count_out;
+    double* scores_out;
+} dc_refine_desc;
+
+size_t dc_refine_generations_workspace_bytes(const dc_refine_desc* d);
+int    dc_refine_generations_f64(const dc_refine_desc* d, void* workspace, size_t workspace_bytes, void* stream);
+
 /* PyramidROIAlign backward: d(maps) += bilinear scatter of d(out) (gradients to the boxes are stopped in the
  * reference, dense_model.py:378-379).  dmaps[l] must be zero-initialised by the caller; accumulation uses
  * float atomics (order-dependent in the last bits).  Same descriptor as the forward; `out` holds d(out) and

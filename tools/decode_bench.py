@@ -20,11 +20,21 @@ step), alternating with the sequence it replaces: ops.beam_select without rows p
 (their row index made outside the timed region).  Device events, medians of --repeats (at least 5).
 
     python tools/decode_bench.py --what beam --out profiles/decode_bench_beam_v1.json
+
+--what refine: the joint model's generate_captions end to end per image (1024 x 1024, ResNet-101 + FPN + RPN, the bf16 model with
+vocab_math='bf16') with postprocess='host' and 'device', at both shapes (K = POST_NMS_ROIS_INFERENCE), incremental and beam k = 3; the
+two legs alternate call by call in one process.  Device events around the call AND wall clock (the host leg's cost is host time, which
+events alone do not show; the call ends with its result on the host, so the wall clock covers all of it); medians of --repeats (at
+least 5) and max - min spreads.  Then ops.refine_generations alone on random RoIs.  --legs host times the host leg alone and names no
+new argument, so the same file measures an older checkout of the package (profiles/refine_generations_bench.json).
+
+    python tools/decode_bench.py --what refine --out profiles/refine_generations_bench.json
 """
 import argparse
 import json
 import os
 import sys
+import time
 
 import numpy as np
 import torch
@@ -146,6 +156,105 @@ def beam_legs(args, shapes, rows):
     print(json.dumps(rows[-1]), flush=True)
 
 
+def joint_for(sh, dtype, S=1024):
+    """The joint model in inference mode on synthetic weights: K proposals per S x S image, the shape's vocabulary."""
+    from image_captioning_amd import synth
+    from image_captioning_amd.config import Config
+    from image_captioning_amd.dense_model import DenseImageCapRCNN
+
+    class Cfg(Config):
+        NAME = "joint"
+        IMAGES_PER_GPU = 1
+        IMAGE_MIN_DIM = S
+        IMAGE_MAX_DIM = S
+        PADDING_SIZE = sh["T"]
+        VOCABULARY_SIZE = sh["V"]
+        EMBEDDING_SIZE = 300
+        RECURRENT_DROPOUT = 0.0
+        POST_NMS_ROIS_INFERENCE = sh["K"]
+    cfg = Cfg()
+    cfg.EMBEDDING_WEIGHTS = synth.embedding_matrix(3, sh["V"])
+    model = DenseImageCapRCNN("inference", cfg, "logs", lstm_units=sh["units"], compute_dtype=dtype)
+    # random FPN maps are O(10): keep the RPN / head activations in a trained network's range (as tools/joint_bench.py)
+    w = model.get_weights_dict()
+    model.set_weights({"rpn_conv_shared/kernel": w["rpn_conv_shared/kernel"] * np.float32(0.02),
+                       "rpn_bbox_pred/kernel": w["rpn_bbox_pred/kernel"] * np.float32(0.3),
+                       "mrcnn_class_conv1/kernel": w["mrcnn_class_conv1/kernel"] * np.float32(0.05)})
+    return model, cfg
+
+
+def timed_alternating_wall(fns, warm, reps):
+    """timed_alternating with the wall clock beside the events: [(median event ms, [ms ...], median wall ms, [ms ...]) per fn].  Every
+    fn returns with its results on the host, so the device is idle when the next one starts."""
+    for _ in range(warm):
+        for fn in fns:
+            fn()
+    torch.cuda.synchronize()
+    ev, wall = [[] for _ in fns], [[] for _ in fns]
+    for _ in range(reps):
+        for i, fn in enumerate(fns):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0 = time.perf_counter()
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            wall[i].append((time.perf_counter() - t0) * 1e3)
+            ev[i].append(a.elapsed_time(b))
+    return [(float(np.median(e)), [round(x, 3) for x in e], float(np.median(w)), [round(x, 3) for x in w]) for e, w in zip(ev, wall)]
+
+
+def refine_legs(args, shapes, rows):
+    """--what refine: generate_captions with the post-processing on the host and on the device, then ops.refine_generations alone."""
+    from image_captioning_amd import ops, synth
+    reps, warm = max(args.repeats, 5), max(args.warmup, 2)
+    posts = ("host",) if args.legs == "host" else ("host", "device")
+    img = synth.images(7, 1, 1024, 1024)[0]
+    for key in args.shapes.split(","):
+        sh = shapes[key]
+        model, cfg = joint_for(sh, "bf16")
+        for kw in (dict(decoder="incremental"), dict(decoder="beam", beam_size=3)):
+            # (the host leg is called without the argument: the default, and the call an older checkout understands)
+            fns = [lambda kw=kw, p=p: model.generate_captions([img], return_probabilities=False, vocab_math="bf16",
+                                                              **dict(kw, **({} if p == "host" else dict(postprocess=p)))) for p in posts]
+            out = [fn() for fn in fns]
+            same = None if len(out) < 2 else all(np.array_equal(out[0][0][k_], out[1][0][k_]) for k_ in out[0][0])
+            res = timed_alternating_wall(fns, warm, reps)
+            for p, (ems, eall, wms, wall) in zip(posts, res):
+                rows.append(dict(what="generate_captions_per_image", shape=sh["name"], dtype="bf16", vocab_math="bf16", postprocess=p, K=sh["K"],
+                                 T=sh["T"], V=sh["V"], image=1024, kept=int(len(out[0][0]["rois"])), event_ms=round(ems, 3),
+                                 event_spread_ms=round(max(eall) - min(eall), 3), wall_ms=round(wms, 3), wall_spread_ms=round(max(wall) - min(wall), 3),
+                                 event_runs_ms=eall, wall_runs_ms=wall, timing="median of %d, legs alternating call by call" % reps, **kw))
+                print(json.dumps(rows[-1]), flush=True)
+            if len(res) == 2:
+                (_, _, wh, rh), (_, _, wd, rd) = res
+                spread = max(max(rh) - min(rh), max(rd) - min(rd))
+                rows.append(dict(what="postprocess_device_vs_host", shape=sh["name"], K=sh["K"], host_wall_ms=round(wh, 3), device_wall_ms=round(wd, 3),
+                                 gain_ms=round(wh - wd, 3), larger_spread_ms=round(spread, 3), device_faster_beyond_spread=bool(wh - wd > spread),
+                                 results_identical=same, **kw))
+                print(json.dumps(rows[-1]), flush=True)
+        del model
+        torch.cuda.empty_cache()
+        if args.legs == "host":
+            continue
+        # the post-processing launches alone: K random RoIs, the greedy decoder's word scores
+        from image_captioning_amd import dense_model
+        K, T = sh["K"], sh["T"]
+        rng = np.random.default_rng(5)
+        yx, hw = rng.uniform(0, 0.8, (K, 2)), rng.uniform(0.03, 0.2, (K, 2))
+        rois = torch.tensor(np.concatenate([yx, yx + hw], axis=1)[None].astype(np.float32), device="cuda:0")
+        ws = torch.tensor(rng.uniform(0.05, 1.0, (K, T)).astype(np.float32), device="cuda:0")
+        consts = torch.tensor(dense_model.refine_constants((0, 0, 1024, 1024), cfg, (1024, 1024, 3))[None], device="cuda:0")
+        ms, all_ms = timed(lambda: ops.refine_generations(rois, consts, 0.3, 100, word_scores=ws), 3, 20)
+        t0 = time.perf_counter()
+        for _ in range(20):
+            dense_model.refine_generations(rois[0].cpu().numpy(), ws.cpu().numpy(), (0, 0, 1024, 1024), cfg)
+        host_ms = (time.perf_counter() - t0) / 20 * 1e3
+        rows.append(dict(what="refine_generations_alone", shape=sh["name"], K=K, T=T, max_instances=100, ms=round(ms, 4), min_ms=min(all_ms),
+                         max_ms=max(all_ms), launches=5, numpy_host_ms=round(host_ms, 3), timing="device events around the call, median of 20", runs_ms=all_ms))
+        print(json.dumps(rows[-1]), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=5)
@@ -153,7 +262,9 @@ def main():
     ap.add_argument("--out", default=None, help="JSON file for all rows (default: print only)")
     ap.add_argument("--shapes", default="c4,c2")
     ap.add_argument("--dtypes", default="f32,bf16")
-    ap.add_argument("--what", default="greedy", choices=("greedy", "beam"), help="greedy: prefix / incremental (default); beam: the beam decoder")
+    ap.add_argument("--what", default="greedy", choices=("greedy", "beam", "refine"),
+                    help="greedy: prefix / incremental (default); beam: the beam decoder; refine: generate_captions' post-processing on the host / device")
+    ap.add_argument("--legs", default="both", choices=("both", "host"), help="--what refine: both legs (default) or the host leg alone")
     args = ap.parse_args()
     from image_captioning_amd import ops
     torch.cuda.set_device(0)
@@ -162,6 +273,8 @@ def main():
               "c2": dict(name="configs[2]-style", K=200, T=15, V=10000, units=512)}
     if args.what == "beam":
         beam_legs(args, shapes, rows)
+    if args.what == "refine":
+        refine_legs(args, shapes, rows)
     for key in args.shapes.split(",") if args.what == "greedy" else ():
         sh = shapes[key]
         for dtype in args.dtypes.split(","):
