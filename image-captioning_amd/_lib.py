@@ -129,6 +129,17 @@ class VocabTopkBf16Desc(C.Structure):
     _fields_ = VocabTopkDesc._fields_ + [("tile", C.c_int)]
 
 
+_SAMPLE_FIELDS = [("inv_t", C.c_float), ("seed", C.c_uint32), ("offset", C.c_uint32), ("top_k", C.c_int)]
+
+
+class VocabSampleDesc(C.Structure):
+    _fields_ = VocabTop1Desc._fields_ + _SAMPLE_FIELDS
+
+
+class VocabSampleBf16Desc(C.Structure):
+    _fields_ = VocabTop1Bf16Desc._fields_ + _SAMPLE_FIELDS
+
+
 class BeamSelectDesc(C.Structure):
     _fields_ = [("R", C.c_int), ("k", C.c_int), ("nb", C.c_int), ("steps", C.c_int), ("j", C.c_int), ("log_score", C.c_int),
                 ("cand_ids", C.c_void_p), ("cand_probs", C.c_void_p), ("scores_in", C.c_void_p), ("scores_out", C.c_void_p),
@@ -288,6 +299,10 @@ SYMBOLS = {
     "dc_vocab_topk_bf16_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "dc_vocab_top1_bf16": (C.c_int, [C.POINTER(VocabTop1Bf16Desc), C.c_void_p, C.c_size_t, C.c_void_p]),
     "dc_vocab_topk_bf16": (C.c_int, [C.POINTER(VocabTopkBf16Desc), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "dc_vocab_sample_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "dc_vocab_sample_bf16_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "dc_vocab_sample_f32": (C.c_int, [C.POINTER(VocabSampleDesc), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "dc_vocab_sample_bf16": (C.c_int, [C.POINTER(VocabSampleBf16Desc), C.c_void_p, C.c_size_t, C.c_void_p]),
     "dc_beam_select_f32": (C.c_int, [C.POINTER(BeamSelectDesc), C.c_void_p]),
     "dc_beam_step_f32": (C.c_int, [C.POINTER(BeamStepDesc), C.c_void_p]),
     "dc_beam_backtrace": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),

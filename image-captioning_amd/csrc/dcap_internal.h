@@ -103,4 +103,17 @@ __device__ __forceinline__ unsigned philox2x32(unsigned c0, unsigned c1, unsigne
     return c0;
 }
 
+// The same ten rounds, both output words (c0, c1): one call serves two elements (the Gumbel noise of vocab_topk.hip's sampler).
+__device__ __forceinline__ uint2 philox2x32_pair(unsigned c0, unsigned c1, unsigned key) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const unsigned long long p = (unsigned long long)0xD256D193u * c0;
+        const unsigned hi = (unsigned)(p >> 32), lo = (unsigned)p;
+        c0 = hi ^ key ^ c1;
+        c1 = lo;
+        key += 0x9E3779B9u;
+    }
+    return make_uint2(c0, c1);
+}
+
 }  // namespace dcap

@@ -9,6 +9,9 @@
 //                       reduces its own 64-column slice in registers and writes its own cells (ceil(V/64) cells per row instead of
 //                       ceil(V/128); no cross-wave combine, no barrier after the main loop), and the row kernel, generic over the
 //                       number of cells per row, combines them unchanged.
+//   dc_vocab_sample_f32 / dc_vocab_sample_bf16   the vocabulary projection FUSED with one draw per row from softmax(z / t) (stochastic
+//                       decoding): the Gumbel-max argmax as one more reduction of the 128 x 128 tile's epilogue, counter-based noise;
+//                       with top_k, the top-k tile kernels unchanged and a row kernel that perturbs the k winners;
 //   dc_beam_step_f32    per RoI, the k best of the k beams' proposals (score + p or score + log p; a beam that has produced the end
 //                       token proposes only itself, with token 0), with the parents' rows of up to four state tensors gathered into
 //                       the next state buffers;  dc_beam_select_f32: the same kernel with one (h, c) pair and no end token;
@@ -264,6 +267,198 @@ __global__ __launch_bounds__(256) void vocab_topk_rows_kernel(int M, int tiles_n
     }
 }
 
+// ------------------------------------------------------------------------------------------------ Gumbel-max sampling
+// dc_vocab_sample_f32 / _bf16 (include/dcap.h): the word argmax_v fma(z_v, inv_t, g(row, v)) is an exact draw from softmax(z inv_t).
+// The noise g is a pure function of (seed, offset + row, v) -- Philox-2x32-10 on the counter (v >> 1, offset + row), both words kept,
+// so a lane's four columns (4 c4 .. 4 c4 + 3) cost two Philox calls -- and nothing else enters it: not M, not the tile, not the grid.
+struct SampleArgs {
+    TopkArgs t;                          // t.k is unused; t.cells: [M][tiles_n][3]: (max, sum exp), (y, column (int bits)), (z of that column, 0)
+    float inv_t;
+    unsigned seed, offset;
+};
+
+// standard Gumbel noise from 32 random bits: u = ((r >> 9) + 0.5) 2^-23 lies in [2^-24, 1 - 2^-24] and is exact; the accurate logf twice
+__device__ __forceinline__ float sm_gumbel(unsigned r) {
+    const float u = ((float)(r >> 9) + 0.5f) * 1.1920928955078125e-07f;
+    return -logf(-logf(u));
+}
+
+__device__ __forceinline__ float sm_noise(unsigned seed, unsigned ctr, int v) {
+    const uint2 r = philox2x32_pair((unsigned)v >> 1, ctr, seed);
+    return sm_gumbel((v & 1) ? r.y : r.x);
+}
+
+// The epilogue of one 128 x 128 tile, topk_epilogue's staging and lane map.  The unperturbed (max, sum exp) of a row are
+// topk_epilogue's at k = 1 (the same maximum, the same terms in the same order), so the reported probabilities are the greedy
+// decoder's to rounding.  The perturbed pair takes one more 32-lane reduction; the lane that owns the winning column writes its logit.
+__device__ __forceinline__ void sample_epilogue(f32x16 (&acc)[2][2], float* Cs, const SampleArgs& sa, int m0, int n0, int wm, int wn, int tile_n) {
+    constexpr int LDC = 128 + 4;
+    const TopkArgs& ta = sa.t;
+    const int tid = threadIdx.x;
+    stage_acc_tile<2, 2, LDC>(acc, Cs, wm, wn);
+    const int c4 = tid & 31, rp = tid >> 5;                    // 32 lanes x 4 columns per row, 8 rows per pass
+    const int col = n0 + 4 * c4;
+    float4 b4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (ta.bias && col + 3 < ta.V) b4 = *reinterpret_cast<const float4*>(ta.bias + col);
+    else if (ta.bias) {
+        if (col < ta.V) b4.x = ta.bias[col];
+        if (col + 1 < ta.V) b4.y = ta.bias[col + 1];
+        if (col + 2 < ta.V) b4.z = ta.bias[col + 2];
+    }
+    const bool v0 = col < ta.V, v1 = col + 1 < ta.V, v2 = col + 2 < ta.V, v3 = col + 3 < ta.V;
+    const unsigned pc = (unsigned)col >> 1;                    // Philox counter word 0 of columns col, col + 1; pc + 1: col + 2, col + 3
+    for (int p = 0; p < 16; ++p) {
+        const int lr = p * 8 + rp, row = m0 + lr;
+        float4 z = *reinterpret_cast<const float4*>(&Cs[lr * LDC + 4 * c4]);
+        z.x += b4.x; z.y += b4.y; z.z += b4.z; z.w += b4.w;
+        float2* out = ta.cells + ((long)row * ta.tiles_n + tile_n) * 3;
+        float mx = -INFINITY;
+        if (v0 && z.x > mx) mx = z.x;
+        if (v1 && z.y > mx) mx = z.y;
+        if (v2 && z.z > mx) mx = z.z;
+        if (v3 && z.w > mx) mx = z.w;
+#pragma unroll
+        for (int o = 16; o > 0; o >>= 1) {
+            const float om = __shfl_xor(mx, o, 64);
+            if (om > mx) mx = om;
+        }
+        float s = (v0 ? expf(z.x - mx) : 0.f) + (v1 ? expf(z.y - mx) : 0.f) + (v2 ? expf(z.z - mx) : 0.f) + (v3 ? expf(z.w - mx) : 0.f);
+#pragma unroll
+        for (int o = 16; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+        float bm = -INFINITY;
+        int bi = INT_MAX;
+        if (row < ta.M && v0) {                                // (a lane past V, or a row past M, proposes nothing)
+            const unsigned ctr = sa.offset + (unsigned)row;
+            const uint2 ra = philox2x32_pair(pc, ctr, sa.seed), rb = philox2x32_pair(pc + 1u, ctr, sa.seed);
+            tk_take(bm, bi, fmaf(z.x, sa.inv_t, sm_gumbel(ra.x)), col);
+            if (v1) tk_take(bm, bi, fmaf(z.y, sa.inv_t, sm_gumbel(ra.y)), col + 1);
+            if (v2) tk_take(bm, bi, fmaf(z.z, sa.inv_t, sm_gumbel(rb.x)), col + 2);
+            if (v3) tk_take(bm, bi, fmaf(z.w, sa.inv_t, sm_gumbel(rb.y)), col + 3);
+        }
+#pragma unroll
+        for (int o = 16; o > 0; o >>= 1) {
+            const float om = __shfl_xor(bm, o, 64);
+            const int oi = __shfl_xor(bi, o, 64);
+            tk_take(bm, bi, om, oi);
+        }
+        if (row < ta.M) {
+            if (c4 == 0) {
+                out[0] = make_float2(mx, s);
+                out[1] = make_float2(bm, __int_as_float(bi));
+            }
+            const unsigned own = (unsigned)(bi - col);         // (no pair: INT_MAX - col >= 4, no lane owns it)
+            if (own < 4u) out[2] = make_float2(own == 0 ? z.x : own == 1 ? z.y : own == 2 ? z.z : z.w, 0.f);
+        }
+    }
+}
+
+// The tile loops of vocab_topk_f32_kernel / vocab_topk_bf16_kernel, ending in the sampling epilogue.
+__global__ __launch_bounds__(256, 2) void vocab_sample_f32_kernel(TKA al, TKB bl, SampleArgs sa, int K) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int wave = threadIdx.x >> 6;
+    const int lid = xcd_remap(blockIdx.x, gridDim.x);
+    const int tile_m = lid % sa.t.tiles_m, tile_n = lid / sa.t.tiles_m;
+    const int m0 = tile_m * 128, n0 = tile_n * 128;
+    const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
+    f32x16 acc[2][2];
+    igemm_mainloop<128, 128, TKA, TKB>(al, bl, smem, m0, n0, 0, K, acc, wm, wn);
+    sample_epilogue(acc, smem, sa, m0, n0, wm, wn, tile_n);
+}
+
+__global__ __launch_bounds__(256, 2) void vocab_sample_bf16_kernel(BOperand a, BOperand b, SampleArgs sa, int K) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int wave = threadIdx.x >> 6;
+    const int lid = xcd_remap(blockIdx.x, gridDim.x);
+    const int tile_m = lid % sa.t.tiles_m, tile_n = lid / sa.t.tiles_m;
+    const int m0 = tile_m * 128, n0 = tile_n * 128;
+    const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
+    f32x16 acc[2][2];
+    bgemm_mainloop<true, false>(a, b, reinterpret_cast<char*>(smem), m0, n0, 0, K, acc, wm, wn);
+    sample_epilogue(acc, smem, sa, m0, n0, wm, wn, tile_n);
+}
+
+// One wave per row; lane 0 writes.  m and s come from the cells exactly as in vocab_topk_rows_kernel (the maximum of the tile
+// maxima; s = sum_j s_j exp(m_j - m), lane-strided over j, then a fixed xor tree), in an order fixed by tiles_n alone.
+// k = 0 (whole vocabulary; cells of sample_epilogue): the best of the tiles' perturbed pairs, and the winner's logit from its tile's cell.
+// k >= 1 (cells of the top-k tile kernels at that k): vocab_topk_rows_kernel's k threshold rounds leave the row's r-th best (z_r, id_r) in
+// lane r; those k lanes perturb their own candidate and a 64-lane reduction takes the best (y, id), its logit carried along.
+// probs = exp(z_w - m) / s, 1 / s when z_w == m (the top-1 kernel's value, bit for bit) or when the row has no orderable logit (id 0).
+__global__ __launch_bounds__(256) void vocab_sample_rows_kernel(int M, int tiles_n, int k, const float2* __restrict__ cells, float inv_t,
+                                                                unsigned seed, unsigned offset, int32_t* __restrict__ ids, long ld_ids,
+                                                                float* __restrict__ probs, long ld_probs, int32_t* __restrict__ tokens,
+                                                                uint8_t* __restrict__ mask) {
+    const int row = (blockIdx.x * 256 + threadIdx.x) >> 6, lane = threadIdx.x & 63;
+    if (row >= M) return;
+    const int cw = k ? k + 1 : 3;                              // float2 per cell
+    const float2* cl = cells + (long)row * tiles_n * cw;
+    float m = -INFINITY, z = -INFINITY, by = -INFINITY;
+    int id = INT_MAX;
+    if (k == 0) {
+        for (int j = lane; j < tiles_n; j += 64) {
+            const float mj = cl[j * 3].x;
+            const float2 q = cl[j * 3 + 1];
+            const int c = __float_as_int(q.y);
+            if (mj > m) m = mj;
+            if (c != INT_MAX) tk_take(by, id, q.x, c);
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float om = __shfl_xor(m, o, 64), oy = __shfl_xor(by, o, 64);
+            const int oi = __shfl_xor(id, o, 64);
+            if (om > m) m = om;
+            tk_take(by, id, oy, oi);
+        }
+        if (id != INT_MAX) z = cl[(id >> 7) * 3 + 2].x;        // the 128-column tile that proposed the winner kept its logit
+    } else {
+        float tv = INFINITY, zr = -INFINITY;
+        int tc = INT_MIN, idr = INT_MAX;
+        for (int r = 0; r < k; ++r) {
+            float bm = -INFINITY;
+            int bi = INT_MAX;
+            for (int j = lane; j < tiles_n; j += 64)
+                for (int i = 1; i <= k; ++i) {
+                    const float2 q = cl[j * (k + 1) + i];
+                    const int c = __float_as_int(q.y);
+                    if (c != INT_MAX && tk_after(q.x, c, tv, tc)) tk_take(bm, bi, q.x, c);
+                }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const float om = __shfl_xor(bm, o, 64);
+                const int oi = __shfl_xor(bi, o, 64);
+                tk_take(bm, bi, om, oi);
+            }
+            if (r == 0) m = bm;
+            if (lane == r) { zr = bm; idr = bi; }
+            tv = bm; tc = bi;
+        }
+        if (idr != INT_MAX) {                                  // (lanes >= k and ranks past the orderable logits propose nothing)
+            by = fmaf(zr, inv_t, sm_noise(seed, offset + (unsigned)row, idr));
+            id = idr;
+            z = zr;
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float oy = __shfl_xor(by, o, 64), oz = __shfl_xor(z, o, 64);
+            const int oi = __shfl_xor(id, o, 64);
+            if (oy > by || (oy == by && oi < id)) { by = oy; id = oi; z = oz; }
+        }
+    }
+    float s = 0.f;
+    for (int j = lane; j < tiles_n; j += 64) {
+        const float2 q = cl[j * cw];
+        s += q.y * expf(q.x - m);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    if (lane != 0) return;
+    const bool none = id == INT_MAX;
+    if (none) id = 0;
+    if (ids) ids[row * ld_ids] = id;
+    if (probs) probs[row * ld_probs] = none || z == m ? 1.f / s : expf(z - m) / s;
+    tokens[row] = id;
+    if (mask) mask[row] = id != 0 ? 1 : 0;
+}
+
 // ------------------------------------------------------------------------------------------------ beam selection
 // One block of four waves per RoI.  Every wave repeats the decision: lane l < nb * k holds candidate (beam b = l / k, rank i = l % k)
 // of the beam-major candidate rows b * R + roi: score = scores_in[roi][b] + (p or log p).  A beam that finished_in marks proposes ONE
@@ -511,6 +706,115 @@ extern "C" int dc_vocab_top1_bf16(const dc_vocab_top1_bf16_desc* d, void* worksp
     DC_REQUIRE((!d->ids || d->ld_ids >= 1) && (!d->probs || d->ld_probs >= 1), DC_EINVAL, "dc_vocab_top1_bf16: ld_ids / ld_probs must be >= 1");
     const dc_vocab_topk_bf16_desc tk{d->M, d->V, d->K, 1, d->X, d->ldx, d->W, d->ldw, d->bias, d->ids, d->probs, d->tile};
     return vocab_topk_bf16_run("dc_vocab_top1_bf16", tk, d->ld_ids, d->ld_probs, d->tokens, d->mask, workspace, workspace_bytes, stream);
+}
+
+// ------------------------------------------------------------------------------------------------ sampling entry points
+// What both sampling entry points ask beyond the operand checks; fn names the entry point in the messages.
+static int vocab_sample_validate(const char* fn, int V, bool tokens, int ld_ids_ok, float inv_t, int top_k) {
+    DC_REQUIRE(tokens, DC_EINVAL, "%s: bad arguments", fn);
+    DC_REQUIRE(ld_ids_ok, DC_EINVAL, "%s: ld_ids / ld_probs must be >= 1", fn);
+    DC_REQUIRE(inv_t > 0.f && inv_t < INFINITY, DC_EINVAL, "%s: inv_t = 1 / temperature must be finite and > 0, got %g", fn, (double)inv_t);
+    DC_REQUIRE(top_k >= 0 && top_k <= TK_MAX && V >= top_k, DC_EINVAL,
+               "%s: top_k must be 0 (the whole vocabulary) or 1 <= top_k <= 8 with V >= top_k (top_k = %d, V = %d)", fn, top_k, V);
+    return DC_OK;
+}
+
+extern "C" size_t dc_vocab_sample_workspace_bytes(int M, int V, int top_k) {
+    if (M <= 0 || V <= 0 || top_k < 0) return 0;
+    if (top_k) return dc_vocab_topk_workspace_bytes(M, V, top_k);
+    return tk_align256((size_t)M * ((V + 127) / 128) * 3 * sizeof(float2));
+}
+
+// whole vocabulary: always the 128 tile (0 means 128 here); top_k: the top-k kernels' rule
+extern "C" size_t dc_vocab_sample_bf16_workspace_bytes(int M, int V, int K, int top_k, int tile) {
+    if (M <= 0 || V <= 0 || K <= 0 || top_k < 0 || (tile != 0 && tile != 128 && tile != 256)) return 0;
+    if (top_k) return dc_vocab_topk_bf16_workspace_bytes(M, V, K, top_k, tile);
+    return tile == 256 ? 0 : dc_vocab_sample_workspace_bytes(M, V, 0);
+}
+
+extern "C" int dc_vocab_sample_f32(const dc_vocab_sample_desc* d, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* fn = "dc_vocab_sample";
+    DC_REQUIRE(d != nullptr, DC_EINVAL, "dc_vocab_sample: null descriptor");
+    DC_REQUIRE(d->M > 0 && d->V > 0 && d->K > 0 && d->X && d->W, DC_EINVAL, "dc_vocab_sample: bad arguments");
+    int rc = vocab_sample_validate(fn, d->V, d->tokens != nullptr, (!d->ids || d->ld_ids >= 1) && (!d->probs || d->ld_probs >= 1), d->inv_t, d->top_k);
+    if (rc) return rc;
+    const dc_vocab_topk_desc tk{d->M, d->V, d->K, d->top_k, d->X, d->ldx, d->W, d->ldw, d->bias, nullptr, nullptr};
+    rc = vocab_f32_validate(fn, tk);
+    if (rc) return rc;
+    const size_t need = dc_vocab_sample_workspace_bytes(d->M, d->V, d->top_k);
+    DC_REQUIRE(workspace && workspace_bytes >= need, DC_EWORKSPACE, "%s: needs %zu workspace bytes, got %zu", fn, need, workspace_bytes);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    SampleArgs sa{};
+    TopkArgs& ta = sa.t;
+    ta.M = d->M; ta.V = d->V; ta.k = d->top_k;
+    ta.tiles_m = (d->M + 127) / 128;
+    ta.tiles_n = (d->V + 127) / 128;
+    ta.bias = d->bias;
+    ta.cells = static_cast<float2*>(workspace);
+    sa.inv_t = d->inv_t; sa.seed = d->seed; sa.offset = d->offset;
+    TKA al{d->X, d->ldx, d->M, nullptr};                        // (operands: as vocab_topk_run)
+    TKB bl{d->W, d->ldw, (d->V + 3) / 4 * 4, nullptr};
+    constexpr size_t lds = igemm_lds_bytes<128, 128, TKA, TKB>();
+    if (d->top_k) {
+        DC_ENSURE_DYN_LDS((&vocab_topk_f32_kernel), 160 * 1024);
+        hipLaunchKernelGGL(vocab_topk_f32_kernel, dim3(ta.tiles_m * ta.tiles_n), dim3(256), lds, s, al, bl, ta, d->K);
+        rc = check_launch("vocab_topk_f32_kernel");
+    } else {
+        DC_ENSURE_DYN_LDS((&vocab_sample_f32_kernel), 160 * 1024);
+        hipLaunchKernelGGL(vocab_sample_f32_kernel, dim3(ta.tiles_m * ta.tiles_n), dim3(256), lds, s, al, bl, sa, d->K);
+        rc = check_launch("vocab_sample_f32_kernel");
+    }
+    if (rc) return rc;
+    hipLaunchKernelGGL(vocab_sample_rows_kernel, dim3((d->M + 3) / 4), dim3(256), 0, s, d->M, ta.tiles_n, d->top_k, ta.cells, sa.inv_t, sa.seed,
+                       sa.offset, d->ids, (long)d->ld_ids, d->probs, (long)d->ld_probs, d->tokens, d->mask);
+    return check_launch("vocab_sample_rows_kernel");
+}
+
+extern "C" int dc_vocab_sample_bf16(const dc_vocab_sample_bf16_desc* d, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* fn = "dc_vocab_sample_bf16";
+    DC_REQUIRE(d != nullptr, DC_EINVAL, "dc_vocab_sample_bf16: null descriptor");
+    DC_REQUIRE(d->M > 0 && d->V > 0 && d->K > 0 && d->X && d->W, DC_EINVAL, "dc_vocab_sample_bf16: bad arguments");
+    int rc = vocab_sample_validate(fn, d->V, d->tokens != nullptr, (!d->ids || d->ld_ids >= 1) && (!d->probs || d->ld_probs >= 1), d->inv_t, d->top_k);
+    if (rc) return rc;
+    const dc_vocab_topk_bf16_desc tk{d->M, d->V, d->K, d->top_k, d->X, d->ldx, d->W, d->ldw, d->bias, nullptr, nullptr, d->tile};
+    rc = vocab_bf16_validate(fn, tk);
+    if (rc) return rc;
+    DC_REQUIRE(d->top_k || d->tile != 256, DC_EINVAL,
+               "%s: sampling over the whole vocabulary (top_k = 0) runs on the 128 x 128 tile only: pass tile = 0 or 128, got 256", fn);
+    const size_t need = dc_vocab_sample_bf16_workspace_bytes(d->M, d->V, d->K, d->top_k, d->tile);
+    DC_REQUIRE(workspace && workspace_bytes >= need, DC_EWORKSPACE, "%s: needs %zu workspace bytes, got %zu", fn, need, workspace_bytes);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int T = d->top_k ? tk_bf16_tile(d->M, d->V, d->K, d->tile) : 128;
+    SampleArgs sa{};
+    TopkArgs& ta = sa.t;
+    ta.M = d->M; ta.V = d->V; ta.k = d->top_k;
+    ta.tiles_m = (d->M + T - 1) / T;
+    ta.tiles_n = tk_bf16_cells(d->V, T);
+    ta.bias = d->bias;
+    ta.cells = static_cast<float2*>(workspace);
+    sa.inv_t = d->inv_t; sa.seed = d->seed; sa.offset = d->offset;
+    const int Vp = (d->V + 7) / 8 * 8;                          // (operands: as vocab_topk_bf16_run)
+    BOperand a{static_cast<const unsigned short*>(d->X), d->ldx, d->M, nullptr, (unsigned)(((size_t)(d->M - 1) * d->ldx + d->K) * 2)};
+    BOperand b{static_cast<const unsigned short*>(d->W), d->ldw, Vp, nullptr, (unsigned)(((size_t)(d->K - 1) * d->ldw + Vp) * 2)};
+    if (!d->top_k) {
+        DC_ENSURE_DYN_LDS((&vocab_sample_bf16_kernel), 160 * 1024);
+        hipLaunchKernelGGL(vocab_sample_bf16_kernel, dim3(ta.tiles_m * ta.tiles_n), dim3(256), bgemm_lds_bytes(), s, a, b, sa, d->K);
+        rc = check_launch("vocab_sample_bf16_kernel");
+    } else if (T == 256) {
+        const int tiles_n = (d->V + 255) / 256;
+        DC_ENSURE_DYN_LDS((&vocab_topk_bf16_256_kernel), 160 * 1024);
+        hipLaunchKernelGGL(vocab_topk_bf16_256_kernel, dim3(ta.tiles_m * tiles_n), dim3(b256::NTHREADS), b256::LDS_BYTES, s, a, b, ta, d->K,
+                           ta.tiles_m, tiles_n);
+        rc = check_launch("vocab_topk_bf16_256_kernel");
+    } else {
+        DC_ENSURE_DYN_LDS((&vocab_topk_bf16_kernel), 160 * 1024);
+        hipLaunchKernelGGL(vocab_topk_bf16_kernel, dim3(ta.tiles_m * ta.tiles_n), dim3(256), bgemm_lds_bytes(), s, a, b, ta, d->K);
+        rc = check_launch("vocab_topk_bf16_kernel");
+    }
+    if (rc) return rc;
+    hipLaunchKernelGGL(vocab_sample_rows_kernel, dim3((d->M + 3) / 4), dim3(256), 0, s, d->M, ta.tiles_n, d->top_k, ta.cells, sa.inv_t, sa.seed,
+                       sa.offset, d->ids, (long)d->ld_ids, d->probs, (long)d->ld_probs, d->tokens, d->mask);
+    return check_launch("vocab_sample_rows_kernel");
 }
 
 static bool bs_overlap(const void* a, const void* b, size_t bytes_a, size_t bytes_b) {

@@ -7,7 +7,7 @@ import torch
 
 from . import ops
 
-DECODERS = ("prefix", "incremental", "beam")
+DECODERS = ("prefix", "incremental", "beam", "sampling")
 SCORES = ("prob", "logprob")
 
 
@@ -15,7 +15,7 @@ def check_decoder(decoder, beam_size, score, beam_only=None, own=None, score_for
     """The argument rules the models share, in their order of refusal: a known decoder; beam_size an integer (not a bool) in
     1..ops.TOPK_MAX with decoder='beam', and neither it nor any of beam_only ({name: value}: the model's further beam-only arguments)
     given otherwise; then own (the model's own refusal at this place: its message, or None); then a known score (score_for_beam_only:
-    asked of 'beam' alone)."""
+    asked of 'beam' alone).  The sampling arguments have their own rules, check_sampling, which the models apply after all of theirs."""
     if decoder not in DECODERS:
         raise ValueError("decoder must be one of %s, got %r" % (DECODERS, decoder))
     beam_only = dict(beam_size=beam_size, **(beam_only or {}))
@@ -28,6 +28,40 @@ def check_decoder(decoder, beam_size, score, beam_only=None, own=None, score_for
         raise ValueError(own)
     if (decoder == "beam" or not score_for_beam_only) and score not in SCORES:
         raise ValueError("score must be one of %s, got %r" % (SCORES, score))
+
+
+def check_sampling(decoder, temperature, top_k, seed):
+    """The rules of decoder='sampling' (the models call this after every other refusal) -> (temperature, top_k, seed) as greedy()'s
+    sampler takes them.  temperature, top_k and seed belong to 'sampling' alone.  With it, seed is required: an integer (not a bool) in
+    [0, 2^32) -- there is no hidden generator state, the same call twice draws the same captions; temperature (default 1.0) is a finite
+    number > 0; top_k is None (the whole vocabulary) or an integer (not a bool) in 1..ops.TOPK_MAX."""
+    if decoder != "sampling":
+        given = [n for n, v in (("temperature", temperature), ("top_k", top_k), ("seed", seed)) if v is not None]
+        if given:
+            raise ValueError("%s %s only for decoder='sampling' (got decoder=%r)" % (" and ".join(given), "are" if len(given) > 1 else "is", decoder))
+        return None
+    if seed is None or isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= seed < 2 ** 32:
+        raise ValueError("decoder='sampling' needs seed, an integer in [0, 2^32), got %r" % (seed,))
+    temperature = 1.0 if temperature is None else temperature
+    if isinstance(temperature, bool) or not isinstance(temperature, (int, float, np.integer, np.floating)) or \
+            not (np.isfinite(temperature) and temperature > 0):
+        raise ValueError("temperature must be a finite number > 0, got %r" % (temperature,))
+    if top_k is not None and (isinstance(top_k, bool) or not isinstance(top_k, (int, np.integer)) or not 1 <= top_k <= ops.TOPK_MAX):
+        raise ValueError("top_k must be None or an integer in 1..%d, got %r" % (ops.TOPK_MAX, top_k))
+    return float(temperature), None if top_k is None else int(top_k), int(seed)
+
+
+def sampler(n, temperature, top_k, seed, offset0=0):
+    """greedy()'s per-step selection that draws every word instead of taking the best: ops.vocab_sample with the noise of step j over the
+    n rows at offset offset0 + j * n (so no two (step, row) cells of a call share noise, and a caller that decodes several calls with
+    one seed spaces their offset0 by n * T)."""
+    def select(j, x, W, bias, **out):
+        ops.vocab_sample(x, W, bias, temperature=temperature, top_k=top_k, seed=seed, offset=(offset0 + j * n) % 2 ** 32, **out)
+    return select
+
+
+def _top1(j, x, W, bias, **out):
+    ops.vocab_top1(x, W, bias, **out)
 
 
 # One decode call over n rows, as a model's setup hands it to the drivers:
@@ -54,10 +88,11 @@ def beam_views(out, B, k, T):
     return out[:B * k * T].reshape(B, k, T), _f32(out[B * k * T:]).reshape(B, k)
 
 
-def greedy(n, T, device, setup):
+def greedy(n, T, device, setup, select=_top1):
     """T greedy steps over n rows into one int32 [2,n,T] device buffer, [0] the ids, [1] the word scores' float32 bits: per step the
     model's step (setup() -> Decode, called when there are rows), then ops.vocab_top1 into column j and into tok / live for the next
-    step.  The steps write the two state sets in turn."""
+    step.  The steps write the two state sets in turn.  select(j, x, W, bias, tokens=, ids=, probs=, mask=) is the per-step selection:
+    the default is that ops.vocab_top1 call; sampler() draws the words instead (decoder='sampling')."""
     out = torch.empty((2, n, T), dtype=torch.int32, device=device)
     if n == 0:
         return out
@@ -66,7 +101,7 @@ def greedy(n, T, device, setup):
     W, bias = d.vocab
     for j in range(T):
         x = d.step(d.tok, d.live if j else d.mask0, d.states[(j + 1) % 2] if j else None, d.states[j % 2])
-        ops.vocab_top1(x, W, bias, tokens=d.tok, ids=ids[:, j], probs=scores[:, j], mask=d.live)
+        select(j, x, W, bias, tokens=d.tok, ids=ids[:, j], probs=scores[:, j], mask=d.live)
     return out
 
 

@@ -1276,7 +1276,7 @@ class DenseImageCapRCNN(object):
         return np.stack(molded), np.stack(metas), np.stack(windows)
 
     def generate_captions(self, images, verbose=0, return_probabilities=True, decoder="prefix", vocab_math=None, beam_size=None, score="logprob",
-                          end_id=None, postprocess="host"):
+                          end_id=None, postprocess="host", temperature=None, top_k=None, seed=None):
         """The inference graph (:1602-1622) + generate_captions (:1964-2003): RPN proposals (POST_NMS_ROIS_INFERENCE) ->
         RoI features -> greedy ROICaptionInferenceLayer -> GenerationMatchLayer -> boxes in the original image.
         Returns [{'rois': int32 [K,4], 'captions': f32 [K,T,V] word probabilities, 'ids': int32 [K,T]}]; with
@@ -1290,20 +1290,25 @@ class DenseImageCapRCNN(object):
         vocab_math as above): CaptionModelV1.decode_beam.  Each RoI's caption is its best beam and the caption score that orders the NMS
         is that beam's score (with end_id: the sum up to and including the end word).  Each result holds 'rois', 'ids' [K,T] (the best
         beam), 'beam_ids' [K,k,T] and 'beam_scores' [K,k] (best first).
+        decoder='sampling' (needs return_probabilities=False and seed=, an integer in [0, 2^32); temperature=, top_k=, vocab_math as
+        above): CaptionModelV1.decode_sampling -- every word drawn from the model's distribution; image b of the batch decodes at noise
+        offset b * T * K, so two images never share noise; the word scores, the caption score that orders the NMS and the result
+        dictionaries are the incremental decoder's.  The same call twice returns the same captions.
         postprocess='host' (default): GenerationMatchLayer and unmold_generations in NumPy, image by image, after each image's decoder
-        results have come to the host.  'device' (needs return_probabilities=False and decoder='incremental' or 'beam'): the images'
+        results have come to the host.  'device' (needs return_probabilities=False and a device decoder: 'incremental', 'beam' or 'sampling'): the images'
         decode calls one after another without waiting, ONE ops.refine_generations for the batch on the decoder's device buffers, a
         device gather of the survivors' captions and ONE device-to-host copy for the batch; nothing synchronises between the image upload and that copy.  The same
         results, bit for bit (the float64 operations of the host path in its order; equal caption scores are ordered as
         np.argsort(kind='stable')[::-1] orders them, where NumPy's default sort promises no order)."""
-        CaptionModelV1.check_decoder(decoder, return_probabilities, vocab_math, getattr(self, "compute_dtype", None) if vocab_math == "bf16" else None,
-                                     beam_size=beam_size, score=score, end_id=end_id, postprocess=postprocess)
+        sampling = CaptionModelV1.check_decoder(decoder, return_probabilities, vocab_math,
+                                                getattr(self, "compute_dtype", None) if vocab_math == "bf16" else None, beam_size=beam_size, score=score,
+                                                end_id=end_id, postprocess=postprocess, temperature=temperature, top_k=top_k, seed=seed)
         assert self.mode == "inference", "Create model in inference mode."
         assert len(images) == self.config.BATCH_SIZE, "len(images) must be equal to BATCH_SIZE"
         molded, metas, windows = self.mold_inputs(images)
         p = self.plan()
         if postprocess == "device":
-            return self._generate_captions_device(p, images, molded, windows, decoder, vocab_math, beam_size, score, end_id)
+            return self._generate_captions_device(p, images, molded, windows, decoder, vocab_math, beam_size, score, end_id, sampling)
         p.forward(torch.as_tensor(molded))
         proposals = p.proposals()
         self.last_proposals = proposals
@@ -1318,8 +1323,13 @@ class DenseImageCapRCNN(object):
                 keep = keep[ok]
                 results.append({"rois": final[ok], "ids": beam_ids[keep, 0], "beam_ids": beam_ids[keep], "beam_scores": beam_scores[keep]})
                 continue
-            probs, ids, word_scores = self.caption_model.generate(feats[b], return_probabilities=return_probabilities, decoder=decoder,
-                                                                  vocab_math=vocab_math)
+            if decoder == "sampling":
+                cm = self.caption_model
+                probs, (ids, word_scores) = None, decoding.greedy_views(
+                    cm._decode_greedy(feats[b], vocab_math, sampling, b * cm.T * feats[b].shape[0]).cpu().numpy())
+            else:
+                probs, ids, word_scores = self.caption_model.generate(feats[b], return_probabilities=return_probabilities, decoder=decoder,
+                                                                      vocab_math=vocab_math)
             boxes, keep = refine_generations(proposals[b].cpu().numpy(), word_scores, windows[b], self.config)
             final, ok = unmold_generations(boxes, images[b].shape, windows[b])
             keep = keep[ok]
@@ -1329,7 +1339,7 @@ class DenseImageCapRCNN(object):
             results.append(out)
         return results
 
-    def _generate_captions_device(self, p, images, molded, windows, decoder, vocab_math, beam_size, score, end_id):
+    def _generate_captions_device(self, p, images, molded, windows, decoder, vocab_math, beam_size, score, end_id, sampling=None):
         """generate_captions(postprocess='device'): see there.  The packed int32 result buffer holds, for the batch, the survivor
         counts [B], the boxes [B,M,4], the survivors' ids [B,M,T] (greedy) or beam tokens [B,M,k,T] and beam scores' bits [B,M,k]."""
         cfg, cm, B = self.config, self.caption_model, len(images)
@@ -1351,7 +1361,7 @@ class DenseImageCapRCNN(object):
             parts = [toks, sc]
             boxes, keep, count, _ = ops.refine_generations(proposals, consts, cfg.DETECTION_NMS_THRESHOLD, M, caption_scores=sc[:, 0])
         else:
-            views = [decoding.greedy_views(cm._decode_greedy(feats[b], vocab_math)) for b in range(B)]
+            views = [decoding.greedy_views(cm._decode_greedy(feats[b], vocab_math, sampling, b * cm.T * K)) for b in range(B)]   # (sampling None: greedy)
             ids, word_scores = (views[0] if B == 1 else tuple(torch.cat([v[i] for v in views]) for i in range(2)))
             T, parts = ids.shape[1], [ids]
             boxes, keep, count, _ = ops.refine_generations(proposals, consts, cfg.DETECTION_NMS_THRESHOLD, M, word_scores=word_scores)

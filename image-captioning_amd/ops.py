@@ -12,7 +12,7 @@ import torch
 
 from . import _lib
 from ._lib import (PwChainDesc, ConvBf16Desc, AmsgradDesc, DetectionTargetsDesc, BnReluDesc, ConvDesc, ConvWgradBf16Desc, GemmBf16Desc, VocabCeDesc, ProposalDesc, RpnLossDesc, GemmDesc, LstmBwdDesc, LstmFwdDesc, RoiAlignDesc, RoiGroupsDesc,
-                   SoftmaxCeDesc, VocabTop1Desc, VocabTopkDesc, VocabTop1Bf16Desc, VocabTopkBf16Desc, BeamSelectDesc, BeamStepDesc, LstmStepDesc, RefineDesc, check)
+                   SoftmaxCeDesc, VocabTop1Desc, VocabTopkDesc, VocabTop1Bf16Desc, VocabTopkBf16Desc, VocabSampleDesc, VocabSampleBf16Desc, BeamSelectDesc, BeamStepDesc, LstmStepDesc, RefineDesc, check)
 
 
 def _stream():
@@ -1082,6 +1082,63 @@ def vocab_topk(X, W, bias, k, ids=None, probs=None, tile=None):
     ws, wsb = WORKSPACE.get(lib.dc_vocab_topk_workspace_bytes(M, V, k), X.device)
     check(lib.dc_vocab_topk_f32(C.byref(d), _ptr(ws), wsb, _stream()), "dc_vocab_topk_f32")
     return ids, probs
+
+
+def vocab_sample(X, W, bias=None, *, temperature=1.0, top_k=None, seed, offset=0, tokens=None, ids=None, probs=None, mask=None, tile=None):
+    """Fused Dense(V) + one draw per row from softmax((X W + bias) / temperature), by the Gumbel-max identity: the word
+    argmax_v (z_v / temperature + g(i, v)), the lower index on equal values, with g standard Gumbel noise that is a pure function of
+    (seed, offset + i, v) (Philox-2x32-10; include/dcap.h, dc_vocab_sample_f32) -- the same seed and offset draw the same words at every
+    M, tile and precision path, row i of a call is row 0 of a call at offset + i, and there is no generator state.  seed and offset are
+    integers in [0, 2^32); temperature a finite float > 0.  top_k (None, or 1..TOPK_MAX with V >= top_k) restricts the draw to the
+    row's top_k best words (vocab_topk's); top_k = 1 is vocab_top1, bit for bit.  Outputs as vocab_top1: tokens int32 [M], optional
+    strided ids / probs, optional mask; probs is the chosen word's softmax probability at temperature 1 over the whole vocabulary
+    (what vocab_top1 and vocab_topk report), not its probability under the sampling distribution.  The [M,V] logits are never
+    materialised.  Operands as vocab_top1 (float32, or bf16 with tile=; over the whole vocabulary bf16 runs on the 128 tile only).
+    Returns tokens."""
+    V = W.shape[1]                                      # the scalar arguments first: refused before any tensor is looked at
+    if isinstance(temperature, bool) or not isinstance(temperature, (int, float, np.floating, np.integer)) or \
+            not (np.isfinite(temperature) and temperature > 0):
+        raise _lib.DcapError("vocab_sample: temperature must be a finite float > 0, got %r" % (temperature,))
+    with np.errstate(over="ignore"):
+        inv_t = float(np.float32(1.0 / float(temperature)))
+    if not (np.isfinite(inv_t) and inv_t > 0):
+        raise _lib.DcapError("vocab_sample: 1 / temperature must be a finite float32 > 0, got temperature %r" % (temperature,))
+    if top_k is not None and (isinstance(top_k, bool) or not isinstance(top_k, (int, np.integer)) or not 1 <= top_k <= TOPK_MAX or top_k > V):
+        raise _lib.DcapError("vocab_sample: top_k must be None or an integer in 1..%d, at most V = %d, got %r" % (TOPK_MAX, V, top_k))
+    for name, v in (("seed", seed), ("offset", offset)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v < 2 ** 32:
+            raise _lib.DcapError("vocab_sample: %s must be an integer in [0, 2^32), got %r" % (name, v))
+    lib, M, K, V, bf = _vocab_args("vocab_sample", X, W, bias, tile)
+    if bf and tile == 256 and top_k is None:
+        raise _lib.DcapError("vocab_sample: sampling over the whole vocabulary (top_k=None) runs on the 128 x 128 tile only: pass tile=128 or "
+                             "None (the 256 x 256 bf16 tile has no sampling epilogue)")
+    if tokens is None:
+        tokens = torch.empty((M,), dtype=torch.int32, device=X.device)
+    if not _chk(tokens, torch.int32, "tokens").is_contiguous() or tokens.numel() != M:
+        raise _lib.DcapError("vocab_sample: tokens must be a contiguous int32 [M] tensor")
+    if mask is not None and (not _chk(mask, torch.uint8, "mask").is_contiguous() or mask.numel() != M):
+        raise _lib.DcapError("vocab_sample: mask must be a contiguous uint8 [M] tensor")
+    ids_p, ld_ids = _row_out(ids, M, torch.int32, "ids")
+    probs_p, ld_probs = _row_out(probs, M, torch.float32, "probs")
+    if M == 0:
+        return tokens
+    X, W, bias = _vocab_operands(X, W, bias)
+    d = VocabSampleBf16Desc() if bf else VocabSampleDesc()
+    d.M, d.V, d.K = M, V, K
+    d.X, d.ldx, d.W, d.ldw = X.data_ptr(), X.stride(0), W.data_ptr(), W.stride(0)
+    d.bias = _ptr(bias)
+    d.tokens = tokens.data_ptr()
+    d.ids, d.ld_ids, d.probs, d.ld_probs = ids_p, ld_ids, probs_p, ld_probs
+    d.mask = _ptr(mask)
+    d.inv_t, d.seed, d.offset, d.top_k = inv_t, int(seed), int(offset), int(top_k or 0)
+    if bf:
+        d.tile = int(tile or 0)
+        ws, wsb = WORKSPACE.get(lib.dc_vocab_sample_bf16_workspace_bytes(M, V, K, d.top_k, d.tile), X.device)
+        check(lib.dc_vocab_sample_bf16(C.byref(d), _ptr(ws), wsb, _stream()), "dc_vocab_sample_bf16")
+        return tokens
+    ws, wsb = WORKSPACE.get(lib.dc_vocab_sample_workspace_bytes(M, V, d.top_k), X.device)
+    check(lib.dc_vocab_sample_f32(C.byref(d), _ptr(ws), wsb, _stream()), "dc_vocab_sample_f32")
+    return tokens
 
 
 def _beam_args(fn, d, cand_ids, cand_probs, scores_in, scores_out, parents, tokens_hist, j, nb, log_score, tokens, mask, more=()):

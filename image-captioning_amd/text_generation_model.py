@@ -601,8 +601,8 @@ class CaptionModelV1(KerasLikeModel):
 
     @classmethod
     def check_decoder(cls, decoder, return_probabilities, vocab_math=None, compute_dtype=None, beam_size=None, score="logprob", end_id=None,
-                      postprocess="host"):
-        """decoder='incremental' and 'beam' never form the per-step [B,V] probability rows: they need return_probabilities=False.
+                      postprocess="host", temperature=None, top_k=None, seed=None):
+        """decoder='incremental', 'beam' and 'sampling' never form the per-step [B,V] probability rows: they need return_probabilities=False.
         decoder='beam' needs beam_size in 1..ops.TOPK_MAX (an integer, not a bool); score is 'logprob' (the sum of log p, the caption score
         of GenerationMatchLayer; the default) or 'prob' (the sum of p); end_id is None (fixed length T) or the end word's id >= 1.
         beam_size and end_id belong to 'beam' alone.
@@ -610,7 +610,10 @@ class CaptionModelV1(KerasLikeModel):
         their bf16 copies on the bf16 matrix pipe, the arithmetic a bf16 model trains that layer in): 'bf16' needs decoder='incremental'
         or 'beam' and a model that computes in bf16 (compute_dtype: the model's; only a bf16 model keeps the weight's bf16 mirror).
         postprocess (the joint model's generate_captions): 'host' or 'device'; 'device' works on the device decoders' buffers, so it needs
-        decoder='incremental' or 'beam' and return_probabilities=False."""
+        decoder='incremental' or 'beam' and return_probabilities=False.
+        decoder='sampling' (the incremental decoder drawing every word from the model's own distribution; vocab_math and postprocess as
+        for 'incremental') needs seed, an integer in [0, 2^32), and takes temperature (default 1.0: finite, > 0) and top_k (None or
+        1..ops.TOPK_MAX); the three belong to 'sampling' alone and are checked last.  Returns decoding.check_sampling's result."""
         decoding.check_decoder(decoder, beam_size, score, dict(end_id=end_id), score_for_beam_only=True, own=None if decoder == "prefix" or
                                return_probabilities is False else "decoder=%r returns no word probabilities: pass return_probabilities=False" % (decoder,))
         if decoder == "beam" and end_id is not None and (isinstance(end_id, bool) or int(end_id) != end_id or end_id < 1):
@@ -629,6 +632,7 @@ class CaptionModelV1(KerasLikeModel):
         if postprocess == "device" and (decoder == "prefix" or return_probabilities is not False):
             raise ValueError("postprocess='device' reads the device decoders' buffers: pass decoder='incremental' or 'beam' and "
                              "return_probabilities=False (got decoder=%r, return_probabilities=%r)" % (decoder, return_probabilities))
+        return decoding.check_sampling(decoder, temperature, top_k, seed)
 
     def decode_greedy(self, feat, vocab_math=None):
         """Greedy decoding of ROICaptionInferenceLayer (:192-232) ONE token per step, entirely on the device: the RoI head and the per-RoI
@@ -689,11 +693,27 @@ class CaptionModelV1(KerasLikeModel):
         # (a1.b: the bf16 copy the Dense-1024 GEMM's epilogue wrote; were that GEMM off the bf16 pipe, one cast of a1.f)
         return a1.b if ctx['vb'] else a1.f
 
-    def _decode_greedy(self, feat, vocab_math=None):
-        """decode_greedy into one int32 [2,B,T] device buffer: [0] the ids, [1] the word scores' float32 bits."""
+    def _decode_greedy(self, feat, vocab_math=None, sampling=None, offset0=0):
+        """decode_greedy into one int32 [2,B,T] device buffer: [0] the ids, [1] the word scores' float32 bits.  sampling: None, or
+        check_decoder's (temperature, top_k, seed) -- every word drawn, with the noise of offsets offset0 .. offset0 + B * T - 1."""
         feat = self._dev_feat(feat)
         B = feat.shape[0]
-        return decoding.greedy(B, self.T, self.device, lambda: self._decode_setup(feat, B, 'dec_', vocab_math))
+        if sampling is not None and sampling[1] is not None and sampling[1] > self.V:
+            raise ValueError("top_k %d exceeds the vocabulary (%d words)" % (sampling[1], self.V))
+        select = {} if sampling is None else dict(select=decoding.sampler(B, *sampling, offset0=offset0))
+        return decoding.greedy(B, self.T, self.device, lambda: self._decode_setup(feat, B, 'dec_', vocab_math), **select)
+
+    def decode_sampling(self, feat, seed, temperature=1.0, top_k=None, vocab_math=None):
+        """decode_greedy with every word DRAWN from the model's distribution instead of taken at its maximum (ops.vocab_sample: the
+        vocabulary layer fused with a Gumbel-max draw, no [B,V] logits): word j of RoI i is a draw from softmax(z / temperature), over
+        the whole vocabulary or (top_k in 1..ops.TOPK_MAX) over the row's top_k best words, with noise that is a pure function of
+        (seed, j * B + i, word) -- the same call twice returns the same captions; another seed, other captions.  top_k=1 is decode_greedy.
+        The drawn word is fed back as decode_greedy feeds its choice (a drawn 0 is masked).  word_scores are the model's softmax
+        probabilities of the drawn words at temperature 1, the quantity decode_greedy reports.  vocab_math as decode_greedy.
+        Returns device tensors (ids int32 [B,T], word_scores float32 [B,T]), two views of one buffer.  No host synchronisation."""
+        sampling = self.check_decoder("sampling", False, vocab_math, self.compute_dtype if vocab_math == "bf16" else None, temperature=temperature,
+                                      top_k=top_k, seed=seed)
+        return decoding.greedy_views(self._decode_greedy(feat, vocab_math, sampling))
 
     def decode_beam(self, feat, beam_size, score="logprob", end_id=None, vocab_math=None):
         """Beam search over ROICaptionInferenceLayer's decoder for every RoI at once, on the device.  Every beam starts from token 1; each
@@ -722,7 +742,8 @@ class CaptionModelV1(KerasLikeModel):
         B, T = feat.shape[0], self.T
         return B, k, T, decoding.beam(B, k, T, self.device, lambda: self._decode_setup(feat, k * B, 'bm_', vocab_math), score == "logprob", end_id)
 
-    def generate(self, feat, return_probabilities=None, decoder="prefix", vocab_math=None, beam_size=None, score="logprob", end_id=None):
+    def generate(self, feat, return_probabilities=None, decoder="prefix", vocab_math=None, beam_size=None, score="logprob", end_id=None,
+                 temperature=None, top_k=None, seed=None):
         """ROICaptionInferenceLayer (:192-232): start token 1; step j feeds [prev..., 0...] through the word
         model and appends float(argmax).  Returns (probs [B,T,V], ids [B,T]); with return_probabilities given (the joint
         model) returns (probs or None, ids, word_scores [B,T] = the probability of each chosen word).
@@ -730,9 +751,13 @@ class CaptionModelV1(KerasLikeModel):
         returning (None, ids, word_scores) through one device-to-host copy; 'prefix' (default): the reference's T-prefix loop below.
         decoder='beam' (needs return_probabilities=False and beam_size=k; score=, end_id=: see decode_beam) returns
         (None, tokens int32 [B,k,T], scores float32 [B,k]), best beam first, through one device-to-host copy.
+        decoder='sampling' (needs return_probabilities=False and seed=; temperature=, top_k=: see decode_sampling) returns what
+        'incremental' returns, for drawn words.
         vocab_math='bf16' (the device decoders of a bf16 model only): see decode_greedy; the default scores words in fp32."""
-        self.check_decoder(decoder, return_probabilities, vocab_math, getattr(self, "compute_dtype", None) if vocab_math == "bf16" else None,
-                           beam_size=beam_size, score=score, end_id=end_id)
+        sampling = self.check_decoder(decoder, return_probabilities, vocab_math, getattr(self, "compute_dtype", None) if vocab_math == "bf16" else None,
+                                      beam_size=beam_size, score=score, end_id=end_id, temperature=temperature, top_k=top_k, seed=seed)
+        if decoder == "sampling":
+            return (None,) + decoding.greedy_views(self._decode_greedy(feat, vocab_math, sampling).cpu().numpy())
         if decoder == "beam":
             B, k, T, out = self._decode_beam(feat, beam_size, score, end_id, vocab_math)
             return (None,) + decoding.beam_views(out.cpu().numpy(), B, k, T)

@@ -574,11 +574,13 @@ class CaptionModelV2(KerasLikeModel):
 
     # ---------------------------------------------------------------------------------- on-device decoding
     @classmethod
-    def check_decoder(cls, decoder, beam_size=None, start_ids=None, score="prob"):
+    def check_decoder(cls, decoder, beam_size=None, start_ids=None, score="prob", temperature=None, top_k=None, seed=None):
         """generate()'s argument rules (no GPU needed): a known decoder, beam_size in 1..8 with decoder='beam' only, no start_ids for
-        'prefix' (greedy_decode always starts from 0) and a known score rule."""
+        'prefix' (greedy_decode always starts from 0) and a known score rule; then those of decoder='sampling' (decoding.check_sampling,
+        whose result is returned): seed required, temperature and top_k optional, all three refused with any other decoder."""
         decoding.check_decoder(decoder, beam_size, score, own=None if decoder != "prefix" or start_ids is None else
                                "decoder='prefix' (greedy_decode) always starts from id 0: start_ids needs 'incremental' or 'beam'")
+        return decoding.check_sampling(decoder, temperature, top_k, seed)
 
     def _decode_steps(self, steps):
         """steps <= Tw: a carried state is the prefix path's state only while pad_sequences has truncated nothing."""
@@ -671,10 +673,24 @@ class CaptionModelV2(KerasLikeModel):
         views of one [2,R,steps] buffer.  No host synchronisation."""
         return decoding.greedy_views(self._decode_greedy(feat, steps, start_ids))
 
-    def _decode_greedy(self, feat, steps, start_ids):
+    def _decode_greedy(self, feat, steps, start_ids, sampling=None):
+        """sampling: None, or check_decoder's (temperature, top_k, seed): every word drawn."""
         steps = self._decode_steps(steps)
         feat = self._dev_feat(feat)
-        return decoding.greedy(feat.shape[0], steps, self.device, lambda: self._decode_call(feat, 1, start_ids))
+        R = feat.shape[0]
+        if sampling is not None and sampling[1] is not None and sampling[1] > self.V:
+            raise ValueError("top_k %d exceeds the vocabulary (%d words)" % (sampling[1], self.V))
+        select = {} if sampling is None else dict(select=decoding.sampler(R, *sampling))
+        return decoding.greedy(R, steps, self.device, lambda: self._decode_call(feat, 1, start_ids), **select)
+
+    def decode_sampling(self, feat, seed, steps=None, start_ids=None, temperature=1.0, top_k=None):
+        """decode_greedy with every word DRAWN from the model's distribution (ops.vocab_sample, a Gumbel-max draw fused into the
+        vocabulary layer): word j of RoI i is a draw from softmax(z / temperature), over the whole vocabulary or over the row's top_k
+        (1..ops.TOPK_MAX) best words, with noise that is a pure function of (seed, j * R + i, word): the same call twice returns the same
+        captions.  top_k=1 is decode_greedy.  word_scores are the model's softmax probabilities of the drawn words at temperature 1.
+        Returns device tensors as decode_greedy.  No host synchronisation."""
+        sampling = self.check_decoder("sampling", None, start_ids, temperature=temperature, top_k=top_k, seed=seed)
+        return decoding.greedy_views(self._decode_greedy(feat, steps, start_ids, sampling))
 
     def decode_beam(self, feat, beam_size, steps=None, start_ids=None, score="prob"):
         """Beam search of the authors' captioner (image captioning/test.py:23-64) over the v2 decoders, for every RoI at once on the
@@ -698,14 +714,14 @@ class CaptionModelV2(KerasLikeModel):
         R = feat.shape[0]
         return R, k, steps, decoding.beam(R, k, steps, self.device, lambda: self._decode_call(feat, k, start_ids), score == "logprob")
 
-    def generate(self, feat, steps=None, decoder="prefix", beam_size=None, start_ids=None, score="prob"):
+    def generate(self, feat, steps=None, decoder="prefix", beam_size=None, start_ids=None, score="prob", temperature=None, top_k=None, seed=None):
         """Caption every RoI of feat [R,7,7,256].  decoder='prefix': greedy_decode per RoI (the reference's loop: the whole model on
         the pre-padded prefix per token); 'incremental': decode_greedy; both return numpy (ids int32 [R,steps], word_scores float32
         [R,steps]).  'beam': decode_beam, returning numpy (tokens int32 [R,k,steps], scores float32 [R,k]).  The device decoders make
         one device-to-host copy."""
-        self.check_decoder(decoder, beam_size, start_ids, score)
-        if decoder == "incremental":
-            return decoding.greedy_views(self._decode_greedy(feat, steps, start_ids).cpu().numpy())
+        sampling = self.check_decoder(decoder, beam_size, start_ids, score, temperature=temperature, top_k=top_k, seed=seed)
+        if decoder in ("incremental", "sampling"):                  # 'sampling' (seed=, temperature=, top_k=): decode_sampling
+            return decoding.greedy_views(self._decode_greedy(feat, steps, start_ids, sampling).cpu().numpy())
         if decoder == "beam":
             R, k, steps, out = self._decode_beam(feat, beam_size, steps, start_ids, score)
             return decoding.beam_views(out.cpu().numpy(), R, k, steps)

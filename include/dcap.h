@@ -685,6 +685,69 @@ int    dc_vocab_top1_bf16(const dc_vocab_top1_bf16_desc* d, void* workspace, siz
 int    dc_vocab_topk_bf16(const dc_vocab_topk_bf16_desc* d, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Vocabulary projection FUSED with a draw from the model's own word distribution (stochastic decoding), by the Gumbel-max
+ * identity: argmax_v (z_v / t + g_v) with g_v i.i.d. standard Gumbel is an exact draw from softmax(z / t).  The [M,V] logits
+ * z = X W + bias are never written; the draw is one more reduction of the tile epilogue.  The reference never samples: this
+ * contract is defined here and restated in float64 by the tests.
+ *   What is drawn: for row i the word argmax_v fma(z_v, inv_t, g(i, v)) (one fused multiply-add in fp32), the LOWER column on
+ *   equal values.  inv_t = 1 / temperature (finite, > 0).  A NaN logit never wins; a row with no orderable logit yields id 0,
+ *   as the top-1 entry points do.
+ *   The noise is counter-based: (r0, r1) = Philox-2x32-10 with counter (v >> 1, offset + i (32-bit wrapping)) and key seed, both
+ *   output words kept; r = (v & 1) ? r1 : r0;  u = ((r >> 9) + 0.5) * 2^-23 (exact in fp32, in [2^-24, 1 - 2^-24]);
+ *   g = -logf(-logf(u)) with the accurate logf.  g is a pure function of (seed, offset + i, v): it does not depend on M, the
+ *   tile shape, the grid, the precision of the operands or the call, so rows [a, b) of a call equal a call on those rows
+ *   with offset + a, and a caller that decodes step j over n rows passes offset0 + j * n.
+ *   probs: the probability the model gives the chosen word at temperature 1 over the whole vocabulary,
+ *   exp(z_w - m) / s with m, s the row's maximum and sum of exp(z - m) over the UNPERTURBED logits (the tile epilogue's
+ *   arithmetic of the top-k kernels): the quantity the greedy and beam entry points report.
+ *   top_k: 0 = the whole vocabulary; 1..8 (V >= top_k) = the draw is restricted to the row's top_k best words, in the order the
+ *   top-k entry points return them: the same g(i, v) is added to those candidates' z * inv_t and the best taken.  probs keeps
+ *   its meaning.  top_k = 1 is greedy: the top-1 entry point's ids and probabilities bit for bit.
+ *   Outputs, operand rules, strides: as the top-1 entry points (tokens [M], optional ids / probs with a row stride, optional
+ *   mask [M] = id != 0).
+ * Kernels: top_k = 0 runs the 128 x 128 tile loop of the top-1 kernels (fp32 MFMA, or bf16 on bgemm_core.h's loop) into an
+ * epilogue that writes, per (row, 128-column tile), a cell of three float2: (max, sum exp) of the unperturbed logits, the tile's
+ * best perturbed pair (y, column (int bits); INT_MAX = none) and that column's unperturbed logit.  A row kernel (one wave per
+ * row) reduces the cells in an order fixed by the tile count alone.  The bf16 256 x 256 tile has no sampling epilogue: tile = 256
+ * with top_k = 0 is refused, 0 means 128.  top_k >= 1 runs the top-k tile kernel unchanged (bf16: tile as there) and a row
+ * kernel that perturbs the k row winners.  Ordinary launches on the caller's stream, capturable.
+ * Workspace: dc_vocab_sample_workspace_bytes(M, V, top_k): 24 bytes per row and tile at top_k = 0, else the top-k workspace.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct {
+    int M, V, K;
+    const float* X;  int ldx;
+    const float* W;  int ldw;
+    const float* bias;
+    int32_t* tokens;
+    int32_t* ids;    int ld_ids;
+    float* probs;    int ld_probs;
+    uint8_t* mask;
+    float inv_t;
+    uint32_t seed, offset;
+    int top_k;
+} dc_vocab_sample_desc;
+
+typedef struct {
+    int M, V, K;
+    const void* X;   int ldx;
+    const void* W;   int ldw;
+    const float* bias;
+    int32_t* tokens;
+    int32_t* ids;    int ld_ids;
+    float* probs;    int ld_probs;
+    uint8_t* mask;
+    int tile;
+    float inv_t;
+    uint32_t seed, offset;
+    int top_k;
+} dc_vocab_sample_bf16_desc;
+
+size_t dc_vocab_sample_workspace_bytes(int M, int V, int top_k);
+size_t dc_vocab_sample_bf16_workspace_bytes(int M, int V, int K, int top_k, int tile);
+int    dc_vocab_sample_f32(const dc_vocab_sample_desc* d, void* workspace, size_t workspace_bytes, void* stream);
+int    dc_vocab_sample_bf16(const dc_vocab_sample_bf16_desc* d, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * One beam-search step for R RoIs with k beams each (image captioning/test.py:33-56).  Rows of the per-beam
  * tensors are BEAM-MAJOR: beam b of RoI r is row b * R + r.
  *   cand_ids / cand_probs [k*R][k]: dc_vocab_topk_f32's output for every beam row;  nb: live beams (1 at the first step, then k);

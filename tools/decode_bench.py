@@ -29,6 +29,15 @@ least 5) and max - min spreads.  Then ops.refine_generations alone on random RoI
 new argument, so the same file measures an older checkout of the package (profiles/refine_generations_bench.json).
 
     python tools/decode_bench.py --what refine --out profiles/refine_generations_bench.json
+
+--what sampling: decoder='sampling' (ops.vocab_sample, the Gumbel-max draw fused into the vocabulary GEMM) over the whole vocabulary and
+at top_k = 5 against decoder='incremental' of the same build, on the fp32 model and on the bf16 model with vocab_math='bf16', at both
+shapes; the bf16 model also with the incremental decoder held to the 128 x 128 tile (the sampler's full-vocabulary epilogue exists on
+that tile alone; the default tile at these shapes is 256 x 256).  The legs alternate call by call in one process; device events and
+wall clock, medians of --repeats (at least 5) with max - min spreads, and each leg's cost over the incremental one per decoded token.
+Then the fused vocabulary kernels alone at the step's shape (profiles/sampling_decode_bench.json).
+
+    python tools/decode_bench.py --what sampling --out profiles/sampling_decode_bench.json
 """
 import argparse
 import json
@@ -255,6 +264,60 @@ def refine_legs(args, shapes, rows):
         print(json.dumps(rows[-1]), flush=True)
 
 
+def sampling_legs(args, shapes, rows):
+    """--what sampling: the sampling decoder against the incremental one, then the fused vocabulary kernels alone at the step's shape."""
+    from image_captioning_amd import decoding, ops
+    reps, warm = max(args.repeats, 5), max(args.warmup, 1)
+    for key in args.shapes.split(","):
+        sh = shapes[key]
+        for dtype in args.dtypes.split(","):
+            model = model_for(sh["V"], sh["T"], sh["K"], sh["units"], dtype)
+            feat = torch.tensor(np.random.default_rng(1).standard_normal((sh["K"], 7, 7, 256)).astype(np.float32), device="cuda:0")
+            vm = "bf16" if dtype == "bf16" else None
+            gen = lambda **kw: model.generate(feat, return_probabilities=False, vocab_math=vm, **kw)
+            legs = [(dict(decoder="incremental"), lambda: gen(decoder="incremental")),
+                    (dict(decoder="sampling", top_k=None), lambda: gen(decoder="sampling", seed=1)),
+                    (dict(decoder="sampling", top_k=5), lambda: gen(decoder="sampling", seed=1, top_k=5))]
+            if vm:                                          # the greedy decoder held to the 128 tile, the one the sampler's epilogue exists on
+                def top1_128(j, x, W, bias, **out):
+                    ops.vocab_top1(x, W, bias, tile=128, **out)
+                B = sh["K"]
+                legs.append((dict(decoder="incremental", tile=128), lambda: decoding.greedy_views(
+                    decoding.greedy(B, model.T, model.device, lambda: model._decode_setup(feat, B, 'dec_', vm), select=top1_128).cpu().numpy())))
+            res = timed_alternating_wall([fn for _, fn in legs], warm, reps)
+            inc = res[0][0]
+            for (kw, _), (ems, eall, wms, wall) in zip(legs, res):
+                rows.append(dict(what="decode_per_image", shape=sh["name"], dtype=dtype, vocab_math=vm or "f32", K=sh["K"], T=sh["T"], V=sh["V"],
+                                 units=sh["units"], event_ms=round(ems, 3), event_spread_ms=round(max(eall) - min(eall), 3), wall_ms=round(wms, 3),
+                                 wall_spread_ms=round(max(wall) - min(wall), 3), times_incremental=round(ems / inc, 3),
+                                 over_incremental_us_per_token=round((ems - inc) * 1e3 / (sh["K"] * sh["T"]), 4), event_runs_ms=eall, wall_runs_ms=wall,
+                                 timing="median of %d, legs alternating call by call" % reps, **kw))
+                print(json.dumps(rows[-1]), flush=True)
+            del model
+            torch.cuda.empty_cache()
+        # the fused vocabulary kernels alone, at the decode step's shape (M = K live rows, 1024 inputs), on fp32 and bf16 operands
+        M_, Kd, V = sh["K"], 1024, sh["V"]
+        rng = np.random.default_rng(2)
+        X = torch.tensor(rng.standard_normal((M_, Kd)).astype(np.float32), device="cuda:0")
+        W = torch.tensor((rng.standard_normal((Kd, V)) / 32).astype(np.float32), device="cuda:0")
+        b = torch.zeros(V, dtype=torch.float32, device="cuda:0")
+        tok = torch.empty(M_, dtype=torch.int32, device="cuda:0")
+        for dtype, (Xo, Wo) in (("f32", (X, W)), ("bf16", (X.to(torch.bfloat16), W.to(torch.bfloat16)))):
+            tiles = ((None, None),) if dtype == "f32" else ((128, 128), (None, ops.vocab_topk_bf16_tile(M_, V, Kd)))
+            legs = [(dict(op="vocab_top1", tile=run), lambda t=t: ops.vocab_top1(Xo, Wo, b, tokens=tok, tile=t)) for t, run in tiles]
+            legs.append((dict(op="vocab_sample", top_k=None, tile=None if dtype == "f32" else 128), lambda: ops.vocab_sample(Xo, Wo, b, seed=1, tokens=tok)))
+            legs += [(dict(op="vocab_sample", top_k=5, tile=run), lambda t=t: ops.vocab_sample(Xo, Wo, b, seed=1, top_k=5, tokens=tok, tile=t))
+                     for t, run in tiles]
+            res = timed_alternating([fn for _, fn in legs], 3, 20)
+            for (kw, _), (ms, all_ms) in zip(legs, res):
+                rows.append(dict(what="vocab_step_alone", shape=sh["name"], dtype=dtype, M=M_, K=Kd, V=V, ms=round(ms, 4),
+                                 spread_ms=round(max(all_ms) - min(all_ms), 4), times_first_leg=round(ms / res[0][0], 3),
+                                 timing="device events, median of 20, legs alternating", runs_ms=all_ms, **kw))
+                print(json.dumps(rows[-1]), flush=True)
+        del X, W
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=5)
@@ -262,8 +325,9 @@ def main():
     ap.add_argument("--out", default=None, help="JSON file for all rows (default: print only)")
     ap.add_argument("--shapes", default="c4,c2")
     ap.add_argument("--dtypes", default="f32,bf16")
-    ap.add_argument("--what", default="greedy", choices=("greedy", "beam", "refine"),
-                    help="greedy: prefix / incremental (default); beam: the beam decoder; refine: generate_captions' post-processing on the host / device")
+    ap.add_argument("--what", default="greedy", choices=("greedy", "beam", "refine", "sampling"),
+                    help="greedy: prefix / incremental (default); beam: the beam decoder; refine: generate_captions' post-processing on the host / device; "
+                         "sampling: the sampling decoder against the incremental one")
     ap.add_argument("--legs", default="both", choices=("both", "host"), help="--what refine: both legs (default) or the host leg alone")
     args = ap.parse_args()
     from image_captioning_amd import ops
@@ -275,6 +339,8 @@ def main():
         beam_legs(args, shapes, rows)
     if args.what == "refine":
         refine_legs(args, shapes, rows)
+    if args.what == "sampling":
+        sampling_legs(args, shapes, rows)
     for key in args.shapes.split(",") if args.what == "greedy" else ():
         sh = shapes[key]
         for dtype in args.dtypes.split(","):
