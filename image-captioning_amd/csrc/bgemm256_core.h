@@ -410,6 +410,7 @@ int launch(const BOperand& a, const BOperand& b, const Epilogue& ep, int M, int 
     if (sp.split > 1) {
         const size_t need = (size_t)sp.split * M * N * sizeof(float);
         DC_REQUIRE(workspace != nullptr && workspace_bytes >= need, DC_EWORKSPACE, "bgemm256 split-K needs %zu workspace bytes, got %zu", need, workspace_bytes);
+        DC_REQUIRE_SLAB_ALIGNED("bgemm256 split-K", workspace, N);
         partial = static_cast<float*>(workspace);
     }
     DC_ENSURE_DYN_LDS((&bgemm256_kernel<AKC, BKC>), 160 * 1024);

@@ -365,6 +365,7 @@ int launch_bgemm(const BOperand& a, const BOperand& b, const Epilogue& ep, int M
         const size_t need = (size_t)sp.split * M * N * sizeof(float);
         DC_REQUIRE(workspace != nullptr && workspace_bytes >= need, DC_EWORKSPACE, "bgemm split-K needs %zu workspace bytes, got %zu", need,
                    workspace_bytes);
+        DC_REQUIRE_SLAB_ALIGNED("bgemm split-K", workspace, N);
         partial = static_cast<float*>(workspace);
     }
     DC_ENSURE_DYN_LDS((&bgemm_kernel<AKC, BKC>), 160 * 1024);

@@ -281,6 +281,7 @@ extern "C" int dc_conv2d_bf16(const dc_conv_bf16_desc* d, void* workspace, size_
         const size_t need = (size_t)sp.split * M * N * sizeof(float);
         DC_REQUIRE(workspace != nullptr && workspace_bytes >= need, DC_EWORKSPACE, "dc_conv2d_bf16 split-K needs %zu workspace bytes, got %zu", need,
                    workspace_bytes);
+        DC_REQUIRE_SLAB_ALIGNED("dc_conv2d_bf16 split-K", workspace, N);
         partial = static_cast<float*>(workspace);
     }
     Epilogue ep{d->y, d->Cout, d->scale, d->shift, d->residual, d->Cout, d->res_mode, d->Ho, d->Wo, d->relu, 0, 0};

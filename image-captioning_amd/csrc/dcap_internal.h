@@ -53,6 +53,11 @@ inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 
         }                                      \
     } while (0)
 
+// Split-K slabs [splits][M][N] live in the caller's workspace.  With N % 4 == 0 the main loop stores them 16 bytes at a time
+// (store_tile), so that workspace must sit on a 16-byte boundary; with a ragged N every slab access is scalar, on any 4-byte boundary.
+#define DC_REQUIRE_SLAB_ALIGNED(who, ws, N) \
+    DC_REQUIRE(((N) & 3) != 0 || ::dcap::aligned16(ws), DC_EALIGN, "%s: the workspace must be 16-byte aligned when N is a multiple of 4", who)
+
 constexpr int kNumCU = 256;   // MI355X: 8 XCDs x 32 CUs
 constexpr int kNumXCD = 8;
 

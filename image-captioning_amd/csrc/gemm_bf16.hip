@@ -248,6 +248,7 @@ extern "C" int dc_conv2d_wgrad_bf16(const dc_conv_wgrad_bf16_desc* d, void* work
         const size_t need = (size_t)sp.split * M * N * sizeof(float);
         DC_REQUIRE(workspace != nullptr && workspace_bytes >= need, DC_EWORKSPACE, "dc_conv2d_wgrad_bf16 split-K needs %zu workspace bytes, got %zu",
                    need, workspace_bytes);
+        DC_REQUIRE_SLAB_ALIGNED("dc_conv2d_wgrad_bf16 split-K", workspace, N);
         partial = static_cast<float*>(workspace);
     }
     Epilogue ep{d->dw, N, nullptr, nullptr, nullptr, 0, 0, 0, 0, 0, d->accumulate, 1};

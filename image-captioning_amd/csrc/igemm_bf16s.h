@@ -230,6 +230,7 @@ int launch_igemm_bs(const AL& al, const BL& bl, const Epilogue& ep, int M, int N
         const size_t need = (size_t)split_k * M * N * sizeof(float);
         DC_REQUIRE(workspace != nullptr && workspace_bytes >= need, DC_EWORKSPACE,
                    "igemm split-K needs %zu workspace bytes, got %zu", need, workspace_bytes);
+        DC_REQUIRE_SLAB_ALIGNED("igemm_bs split-K", workspace, N);
         partial = static_cast<float*>(workspace);
     }
     constexpr size_t lds = igemm_bs_lds_bytes<BM, BN, NP>();

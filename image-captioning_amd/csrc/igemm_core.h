@@ -1040,6 +1040,7 @@ int launch_igemm(const AL& al, const BL& bl, const Epilogue& ep, int M, int N, i
         const size_t need = (size_t)split_k * M * N * sizeof(float);
         DC_REQUIRE(workspace != nullptr && workspace_bytes >= need, DC_EWORKSPACE,
                    "igemm split-K needs %zu workspace bytes, got %zu", need, workspace_bytes);
+        DC_REQUIRE_SLAB_ALIGNED("igemm split-K", workspace, N);
         partial = static_cast<float*>(workspace);
     }
     constexpr size_t lds = PC ? igemm_pc_lds_bytes<BM, BN, AL, BL>() : igemm_lds_bytes<BM, BN, AL, BL>();

@@ -609,6 +609,10 @@ extern "C" size_t dc_lstm_seq_workspace_bytes(int B, int T, int U) {
 extern "C" int dc_lstm_seq_fwd_f32(const dc_lstm_fwd_desc* d, void* workspace, size_t workspace_bytes, void* stream) {
     DC_REQUIRE(d && d->z && d->U_rec && d->h_seq && d->c_seq, DC_EINVAL, "dc_lstm_seq_fwd: null pointer");
     DC_REQUIRE(d->B > 0 && d->T > 0 && d->U > 0 && (d->U & 3) == 0, DC_EINVAL, "dc_lstm_seq_fwd: bad B/T/U (U %% 4 == 0)");
+    // h_{t-1}, the masks and the repacked U_rec (in the workspace) are read 16 bytes at a time by the fused steps; the unfused steps hand
+    // h_{t-1} and U_rec to dc_gemm_f32 from step 1 on: refused here, before the first launch
+    DC_REQUIRE(aligned16(d->U_rec) && aligned16(d->h_seq) && (!d->rec_masks || aligned16(d->rec_masks)) && aligned16(workspace), DC_EALIGN,
+               "dc_lstm_seq_fwd: U_rec, h_seq, rec_masks and the workspace must be 16-byte aligned");
     DC_REQUIRE(workspace_bytes >= dc_lstm_seq_workspace_bytes(d->B, d->T, d->U) && (workspace || workspace_bytes == 0),
                DC_EWORKSPACE, "dc_lstm_seq_fwd: workspace too small");
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -686,6 +690,10 @@ extern "C" int dc_lstm_seq_fwd_f32(const dc_lstm_fwd_desc* d, void* workspace, s
 extern "C" int dc_lstm_seq_bwd_f32(const dc_lstm_bwd_desc* d, void* workspace, size_t workspace_bytes, void* stream) {
     DC_REQUIRE(d && d->z && d->U_rec && d->h_seq && d->c_seq && d->dz, DC_EINVAL, "dc_lstm_seq_bwd: null pointer");
     DC_REQUIRE(d->B > 0 && d->T > 0 && d->U > 0 && (d->U & 3) == 0, DC_EINVAL, "dc_lstm_seq_bwd: bad B/T/U (U %% 4 == 0)");
+    // dz_{t+1} and U_rec are read 16 bytes at a time by the fused step; h_seq, dz, U_rec and buffers inside the workspace are dc_gemm_f32
+    // operands of later steps: refused here, before the first launch (rec_masks is read element by element)
+    DC_REQUIRE(aligned16(d->U_rec) && aligned16(d->h_seq) && aligned16(d->dz) && aligned16(workspace), DC_EALIGN,
+               "dc_lstm_seq_bwd: U_rec, h_seq, dz and the workspace must be 16-byte aligned");
     DC_REQUIRE(workspace && workspace_bytes >= dc_lstm_seq_workspace_bytes(d->B, d->T, d->U), DC_EWORKSPACE,
                "dc_lstm_seq_bwd: workspace too small");
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -805,6 +813,8 @@ extern "C" int dc_lstm_step_f32(const dc_lstm_step_desc* d, void* workspace, siz
     DC_REQUIRE(d->B > 0 && d->U > 0 && (d->U & 3) == 0, DC_EINVAL, "dc_lstm_step: bad B/U (U %% 4 == 0)");
     DC_REQUIRE((d->h_prev == nullptr) == (d->c_prev == nullptr), DC_EINVAL, "dc_lstm_step: h_prev and c_prev are both given or both NULL");
     DC_REQUIRE(d->h != d->h_prev && d->c != d->c_prev && d->h != d->c, DC_EINVAL, "dc_lstm_step: h / c must not alias h_prev / c_prev / each other");
+    // the fused step reads h_prev 16 bytes at a time (U_packed and U_rec element by element; the unfused step's dc_gemm_f32 is its first launch)
+    DC_REQUIRE(aligned16(d->h_prev), DC_EALIGN, "dc_lstm_step: h_prev must be 16-byte aligned");
     const size_t need = dc_lstm_step_workspace_bytes(d->B, d->U);
     DC_REQUIRE(workspace_bytes >= need && (workspace || need == 0), DC_EWORKSPACE, "dc_lstm_step: needs %zu workspace bytes, got %zu", need, workspace_bytes);
     hipStream_t s = static_cast<hipStream_t>(stream);

@@ -12,7 +12,8 @@
  *   - plain pointers and sizes only; every pointer is DEVICE memory owned by the caller;
  *   - enqueue-only on `stream` (a hipStream_t passed as void*): no allocation, no synchronisation,
  *     safe under hipGraph stream capture; stateless and re-entrant on distinct streams;
- *   - scratch memory is a caller-provided workspace; dc_*_workspace_bytes() gives the size;
+ *   - scratch memory is a caller-provided workspace; dc_*_workspace_bytes() gives the size; a workspace that receives split-K
+ *     slabs (the GEMMs and convolutions) sits on a 16-byte boundary unless the output width N is not a multiple of 4 (DC_EALIGN);
  *   - tensors are row-major, activations NHWC, float32 unless stated.
  */
 #ifndef DCAP_H
@@ -461,6 +462,9 @@ int dc_downsample2x_sum_dual_f32(const float* fine, float* out, uint16_t* out_bf
  *   masked rows (mask[t*B+b]==0) carry h,c from t-1 (zeros before the first unmasked step).
  * zx is updated IN PLACE to the full pre-activation z (saved for backward).
  *   z [T*B][4U] in/out, U_rec [U][4U], mask [T*B] uint8 or NULL, h_seq/c_seq [T*B][U] out.
+ *   Forward: U_rec, h_seq, rec_masks and the workspace are 16-byte aligned; backward: U_rec, h_seq, dz and the workspace; the single
+ *   step: h_prev.  A fused step reads them 16 bytes at a time or a later step hands them to dc_gemm_f32 as A / B: DC_EALIGN before
+ *   the first launch otherwise.
  * ------------------------------------------------------------------------------------------------ */
 typedef struct {
     int B, T, U;
