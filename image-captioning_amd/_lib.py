@@ -191,6 +191,14 @@ class RefineDesc(C.Structure):
                 ("boxes_out", C.c_void_p), ("keep_out", C.c_void_p), ("count_out", C.c_void_p), ("scores_out", C.c_void_p)]
 
 
+RESIZE_RECORD_INTS = 8    # DC_RESIZE_RECORD_INTS: int32 words per image at the head of ResizePadDesc.packed
+
+
+class ResizePadDesc(C.Structure):
+    _fields_ = [("B", C.c_int), ("packed", C.c_void_p), ("packed_bytes", C.c_size_t), ("records", C.c_void_p),
+                ("out", C.c_void_p), ("H", C.c_int), ("W", C.c_int)]
+
+
 class RpnLossDesc(C.Structure):
     _fields_ = [("levels", C.c_int), ("anchors_per_loc", C.c_int), ("head_stride", C.c_int),
                 ("heads", C.c_void_p * 5), ("dheads", C.c_void_p * 5), ("Hs", C.c_int * 5), ("Ws", C.c_int * 5),
@@ -269,6 +277,8 @@ SYMBOLS = {
     "dc_mold_image_padded_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_void_p]),
     "dc_mold_image_rgbx_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                          C.c_float, C.c_float, C.c_float, C.c_void_p]),
+    "dc_resize_pad_u8_workspace_bytes": (C.c_size_t, [C.POINTER(ResizePadDesc)]),
+    "dc_resize_pad_u8": (C.c_int, [C.POINTER(ResizePadDesc), C.c_void_p, C.c_size_t, C.c_void_p]),
     "dc_roi_align_pyramid_f32": (C.c_int, [C.POINTER(RoiAlignDesc), C.c_void_p]),
     "dc_roi_tile_groups": (C.c_int, [C.POINTER(RoiGroupsDesc), C.c_void_p]),
     "dc_conv2d_winograd_group_count": (C.c_int, [C.c_int, C.c_int]),

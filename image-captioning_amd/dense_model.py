@@ -1275,8 +1275,14 @@ class DenseImageCapRCNN(object):
             windows.append(window)
         return np.stack(molded), np.stack(metas), np.stack(windows)
 
+    def _mold_device(self, p, images):
+        """mold='device': the plan's image buffer written by EncoderPlan.mold_images; returns mold_inputs' windows."""
+        cfg = self.config
+        geo = p.mold_images(images, cfg.IMAGE_MIN_DIM, cfg.IMAGE_MAX_DIM, cfg.IMAGE_PADDING)
+        return np.stack([g[2] for g in geo])
+
     def generate_captions(self, images, verbose=0, return_probabilities=True, decoder="prefix", vocab_math=None, beam_size=None, score="logprob",
-                          end_id=None, postprocess="host", temperature=None, top_k=None, seed=None):
+                          end_id=None, postprocess="host", temperature=None, top_k=None, seed=None, mold="host"):
         """The inference graph (:1602-1622) + generate_captions (:1964-2003): RPN proposals (POST_NMS_ROIS_INFERENCE) ->
         RoI features -> greedy ROICaptionInferenceLayer -> GenerationMatchLayer -> boxes in the original image.
         Returns [{'rois': int32 [K,4], 'captions': f32 [K,T,V] word probabilities, 'ids': int32 [K,T]}]; with
@@ -1299,17 +1305,27 @@ class DenseImageCapRCNN(object):
         decode calls one after another without waiting, ONE ops.refine_generations for the batch on the decoder's device buffers, a
         device gather of the survivors' captions and ONE device-to-host copy for the batch; nothing synchronises between the image upload and that copy.  The same
         results, bit for bit (the float64 operations of the host path in its order; equal caption scores are ordered as
-        np.argsort(kind='stable')[::-1] orders them, where NumPy's default sort promises no order)."""
+        np.argsort(kind='stable')[::-1] orders them, where NumPy's default sort promises no order).
+        mold='host' (default): mold_inputs -- utils.resize_image on the host (PIL, np.pad, np.stack), the molded batch uploaded.
+        'device' (uint8 [h,w,3] images, IMAGE_PADDING on): the raw images are uploaded and EncoderPlan.mold_images resamples them into
+        the plan's image buffer with PIL's integer arithmetic, so every result is the host path's bit for bit; windows and metas come
+        from utils.resize_geometry.  Works with every decoder and both postprocess paths."""
         sampling = CaptionModelV1.check_decoder(decoder, return_probabilities, vocab_math,
                                                 getattr(self, "compute_dtype", None) if vocab_math == "bf16" else None, beam_size=beam_size, score=score,
-                                                end_id=end_id, postprocess=postprocess, temperature=temperature, top_k=top_k, seed=seed)
+                                                end_id=end_id, postprocess=postprocess, temperature=temperature, top_k=top_k, seed=seed, mold=mold)
+        if mold == "device":
+            images = [utils.check_device_mold_image(im) for im in images]
         assert self.mode == "inference", "Create model in inference mode."
         assert len(images) == self.config.BATCH_SIZE, "len(images) must be equal to BATCH_SIZE"
-        molded, metas, windows = self.mold_inputs(images)
         p = self.plan()
+        if mold == "device":
+            molded, windows = None, self._mold_device(p, images)
+        else:
+            molded, metas, windows = self.mold_inputs(images)
+            molded = torch.as_tensor(molded)
         if postprocess == "device":
             return self._generate_captions_device(p, images, molded, windows, decoder, vocab_math, beam_size, score, end_id, sampling)
-        p.forward(torch.as_tensor(molded))
+        p.forward(molded)
         proposals = p.proposals()
         self.last_proposals = proposals
         feats = p.roi_features(boxes_norm=proposals)
@@ -1345,7 +1361,7 @@ class DenseImageCapRCNN(object):
         cfg, cm, B = self.config, self.caption_model, len(images)
         consts = np.stack([refine_constants(windows[b], cfg, images[b].shape) for b in range(B)])
         consts = torch.as_tensor(consts).to(p.device)       # before the image upload: the stream is idle, nothing waits on this copy
-        p.forward(torch.as_tensor(molded))
+        p.forward(molded)                                   # (mold='device': None, the plan's image buffer is already written)
         proposals = p.proposals()
         self.last_proposals = proposals
         feats = p.roi_features(boxes_norm=proposals)

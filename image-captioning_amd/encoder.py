@@ -557,6 +557,19 @@ class EncoderPlan:
         self._run_part("all", self._run_ops)
         return self.P
 
+    def mold_images(self, images, min_dim, max_dim, padding=True):
+        """mold='device': the raw uint8 [h,w,3] images of one batch (any sizes) resized and zero-padded as utils.resize_image does it,
+        straight into self.images (ops.resize_pad_images: one upload of the raw bytes, every byte of the buffer written); follow
+        with forward() / forward_rois(None, ...).  Returns utils.resize_geometry's tuple per image."""
+        from . import utils
+        utils.check_mold("device", padding)
+        if len(images) != self.B or max_dim != self.H or max_dim != self.W:
+            raise ValueError("mold_images: this plan reads %d images of %d x %d, got %d images for max_dim %r; pass mold=\"host\""
+                             % (self.B, self.H, self.W, len(images), max_dim))
+        geo = [utils.resize_geometry(utils.check_device_mold_image(im).shape, min_dim, max_dim, True) for im in images]
+        ops.resize_pad_images(images, placements=[(g[0], g[1], g[2][0], g[2][1]) for g in geo], out=self.images)
+        return geo
+
     # The pass in two halves, for a caller that runs the frozen backbone of the NEXT batch beside the rest of this batch's step
     # (pipeline.JointTrainPipeline): forward_trunk() = image -> C2..C5 (reads nothing a train step changes when no ResNet stage is
     # trainable), forward_top() = the FPN and the RPN on the C maps of the last forward_trunk().  Each half is its own hipGraph;

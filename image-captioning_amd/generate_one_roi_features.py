@@ -6,6 +6,7 @@ import os
 
 import numpy as np
 
+from . import utils
 from .config import Config
 from .modified_dense_model import DenseImageCapRCNN
 
@@ -33,15 +34,19 @@ def load_model(weights=None, model_path=None, **kw):
     return model
 
 
-def generate_features(dataset, image_id, model, device_features=False):
+def generate_features(dataset, image_id, model, device_features=False, mold="host"):
     """[N,7,7,256] features of the image's ground-truth regions (one batch of one image); device_features=True: a torch
-    tensor that stays on the GPU (text_generation_model_v2.data_generator(device_resident=True))."""
+    tensor that stays on the GPU (text_generation_model_v2.data_generator(device_resident=True)); mold='device': the image is
+    resized on the GPU (DenseImageCapRCNN.generate_captions), the same features bit for bit."""
+    utils.check_mold(mold)
     boxes = dataset.load_captions_and_rois(image_id)[0]
     kw = {"device_features": True} if device_features else {}          # (feature models with the reference's plain signature keep working)
+    if mold != "host":
+        kw["mold"] = mold
     out = model.generate_captions([dataset.load_image(image_id)], boxes[np.newaxis], verbose=0, **kw)
     return out[0]['features']
 
 
-def generate_image_level_features(dataset, image_id, model):
+def generate_image_level_features(dataset, image_id, model, mold="host"):
     """feature_generation/generate_roi_features.py: np.mean(features, axis=0).flatten()."""
-    return np.mean(generate_features(dataset, image_id, model), axis=0).flatten()
+    return np.mean(generate_features(dataset, image_id, model, mold=mold), axis=0).flatten()

@@ -5,6 +5,7 @@ import os
 
 import numpy as np
 
+from . import utils
 from .config import Config
 from .modified_dense_model import DenseImageCapRCNN
 
@@ -30,7 +31,9 @@ def load_model(weights=None, model_path=None, **kw):
     return model
 
 
-def generate_features(image, model):
-    """image: [H,W,3] uint8 array (the reference reads a JPEG path with skimage, which is absent here)."""
-    results = model.generate_captions([np.asarray(image)], verbose=0)
+def generate_features(image, model, mold="host"):
+    """image: [H,W,3] uint8 array (the reference reads a JPEG path with skimage, which is absent here).
+    mold='device': the image is resized on the GPU (DenseImageCapRCNN.generate_captions), the same features bit for bit."""
+    kw = {"mold": utils.check_mold(mold)} if mold != "host" else {}      # (feature models with the reference's plain signature keep working)
+    results = model.generate_captions([np.asarray(image)], verbose=0, **kw)
     return np.mean(results[0]['features'], axis=0).flatten()

@@ -123,7 +123,10 @@ class DenseImageCapRCNN(object):
         (EncoderPlan.forward_rois) -- the same features bit for bit, but the plan's pyramid maps are then valid only there."""
         imgs = torch.as_tensor(images_u8)
         B, H, W, _ = imgs.shape
-        p = self.plan(B, H, W)
+        return self._plan_features(self.plan(B, H, W), imgs, rois_px, sparse)
+
+    def _plan_features(self, p, imgs, rois_px, sparse):
+        """extract_features on plan p; imgs None: the plan's image buffer is already written (mold='device')."""
         if sparse and not self.use_generated_rois and p.sparse_rois:
             return p.forward_rois(imgs, p.normalize_boxes(rois_px))
         p.forward(imgs)
@@ -144,17 +147,29 @@ class DenseImageCapRCNN(object):
             windows.append(window)
         return np.stack(molded), np.stack(metas), np.stack(windows)
 
-    def generate_captions(self, images, rois=None, verbose=0, device_features=False):
+    def generate_captions(self, images, rois=None, verbose=0, device_features=False, mold="host"):
         """images: list of [H,W,3] uint8; rois: [len(images), N, 4] (y1,x1,y2,x2) pixels.
         Returns [{'features': float32 [N,7,7,256]}] like the reference (whose slice
         features[i][1000*i:1000*(i+1)] only works for BATCH_SIZE == 1; image i > 0 gets its own RoIs here).
         device_features=True keeps the features on the GPU (torch tensors, a copy the caller owns): a training generator that
-        feeds them back to the decoder then never moves [N,7,7,256] floats through host memory."""
+        feeds them back to the decoder then never moves [N,7,7,256] floats through host memory.
+        mold='host' (default): mold_inputs -- utils.resize_image on the host, the molded batch uploaded.  'device' (uint8 [h,w,3]
+        images, IMAGE_PADDING on): the raw images are uploaded and resampled into the plan's image buffer with PIL's integer
+        arithmetic (EncoderPlan.mold_images): the same bytes, so the same features bit for bit."""
+        utils.check_mold(mold)
+        if mold == "device":
+            images = [utils.check_device_mold_image(im) for im in images]
         assert self.mode == "inference", "Create model in inference mode."
         assert len(images) == self.config.BATCH_SIZE, "len(images) must be equal to BATCH_SIZE"
-        molded, metas, windows = self.mold_inputs(images)
         rois = None if self.use_generated_rois else np.asarray(rois, np.float32)
-        feats = self.extract_features(molded, rois, sparse=True)      # (only the features leave this call: nothing reads the maps whole)
+        if mold == "device":
+            cfg = self.config
+            p = self.plan(len(images), cfg.IMAGE_MAX_DIM, cfg.IMAGE_MAX_DIM)
+            p.mold_images(images, cfg.IMAGE_MIN_DIM, cfg.IMAGE_MAX_DIM, cfg.IMAGE_PADDING)
+            feats = self._plan_features(p, None, rois, sparse=True)
+        else:
+            molded, metas, windows = self.mold_inputs(images)
+            feats = self.extract_features(molded, rois, sparse=True)      # (only the features leave this call: nothing reads the maps whole)
         feats = feats.clone() if device_features else feats.cpu().numpy()
         n = self.config.POST_NMS_ROIS_INFERENCE
         results = [{"features": feats[i][:n]} for i in range(len(images))]

@@ -19,7 +19,7 @@ import os
 import numpy as np
 import torch
 
-from . import decoding, ops, step_graph, synth
+from . import decoding, ops, step_graph, synth, utils
 from .config import Config
 from .keras_like import KerasLikeModel, ModelCheckpoint, CSVLogger  # noqa: F401
 from .params import ParamStore, Adam  # noqa: F401
@@ -601,7 +601,7 @@ class CaptionModelV1(KerasLikeModel):
 
     @classmethod
     def check_decoder(cls, decoder, return_probabilities, vocab_math=None, compute_dtype=None, beam_size=None, score="logprob", end_id=None,
-                      postprocess="host", temperature=None, top_k=None, seed=None):
+                      postprocess="host", temperature=None, top_k=None, seed=None, mold="host"):
         """decoder='incremental', 'beam' and 'sampling' never form the per-step [B,V] probability rows: they need return_probabilities=False.
         decoder='beam' needs beam_size in 1..ops.TOPK_MAX (an integer, not a bool); score is 'logprob' (the sum of log p, the caption score
         of GenerationMatchLayer; the default) or 'prob' (the sum of p); end_id is None (fixed length T) or the end word's id >= 1.
@@ -613,7 +613,8 @@ class CaptionModelV1(KerasLikeModel):
         decoder='incremental' or 'beam' and return_probabilities=False.
         decoder='sampling' (the incremental decoder drawing every word from the model's own distribution; vocab_math and postprocess as
         for 'incremental') needs seed, an integer in [0, 2^32), and takes temperature (default 1.0: finite, > 0) and top_k (None or
-        1..ops.TOPK_MAX); the three belong to 'sampling' alone and are checked last.  Returns decoding.check_sampling's result."""
+        1..ops.TOPK_MAX); the three belong to 'sampling' alone and are checked last.  Returns decoding.check_sampling's result.
+        mold (the joint model's generate_captions): 'host' or 'device' (utils.check_mold), whatever the other arguments are."""
         decoding.check_decoder(decoder, beam_size, score, dict(end_id=end_id), score_for_beam_only=True, own=None if decoder == "prefix" or
                                return_probabilities is False else "decoder=%r returns no word probabilities: pass return_probabilities=False" % (decoder,))
         if decoder == "beam" and end_id is not None and (isinstance(end_id, bool) or int(end_id) != end_id or end_id < 1):
@@ -632,6 +633,7 @@ class CaptionModelV1(KerasLikeModel):
         if postprocess == "device" and (decoder == "prefix" or return_probabilities is not False):
             raise ValueError("postprocess='device' reads the device decoders' buffers: pass decoder='incremental' or 'beam' and "
                              "return_probabilities=False (got decoder=%r, return_probabilities=%r)" % (decoder, return_probabilities))
+        utils.check_mold(mold)
         return decoding.check_sampling(decoder, temperature, top_k, seed)
 
     def decode_greedy(self, feat, vocab_math=None):

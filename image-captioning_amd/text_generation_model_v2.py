@@ -193,7 +193,7 @@ def _data_generator_device(dataset, features_model, config, batch_size, shuffle)
 
 
 def train_on_dataset(model, features_model, dataset, images_per_step, rois_per_image, epochs=1, steps_per_epoch=None, shuffle=False,
-                     max_queue_size=4, callbacks=None, verbose=1):
+                     max_queue_size=4, callbacks=None, verbose=1, mold="host"):
     """The measured pipeline (bench.py) behind the training script's objects: trains `model` (build_model(...), compiled) on
     `dataset` (a VisualGenomeDataset-like utils.Dataset: load_image, load_captions_and_rois) with the feature model's encoder
     plan and the decoder on TWO HIP streams (pipeline.CaptionTrainPipeline): the encoder of step i + 1 runs while the decoder
@@ -204,10 +204,15 @@ def train_on_dataset(model, features_model, dataset, images_per_step, rois_per_i
     Differences to fit_generator(data_generator(...)): a batch is whole captions of whole images instead of 64 consecutive
     prefix samples, so batch boundaries fall differently unless images_per_step x rois_per_image x caption length equals the
     batch size (tests/test_gpu_models.py::test_train_on_dataset_equals_fit_generator builds exactly that case).
+    mold='host' (default): utils.resize_image on the producer thread.  'device' (uint8 [h,w,3] images, IMAGE_PADDING on): the producer
+    thread packs the raw images, uploads them and runs ops.resize_pad_images on its own stream -- PIL's integer arithmetic, the same
+    bytes, so the same losses.
     Returns the per-epoch logs like fit_generator."""
     from .keras_like import GeneratorEnqueuer
     from .pipeline import CaptionTrainPipeline
+    utils.check_mold(mold)
     cfg = features_model.config
+    utils.check_mold(mold, cfg.IMAGE_PADDING)
     H = W = cfg.IMAGE_MAX_DIM
     plan = features_model.plan(images_per_step, H, W)
     inner = getattr(model, "inner_model", model)
@@ -221,9 +226,9 @@ def train_on_dataset(model, features_model, dataset, images_per_step, rois_per_i
     def batches():
         ids = np.array(dataset.image_ids)
         pos = 0
-        stage = np.empty((images_per_step, H, W, 3), np.uint8)      # molded images are written here one by one: no np.stack copy
+        stage = np.empty((images_per_step, H, W, 3), np.uint8) if mold == "host" else None      # molded images are written here one by one: no np.stack copy
         while True:
-            imgs, boxes, caps = [], [], []
+            imgs, boxes, caps, raw = [], [], [], []
             while len(imgs) < images_per_step:
                 if pos == 0 and shuffle:
                     np.random.shuffle(ids)
@@ -236,16 +241,22 @@ def train_on_dataset(model, features_model, dataset, images_per_step, rois_per_i
                     words = [[int(np.argmax(w)) for w in c] for c in captions[:rois_per_image]]
                 if len(rois) < rois_per_image:
                     continue
-                molded = utils.resize_image(dataset.load_image(image_id), min_dim=cfg.IMAGE_MIN_DIM, max_dim=cfg.IMAGE_MAX_DIM,
-                                            padding=cfg.IMAGE_PADDING)[0]       # mold_inputs() without its stack / meta (mean pixel: on the GPU)
-                stage[len(imgs)] = molded
+                if mold == "device":
+                    raw.append(utils.check_device_mold_image(dataset.load_image(image_id)))
+                else:
+                    molded = utils.resize_image(dataset.load_image(image_id), min_dim=cfg.IMAGE_MIN_DIM, max_dim=cfg.IMAGE_MAX_DIM,
+                                                padding=cfg.IMAGE_PADDING)[0]       # mold_inputs() without its stack / meta (mean pixel: on the GPU)
+                    stage[len(imgs)] = molded
                 imgs.append(image_id)
                 boxes.append(np.asarray(rois[:rois_per_image], np.float32))
                 caps += [[int(t) for t in c] for c in words[:rois_per_image]]
             # everything the step needs goes to the GPU here, on the producer thread (blocking copies on its stream: complete when
             # the batch is queued), so the training loop below only enqueues kernels
             with torch.cuda.stream(s_copy):
-                images_dev = torch.as_tensor(stage).to(dev)              # blocking copy: `stage` is free again when it returns
+                if mold == "device":                                     # one upload of the raw bytes, resized on this stream
+                    images_dev = ops.resize_pad_images(raw, cfg.IMAGE_MIN_DIM, cfg.IMAGE_MAX_DIM, device=dev)
+                else:
+                    images_dev = torch.as_tensor(stage).to(dev)          # blocking copy: `stage` is free again when it returns
                 boxes_dev = plan.normalize_boxes(np.stack(boxes))
                 tables = SampleTables.from_captions(caps, dev)
                 s_copy.synchronize()

@@ -103,6 +103,51 @@ def resize_image(image, min_dim=None, max_dim=None, padding=False):
     return image.astype(dtype, copy=False), window, scale, padding
 
 
+def resize_geometry(shape, min_dim=None, max_dim=None, padding=False):
+    """resize_image's arithmetic with no pixel touched: (new_h, new_w, window, scale, padding) for an image of `shape`, where
+    (new_h, new_w) is the resampled size (Python's round, as resize_image calls it) and window, scale, padding are resize_image's own
+    return values.  What mold='device' needs of the host: the resampling itself runs on the GPU (ops.resize_pad_images)."""
+    h, w = int(shape[0]), int(shape[1])
+    window = (0, 0, h, w)
+    scale = 1
+    if min_dim:
+        scale = max(1, min_dim / min(h, w))
+    if max_dim:
+        if round(max(h, w) * scale) > max_dim:
+            scale = max_dim / max(h, w)
+    if scale != 1:
+        h, w = round(h * scale), round(w * scale)
+    if padding:
+        top = (max_dim - h) // 2
+        left = (max_dim - w) // 2
+        padding = [(top, max_dim - h - top), (left, max_dim - w - left), (0, 0)]
+        window = (top, left, h + top, w + left)
+    return h, w, window, scale, padding
+
+
+MOLD = ("host", "device")
+
+
+def check_mold(mold, padding=True):
+    """mold= of the inference and training entry points: 'host' (utils.resize_image: PIL, np.pad, np.stack) or 'device' (the raw
+    images are uploaded and ops.resize_pad_images writes the encoder plan's image buffer: the same bytes).  'device' writes the
+    zero-padded square the plan reads, so it needs padding (IMAGE_PADDING) on."""
+    if mold not in MOLD:
+        raise ValueError("mold must be one of %s, got %r" % (MOLD, mold))
+    if mold == "device" and not padding:
+        raise ValueError("mold='device' writes the zero-padded square the encoder plan reads; padding=False needs mold=\"host\"")
+    return mold
+
+
+def check_device_mold_image(image):
+    """What mold='device' resamples: a uint8 [h,w,3] array.  The host path byte-scales other dtypes (imresize) and takes whatever
+    channel count PIL does, a road the device kernel does not have."""
+    a = np.asarray(image)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError("mold='device' resamples uint8 [h,w,3] images only, got %s %s: pass mold=\"host\"" % (a.dtype, tuple(a.shape)))
+    return a
+
+
 def compose_image_meta(image_id, image_shape, window):
     """[id, h, w, c, y1, x1, y2, x2]"""
     return np.array([image_id] + list(image_shape) + list(window))

@@ -296,6 +296,39 @@ int dc_mold_image_padded_f32(const uint8_t* img, float* out, int N, int H, int W
                              float mean_r, float mean_g, float mean_b, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * utils.resize_image (dense_img_cap_separate_models/utils.py:290-340) for a batch of raw uint8 RGB images of ANY sizes in one call:
+ * image b [h][w][3] is resampled to [new_h][new_w][3] exactly as PIL.Image.resize((new_w, new_h), resample=BILINEAR) does it
+ * (ImagingResample, 8 bits per channel: horizontal pass into a uint8 intermediate, then the vertical pass; per axis the window
+ * and triangle-filter weights in float64, normalised, rounded to 22 fractional bits; pixel = clamp(((1 << 21) + sum k * p) >> 22))
+ * and written into out[b] of the uint8 canvas [B][H][W][3] at (top, left); every other byte of the canvas is written as 0, so the
+ * canvas may be a reused buffer.  The device's bytes are PIL's, bit for bit.
+ *   packed: ONE device buffer (4-byte aligned: its head is int32), B records of DC_RESIZE_RECORD_INTS int32
+ *     { byte offset of the image in `packed`, h, w, new_h, new_w, top, left, byte offset of the intermediate in the workspace }
+ *     followed by the images' bytes end to end, each at any byte offset: one host-to-device copy per batch.
+ *   records: the HOST's copy of those B records (the one host pointer of this interface): it sizes the grids and the workspace and
+ *     is checked before anything is launched -- a null pointer, a zero size, a window that leaves the canvas, an image that leaves
+ *     `packed`, an intermediate offset other than the sum of h * new_w * 3 over the images before, or any byte count (packed,
+ *     canvas, workspace) of 2^31 or more is DC_EINVAL.  The device never reads it and nothing is read back.
+ *   workspace (16-byte aligned): the intermediates (sum of h * new_w * 3 bytes), then the coefficient tables, which a first
+ *     kernel fills from the records' sizes alone.
+ * Neither the images nor the canvas have an alignment rule (every access to them is one byte).  Three launches on `stream`
+ * whatever B is; no allocation, no synchronisation, capturable.
+ * ------------------------------------------------------------------------------------------------ */
+#define DC_RESIZE_RECORD_INTS 8
+
+typedef struct {
+    int B;
+    const uint8_t* packed;
+    size_t         packed_bytes;
+    const int32_t* records;
+    uint8_t*       out;
+    int H, W;
+} dc_resize_pad_desc;
+
+size_t dc_resize_pad_u8_workspace_bytes(const dc_resize_pad_desc* d);
+int    dc_resize_pad_u8(const dc_resize_pad_desc* d, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * PyramidROIAlign forward (feature_generation/dense_model.py:317-418): level routing
  * k = clamp(4 + round_half_even(log2(sqrt(h*w) / (224/sqrt(image_area)))), 2, 5) and
  * tf.image.crop_and_resize(bilinear, 1 sample per bin, extrapolation 0) in one gather kernel.
