@@ -215,6 +215,17 @@ class DetectionTargetsDesc(C.Structure):
                 ("rois", C.c_void_p), ("captions", C.c_void_p), ("counts", C.c_void_p)]
 
 
+class RpnTargetsDesc(C.Structure):
+    _fields_ = [("B", C.c_int), ("A", C.c_int), ("n_levels", C.c_int), ("level_sizes", C.c_int * 5),
+                ("gt_capacity", C.c_int), ("budget", C.c_int),
+                ("anchors", C.c_void_p), ("gt_boxes", C.c_void_p), ("gt_counts", C.c_void_p), ("std_dev", C.c_double * 4),
+                ("seed", C.c_uint32), ("offset", C.c_uint32), ("offset_dev", C.c_void_p),
+                ("counts", C.c_void_p), ("sel_level", C.c_void_p), ("sel_index", C.c_void_p), ("sel_match", C.c_void_p), ("deltas", C.c_void_p)]
+
+
+RPN_TARGETS_MAX_GT = 512     # include/dcap.h, dc_rpn_targets_desc: the box capacity's limit
+
+
 class PwChainDesc(C.Structure):
     _fields_ = [("M", C.c_int), ("K1", C.c_int), ("N1", C.c_int), ("N2", C.c_int),
                 ("x", C.c_void_p), ("w1", C.c_void_p), ("scale1", C.c_void_p), ("shift1", C.c_void_p), ("residual", C.c_void_p),
@@ -324,6 +335,8 @@ SYMBOLS = {
     "dc_rpn_loss_grad_f32": (C.c_int, [C.POINTER(RpnLossDesc), C.c_void_p]),
     "dc_scatter2_add_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "dc_detection_targets_f32": (C.c_int, [C.POINTER(DetectionTargetsDesc), C.c_void_p]),
+    "dc_rpn_targets_workspace": (C.c_size_t, [C.POINTER(RpnTargetsDesc)]),
+    "dc_rpn_targets_f64": (C.c_int, [C.POINTER(RpnTargetsDesc), C.c_void_p, C.c_size_t, C.c_void_p]),
     "dc_caption_tables_i32": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dc_set_persistent_cus": (C.c_int, [C.c_int]),
     "dc_get_persistent_cus": (C.c_int, []),

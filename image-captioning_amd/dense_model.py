@@ -25,7 +25,7 @@ import re
 import numpy as np
 import torch
 
-from . import decoding, ops, step_graph, synth, utils
+from . import _lib, decoding, ops, step_graph, synth, utils
 from .encoder import EncoderPlan, fuse_rpn_head
 from .layers import resnet_fpn_convs
 from .modified_dense_model import load_weight_file, save_weight_file
@@ -206,9 +206,25 @@ def load_image_gt(dataset, config, image_id, augment=False, rng=np.random):
     return image, utils.compose_image_meta(image_id, shape, window), captions, boxes
 
 
-def data_generator(dataset, config, shuffle=True, augment=True, batch_size=1, rng=np.random):
+RPN_TARGET_MODES = ("host", "device")
+
+
+def check_rpn_targets_mode(rpn_targets):
+    if rpn_targets not in RPN_TARGET_MODES:
+        raise ValueError("rpn_targets must be one of %s, got %r" % (" | ".join(repr(m) for m in RPN_TARGET_MODES), rpn_targets))
+    return rpn_targets
+
+
+def data_generator(dataset, config, shuffle=True, augment=True, batch_size=1, rng=np.random, rpn_targets="host"):
     """Infinite generator of ([images f32 molded, image_meta, rpn_match [B,A,1], rpn_bbox [B,256,4], gt_captions
-    [B,MAX_GT,T], gt_boxes [B,MAX_GT,4]], []) -- the six training inputs of the reference's generator (:1260-1403)."""
+    [B,MAX_GT,T], gt_boxes [B,MAX_GT,4]], []) -- the six training inputs of the reference's generator (:1260-1403).
+    rpn_targets="device": build_rpn_targets is not called; position 2 is a list of the B images' FULL box arrays (every box of the
+    image: the host builds the RPN targets from them before the MAX_GT_INSTANCES pick) and position 3 is None -- the model builds
+    the targets on the device (ops.rpn_targets).  An image without boxes is skipped like any image whose targets fail on the host;
+    one with more than 512 boxes raises.  This mode draws less from `rng` (no np.random.choice inside build_rpn_targets), so from the
+    second epoch's shuffle on its image order differs from the host mode's."""
+    check_rpn_targets_mode(rpn_targets)
+    on_device = rpn_targets == "device"
     image_ids = np.copy(dataset.image_ids)
     anchors = utils.generate_pyramid_anchors(config.RPN_ANCHOR_SCALES, config.RPN_ANCHOR_RATIOS, config.BACKBONE_SHAPES,
                                              config.BACKBONE_STRIDES, config.RPN_ANCHOR_STRIDE)
@@ -220,7 +236,10 @@ def data_generator(dataset, config, shuffle=True, augment=True, batch_size=1, rn
         image_id = image_ids[index]
         try:
             image, meta, caps, boxes = load_image_gt(dataset, config, image_id, augment, rng)
-            match, deltas = build_rpn_targets(image.shape, anchors, caps, boxes, config, rng)
+            if not on_device:
+                match, deltas = build_rpn_targets(image.shape, anchors, caps, boxes, config, rng)
+            elif boxes.shape[0] == 0:
+                raise ValueError("image %r has no boxes" % (image_id,))       # (the host's argmax over no boxes raises here too)
         except (GeneratorExit, KeyboardInterrupt):
             raise
         except Exception:
@@ -228,22 +247,32 @@ def data_generator(dataset, config, shuffle=True, augment=True, batch_size=1, rn
             if errors > 5:
                 raise
             continue
+        if on_device and boxes.shape[0] > _lib.RPN_TARGETS_MAX_GT:
+            raise ValueError("image %r has %d boxes, the device builds RPN targets from at most %d: use rpn_targets=\"host\""
+                             % (image_id, boxes.shape[0], _lib.RPN_TARGETS_MAX_GT))
+        all_boxes = boxes
         if boxes.shape[0] > config.MAX_GT_INSTANCES:
             pick = rng.choice(np.arange(boxes.shape[0]), config.MAX_GT_INSTANCES, replace=False)
             caps, boxes = caps[pick], boxes[pick]
         if b == 0:
             images = np.zeros((batch_size,) + image.shape, np.float32)
             metas = np.zeros((batch_size,) + meta.shape, meta.dtype)
-            matches = np.zeros((batch_size, anchors.shape[0], 1), match.dtype)
-            bboxes = np.zeros((batch_size, config.RPN_TRAIN_ANCHORS_PER_IMAGE, 4), deltas.dtype)
+            if not on_device:
+                matches = np.zeros((batch_size, anchors.shape[0], 1), match.dtype)
+                bboxes = np.zeros((batch_size, config.RPN_TRAIN_ANCHORS_PER_IMAGE, 4), deltas.dtype)
             gt_caps = np.zeros((batch_size, config.MAX_GT_INSTANCES, config.PADDING_SIZE), caps.dtype)
             gt_boxes = np.zeros((batch_size, config.MAX_GT_INSTANCES, 4), boxes.dtype)
+            rpn_boxes = []
         images[b] = mold_image(image.astype(np.float32), config)
-        metas[b], matches[b], bboxes[b] = meta, match[:, None], deltas
+        if on_device:
+            metas[b] = meta
+            rpn_boxes.append(np.array(all_boxes))
+        else:
+            metas[b], matches[b], bboxes[b] = meta, match[:, None], deltas
         gt_caps[b, :caps.shape[0]], gt_boxes[b, :boxes.shape[0]] = caps, boxes
         b += 1
         if b >= batch_size:
-            yield [images, metas, matches, bboxes, gt_caps, gt_boxes], []
+            yield [images, metas, rpn_boxes if on_device else matches, None if on_device else bboxes, gt_caps, gt_boxes], []
             b = 0
 
 
@@ -257,11 +286,14 @@ class StepInputs(step_graph.PackedInputs):
     target deltas -- fixed capacity, the image's own counts travel as words), the normalised GT boxes, the GT captions and the step
     scalars (Keras' lr_t, the dropout-mask and detection-target stream positions)."""
 
-    def __init__(self, device, cap, n_gt, T, B=1):
-        """cap: selected anchors / target rows of the WHOLE batch (the images' selections travel concatenated); n_gt, T: per image."""
-        self.cap, self.n_gt, self.T, self.B = cap, n_gt, T, B
-        step_graph.PackedInputs.__init__(self, device, [("counts", 2), ("lvl", cap), ("idx", cap), ("mt", cap), ("deltas", 4 * cap), ("gt", 4 * n_gt * B),
-                                                         ("gtc", n_gt * T * B), ("scalars", 4)])
+    def __init__(self, device, cap, n_gt, T, B=1, rpn_gt=0):
+        """cap: selected anchors / target rows of the WHOLE batch (the images' selections travel concatenated); n_gt, T: per image.
+        rpn_gt > 0 (device-built RPN targets): the selection parts are left out -- the device writes its own -- and the images' full box
+        lists travel instead: rpn_gt float64 boxes per image (two words a value) and one count word per image."""
+        self.cap, self.n_gt, self.T, self.B, self.rpn_gt = cap, n_gt, T, B, rpn_gt
+        rpn = ([("counts", 2), ("lvl", cap), ("idx", cap), ("mt", cap), ("deltas", 4 * cap)] if rpn_gt == 0 else
+               [("rpn_gt", 8 * rpn_gt * B), ("rpn_gtc", B)])
+        step_graph.PackedInputs.__init__(self, device, rpn + [("gt", 4 * n_gt * B), ("gtc", n_gt * T * B), ("scalars", 4)])
 
 
 class _EarlyRanges(object):
@@ -370,6 +402,8 @@ class DenseImageCapRCNN(object):
         self._dt_rank = 0                                    # ParallelModel sets the tower's rank: towers shuffle their proposals independently
         self._last_targets = None
         self._step_in = None
+        self._step_in_boxes = None                           # ... of batches that carry boxes instead of RPN targets (rpn_targets="device")
+        self._rpn_anchors = None                             # float64 pyramid anchors on the device (device-built RPN targets)
         self._pins = {}                                      # page-locked host buffers (_pinned)
         self.optimizer = None
         self.grad_sync = None
@@ -805,27 +839,36 @@ class DenseImageCapRCNN(object):
 
     def _step_uploads(self, p, rpn_match, rpn_bbox, gt_norm, gt_caps, training):
         """This step's host inputs -> the device, one asynchronous copy (StepInputs).  Returns the device views the step's kernels read.
-        rpn_match / rpn_bbox / gt_norm / gt_caps: the generator's arrays with the image axis first (IMAGES_PER_GPU entries)."""
+        rpn_match / rpn_bbox / gt_norm / gt_caps: the generator's arrays with the image axis first (IMAGES_PER_GPU entries).
+        rpn_bbox None (data_generator(rpn_targets="device")): rpn_match is the list of the images' full box arrays; they travel in the
+        same copy and the selection is built on the device right behind it (_device_rpn_targets)."""
         cfg = self.config
         B = self.images_per_gpu
-        sel, rows = [], []
-        for b in range(B):
-            l_, i_, m_ = self._rpn_selection(rpn_match[b], b)
-            t_ = np.asarray(rpn_bbox[b], np.float32).reshape(-1, 4)
-            npos_b = int((m_ == 1).sum())
-            if npos_b > t_.shape[0]:
-                raise ValueError("%d positive anchors but only %d target rows" % (npos_b, t_.shape[0]))
-            sel.append((l_, i_, m_))
-            rows.append(t_ if B == 1 else t_[:npos_b])       # batch_pack_graph: the images' first-count rows, concatenated
-        lvl, idx, mt = (np.concatenate([s_[k] for s_ in sel]) for k in range(3))
-        tdl = np.concatenate(rows)
-        n_pos = int((mt == 1).sum())
+        on_device = rpn_bbox is None
         gt_norm = np.asarray(gt_norm, np.float32).reshape(B, -1, 4)
         gtc = np.asarray(gt_caps).astype(np.int32).reshape(B, gt_norm.shape[1], -1)
-        cap = max(B * int(cfg.RPN_TRAIN_ANCHORS_PER_IMAGE), len(lvl), tdl.shape[0], 1)
-        si = self._step_in
+        if on_device:
+            parts, rpn_gt = self._rpn_box_parts(rpn_match), _lib.RPN_TARGETS_MAX_GT
+            cap = max(B * int(cfg.RPN_TRAIN_ANCHORS_PER_IMAGE), 1)
+        else:
+            sel, rows = [], []
+            for b in range(B):
+                l_, i_, m_ = self._rpn_selection(rpn_match[b], b)
+                t_ = np.asarray(rpn_bbox[b], np.float32).reshape(-1, 4)
+                npos_b = int((m_ == 1).sum())
+                if npos_b > t_.shape[0]:
+                    raise ValueError("%d positive anchors but only %d target rows" % (npos_b, t_.shape[0]))
+                sel.append((l_, i_, m_))
+                rows.append(t_ if B == 1 else t_[:npos_b])       # batch_pack_graph: the images' first-count rows, concatenated
+            lvl, idx, mt = (np.concatenate([s_[k] for s_ in sel]) for k in range(3))
+            tdl = np.concatenate(rows)
+            n_pos = int((mt == 1).sum())
+            cap, rpn_gt = max(B * int(cfg.RPN_TRAIN_ANCHORS_PER_IMAGE), len(lvl), tdl.shape[0], 1), 0
+        slot = "_step_in_boxes" if on_device else "_step_in"      # one buffer per batch format: a run may alternate between them
+        si = getattr(self, slot)
         if si is None or si.cap < cap or si.n_gt != gt_norm.shape[1] or si.T != gtc.shape[2] or si.B != B:
-            si = self._step_in = StepInputs(self.device, cap, gt_norm.shape[1], gtc.shape[2], B)
+            si = StepInputs(self.device, cap, gt_norm.shape[1], gtc.shape[2], B, rpn_gt)
+            setattr(self, slot, si)
             self._invalidate_graphs()                       # captured graphs hold the old views
         if training:
             self._dt_step += 1
@@ -840,14 +883,61 @@ class DenseImageCapRCNN(object):
         scal = np.zeros(4, np.int32)
         scal[0:1] = np.array([lr_next], np.float32).view(np.int32)
         # Philox stream positions as 32-bit words, masked like the eager launches' host arguments (ops.dropout_mask / detection_targets)
-        scal[1:3] = np.array([(2 * (cm._drop_step + 1)) & 0xFFFFFFFF,            # this step's recurrent-dropout masks (lstm l: + l)
-                              (self._dt_step if training else self._dt_val_step) & 0xFFFFFFFF], np.uint32).view(np.int32)
-        si.upload({"counts": np.array([len(lvl), n_pos], np.int32), "lvl": lvl, "idx": idx, "mt": mt, "deltas": tdl[:si.cap],
-                   "gt": gt_norm, "gtc": gtc, "scalars": scal})
+        step = (self._dt_step if training else self._dt_val_step) & 0xFFFFFFFF
+        scal[1:4] = np.array([(2 * (cm._drop_step + 1)) & 0xFFFFFFFF,            # this step's recurrent-dropout masks (lstm l: + l)
+                              step,                                              # the detection-target keys' stream position
+                              step if on_device else 0], np.uint32).view(np.int32)   # ... and the RPN-target keys' (a stream of its own seed)
+        if not on_device:
+            parts = {"counts": np.array([len(lvl), n_pos], np.int32), "lvl": lvl, "idx": idx, "mt": mt, "deltas": tdl[:si.cap]}
+        parts.update({"gt": gt_norm, "gtc": gtc, "scalars": scal})
+        si.upload(parts)
         sc = si.view("scalars")
-        return dict(counts=si.view("counts"), lvl=si.view("lvl"), idx=si.view("idx"), mt=si.view("mt"),
-                    deltas=si.view("deltas", torch.float32).view(si.cap, 4), gt=si.view("gt", torch.float32).view(si.B, si.n_gt, 4),
-                    gtc=si.view("gtc").view(si.B, si.n_gt, si.T), cap=si.cap, lr_t=sc[0:1].view(torch.float32), drop_offset=sc[1:2], dt_offset=sc[2:3])
+        out = dict(on_device=on_device, gt=si.view("gt", torch.float32).view(si.B, si.n_gt, 4), gtc=si.view("gtc").view(si.B, si.n_gt, si.T), cap=si.cap,
+                   lr_t=sc[0:1].view(torch.float32), drop_offset=sc[1:2], dt_offset=sc[2:3])
+        if on_device:
+            out.update(self._device_rpn_targets(p, si, sc[3:4], training))
+        else:
+            out.update(counts=si.view("counts"), lvl=si.view("lvl"), idx=si.view("idx"), mt=si.view("mt"),
+                       deltas=si.view("deltas", torch.float32).view(si.cap, 4))
+        return out
+
+    def _rpn_box_parts(self, boxes):
+        """The images' full box lists (data_generator(rpn_targets="device"), position 2) as StepInputs parts: float64 [B, 512, 4] the
+        way compute_overlaps widens them, and the box counts."""
+        B, G = self.images_per_gpu, _lib.RPN_TARGETS_MAX_GT
+        if len(boxes) != B:
+            raise ValueError("%d box list(s) handed to a model built for IMAGES_PER_GPU = %d" % (len(boxes), B))
+        packed, counts = np.zeros((B, G, 4), np.float64), np.zeros(B, np.int32)
+        for b, bx in enumerate(boxes):
+            bx = np.asarray(bx, np.float64).reshape(-1, 4)
+            if bx.shape[0] > G:
+                raise ValueError("image %d of the batch has %d boxes, the device builds RPN targets from at most %d: use rpn_targets=\"host\""
+                                 % (b, bx.shape[0], G))
+            packed[b, :bx.shape[0]], counts[b] = bx, bx.shape[0]
+        return {"rpn_gt": packed.view(np.int32), "rpn_gtc": counts}
+
+    def _rpn_target_seed(self, training):
+        """Key of the RPN targets' subsampling stream: the model seed, training or validation and the tower's rank mixed as _device_sample
+        mixes the detection targets' key, with another multiplier -- the two streams differ, and so do data-parallel ranks'; the kernel
+        adds b * 0x85EBCA6B for image b."""
+        return ((self._seed + (0 if training else 1)) * 0xC2B2AE35 + 0x27D4EB2F + self._dt_rank * 0x9E3779B9) & 0xFFFFFFFF
+
+    def _device_rpn_targets(self, p, si, offset_dev, training):
+        """build_rpn_targets on the device (ops.rpn_targets) from the boxes that just went up: eight short launches in front of the encoder
+        pass, on the stream the step runs on.  Returns the selection as _rpn_losses reads it (model-owned buffers of fixed capacity)."""
+        cfg, B = self.config, self.images_per_gpu
+        sizes = [h.shape[1] * h.shape[2] * self.A for h in p.rpn_heads]
+        if self._rpn_anchors is None or self._rpn_anchors.shape[0] != sum(sizes):
+            a = utils.generate_pyramid_anchors(cfg.RPN_ANCHOR_SCALES, cfg.RPN_ANCHOR_RATIOS, cfg.BACKBONE_SHAPES, cfg.BACKBONE_STRIDES, cfg.RPN_ANCHOR_STRIDE)
+            if a.shape[0] != sum(sizes):
+                raise ValueError("the config generates %d anchors, the pyramid has %d" % (a.shape[0], sum(sizes)))
+            self._rpn_anchors = torch.as_tensor(np.ascontiguousarray(a, np.float64)).to(self.device)     # once: the model owns them
+        out = (self._buf("rt_counts", (2,), torch.int32), self._buf("rt_lvl", (si.cap,), torch.int32), self._buf("rt_idx", (si.cap,), torch.int32),
+               self._buf("rt_mt", (si.cap,), torch.int32), self._buf("rt_deltas", (si.cap, 4)))
+        counts, lvl, idx, mt, deltas = ops.rpn_targets(
+            self._rpn_anchors, si.view("rpn_gt").view(torch.float64).view(B, si.rpn_gt, 4), si.view("rpn_gtc"), sizes,
+            int(cfg.RPN_TRAIN_ANCHORS_PER_IMAGE), cfg.RPN_BBOX_STD_DEV, self._rpn_target_seed(training), offset=0, offset_dev=offset_dev, out=out)
+        return dict(counts=counts, lvl=lvl, idx=idx, mt=mt, deltas=deltas)
 
     def _rpn_losses(self, p, rpn_up, dheads, losses):
         """RPN losses (dense_model.py:1008-1075) into losses[0:2], their gradients into the zeroed `dheads` (selection and counts: StepInputs views)."""
@@ -1221,7 +1311,8 @@ class DenseImageCapRCNN(object):
         if not path.use_graph:
             return body()
         dropout = float(cm.recurrent_dropout or 0.0)
-        key = ("train", dropout, opt.baked_key())            # (with dropout the mask kernels are launches of the step)
+        # (with dropout the mask kernels are launches of the step; the two batch formats read different step buffers)
+        key = ("train", dropout, opt.baked_key(), rpn_up["on_device"])
         cs = self._steps.get(key)
         if cs is None:
             cs = self._steps[key] = step_graph.CapturedStep()
@@ -1396,13 +1487,16 @@ class DenseImageCapRCNN(object):
         return [{"rois": rois[b, :n[b]].copy(), "ids": ids[b, :n[b]].copy()} for b in range(B)]
 
     # ---- training loop ----------------------------------------------------------------------
-    def train(self, train_dataset, val_dataset, learning_rate, epochs, layers):
-        """fit_generator over data_generator with a checkpoint per epoch (:1810-1888)."""
+    def train(self, train_dataset, val_dataset, learning_rate, epochs, layers, rpn_targets="host"):
+        """fit_generator over data_generator with a checkpoint per epoch (:1810-1888).  rpn_targets="device": the generators hand on the
+        images' boxes and every step builds its RPN targets on the device (data_generator, ops.rpn_targets) instead of in NumPy on this
+        thread; opt-in, because the subsample is then drawn from Philox keys, not from np.random.choice."""
+        check_rpn_targets_mode(rpn_targets)
         assert self.mode == "training", "Create model in training mode."
         layers = self.LAYER_REGEX.get(layers, layers)
         cfg = self.config
-        train_generator = data_generator(train_dataset, cfg, shuffle=True, batch_size=cfg.BATCH_SIZE)
-        val_generator = data_generator(val_dataset, cfg, shuffle=True, batch_size=cfg.BATCH_SIZE, augment=False)
+        train_generator = data_generator(train_dataset, cfg, shuffle=True, batch_size=cfg.BATCH_SIZE, rpn_targets=rpn_targets)
+        val_generator = data_generator(val_dataset, cfg, shuffle=True, batch_size=cfg.BATCH_SIZE, augment=False, rpn_targets=rpn_targets)
         self.set_trainable(layers)
         self.compile(learning_rate)
         val_batch = next(val_generator)[0]

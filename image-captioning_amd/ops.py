@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import (PwChainDesc, ConvBf16Desc, AmsgradDesc, DetectionTargetsDesc, BnReluDesc, ConvDesc, ConvWgradBf16Desc, GemmBf16Desc, VocabCeDesc, ProposalDesc, RpnLossDesc, GemmDesc, LstmBwdDesc, LstmFwdDesc, RoiAlignDesc, RoiGroupsDesc,
+from ._lib import (RpnTargetsDesc, PwChainDesc, ConvBf16Desc, AmsgradDesc, DetectionTargetsDesc, BnReluDesc, ConvDesc, ConvWgradBf16Desc, GemmBf16Desc, VocabCeDesc, ProposalDesc, RpnLossDesc, GemmDesc, LstmBwdDesc, LstmFwdDesc, RoiAlignDesc, RoiGroupsDesc,
                    SoftmaxCeDesc, VocabTop1Desc, VocabTopkDesc, VocabTop1Bf16Desc, VocabTopkBf16Desc, VocabSampleDesc, VocabSampleBf16Desc, BeamSelectDesc, BeamStepDesc, LstmStepDesc, RefineDesc, ResizePadDesc, check)
 
 
@@ -1433,6 +1433,49 @@ def detection_targets(proposals, gt_boxes, gt_captions, n_rois, positive_ratio, 
     d.rois, d.captions, d.counts = _chk(rois, name="rois").data_ptr(), _chk(caps, torch.int32, "captions").data_ptr(), _chk(counts, torch.int32, "counts").data_ptr()
     check(lib.dc_detection_targets_f32(C.byref(d), _stream()), "dc_detection_targets_f32")
     return rois, caps, counts
+
+
+def rpn_targets(anchors, gt_boxes, gt_counts, level_sizes, anchors_per_image_budget, std_dev, seed, offset=0, offset_dev=None, out=None):
+    """build_rpn_targets for B images on the device (dc_rpn_targets_f64), in the packed form rpn_loss_grad(batched=True) reads.
+    anchors [A,4] float64, gt_boxes [B,G,4] float64 (G <= 512: the capacity), gt_counts int32 [B] (the images' box counts, read on the
+    device), level_sizes: anchors per image of each pyramid level, std_dev: RPN_BBOX_STD_DEV.  Image b's subsampling keys are
+    Philox(anchor, offset + offset_dev, seed + b * 0x85EBCA6B).  out / returns (counts int32 [2] = {n_sel, n_pos}, lvl, idx, mt int32
+    [B * budget], deltas float32 [B * budget, 4]) -- device tensors, nothing is read back."""
+    lib = _lib.load()
+    _chk(anchors, torch.float64, "anchors"), _chk(gt_boxes, torch.float64, "gt_boxes"), _chk(gt_counts, torch.int32, "gt_counts")
+    if anchors.dim() != 2 or anchors.shape[1] != 4 or gt_boxes.dim() != 3 or gt_boxes.shape[2] != 4 or gt_counts.numel() != gt_boxes.shape[0]:
+        raise _lib.DcapError("rpn_targets: anchors [A,4], gt_boxes [B,G,4], gt_counts [B]")
+    if not (anchors.is_contiguous() and gt_boxes.is_contiguous() and gt_counts.is_contiguous()):
+        raise _lib.DcapError("rpn_targets: operands must be contiguous")
+    B, n = gt_boxes.shape[0], int(anchors_per_image_budget)
+    sizes = [int(v) for v in level_sizes]
+    if not 1 <= len(sizes) <= 5:
+        raise _lib.DcapError("rpn_targets: 1..5 pyramid levels, got %d" % len(sizes))
+    cap = B * max(n, 0)
+    if out is None:
+        dev = anchors.device
+        out = (torch.empty(2, dtype=torch.int32, device=dev),) + tuple(torch.empty(max(cap, 1), dtype=torch.int32, device=dev) for _ in range(3)) + (
+            torch.empty((max(cap, 1), 4), dtype=torch.float32, device=dev),)
+    counts, lvl, idx, mt, deltas = out
+    for t, name in ((counts, "counts"), (lvl, "lvl"), (idx, "idx"), (mt, "mt")):
+        _chk(t, torch.int32, name)
+    _chk(deltas, name="deltas")
+    if counts.numel() < 2 or min(lvl.numel(), idx.numel(), mt.numel()) < cap or deltas.numel() < 4 * cap or not deltas.is_contiguous():
+        raise _lib.DcapError("rpn_targets: outputs need 2 count words and B * budget = %d rows" % cap)
+    d = RpnTargetsDesc()
+    d.B, d.A, d.n_levels = B, anchors.shape[0], len(sizes)
+    for i, v in enumerate(sizes):
+        d.level_sizes[i] = v
+    d.gt_capacity, d.budget = gt_boxes.shape[1], n
+    d.anchors, d.gt_boxes, d.gt_counts = anchors.data_ptr(), gt_boxes.data_ptr(), gt_counts.data_ptr()
+    for i, v in enumerate(std_dev):
+        d.std_dev[i] = float(v)
+    d.seed, d.offset = int(seed) & 0xFFFFFFFF, int(offset) & 0xFFFFFFFF
+    d.offset_dev = None if offset_dev is None else _chk(offset_dev, torch.int32, "offset_dev").data_ptr()
+    d.counts, d.sel_level, d.sel_index, d.sel_match, d.deltas = counts.data_ptr(), lvl.data_ptr(), idx.data_ptr(), mt.data_ptr(), deltas.data_ptr()
+    ws, wsb = WORKSPACE.get(lib.dc_rpn_targets_workspace(C.byref(d)), anchors.device)
+    check(lib.dc_rpn_targets_f64(C.byref(d), _ptr(ws), wsb, _stream()), "dc_rpn_targets_f64")
+    return counts, lvl, idx, mt, deltas
 
 
 def caption_tables(captions, out=None, live_count=None):

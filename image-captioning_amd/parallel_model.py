@@ -231,7 +231,7 @@ class ParallelModel(object):
         return getattr(self.inner_model, name)
 
     def shard_inputs(self, inputs):
-        return [shard(x, self.rank, self.gpu_count) for x in inputs]
+        return [None if x is None else shard(x, self.rank, self.gpu_count) for x in inputs]     # (None: the device builds the RPN targets)
 
     def mean_over_towers(self, raw):
         """tf.reduce_mean over the towers' loss terms (parallel_model.py:88-102): all-reduce(sum) of a small float32 device

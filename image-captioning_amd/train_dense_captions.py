@@ -12,7 +12,7 @@ import time
 import numpy as np
 
 from .config import Config
-from .dense_model import DenseImageCapRCNN
+from .dense_model import DenseImageCapRCNN, check_rpn_targets_mode
 from .preprocess import encode_caption, load_corpus, load_embeddings, tokenize_corpus
 from .text_generation_model_v2 import pad_sequences
 from .utils import Dataset
@@ -93,7 +93,9 @@ def load_vocabulary(cache_dir, embeddings_file, data_file, train_image_ids):
     return id_to_word, word_to_id, matrix
 
 
-def main(root_dir=None, init_with='coco', epochs=100):
+def main(root_dir=None, init_with='coco', epochs=100, rpn_targets="host"):
+    """rpn_targets="device": the RPN targets of every step are built on the GPU (DenseImageCapRCNN.train)."""
+    check_rpn_targets_mode(rpn_targets)
     from .parallel_model import ParallelModel, init_process_group_from_env
     rank, world, _ = init_process_group_from_env()
     root_dir = root_dir or os.getcwd()
@@ -127,7 +129,7 @@ def main(root_dir=None, init_with='coco', epochs=100):
     if rank == 0:
         print(model.summary())
     start_time = time.time()
-    model.train(datasets[0], datasets[1], learning_rate=config.LEARNING_RATE, epochs=epochs, layers="no_backbone")
+    model.train(datasets[0], datasets[1], learning_rate=config.LEARNING_RATE, epochs=epochs, layers="no_backbone", rpn_targets=rpn_targets)
     print(time.time() - start_time)
 
 

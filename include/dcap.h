@@ -935,6 +935,38 @@ typedef struct {
     int32_t* counts;          /* [2] */
 } dc_detection_targets_desc;
 int dc_detection_targets_f32(const dc_detection_targets_desc* d, void* stream);
+/* build_rpn_targets (dense_img_cap/dense_model.py:1095-1183) for B images on the device, written in the packed form dc_rpn_loss_grad_f32
+ * reads with batched heads.  anchors [A][4] float64 (utils.generate_pyramid_anchors' own array), gt_boxes [B][gt_capacity][4] float64,
+ * gt_counts [B]: the images' box counts as DEVICE words (clamped to 0..gt_capacity; no launch shape depends on them).  Per image: the
+ * float64 IoU matrix with utils.compute_overlaps' operations in its order, best box = first argmax; negative (-1) below 0.3, positive
+ * (1) where an anchor attains a box's column maximum (a column maximum of 0 claims every anchor with IoU 0, as on the host) or reaches
+ * 0.7; without boxes every anchor is a negative.  np.random.choice is replaced by counter-based keys: key(a) = word 0 of
+ * Philox-2x32-10(counter = (a, offset + *offset_dev), key = seed + b * 0x85EBCA6B) for anchor a of image b; the budget / 2 positives
+ * with the smallest (key, a) pairs stay, then the budget - (positives kept) negatives with the smallest pairs; the rest is neutral.
+ * Output, images in order and anchors ascending: sel_level / sel_index (a - start of its level + b * level_sizes[level]: the index
+ * inside the level's [B,h,w,anchors] head tensor) / sel_match, each [B * budget]; deltas [B * budget][4] float32: the kept positives'
+ * ((gcy - acy) / ah, (gcx - acx) / aw, log(gh / ah), log(gw / aw)) / std_dev against their best box, computed in float64, rows packed in
+ * the same order; counts = {n_sel, n_pos} over the batch; the unused tail of every output is zeroed.  Limits: budget 2..1024,
+ * gt_capacity 1..512, B <= 64, at most 5 levels whose sizes sum to A; anchors / gt_boxes 8-byte, the workspace 16-byte aligned
+ * (DC_EALIGN).  Eight launches, integer atomics only: two calls give identical bits.  Boxes are expected finite. */
+typedef struct {
+    int B, A, n_levels;
+    int level_sizes[5];           /* anchors per image of each pyramid level (h * w * anchors per location) */
+    int gt_capacity, budget;
+    const double*   anchors;
+    const double*   gt_boxes;
+    const int32_t*  gt_counts;
+    double   std_dev[4];
+    uint32_t seed, offset;
+    const uint32_t* offset_dev;   /* optional device word added to offset (a captured hipGraph draws fresh keys every replay) */
+    int32_t* counts;              /* [2] */
+    int32_t* sel_level;
+    int32_t* sel_index;
+    int32_t* sel_match;
+    float*   deltas;
+} dc_rpn_targets_desc;
+size_t dc_rpn_targets_workspace(const dc_rpn_targets_desc* d);
+int dc_rpn_targets_f64(const dc_rpn_targets_desc* d, void* workspace, size_t workspace_bytes, void* stream);
 /* Index tables of the Model-3 decoder from device-resident captions [B][T] (dense_img_cap/dense_model.py:1572-1580: target = caption
  * shifted left by one; imgcap_caption_loss_graph :936-946: mean over positions with target > 0): ids_tm / targets_tm [T*B] time-major
  * (row t*B + b), mask = ids != 0, row_weights = [target > 0] / max(count, 1), live_count[0] = count (may be NULL). */
