@@ -33,64 +33,43 @@
 namespace dcap {
 namespace b256 {
 
-constexpr int BM = 256, BN = 256, BK = 64, NTHREADS = 512;
-constexpr int SUB = 128 * BK * 2;          // one sub-image: 128 rows (or columns) x 64 k of bf16 = 16 KiB
-constexpr int STAGE = 4 * SUB;             // A half 0, A half 1, B half 0, B half 1
-constexpr int LDS_BYTES = 2 * STAGE;       // 128 KiB
-constexpr int OFF_A = 0, OFF_B = 2 * SUB;
-
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// sub-image row r' (0..127) of half u  ->  row (column) of the 256-wide tile
-template <bool IS_A>
-__device__ __forceinline__ int tile_index(int u, int rp) {
-    if constexpr (IS_A) return (rp >> 6) * 128 + u * 64 + (rp & 63);     // wave group g = r' >> 6 owns rows g*128 .. g*128+127
-    else return (rp >> 5) * 64 + u * 32 + (rp & 31);                     // wave column c = r' >> 5 owns columns c*64 .. c*64+63
+// tile id -> (tile row, tile column): ids walk down up to GM tile rows first (they share the B panel in the XCD's L2), then across
+__device__ __forceinline__ void tile_coords(int lid, int tiles_m, int tiles_n, int& tm, int& tn) {
+    constexpr int GM = 16;
+    const int width = GM * tiles_n, g = lid / width, first = g * GM;
+    const int gsz = min(tiles_m - first, GM), r = lid - g * width;
+    tm = first + r % gsz;
+    tn = r / gsz;
 }
 
-// A dense operand (BOperand of bgemm_core.h): the LDS-DMA of its two sub-images, two 1-KiB pieces per wave and sub-image.
-template <bool KC_, bool IS_A>
-struct Load {
-    static constexpr bool KC = KC_;
-    __amdgpu_buffer_rsrc_t rsrc;
-    unsigned voff[2][2];       // [half][piece]: per-lane byte offset of the 16-byte chunk at K-tile 0
-    int kloc[2][2];            // k of the chunk inside the tile (KC) / k row inside the tile (MC)
-    long ld;
-    __device__ __forceinline__ void init(const BOperand& o, int origin, int lane, int wave) {
-        rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(o.p), 0, (int)o.bytes, 0x00020000);
-        ld = o.ld;
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-            for (int jj = 0; jj < 2; ++jj) {
-                const int pc = 2 * wave + jj;                                  // piece 0..15 of the sub-image
-                if constexpr (KC) {
-                    const int rp = 8 * pc + (lane >> 3);                       // sub-image row of this lane's chunk
-                    const int c = (lane & 7) ^ ((rp >> 1) & 7);                // source chunk that lands in LDS chunk (lane & 7)
-                    const int row = min(origin + tile_index<IS_A>(u, rp), o.extent - 1);   // past the edge: feeds nothing that is stored
-                    const long src = o.gather ? (long)o.gather[row] : (long)row;
-                    voff[u][jj] = (unsigned)((src * o.ld + 8 * c) * 2);
-                    kloc[u][jj] = 8 * c;
-                } else {
-                    const int k = 4 * pc + (lane >> 4);                        // K row inside the tile
-                    const int c = (lane & 15) ^ (((k & 3) << 2) | ((k >> 2) & 3));
-                    const int col = min(origin + tile_index<IS_A>(u, 8 * c), o.extent - 8);  // clamped, never stored
-                    voff[u][jj] = (unsigned)(((long)k * o.ld + col) * 2);
-                    kloc[u][jj] = k;
-                }
-            }
+// The geometry (see BGeo128): two 128-row sub-images per operand, two 1-KiB pieces per wave and sub-image.
+struct Geo {
+    static constexpr int BM = 256, BN = 256, BK = 64, NTHREADS = 512;
+    static constexpr int HALVES = 2, ROWS = 128;
+    static constexpr int IMG = ROWS * BK * 2;                        // one sub-image: 128 rows (or columns) x 64 k of bf16 = 16 KiB
+    static constexpr int NP = IMG / 1024 / (NTHREADS / 64);          // 2
+    static constexpr bool K_ROW_GATHER = false;
+    static constexpr int STAGE = 2 * HALVES * IMG;                   // A half 0, A half 1, B half 0, B half 1
+    static constexpr int LDS_BYTES = 2 * STAGE;                      // 128 KiB
+    // sub-image row r' (0..127) of half u  ->  row (column) of the 256-wide tile
+    template <bool IS_A>
+    static __device__ __forceinline__ int tile_index(int u, int rp) {
+        if constexpr (IS_A) return (rp >> 6) * 128 + u * 64 + (rp & 63);     // wave group g = r' >> 6 owns rows g*128 .. g*128+127
+        else return (rp >> 5) * 64 + u * 32 + (rp & 31);                     // wave column c = r' >> 5 owns columns c*64 .. c*64+63
     }
-    // LDS-DMA of half u of the K-tile starting at k0 into the sub-image at `sub` (wave-uniform LDS address)
-    __device__ __forceinline__ void issue(int u, char* sub, int k0, int kend, int wave) const {
-        const bool tail = k0 + BK > kend;                                      // block-uniform; also covers "no such tile" (k0 >= kend)
-        const int soff = KC ? k0 * 2 : (int)((long)k0 * ld * 2);               // < 2 GiB (host-checked span)
-#pragma unroll
-        for (int jj = 0; jj < 2; ++jj) {
-            const unsigned v = (tail && k0 + kloc[u][jj] >= kend) ? kOobOffset : voff[u][jj];
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (DC_LDS void*)(sub + (2 * wave + jj) * 1024), 16, (int)v, soff, 0, 0);
-        }
+    static __device__ __forceinline__ void origin(int M, int N, int& m0, int& n0) {
+        const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
+        int tm, tn;
+        tile_coords(xcd_remap(blockIdx.x, gridDim.x), tiles_m, tiles_n, tm, tn);
+        m0 = tm * BM;
+        n0 = tn * BN;
     }
 };
+constexpr int BM = Geo::BM, BN = Geo::BN, BK = Geo::BK, NTHREADS = Geo::NTHREADS;
+constexpr int SUB = Geo::IMG, STAGE = Geo::STAGE, LDS_BYTES = Geo::LDS_BYTES;
+constexpr int OFF_A = 0, OFF_B = 2 * SUB;
 
 // One fragment (16 rows x 32 k) in registers: KC one 128-bit read, MC two transposing 64-bit reads.
 template <bool KC> struct FragReg;
@@ -178,7 +157,8 @@ __device__ __forceinline__ void frag_touch(FragReg<false> (&r)[NT][2]) {
 
 // The main loop.  acc[mt][nt]: mt = 4 * (A half) + tile, nt = 2 * (B half) + tile; element j of lane l is
 //   C[m0 + 128 group + 64 (mt >> 2) + 16 (mt & 3) + (l & 15)][n0 + 64 wcol + 32 (nt >> 1) + 16 (nt & 1) + 4 (l >> 4) + j].
-// LA / LB: loaders with  static constexpr bool KC  and  issue(int half, char* sub_image, int k0, int kend, int wave).
+// LA / LB: operand loaders on Geo (bgemm_core.h).  Every (K-tile, half) is issued exactly once and in order -- half 0, then half 1 --
+// starting at kbeg, and one (empty) K-tile past the end.
 template <class LA, class LB>
 __device__ __forceinline__ void mainloop(LA& la, LB& lb, char* smem, int kbeg, int kend, f32x4 (&acc)[8][4]) {
     constexpr bool AKC = LA::KC, BKC = LB::KC;
@@ -331,28 +311,17 @@ __device__ __forceinline__ void store_tile(f32x4 (&acc)[8][4], const Epilogue& e
     }
 }
 
-// tile id -> (tile row, tile column): ids walk down up to GM tile rows first (they share the B panel in the XCD's L2), then across
-__device__ __forceinline__ void tile_coords(int lid, int tiles_m, int tiles_n, int& tm, int& tn) {
-    constexpr int GM = 16;
-    const int width = GM * tiles_n, g = lid / width, first = g * GM;
-    const int gsz = min(tiles_m - first, GM), r = lid - g * width;
-    tm = first + r % gsz;
-    tn = r / gsz;
-}
-
 template <bool AKC, bool BKC>
 __global__ __launch_bounds__(NTHREADS, 2) void bgemm256_kernel(BOperand a, BOperand b, Epilogue ep, int M, int N, int K, int klen, float* __restrict__ partial) {
     extern __shared__ __attribute__((aligned(16))) float smem_f[];
     char* smem = reinterpret_cast<char*>(smem_f);
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
-    int tm, tn;
-    tile_coords(xcd_remap(blockIdx.x, gridDim.x), tiles_m, tiles_n, tm, tn);
-    const int m0 = tm * BM, n0 = tn * BN;
+    int m0, n0;
+    Geo::origin(M, N, m0, n0);
     const int kbeg = blockIdx.z * klen, kend = min(K, kbeg + klen);
-    Load<AKC, true> la;
-    Load<BKC, false> lb;
+    BLoadDense<Geo, AKC, true> la;
+    BLoadDense<Geo, BKC, false> lb;
     la.init(a, m0, lane, wave);
     lb.init(b, n0, lane, wave);
     f32x4 acc[8][4];
@@ -402,28 +371,9 @@ inline bool prefer(int M, int N, int K, int user_split, bool vec4 = true) {
     return tile_cost_us(M, N, K, 256, split(M, N, K, user_split)) < tile_cost_us(M, N, K, 128, bgemm_split(M, N, K, user_split));
 }
 
-template <bool AKC, bool BKC>
-int launch(const BOperand& a, const BOperand& b, const Epilogue& ep, int M, int N, int K, int user_split, void* workspace, size_t workspace_bytes,
-           hipStream_t stream) {
-    const BSplit sp = split(M, N, K, user_split);
-    float* partial = nullptr;
-    if (sp.split > 1) {
-        const size_t need = (size_t)sp.split * M * N * sizeof(float);
-        DC_REQUIRE(workspace != nullptr && workspace_bytes >= need, DC_EWORKSPACE, "bgemm256 split-K needs %zu workspace bytes, got %zu", need, workspace_bytes);
-        DC_REQUIRE_SLAB_ALIGNED("bgemm256 split-K", workspace, N);
-        partial = static_cast<float*>(workspace);
-    }
-    DC_ENSURE_DYN_LDS((&bgemm256_kernel<AKC, BKC>), 160 * 1024);
-    const int tiles = ((M + BM - 1) / BM) * ((N + BN - 1) / BN);
-    hipLaunchKernelGGL((bgemm256_kernel<AKC, BKC>), dim3(tiles, 1, sp.split), dim3(NTHREADS), LDS_BYTES, stream, a, b, ep, M, N, K, sp.klen, partial);
-    int rc = check_launch("bgemm256_kernel");
-    if (rc) return rc;
-    if (sp.split > 1) {
-        const long total = (long)M * N;
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(splitk_reduce_blocks(total)), dim3(256), 0, stream, partial, sp.split, M, N, ep);
-        rc = check_launch("splitk_reduce_kernel");
-    }
-    return rc;
+// the plan of an entry point that runs on this tile (`big`) or on the 128-square one
+inline BPlan plan(bool big, int M, int N, int K, int user_split) {
+    return big ? BPlan{256, split(M, N, K, user_split)} : BPlan{128, bgemm_split(M, N, K, user_split)};
 }
 
 }  // namespace b256

@@ -19,43 +19,28 @@
 namespace dcap {
 namespace b64 {
 
-constexpr int BM = 64, BN = 64, BK = 64, NTHREADS = 256, NS = 4;
-constexpr int IMG = 64 * BK * 2;           // one operand image: 64 rows x 64 k of bf16 = 8 KiB
-constexpr int STAGE = 2 * IMG;             // A, B
-constexpr int LDS_BYTES = NS * STAGE;      // 64 KiB
+// The geometry (see BGeo128): one 64-row image per operand, two 1-KiB pieces per wave (wave w fills rows 16 w .. 16 w + 15).
+struct Geo {
+    static constexpr int BM = 64, BN = 64, BK = 64, NTHREADS = 256;
+    static constexpr int HALVES = 1, ROWS = 64;
+    static constexpr int IMG = ROWS * BK * 2;                        // one operand image: 64 rows x 64 k of bf16 = 8 KiB
+    static constexpr int NP = IMG / 1024 / (NTHREADS / 64);          // 2
+    static constexpr bool K_ROW_GATHER = false;
+    static constexpr int NS = 4;                                     // stages of the ring
+    static constexpr int STAGE = 2 * IMG;                            // A, B
+    static constexpr int LDS_BYTES = NS * STAGE;                     // 64 KiB
+    template <bool IS_A>
+    static __device__ __forceinline__ int tile_index(int, int r) { return r; }
+    static __device__ __forceinline__ void origin(int, int N, int& m0, int& n0) { brow_major_origin(N, BM, BN, m0, n0); }
+};
+constexpr int BM = Geo::BM, BN = Geo::BN, BK = Geo::BK, NTHREADS = Geo::NTHREADS, NS = Geo::NS;
+constexpr int IMG = Geo::IMG, STAGE = Geo::STAGE, LDS_BYTES = Geo::LDS_BYTES;
 
 typedef b256::f32x4 f32x4;
 
-// A dense K-contiguous operand: two 1-KiB pieces per wave and K-tile (wave w fills rows 16 w .. 16 w + 15).
-struct Load {
-    static constexpr bool KC = true;
-    __amdgpu_buffer_rsrc_t rsrc;
-    unsigned voff[2];
-    int kloc[2];
-    __device__ __forceinline__ void init(const BOperand& o, int origin, int lane, int wave) {
-        rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(o.p), 0, (int)o.bytes, 0x00020000);
-#pragma unroll
-        for (int jj = 0; jj < 2; ++jj) {
-            const int rp = 8 * (2 * wave + jj) + (lane >> 3);
-            const int c = (lane & 7) ^ ((rp >> 1) & 7);
-            const int row = min(origin + rp, o.extent - 1);
-            const long src = o.gather ? (long)o.gather[row] : (long)row;
-            voff[jj] = (unsigned)((src * o.ld + 8 * c) * 2);
-            kloc[jj] = 8 * c;
-        }
-    }
-    __device__ __forceinline__ void issue(char* img, int k0, int kend, int wave) const {
-        const bool tail = k0 + BK > kend;
-#pragma unroll
-        for (int jj = 0; jj < 2; ++jj) {
-            const unsigned v = (tail && k0 + kloc[jj] >= kend) ? kOobOffset : voff[jj];
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (DC_LDS void*)(img + (2 * wave + jj) * 1024), 16, (int)v, k0 * 2, 0, 0);
-        }
-    }
-};
-
 // acc[tm][tn]: element j of lane l is C[m0 + 32 wm + 16 tm + (l & 15)][n0 + 32 wn + 16 tn + 4 (l >> 4) + j].
-// LA / LB: loaders with issue(char* image, int k0, int kend, int wave) issuing exactly two pieces each.
+// LA / LB: operand loaders on Geo (bgemm_core.h), both KC; the vmcnt(8) below counts their Geo::NP = 2 pieces each.  Every K-tile is
+// issued exactly once and in order starting at kbeg, and up to three (empty) K-tiles past the end.
 template <class LA, class LB>
 __device__ __forceinline__ void mainloop(LA& la, LB& lb, char* smem, int kbeg, int kend, f32x4 (&acc)[2][2]) {
     const int lane = threadIdx.x & 63;
@@ -73,16 +58,16 @@ __device__ __forceinline__ void mainloop(LA& la, LB& lb, char* smem, int kbeg, i
     // prologue: K-tiles 0, 1, 2 into stages 0, 1, 2 (tiles past the end are issued out of range: hardware zeros, uniform counts)
 #pragma unroll
     for (int j = 0; j < NS - 1; ++j) {
-        la.issue(smem + j * STAGE, kbeg + j * BK, kend, wave);
-        lb.issue(smem + j * STAGE + IMG, kbeg + j * BK, kend, wave);
+        la.issue(0, smem + j * STAGE, kbeg + j * BK, kend, wave);
+        lb.issue(0, smem + j * STAGE + IMG, kbeg + j * BK, kend, wave);
     }
     auto step = [&](int kt, auto st_c) {
         constexpr int ST = decltype(st_c)::value;                          // stage of K-tile kt
         constexpr int NX = (ST + NS - 1) % NS;                             // stage that tile kt + 3 goes into (= tile kt - 1's)
         asm volatile("s_waitcnt vmcnt(8)" ::: "memory");                   // this wave's pieces of tile kt have landed (kt + 1, kt + 2 in flight)
         __builtin_amdgcn_s_barrier();                                      // every wave's have; every wave is done reading tile kt - 1
-        la.issue(smem + NX * STAGE, kbeg + (kt + NS - 1) * BK, kend, wave);
-        lb.issue(smem + NX * STAGE + IMG, kbeg + (kt + NS - 1) * BK, kend, wave);
+        la.issue(0, smem + NX * STAGE, kbeg + (kt + NS - 1) * BK, kend, wave);
+        lb.issue(0, smem + NX * STAGE + IMG, kbeg + (kt + NS - 1) * BK, kend, wave);
         b256::FragReg<true> A[2][2], B[2][2];
         b256::frag_read<true, 2, 0>(fa, (unsigned)(ST * STAGE), A);
         b256::frag_read<true, 2, 0>(fb, (unsigned)(ST * STAGE), B);

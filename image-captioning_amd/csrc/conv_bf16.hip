@@ -20,41 +20,55 @@ struct BConvA {
     unsigned bytes;
 };
 
+// The A operand on any of the three tiles (geometry G: bgemm_core.h).  (ky, kx, c0) is the (tap, channel chunk) of the NEXT K-tile:
+// derived once from kbeg, then advanced by an add and two compares after the last half of each K-tile -- the main loops issue every
+// (K-tile, half) exactly once and in order, 64 channels at a time, so k0 serves only the k0 < kend test.  The empty K-tiles that
+// b64::mainloop and b256::mainloop issue past the end advance the walk too; nothing live is loaded after them.
+template <class G>
 struct BLoadConvA {
     static constexpr bool KC = true;
     __amdgpu_buffer_rsrc_t rsrc;
     BConvA c;
-    unsigned base[B_NP];           // byte offset of (image n, row 0, col 0, this lane's channel chunk)
-    int iy0[B_NP], ix0[B_NP];      // input row / column of tap (0, 0) for this lane's output pixel
-    int kpt;                       // K-tiles per tap = Cin / 64
-    __device__ __forceinline__ void init(const BConvA& cc, int m0, int lane, int wave) {
+    unsigned base[G::HALVES][G::NP];               // [half][piece]: byte offset of (image n, row 0, col 0, this lane's channel chunk)
+    int iy0[G::HALVES][G::NP], ix0[G::HALVES][G::NP];   // input row / column of tap (0, 0) for this lane's output pixel
+    int ky, kx, c0;
+    __device__ __forceinline__ void init(const BConvA& cc, int m0, int lane, int wave, int kbeg) {
         c = cc;
-        kpt = c.Cin / BKB;
+        const int tap = kbeg / c.Cin;                                      // block-uniform; k = tap * Cin + channel
+        ky = tap / c.kw;
+        kx = tap - ky * c.kw;
+        c0 = kbeg - tap * c.Cin;
         rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(c.x), 0, (int)c.bytes, 0x00020000);
 #pragma unroll
-        for (int j = 0; j < B_NP; ++j) {
-            const int pc = wave * B_NP + j;
-            const int r = 8 * pc + (lane >> 3);                       // tile row (output pixel) of this lane's chunk
-            const int ch = (lane & 7) ^ ((r >> 1) & 7);               // source chunk that lands in LDS chunk (lane & 7)
-            const int p = min(m0 + r, c.M - 1);                       // pixels past the end feed rows that are never stored
-            const int n = p / (c.Ho * c.Wo), rem = p - n * (c.Ho * c.Wo);
-            const int oy = rem / c.Wo, ox = rem - oy * c.Wo;
-            iy0[j] = oy * c.stride - c.pad_t;
-            ix0[j] = ox * c.stride - c.pad_l;
-            base[j] = (unsigned)(((long)n * c.H * c.W * c.Cin + 8 * ch) * 2);
-        }
-    }
-    __device__ __forceinline__ void issue(char* img, int k0, int kend, int wave) const {
-        const int t = k0 / BKB;                                        // block-uniform: K-tile -> (tap, channel chunk)
-        const int tap = t / kpt, c0 = (t - tap * kpt) * BKB;
-        const int ky = tap / c.kw, kx = tap - ky * c.kw;
-        const bool live = k0 < kend;
+        for (int u = 0; u < G::HALVES; ++u)
 #pragma unroll
-        for (int j = 0; j < B_NP; ++j) {
-            const int iy = iy0[j] + ky, ix = ix0[j] + kx;
+            for (int j = 0; j < G::NP; ++j) {
+                const int r = 8 * (wave * G::NP + j) + (lane >> 3);        // sub-image row (output pixel) of this lane's chunk
+                const int ch = (lane & 7) ^ ((r >> 1) & 7);                // source chunk that lands in LDS chunk (lane & 7)
+                const int p = min(m0 + G::template tile_index<true>(u, r), c.M - 1);   // pixels past the end feed rows that are never stored
+                const int n = p / (c.Ho * c.Wo), rem = p - n * (c.Ho * c.Wo);
+                const int oy = rem / c.Wo, ox = rem - oy * c.Wo;
+                iy0[u][j] = oy * c.stride - c.pad_t;
+                ix0[u][j] = ox * c.stride - c.pad_l;
+                base[u][j] = (unsigned)(((long)n * c.H * c.W * c.Cin + 8 * ch) * 2);
+            }
+    }
+    __device__ __forceinline__ void issue(int u, char* img, int k0, int kend, int wave) {
+        const bool live = k0 < kend;
+        const int tapoff = ((ky * c.W + kx) * c.Cin + c0) * 2;             // block-uniform
+#pragma unroll
+        for (int j = 0; j < G::NP; ++j) {
+            const int iy = iy0[u][j] + ky, ix = ix0[u][j] + kx;
             const bool in = live && (unsigned)iy < (unsigned)c.H && (unsigned)ix < (unsigned)c.W;
-            const unsigned off = base[j] + (unsigned)(((iy * c.W + ix) * c.Cin + c0) * 2);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (DC_LDS void*)(img + (wave * B_NP + j) * 1024), 16, (int)(in ? off : kOobOffset), 0, 0, 0);
+            const unsigned off = base[u][j] + (unsigned)((iy0[u][j] * c.W + ix0[u][j]) * c.Cin * 2);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (DC_LDS void*)(img + (wave * G::NP + j) * 1024), 16, (int)(in ? off + (unsigned)tapoff : kOobOffset), 0, 0, 0);
+        }
+        if (u == G::HALVES - 1) {
+            c0 += G::BK;
+            if (c0 >= c.Cin) {
+                c0 = 0;
+                if (++kx >= c.kw) { kx = 0; ++ky; }
+            }
         }
     }
 };
@@ -65,133 +79,47 @@ __global__ __launch_bounds__(256, 2) void bconv_kernel(BConvA a, BOperand b, Epi
     char* smem = reinterpret_cast<char*>(smem_f);
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int tiles_n = (N + BT - 1) / BT;
-    const int lid = xcd_remap(blockIdx.x, gridDim.x);
-    const int m0 = (lid / tiles_n) * BT, n0 = (lid % tiles_n) * BT;
+    int m0, n0;
+    BGeo128::origin(M, N, m0, n0);
     const int kbeg = blockIdx.z * klen, kend = min(K, kbeg + klen);
     const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
-    BLoadConvA la;
-    BLoadOp<true> lb;
-    la.init(a, m0, lane, wave);
-    lb.init(b, n0, lane, wave);
+    BLoadConvA<BGeo128> la;
+    BLoadDense<BGeo128, true, false> lb;
+    la.init(a, m0, lane, wave, kbeg);
+    lb.init(b, n0, lane, wave, kbeg);
     f32x16 acc[2][2];
     bgemm_mainloop_t(la, lb, smem, kbeg, kend, acc, wm, wn);
     store_tile<BT, BT>(acc, smem_f, ep, partial, M, N, m0, n0, wm, wn);
 }
 
-// The same A operand for the 256 x 256 tile (bgemm256_core.h): two 128-row sub-images per K-tile, two 1-KiB pieces per wave each.
-struct BLoadConvA256 {
-    static constexpr bool KC = true;
-    __amdgpu_buffer_rsrc_t rsrc;
-    BConvA c;
-    unsigned base[2][2];           // [half][piece]: byte offset of (image n, row 0, col 0, this lane's channel chunk)
-    int iy0[2][2], ix0[2][2];      // input row / column of tap (0, 0) for this lane's output pixel
-    int kpt;                       // K-tiles per tap = Cin / 64
-    __device__ __forceinline__ void init(const BConvA& cc, int m0, int lane, int wave) {
-        c = cc;
-        kpt = c.Cin / BKB;
-        rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(c.x), 0, (int)c.bytes, 0x00020000);
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-            for (int jj = 0; jj < 2; ++jj) {
-                const int rp = 8 * (2 * wave + jj) + (lane >> 3);         // sub-image row of this lane's chunk
-                const int ch = (lane & 7) ^ ((rp >> 1) & 7);
-                const int p = min(m0 + b256::tile_index<true>(u, rp), c.M - 1);   // pixels past the end feed rows that are never stored
-                const int n = p / (c.Ho * c.Wo), rem = p - n * (c.Ho * c.Wo);
-                const int oy = rem / c.Wo, ox = rem - oy * c.Wo;
-                iy0[u][jj] = oy * c.stride - c.pad_t;
-                ix0[u][jj] = ox * c.stride - c.pad_l;
-                base[u][jj] = (unsigned)(((long)n * c.H * c.W * c.Cin + 8 * ch) * 2);
-            }
-    }
-    __device__ __forceinline__ void issue(int u, char* sub, int k0, int kend, int wave) const {
-        const int t = k0 / BKB;                                        // block-uniform: K-tile -> (tap, channel chunk)
-        const int tap = t / kpt, c0 = (t - tap * kpt) * BKB;
-        const int ky = tap / c.kw, kx = tap - ky * c.kw;
-        const bool live = k0 < kend;
-#pragma unroll
-        for (int jj = 0; jj < 2; ++jj) {
-            const int iy = iy0[u][jj] + ky, ix = ix0[u][jj] + kx;
-            const bool in = live && (unsigned)iy < (unsigned)c.H && (unsigned)ix < (unsigned)c.W;
-            const unsigned off = base[u][jj] + (unsigned)(((iy * c.W + ix) * c.Cin + c0) * 2);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (DC_LDS void*)(sub + (2 * wave + jj) * 1024), 16, (int)(in ? off : kOobOffset), 0, 0, 0);
-        }
-    }
-};
-
+// The 256 x 256 tile (bgemm256_core.h)
 __global__ __launch_bounds__(b256::NTHREADS, 2) void bconv256_kernel(BConvA a, BOperand b, Epilogue ep, int M, int N, int K, int klen, float* __restrict__ partial) {
     extern __shared__ __attribute__((aligned(16))) float smem_f[];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int tiles_m = (M + b256::BM - 1) / b256::BM, tiles_n = (N + b256::BN - 1) / b256::BN;
-    int tm, tn;
-    b256::tile_coords(xcd_remap(blockIdx.x, gridDim.x), tiles_m, tiles_n, tm, tn);
-    const int m0 = tm * b256::BM, n0 = tn * b256::BN;
+    int m0, n0;
+    b256::Geo::origin(M, N, m0, n0);
     const int kbeg = blockIdx.z * klen, kend = min(K, kbeg + klen);
-    BLoadConvA256 la;
-    b256::Load<true, false> lb;
-    la.init(a, m0, lane, wave);
-    lb.init(b, n0, lane, wave);
+    BLoadConvA<b256::Geo> la;
+    BLoadDense<b256::Geo, true, false> lb;
+    la.init(a, m0, lane, wave, kbeg);
+    lb.init(b, n0, lane, wave, kbeg);
     b256::f32x4 acc[8][4];
     b256::mainloop(la, lb, reinterpret_cast<char*>(smem_f), kbeg, kend, acc);
     b256::store_tile(acc, ep, partial, M, N, m0, n0);
 }
 
-// ... and for the 64 x 64 tile (bgemm64_core.h): one 64-row image per K-tile, two pieces per wave.
-struct BLoadConvA64 {
-    static constexpr bool KC = true;
-    __amdgpu_buffer_rsrc_t rsrc;
-    BConvA c;
-    unsigned base[2];
-    int iy0[2], ix0[2];
-    int ky, kx, c0;                // (tap, channel chunk) of the NEXT K-tile: the main loop issues K-tiles in order, 64 channels at a time
-    __device__ __forceinline__ void init(const BConvA& cc, int m0, int lane, int wave) {
-        c = cc;
-        ky = kx = c0 = 0;
-        rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(c.x), 0, (int)c.bytes, 0x00020000);
-#pragma unroll
-        for (int jj = 0; jj < 2; ++jj) {
-            const int rp = 8 * (2 * wave + jj) + (lane >> 3);
-            const int ch = (lane & 7) ^ ((rp >> 1) & 7);
-            const int p = min(m0 + rp, c.M - 1);
-            const int n = p / (c.Ho * c.Wo), rem = p - n * (c.Ho * c.Wo);
-            const int oy = rem / c.Wo, ox = rem - oy * c.Wo;
-            iy0[jj] = oy * c.stride - c.pad_t;
-            ix0[jj] = ox * c.stride - c.pad_l;
-            base[jj] = (unsigned)(((long)n * c.H * c.W * c.Cin + 8 * ch) * 2);
-        }
-    }
-    // K-tiles arrive in order starting at k = 0 (bgemm64_core.h: no split-K), so the tap walk is an add and two compares
-    __device__ __forceinline__ void issue(char* img, int k0, int kend, int wave) {
-        const bool live = k0 < kend;
-        const int tapoff = ((ky * c.W + kx) * c.Cin + c0) * 2;             // block-uniform
-#pragma unroll
-        for (int jj = 0; jj < 2; ++jj) {
-            const int iy = iy0[jj] + ky, ix = ix0[jj] + kx;
-            const bool in = live && (unsigned)iy < (unsigned)c.H && (unsigned)ix < (unsigned)c.W;
-            const unsigned off = base[jj] + (unsigned)((iy0[jj] * c.W + ix0[jj]) * c.Cin * 2);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (DC_LDS void*)(img + (2 * wave + jj) * 1024), 16, (int)(in ? off + (unsigned)tapoff : kOobOffset), 0, 0, 0);
-        }
-        c0 += BKB;
-        if (c0 >= c.Cin) {
-            c0 = 0;
-            if (++kx >= c.kw) { kx = 0; ++ky; }
-        }
-    }
-};
-
+// ... and the 64 x 64 tile (bgemm64_core.h): the whole K loop in one block
 __global__ __launch_bounds__(b64::NTHREADS, 2) void bconv64_kernel(BConvA a, BOperand b, Epilogue ep, int M, int N, int K) {
     extern __shared__ __attribute__((aligned(16))) float smem_f[];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int tiles_n = (N + b64::BN - 1) / b64::BN;
-    const int lid = xcd_remap(blockIdx.x, gridDim.x);
-    const int m0 = (lid / tiles_n) * b64::BM, n0 = (lid % tiles_n) * b64::BN;
-    BLoadConvA64 la;
-    b64::Load lb;
-    la.init(a, m0, lane, wave);
-    lb.init(b, n0, lane, wave);
+    int m0, n0;
+    b64::Geo::origin(M, N, m0, n0);
+    BLoadConvA<b64::Geo> la;
+    BLoadDense<b64::Geo, true, false> lb;
+    la.init(a, m0, lane, wave, 0);
+    lb.init(b, n0, lane, wave, 0);
     b64::f32x4 acc[2][2];
     b64::mainloop(la, lb, reinterpret_cast<char*>(smem_f), 0, K, acc);
     b64::store_tile(acc, ep, M, N, m0, n0);
@@ -234,8 +162,7 @@ using namespace dcap;
 // Which tile runs this layer: 256 (the P2 / P3-level FPN and RPN layers and their data gradients), 64 (the one-image trunk layers:
 // whole K loop in one block, no split-K slabs) or 128, by the cost model of bgemm256_core.h / bgemm64_core.h.
 // dc_conv_bf16_desc.tile = 64 | 128 | 256 forces a choice where the shape allows it (tests, benches).
-static int bconv_tile(const dc_conv_bf16_desc* d, int M, int N, int K) {
-    const bool vec4 = (d->Cout & 3) == 0 && (!d->residual || aligned16(d->residual)) && (!d->scale || aligned16(d->scale)) && (!d->shift || aligned16(d->shift));
+static int bconv_tile(const dc_conv_bf16_desc* d, bool vec4, int M, int N, int K) {
     const int forced = d->tile;
     if (!vec4 || M < 4 || N < 4) return 128;
     if (forced == 128) return 128;
@@ -247,68 +174,48 @@ static int bconv_tile(const dc_conv_bf16_desc* d, int M, int N, int K) {
     const double c64 = d->split_k > 1 ? 1e30 : b64::cost_us(M, N, K);           // (a caller that asks for slabs gets a split-K tile)
     return (c256 <= c128 && c256 <= c64) ? 256 : (c64 < c128 ? 64 : 128);
 }
-static BSplit bconv_split_for(int tile, int M, int N, int K, int user_split) {
-    if (tile == 256) return b256::split(M, N, K, user_split);
-    if (tile == 64) return BSplit{1, ((K + BKB - 1) / BKB) * BKB};
-    return bconv_split(M, N, K, user_split);
+
+struct BConvPlan : BPlan {
+    int M, N, K;                   // the implicit GEMM
+    bool vec4;                     // 16-byte epilogue accesses are possible (Epilogue::vec4)
+};
+static BConvPlan bconv_plan(const dc_conv_bf16_desc* d) {
+    const int M = d->N * d->Ho * d->Wo, N = d->Cout, K = d->kh * d->kw * d->Cin;
+    const bool vec4 = (d->Cout & 3) == 0 && (!d->residual || aligned16(d->residual)) && (!d->scale || aligned16(d->scale)) && (!d->shift || aligned16(d->shift));
+    const int tile = bconv_tile(d, vec4, M, N, K);
+    const BSplit sp = tile == 256 ? b256::split(M, N, K, d->split_k) : tile == 64 ? BSplit{1, ((K + BKB - 1) / BKB) * BKB} : bconv_split(M, N, K, d->split_k);
+    return BConvPlan{{tile, sp}, M, N, K, vec4};
 }
 
 extern "C" size_t dc_conv2d_bf16_workspace_bytes(const dc_conv_bf16_desc* d) {
     if (!d || conv_bf16_validate(d)) return 0;
-    const int M = d->N * d->Ho * d->Wo, N = d->Cout, K = d->kh * d->kw * d->Cin;
-    const BSplit sp = bconv_split_for(bconv_tile(d, M, N, K), M, N, K, d->split_k);
-    return sp.split > 1 ? (size_t)sp.split * M * N * sizeof(float) : 0;
+    const BConvPlan p = bconv_plan(d);
+    return p.workspace_bytes(p.M, p.N);
 }
 
 extern "C" int dc_conv2d_bf16_tile(const dc_conv_bf16_desc* d, int* split_k) {
     if (!d || conv_bf16_validate(d)) return 0;
-    const int M = d->N * d->Ho * d->Wo, N = d->Cout, K = d->kh * d->kw * d->Cin;
-    const int tile = bconv_tile(d, M, N, K);
-    if (split_k) *split_k = bconv_split_for(tile, M, N, K, d->split_k).split;
-    return tile;
+    const BConvPlan p = bconv_plan(d);
+    if (split_k) *split_k = p.sp.split;
+    return p.tile;
 }
 
 extern "C" int dc_conv2d_bf16(const dc_conv_bf16_desc* d, void* workspace, size_t workspace_bytes, void* stream) {
     int rc = conv_bf16_validate(d);
     if (rc) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int M = d->N * d->Ho * d->Wo, N = d->Cout, K = d->kh * d->kw * d->Cin;
-    const int tile = bconv_tile(d, M, N, K);
-    const bool big = tile == 256;
-    const BSplit sp = bconv_split_for(tile, M, N, K, d->split_k);
-    float* partial = nullptr;
-    if (sp.split > 1) {
-        const size_t need = (size_t)sp.split * M * N * sizeof(float);
-        DC_REQUIRE(workspace != nullptr && workspace_bytes >= need, DC_EWORKSPACE, "dc_conv2d_bf16 split-K needs %zu workspace bytes, got %zu", need,
-                   workspace_bytes);
-        DC_REQUIRE_SLAB_ALIGNED("dc_conv2d_bf16 split-K", workspace, N);
-        partial = static_cast<float*>(workspace);
-    }
-    Epilogue ep{d->y, d->Cout, d->scale, d->shift, d->residual, d->Cout, d->res_mode, d->Ho, d->Wo, d->relu, 0, 0};
-    ep.vec4 = (d->Cout & 3) == 0 && (!d->residual || aligned16(d->residual)) && (!d->scale || aligned16(d->scale)) && (!d->shift || aligned16(d->shift));
+    const BConvPlan p = bconv_plan(d);
+    const int M = p.M, N = p.N, K = p.K;
+    Epilogue ep{d->y, d->Cout, d->scale, d->shift, d->residual, d->Cout, d->res_mode, d->Ho, d->Wo, d->relu, 0, p.vec4};
     ep.Cb = d->y_bf16;
     ep.ldcb = d->Cout;
-    BConvA a{d->x, d->H, d->W, d->Cin, d->Ho, d->Wo, d->stride, d->pad_t, d->pad_l, d->kw, M, (unsigned)((size_t)d->N * d->H * d->W * d->Cin * 2)};
-    BOperand b{d->w, K, N, nullptr, (unsigned)((size_t)N * K * 2)};
-    if (tile == 64) {
-        DC_ENSURE_DYN_LDS(&bconv64_kernel, 160 * 1024);
-        const int tiles = ((M + b64::BM - 1) / b64::BM) * ((N + b64::BN - 1) / b64::BN);
-        hipLaunchKernelGGL(bconv64_kernel, dim3(tiles), dim3(b64::NTHREADS), b64::LDS_BYTES, s, a, b, ep, M, N, K);
-        return check_launch("bconv64_kernel");
-    }
-    if (big) {
-        DC_ENSURE_DYN_LDS(&bconv256_kernel, 160 * 1024);
-        const int tiles = ((M + b256::BM - 1) / b256::BM) * ((N + b256::BN - 1) / b256::BN);
-        hipLaunchKernelGGL(bconv256_kernel, dim3(tiles, 1, sp.split), dim3(b256::NTHREADS), b256::LDS_BYTES, s, a, b, ep, M, N, K, sp.klen, partial);
-        rc = check_launch("bconv256_kernel");
-    } else {
-        DC_ENSURE_DYN_LDS(&bconv_kernel, 160 * 1024);
-        const int tiles = ((M + BT - 1) / BT) * ((N + BT - 1) / BT);
-        hipLaunchKernelGGL(bconv_kernel, dim3(tiles, 1, sp.split), dim3(256), bgemm_lds_bytes(), s, a, b, ep, M, N, K, sp.klen, partial);
-        rc = check_launch("bconv_kernel");
-    }
-    if (rc || sp.split <= 1) return rc;
-    const long total = (long)M * N;
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(splitk_reduce_blocks(total)), dim3(256), 0, s, partial, sp.split, M, N, ep);
-    return check_launch("splitk_reduce_kernel");
+    const BConvA a{d->x, d->H, d->W, d->Cin, d->Ho, d->Wo, d->stride, d->pad_t, d->pad_l, d->kw, M, (unsigned)((size_t)d->N * d->H * d->W * d->Cin * 2)};
+    const BOperand b{d->w, K, N, nullptr, (unsigned)((size_t)N * K * 2)};
+    const char* who = "dc_conv2d_bf16 split-K";
+    if (p.tile == 256) return bgemm_run<b256::Geo, &bconv256_kernel>(who, "bconv256_kernel", a, b, ep, M, N, K, p.sp, workspace, workspace_bytes, s);
+    if (p.tile == 128) return bgemm_run<BGeo128, &bconv_kernel>(who, "bconv_kernel", a, b, ep, M, N, K, p.sp, workspace, workspace_bytes, s);
+    DC_ENSURE_DYN_LDS(&bconv64_kernel, 160 * 1024);
+    const int tiles = ((M + b64::BM - 1) / b64::BM) * ((N + b64::BN - 1) / b64::BN);
+    hipLaunchKernelGGL(bconv64_kernel, dim3(tiles), dim3(b64::NTHREADS), b64::LDS_BYTES, s, a, b, ep, M, N, K);
+    return check_launch("bconv64_kernel");
 }

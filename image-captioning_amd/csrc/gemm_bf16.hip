@@ -14,85 +14,31 @@ __global__ __launch_bounds__(256, 2) void bgemm_wgrad_kernel(BOperand dy, BIm2co
     char* smem = reinterpret_cast<char*>(smem_f);
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int tiles_n = (N + BT - 1) / BT;
-    const int lid = xcd_remap(blockIdx.x, gridDim.x);
-    const int m0 = (lid / tiles_n) * BT, n0 = (lid % tiles_n) * BT;
+    int m0, n0;
+    BGeo128::origin(M, N, m0, n0);
     const int kbeg = blockIdx.z * klen, kend = min(K, kbeg + klen);
     const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
-    BLoadOp<false> la;
-    BLoadIm2col lb;
-    la.init(dy, m0, lane, wave);
-    lb.init(xc, n0, kbeg, lane, wave);
+    BLoadDense<BGeo128, false, true> la;
+    BLoadIm2col<BGeo128> lb;
+    la.init(dy, m0, lane, wave, kbeg);
+    lb.init(xc, n0, lane, wave, kbeg);
     f32x16 acc[2][2];
     bgemm_mainloop_t(la, lb, smem, kbeg, kend, acc, wm, wn);
     store_tile<BT, BT>(acc, smem_f, ep, partial, M, N, m0, n0, wm, wn);
 }
 
 // The same weight gradient on the 256 x 256 tile (bgemm256_core.h): the K-major im2col operand as two 128-column sub-images.
-// A 256-column tile may span several taps (Cin = 128: two), so the tap offset is per lane (fixed over the K loop: a lane's columns
-// never change); the pixel walk advances once per K-tile, after the second half has been issued (the main loop always issues
-// half 0, then half 1 of a K-tile).
-struct BLoadIm2col256 {
-    static constexpr bool KC = false;
-    __amdgpu_buffer_rsrc_t rsrc;
-    BIm2col c;
-    int n[2], oy[2], ox[2];        // [piece]: output pixel of this lane's K row in the NEXT K-tile to issue
-    int dy[2][2], dx[2][2];        // [half][piece]: tap offset of this lane's 8-column chunk
-    unsigned cio[2][2];            // byte offset of its first channel inside the pixel
-    int krow[2];
-    __device__ __forceinline__ void init(const BIm2col& cc, int col0, int kbeg, int lane, int wave) {
-        c = cc;
-        rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(c.x), 0, (int)c.bytes, 0x00020000);
-#pragma unroll
-        for (int jj = 0; jj < 2; ++jj) {
-            const int k = 4 * (2 * wave + jj) + (lane >> 4);               // K row inside the tile
-            krow[jj] = k;
-            const int p = kbeg + k;
-            const int nn = p / (c.Ho * c.Wo), rem = p - nn * (c.Ho * c.Wo);
-            n[jj] = nn;
-            oy[jj] = rem / c.Wo;
-            ox[jj] = rem - oy[jj] * c.Wo;
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                const int ch = (lane & 15) ^ (((k & 3) << 2) | ((k >> 2) & 3));
-                const int col = min(col0 + b256::tile_index<false>(u, 8 * ch), c.ncols - 8);   // columns past the edge: clamped, never stored
-                const int tap = col / c.Cin, ci = col - tap * c.Cin;
-                const int ky = tap / c.kw, kx = tap - ky * c.kw;
-                dy[u][jj] = ky - c.pad_t;
-                dx[u][jj] = kx - c.pad_l;
-                cio[u][jj] = (unsigned)(ci * 2);
-            }
-        }
-    }
-    __device__ __forceinline__ void issue(int u, char* sub, int k0, int kend, int wave) {
-#pragma unroll
-        for (int jj = 0; jj < 2; ++jj) {
-            const int iy = oy[jj] * c.stride + dy[u][jj], ix = ox[jj] * c.stride + dx[u][jj];
-            const bool in = (unsigned)iy < (unsigned)c.H && (unsigned)ix < (unsigned)c.W && k0 + krow[jj] < min(c.P, kend);
-            const unsigned off = (unsigned)((((long)n[jj] * c.H + iy) * c.W + ix) * c.Cin * 2) + cio[u][jj];
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (DC_LDS void*)(sub + (2 * wave + jj) * 1024), 16, (int)(in ? off : kOobOffset), 0, 0, 0);
-            if (u == 1) {                                                       // both halves of this K-tile are out: 64 pixels on
-                ox[jj] += b256::BK;
-                while (ox[jj] >= c.Wo) { ox[jj] -= c.Wo; ++oy[jj]; }
-                while (oy[jj] >= c.Ho) { oy[jj] -= c.Ho; ++n[jj]; }
-            }
-        }
-    }
-};
-
 __global__ __launch_bounds__(b256::NTHREADS, 2) void bgemm256_wgrad_kernel(BOperand dy, BIm2col xc, Epilogue ep, int M, int N, int K, int klen, float* __restrict__ partial) {
     extern __shared__ __attribute__((aligned(16))) float smem_f[];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int tiles_m = (M + b256::BM - 1) / b256::BM, tiles_n = (N + b256::BN - 1) / b256::BN;
-    int tm, tn;
-    b256::tile_coords(xcd_remap(blockIdx.x, gridDim.x), tiles_m, tiles_n, tm, tn);
-    const int m0 = tm * b256::BM, n0 = tn * b256::BN;
+    int m0, n0;
+    b256::Geo::origin(M, N, m0, n0);
     const int kbeg = blockIdx.z * klen, kend = min(K, kbeg + klen);
-    b256::Load<false, true> la;
-    BLoadIm2col256 lb;
-    la.init(dy, m0, lane, wave);
-    lb.init(xc, n0, kbeg, lane, wave);
+    BLoadDense<b256::Geo, false, true> la;
+    BLoadIm2col<b256::Geo> lb;
+    la.init(dy, m0, lane, wave, kbeg);
+    lb.init(xc, n0, lane, wave, kbeg);
     b256::f32x4 acc[8][4];
     b256::mainloop(la, lb, reinterpret_cast<char*>(smem_f), kbeg, kend, acc);
     b256::store_tile(acc, ep, partial, M, N, m0, n0);
@@ -173,38 +119,43 @@ using namespace dcap;
 
 // the 256-square kernel (bgemm256_core.h) where its grid fills the chip; the K-major gather (embedding-side weight gradient) stays
 // on the 128-square loop
-static bool use_b256(const dc_gemm_bf16_desc* d) { return !(d->a_gather && d->a_trans) && b256::prefer(d->M, d->N, d->K, d->split_k, bgemm_epilogue(d).vec4 != 0); }
+static BPlan bgemm_plan(const dc_gemm_bf16_desc* d) {
+    const bool big = !(d->a_gather && d->a_trans) && b256::prefer(d->M, d->N, d->K, d->split_k, bgemm_epilogue(d).vec4 != 0);
+    return b256::plan(big, d->M, d->N, d->K, d->split_k);
+}
 
 extern "C" size_t dc_gemm_bf16_workspace_bytes(const dc_gemm_bf16_desc* d) {
     if (!d || d->M <= 0 || d->N <= 0 || d->K <= 0) return 0;
-    const BSplit sp = use_b256(d) ? b256::split(d->M, d->N, d->K, d->split_k) : bgemm_split(d->M, d->N, d->K, d->split_k);
-    return sp.split > 1 ? (size_t)sp.split * d->M * d->N * sizeof(float) : 0;
+    return bgemm_plan(d).workspace_bytes(d->M, d->N);
 }
 
 extern "C" int dc_gemm_bf16_tile(const dc_gemm_bf16_desc* d, int* split_k) {
     if (!d || d->M <= 0 || d->N <= 0 || d->K <= 0) return 0;
-    const bool big = use_b256(d);
-    if (split_k) *split_k = (big ? b256::split(d->M, d->N, d->K, d->split_k) : bgemm_split(d->M, d->N, d->K, d->split_k)).split;
-    return big ? 256 : 128;
+    const BPlan p = bgemm_plan(d);
+    if (split_k) *split_k = p.sp.split;
+    return p.tile;
+}
+
+template <bool AKC, bool BKC>
+static int bgemm_launch(const dc_gemm_bf16_desc* d, void* workspace, size_t workspace_bytes, hipStream_t s) {
+    const BPlan p = bgemm_plan(d);
+    const Epilogue ep = bgemm_epilogue(d);
+    BOperand a, b;
+    bgemm_operands(d, a, b);
+    if (p.tile == 256)
+        return bgemm_run<b256::Geo, &b256::bgemm256_kernel<AKC, BKC>>("bgemm256 split-K", "bgemm256_kernel", a, b, ep, d->M, d->N, d->K, p.sp, workspace,
+                                                                      workspace_bytes, s);
+    return bgemm_run<BGeo128, &bgemm_kernel<AKC, BKC>>("bgemm split-K", "bgemm_kernel", a, b, ep, d->M, d->N, d->K, p.sp, workspace, workspace_bytes, s);
 }
 
 extern "C" int dc_gemm_bf16(const dc_gemm_bf16_desc* d, void* workspace, size_t workspace_bytes, void* stream) {
     int rc = bgemm_validate(d);
     if (rc) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const Epilogue ep = bgemm_epilogue(d);
-    BOperand a, b;
-    bgemm_operands(d, a, b);
-    if (use_b256(d)) {
-        if (!d->a_trans && !d->b_trans) return b256::launch<true, false>(a, b, ep, d->M, d->N, d->K, d->split_k, workspace, workspace_bytes, s);
-        if (!d->a_trans && d->b_trans) return b256::launch<true, true>(a, b, ep, d->M, d->N, d->K, d->split_k, workspace, workspace_bytes, s);
-        if (d->a_trans && !d->b_trans) return b256::launch<false, false>(a, b, ep, d->M, d->N, d->K, d->split_k, workspace, workspace_bytes, s);
-        return b256::launch<false, true>(a, b, ep, d->M, d->N, d->K, d->split_k, workspace, workspace_bytes, s);
-    }
-    if (!d->a_trans && !d->b_trans) return launch_bgemm<true, false>(a, b, ep, d->M, d->N, d->K, d->split_k, workspace, workspace_bytes, s);
-    if (!d->a_trans && d->b_trans) return launch_bgemm<true, true>(a, b, ep, d->M, d->N, d->K, d->split_k, workspace, workspace_bytes, s);
-    if (d->a_trans && !d->b_trans) return launch_bgemm<false, false>(a, b, ep, d->M, d->N, d->K, d->split_k, workspace, workspace_bytes, s);
-    return launch_bgemm<false, true>(a, b, ep, d->M, d->N, d->K, d->split_k, workspace, workspace_bytes, s);
+    if (!d->a_trans && !d->b_trans) return bgemm_launch<true, false>(d, workspace, workspace_bytes, s);
+    if (!d->a_trans && d->b_trans) return bgemm_launch<true, true>(d, workspace, workspace_bytes, s);
+    if (d->a_trans && !d->b_trans) return bgemm_launch<false, false>(d, workspace, workspace_bytes, s);
+    return bgemm_launch<false, true>(d, workspace, workspace_bytes, s);
 }
 
 static int wgrad_bf16_validate(const dc_conv_wgrad_bf16_desc* d) {
@@ -219,21 +170,22 @@ static int wgrad_bf16_validate(const dc_conv_wgrad_bf16_desc* d) {
     return DC_OK;
 }
 
-static bool wgrad_big(const dc_conv_wgrad_bf16_desc* d, int M, int N, int K) { return (d->Cout & 7) == 0 && b256::prefer(M, N, K, d->split_k, true); }
+static BPlan wgrad_plan(const dc_conv_wgrad_bf16_desc* d) {
+    const int M = d->Cout, N = d->kh * d->kw * d->Cin, K = d->N * d->Ho * d->Wo;
+    const bool big = (d->Cout & 7) == 0 && b256::prefer(M, N, K, d->split_k, true);
+    return b256::plan(big, M, N, K, d->split_k);
+}
 
 extern "C" size_t dc_conv2d_wgrad_bf16_workspace_bytes(const dc_conv_wgrad_bf16_desc* d) {
     if (!d || wgrad_bf16_validate(d)) return 0;
-    const int M = d->Cout, N = d->kh * d->kw * d->Cin, K = d->N * d->Ho * d->Wo;
-    const BSplit sp = wgrad_big(d, M, N, K) ? b256::split(M, N, K, d->split_k) : bgemm_split(M, N, K, d->split_k);
-    return sp.split > 1 ? (size_t)sp.split * M * N * sizeof(float) : 0;
+    return wgrad_plan(d).workspace_bytes(d->Cout, d->kh * d->kw * d->Cin);
 }
 
 extern "C" int dc_conv2d_wgrad_bf16_tile(const dc_conv_wgrad_bf16_desc* d, int* split_k) {
     if (!d || wgrad_bf16_validate(d)) return 0;
-    const int M = d->Cout, N = d->kh * d->kw * d->Cin, K = d->N * d->Ho * d->Wo;
-    const bool big = wgrad_big(d, M, N, K);
-    if (split_k) *split_k = (big ? b256::split(M, N, K, d->split_k) : bgemm_split(M, N, K, d->split_k)).split;
-    return big ? 256 : 128;
+    const BPlan p = wgrad_plan(d);
+    if (split_k) *split_k = p.sp.split;
+    return p.tile;
 }
 
 extern "C" int dc_conv2d_wgrad_bf16(const dc_conv_wgrad_bf16_desc* d, void* workspace, size_t workspace_bytes, void* stream) {
@@ -241,35 +193,13 @@ extern "C" int dc_conv2d_wgrad_bf16(const dc_conv_wgrad_bf16_desc* d, void* work
     if (rc) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int M = d->Cout, N = d->kh * d->kw * d->Cin, K = d->N * d->Ho * d->Wo;
-    const bool big = wgrad_big(d, M, N, K);
-    const BSplit sp = big ? b256::split(M, N, K, d->split_k) : bgemm_split(M, N, K, d->split_k);
-    float* partial = nullptr;
-    if (sp.split > 1) {
-        const size_t need = (size_t)sp.split * M * N * sizeof(float);
-        DC_REQUIRE(workspace != nullptr && workspace_bytes >= need, DC_EWORKSPACE, "dc_conv2d_wgrad_bf16 split-K needs %zu workspace bytes, got %zu",
-                   need, workspace_bytes);
-        DC_REQUIRE_SLAB_ALIGNED("dc_conv2d_wgrad_bf16 split-K", workspace, N);
-        partial = static_cast<float*>(workspace);
-    }
-    Epilogue ep{d->dw, N, nullptr, nullptr, nullptr, 0, 0, 0, 0, 0, d->accumulate, 1};
-    BOperand dy{d->dy, d->Cout, M, nullptr, (unsigned)((size_t)K * d->Cout * 2)};
-    BIm2col xc{d->x, d->H, d->W, d->Cin, d->Ho, d->Wo, d->stride, d->pad_t, d->pad_l, d->kw, K, (unsigned)((size_t)d->N * d->H * d->W * d->Cin * 2), N};
-    if (big) {
-        ep.vec4 = 1;                                           // dw rows are k*k*Cin floats (Cin % 128 == 0), 16-byte aligned base
-        DC_ENSURE_DYN_LDS(&bgemm256_wgrad_kernel, 160 * 1024);
-        const int tiles = ((M + b256::BM - 1) / b256::BM) * ((N + b256::BN - 1) / b256::BN);
-        hipLaunchKernelGGL(bgemm256_wgrad_kernel, dim3(tiles, 1, sp.split), dim3(b256::NTHREADS), b256::LDS_BYTES, s, dy, xc, ep, M, N, K, sp.klen, partial);
-        rc = check_launch("bgemm256_wgrad_kernel");
-    } else {
-        DC_ENSURE_DYN_LDS(&bgemm_wgrad_kernel, 160 * 1024);
-        const int tiles = ((M + BT - 1) / BT) * ((N + BT - 1) / BT);
-        hipLaunchKernelGGL(bgemm_wgrad_kernel, dim3(tiles, 1, sp.split), dim3(256), bgemm_lds_bytes(), s, dy, xc, ep, M, N, K, sp.klen, partial);
-        rc = check_launch("bgemm_wgrad_kernel");
-    }
-    if (rc || sp.split <= 1) return rc;
-    const long total = (long)M * N;
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(splitk_reduce_blocks(total)), dim3(256), 0, s, partial, sp.split, M, N, ep);
-    return check_launch("splitk_reduce_kernel");
+    const BPlan p = wgrad_plan(d);
+    const Epilogue ep{d->dw, N, nullptr, nullptr, nullptr, 0, 0, 0, 0, 0, d->accumulate, 1};   // vec4: dw rows are k*k*Cin floats (Cin % 128 == 0), 16-byte aligned base
+    const BOperand dy{d->dy, d->Cout, M, nullptr, (unsigned)((size_t)K * d->Cout * 2)};
+    const BIm2col xc{d->x, d->H, d->W, d->Cin, d->Ho, d->Wo, d->stride, d->pad_t, d->pad_l, d->kw, K, (unsigned)((size_t)d->N * d->H * d->W * d->Cin * 2), N};
+    const char* who = "dc_conv2d_wgrad_bf16 split-K";
+    if (p.tile == 256) return bgemm_run<b256::Geo, &bgemm256_wgrad_kernel>(who, "bgemm256_wgrad_kernel", dy, xc, ep, M, N, K, p.sp, workspace, workspace_bytes, s);
+    return bgemm_run<BGeo128, &bgemm_wgrad_kernel>(who, "bgemm_wgrad_kernel", dy, xc, ep, M, N, K, p.sp, workspace, workspace_bytes, s);
 }
 
 extern "C" int dc_cast_f32_bf16(const float* x, uint16_t* out, size_t n, void* stream) {

@@ -204,8 +204,8 @@ __global__ __launch_bounds__(b256::NTHREADS, 2) void vocab_topk_bf16_256_kernel(
     int tile_m, tile_n;
     b256::tile_coords(xcd_remap(blockIdx.x, gridDim.x), tiles_m, tiles_n, tile_m, tile_n);
     const int m0 = tile_m * b256::BM, n0 = tile_n * b256::BN;
-    b256::Load<true, true> la;
-    b256::Load<false, false> lb;
+    BLoadDense<b256::Geo, true, true> la;
+    BLoadDense<b256::Geo, false, false> lb;
     la.init(a, m0, lane, wave);
     lb.init(b, n0, lane, wave);
     b256::f32x4 acc[8][4];
