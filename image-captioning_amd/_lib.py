@@ -290,6 +290,7 @@ SYMBOLS = {
                                          C.c_float, C.c_float, C.c_float, C.c_void_p]),
     "dc_resize_pad_u8_workspace_bytes": (C.c_size_t, [C.POINTER(ResizePadDesc)]),
     "dc_resize_pad_u8": (C.c_int, [C.POINTER(ResizePadDesc), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "dc_resize_pad_flip_u8": (C.c_int, [C.POINTER(ResizePadDesc), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
     "dc_roi_align_pyramid_f32": (C.c_int, [C.POINTER(RoiAlignDesc), C.c_void_p]),
     "dc_roi_tile_groups": (C.c_int, [C.POINTER(RoiGroupsDesc), C.c_void_p]),
     "dc_conv2d_winograd_group_count": (C.c_int, [C.c_int, C.c_int]),

@@ -11,6 +11,12 @@
 //   resize_h_kernel     one thread per byte of the intermediate
 //   resize_v_kernel     one thread per byte of the canvas: the vertical pass inside the image's window, 0 everywhere else
 // Every access to the images and the canvas is a single byte, so neither has an alignment rule.
+//
+// dc_resize_pad_flip_u8 adds load_image_gt's augmentation, the mirror of the PADDED square (image[:, ::-1] behind np.pad), per image:
+// the first two launches are the unflipped call's, and the vertical kernel's thread for canvas byte (x, c) of a flagged image computes
+// the unflipped canvas' byte (W - 1 - x, c) -- the same window test, the same column of the intermediate, the same coefficients and
+// sum -- and stores it at (x, c).  Nothing is resampled from a mirrored source, so the mirrored bytes are the unflipped pass's by
+// construction.  The flags are an int32 [B] block inside the packed buffer (one upload); the old entry point passes none.
 #include "dcap_internal.h"
 #include <math.h>
 
@@ -104,18 +110,25 @@ __global__ __launch_bounds__(RS_THREADS) void resize_h_kernel(const uint8_t* __r
 
 // out[b][yy][j]: inside the window (rows top .. top + new_h, bytes left * 3 .. (left + new_w) * 3) the vertical pass over the
 // intermediate's column j - left * 3, outside it 0.  The pass never looks at channels: a row is new_w * 3 independent columns.
+// flips (null: no image is mirrored) holds one int32 per image; with flips[b] == 1 the thread of byte j = x * 3 + c computes the
+// unflipped row's byte js = (W - 1 - x) * 3 + c and stores it at j.
 __global__ __launch_bounds__(RS_THREADS) void resize_v_kernel(const int* __restrict__ rec, const int* __restrict__ tables,
-                                                              const uint8_t* __restrict__ mids, uint8_t* __restrict__ out, int B, int H, int W,
-                                                              int ax, int ay) {
+                                                              const uint8_t* __restrict__ mids, uint8_t* __restrict__ out,
+                                                              const int* __restrict__ flips, int B, int H, int W, int ax, int ay) {
     const int b = blockIdx.z;
     const int* r = rec + b * DC_RESIZE_RECORD_INTS;
     const int new_h = r[3], row = r[4] * 3, top = r[5], left = r[6] * 3;
     const int j = blockIdx.x * RS_THREADS + threadIdx.x;
     if (j >= W * 3) return;
+    int js = j;
+    if (flips != nullptr && flips[b] != 0) {
+        const int x = j / 3;
+        js = (W - 1 - x) * 3 + (j - x * 3);
+    }
     const int* bounds = tables + (size_t)B * ax + (size_t)b * ay;
     const int* coefs = bounds + 2 * (size_t)new_h;
-    const bool in_x = j >= left && j < left + row;
-    const uint8_t* mid = mids + r[7] + (j - left);
+    const bool in_x = js >= left && js < left + row;
+    const uint8_t* mid = mids + r[7] + (js - left);
     uint8_t* o = out + ((size_t)b * H * W) * 3 + j;
     for (int yy = blockIdx.y; yy < H; yy += gridDim.y) {
         const int y = yy - top;
@@ -187,12 +200,8 @@ extern "C" size_t dc_resize_pad_u8_workspace_bytes(const dc_resize_pad_desc* d) 
     return L.total;
 }
 
-extern "C" int dc_resize_pad_u8(const dc_resize_pad_desc* d, void* workspace, size_t workspace_bytes, void* stream) {
-    ResizeWs L;
-    int rc = resize_plan(d, &L);
-    if (rc) return rc;
-    DC_REQUIRE(workspace && workspace_bytes >= L.total && aligned16(workspace), DC_EWORKSPACE,
-               "dc_resize_pad_u8: needs %zu workspace bytes (16-byte aligned), got %zu", L.total, workspace_bytes);
+// The three launches of both entry points; flips: the device's flag block, or null.
+static int resize_launch(const dc_resize_pad_desc* d, const ResizeWs& L, const int* flips, void* workspace, void* stream) {
     hipStream_t s = static_cast<hipStream_t>(stream);
     uint8_t* mids = static_cast<uint8_t*>(workspace);
     int* tables = reinterpret_cast<int*>(mids + L.tables);
@@ -209,7 +218,41 @@ extern "C" int dc_resize_pad_u8(const dc_resize_pad_desc* d, void* workspace, si
     hipLaunchKernelGGL(resize_coef_kernel, dim3(blocks(max_out), 2, B), dim3(RS_THREADS), 0, s, rec, tables, B, L.ax, L.ay);
     hipLaunchKernelGGL(resize_h_kernel, dim3(blocks(L.max_mid_row), rows(L.max_h), B), dim3(RS_THREADS), 0, s, d->packed, rec, tables, mids, B, L.ax,
                        L.ay);
-    hipLaunchKernelGGL(resize_v_kernel, dim3(blocks(d->W * 3), rows(d->H), B), dim3(RS_THREADS), 0, s, rec, tables, mids, d->out, B, d->H, d->W, L.ax,
-                       L.ay);
+    hipLaunchKernelGGL(resize_v_kernel, dim3(blocks(d->W * 3), rows(d->H), B), dim3(RS_THREADS), 0, s, rec, tables, mids, d->out, flips, B, d->H,
+                       d->W, L.ax, L.ay);
     return check_launch("resize_pad kernels");
+}
+
+extern "C" int dc_resize_pad_u8(const dc_resize_pad_desc* d, void* workspace, size_t workspace_bytes, void* stream) {
+    ResizeWs L;
+    int rc = resize_plan(d, &L);
+    if (rc) return rc;
+    DC_REQUIRE(workspace && workspace_bytes >= L.total && aligned16(workspace), DC_EWORKSPACE,
+               "dc_resize_pad_u8: needs %zu workspace bytes (16-byte aligned), got %zu", L.total, workspace_bytes);
+    return resize_launch(d, L, nullptr, workspace, stream);
+}
+
+extern "C" int dc_resize_pad_flip_u8(const dc_resize_pad_desc* d, const int32_t* flips, size_t flips_offset, void* workspace,
+                                     size_t workspace_bytes, void* stream) {
+    ResizeWs L;
+    int rc = resize_plan(d, &L);
+    if (rc) return rc;
+    DC_REQUIRE(flips, DC_EINVAL, "dc_resize_pad_flip_u8: null flags (the host's copy of the B flags in the packed buffer)");
+    const size_t head = (size_t)d->B * DC_RESIZE_RECORD_INTS * sizeof(int32_t), fbytes = (size_t)d->B * sizeof(int32_t);
+    DC_REQUIRE((flips_offset & 3u) == 0, DC_EINVAL, "dc_resize_pad_flip_u8: the flags are int32, their block at byte %zu is off a 4-byte boundary",
+               flips_offset);
+    DC_REQUIRE(flips_offset >= head && flips_offset <= d->packed_bytes && fbytes <= d->packed_bytes - flips_offset, DC_EINVAL,
+               "dc_resize_pad_flip_u8: the flags block [%zu, %zu) overlaps the records (%zu bytes) or leaves the packed buffer (%zu bytes)",
+               flips_offset, flips_offset + fbytes, head, d->packed_bytes);
+    for (int b = 0; b < d->B; ++b) {
+        const int32_t* r = d->records + (size_t)b * DC_RESIZE_RECORD_INTS;
+        const size_t off = (size_t)r[0], end = off + (size_t)r[1] * r[2] * 3;
+        DC_REQUIRE(end <= flips_offset || off >= flips_offset + fbytes, DC_EINVAL,
+                   "dc_resize_pad_flip_u8: the flags block [%zu, %zu) overlaps image %d's bytes [%zu, %zu)", flips_offset, flips_offset + fbytes, b, off,
+                   end);
+        DC_REQUIRE(flips[b] == 0 || flips[b] == 1, DC_EINVAL, "dc_resize_pad_flip_u8: image %d's flag is %d, a flag is 0 or 1", b, flips[b]);
+    }
+    DC_REQUIRE(workspace && workspace_bytes >= L.total && aligned16(workspace), DC_EWORKSPACE,
+               "dc_resize_pad_flip_u8: needs %zu workspace bytes (16-byte aligned), got %zu", L.total, workspace_bytes);
+    return resize_launch(d, L, reinterpret_cast<const int*>(d->packed + flips_offset), workspace, stream);
 }

@@ -191,14 +191,21 @@ def refine_constants(window, config, image_shape):
     return np.array([window[0], window[1], window[2], window[3], h, w, window[0], window[1], scale, 0.0], np.float64)
 
 
-def load_image_gt(dataset, config, image_id, augment=False, rng=np.random):
+def load_image_gt(dataset, config, image_id, augment=False, rng=np.random, mold="host"):
     """image (resized + padded), image_meta, gt_captions [G,T], gt_boxes [G,4] (dense_model.py:953-984).
     As in the reference the boxes are handed on exactly as the dataset stores them: they are NOT rescaled or padded
     with the image, and the horizontal flip mirrors only the image (quirk kept so that the same dataset yields the
-    same training inputs)."""
+    same training inputs).
+    mold="device": no pixel is touched.  `image` is a utils.RawImageBatch of one -- the array dataset.load_image returned and the flip
+    flag, drawn from `rng` where the host mode draws it -- and image_meta is the host mode's (utils.resize_geometry: the unflipped
+    window).  An image that is not uint8 [h,w,3] raises utils.DeviceMoldError."""
     image = dataset.load_image(image_id)
     boxes, captions = dataset.load_captions_and_rois(image_id)
     shape = image.shape
+    if mold == "device":
+        window = utils.resize_geometry(utils.check_device_mold_image(image).shape, config.IMAGE_MIN_DIM, config.IMAGE_MAX_DIM, True)[2]
+        flip = bool(augment and rng.randint(0, 2))
+        return utils.RawImageBatch([image], [flip]), utils.compose_image_meta(image_id, shape, window), captions, boxes
     image, window, scale, padding = utils.resize_image(image, min_dim=config.IMAGE_MIN_DIM, max_dim=config.IMAGE_MAX_DIM,
                                                        padding=config.IMAGE_PADDING)
     if augment and rng.randint(0, 2):
@@ -215,15 +222,26 @@ def check_rpn_targets_mode(rpn_targets):
     return rpn_targets
 
 
-def data_generator(dataset, config, shuffle=True, augment=True, batch_size=1, rng=np.random, rpn_targets="host"):
+def check_prefetch(prefetch):
+    if not isinstance(prefetch, (int, np.integer)) or isinstance(prefetch, bool) or prefetch < 0:
+        raise ValueError("prefetch must be an integer >= 0 (batches the training generator runs ahead), got %r" % (prefetch,))
+    return int(prefetch)
+
+
+def data_generator(dataset, config, shuffle=True, augment=True, batch_size=1, rng=np.random, rpn_targets="host", mold="host"):
     """Infinite generator of ([images f32 molded, image_meta, rpn_match [B,A,1], rpn_bbox [B,256,4], gt_captions
     [B,MAX_GT,T], gt_boxes [B,MAX_GT,4]], []) -- the six training inputs of the reference's generator (:1260-1403).
     rpn_targets="device": build_rpn_targets is not called; position 2 is a list of the B images' FULL box arrays (every box of the
     image: the host builds the RPN targets from them before the MAX_GT_INSTANCES pick) and position 3 is None -- the model builds
     the targets on the device (ops.rpn_targets).  An image without boxes is skipped like any image whose targets fail on the host;
     one with more than 512 boxes raises.  This mode draws less from `rng` (no np.random.choice inside build_rpn_targets), so from the
-    second epoch's shuffle on its image order differs from the host mode's."""
+    second epoch's shuffle on its image order differs from the host mode's.
+    mold="device" (uint8 [h,w,3] images, IMAGE_PADDING on): no pixel is resampled, converted or copied on the host.  Position 0 is a
+    utils.RawImageBatch -- the B arrays as the dataset loaded them and the B flip flags -- that the step resizes, pads and mirrors on
+    the device into the same bytes; positions 1 - 5 and every draw from `rng` are the host mold's."""
     check_rpn_targets_mode(rpn_targets)
+    raw = utils.check_mold(mold, config.IMAGE_PADDING) == "device"
+    molded_shape = (config.IMAGE_MAX_DIM, config.IMAGE_MAX_DIM, 3)          # (device mold: what image.shape is on the host)
     on_device = rpn_targets == "device"
     image_ids = np.copy(dataset.image_ids)
     anchors = utils.generate_pyramid_anchors(config.RPN_ANCHOR_SCALES, config.RPN_ANCHOR_RATIOS, config.BACKBONE_SHAPES,
@@ -235,12 +253,12 @@ def data_generator(dataset, config, shuffle=True, augment=True, batch_size=1, rn
             rng.shuffle(image_ids)
         image_id = image_ids[index]
         try:
-            image, meta, caps, boxes = load_image_gt(dataset, config, image_id, augment, rng)
+            image, meta, caps, boxes = load_image_gt(dataset, config, image_id, augment, rng, mold)
             if not on_device:
-                match, deltas = build_rpn_targets(image.shape, anchors, caps, boxes, config, rng)
+                match, deltas = build_rpn_targets(molded_shape if raw else image.shape, anchors, caps, boxes, config, rng)
             elif boxes.shape[0] == 0:
                 raise ValueError("image %r has no boxes" % (image_id,))       # (the host's argmax over no boxes raises here too)
-        except (GeneratorExit, KeyboardInterrupt):
+        except (GeneratorExit, KeyboardInterrupt, utils.DeviceMoldError):     # (an image the device mold cannot take: not a bad sample)
             raise
         except Exception:
             errors += 1
@@ -255,7 +273,7 @@ def data_generator(dataset, config, shuffle=True, augment=True, batch_size=1, rn
             pick = rng.choice(np.arange(boxes.shape[0]), config.MAX_GT_INSTANCES, replace=False)
             caps, boxes = caps[pick], boxes[pick]
         if b == 0:
-            images = np.zeros((batch_size,) + image.shape, np.float32)
+            images = utils.RawImageBatch([], []) if raw else np.zeros((batch_size,) + image.shape, np.float32)
             metas = np.zeros((batch_size,) + meta.shape, meta.dtype)
             if not on_device:
                 matches = np.zeros((batch_size, anchors.shape[0], 1), match.dtype)
@@ -263,7 +281,11 @@ def data_generator(dataset, config, shuffle=True, augment=True, batch_size=1, rn
             gt_caps = np.zeros((batch_size, config.MAX_GT_INSTANCES, config.PADDING_SIZE), caps.dtype)
             gt_boxes = np.zeros((batch_size, config.MAX_GT_INSTANCES, 4), boxes.dtype)
             rpn_boxes = []
-        images[b] = mold_image(image.astype(np.float32), config)
+        if raw:
+            images.images += image.images
+            images.flips += image.flips
+        else:
+            images[b] = mold_image(image.astype(np.float32), config)
         if on_device:
             metas[b] = meta
             rpn_boxes.append(np.array(all_boxes))
@@ -1109,6 +1131,10 @@ class DenseImageCapRCNN(object):
         """backbone + FPN + RPN (the plan's hipGraph); trunk_done: the backbone pass of these images has run on this plan (JointTrainPipeline)."""
         if trunk_done:
             p.forward_top()
+        elif isinstance(images, utils.RawImageBatch):       # data_generator(mold="device"): resized, padded and mirrored into p.images
+            cfg = self.config
+            p.mold_images(images.images, cfg.IMAGE_MIN_DIM, cfg.IMAGE_MAX_DIM, cfg.IMAGE_PADDING, flips=images.flips)
+            p.forward(None)
         else:
             p.forward(self._images_u8(images))
 
@@ -1487,19 +1513,36 @@ class DenseImageCapRCNN(object):
         return [{"rois": rois[b, :n[b]].copy(), "ids": ids[b, :n[b]].copy()} for b in range(B)]
 
     # ---- training loop ----------------------------------------------------------------------
-    def train(self, train_dataset, val_dataset, learning_rate, epochs, layers, rpn_targets="host"):
+    def train(self, train_dataset, val_dataset, learning_rate, epochs, layers, rpn_targets="host", mold="host", prefetch=0):
         """fit_generator over data_generator with a checkpoint per epoch (:1810-1888).  rpn_targets="device": the generators hand on the
         images' boxes and every step builds its RPN targets on the device (data_generator, ops.rpn_targets) instead of in NumPy on this
-        thread; opt-in, because the subsample is then drawn from Philox keys, not from np.random.choice."""
+        thread; opt-in, because the subsample is then drawn from Philox keys, not from np.random.choice.
+        mold="device" (uint8 [h,w,3] images, IMAGE_PADDING on): the generators hand on the raw images and their flip flags, and every
+        step resizes, pads and mirrors them on the device (EncoderPlan.mold_images) -- the same bytes, so the same run bit for bit.
+        prefetch=n > 0: the training generator runs in one daemon thread, at most n batches ahead (utils.Prefetcher); the thread is
+        stopped when train() returns or raises.  0: next() on this thread."""
         check_rpn_targets_mode(rpn_targets)
+        utils.check_mold(mold)
+        prefetch = check_prefetch(prefetch)
         assert self.mode == "training", "Create model in training mode."
         layers = self.LAYER_REGEX.get(layers, layers)
         cfg = self.config
-        train_generator = data_generator(train_dataset, cfg, shuffle=True, batch_size=cfg.BATCH_SIZE, rpn_targets=rpn_targets)
-        val_generator = data_generator(val_dataset, cfg, shuffle=True, batch_size=cfg.BATCH_SIZE, augment=False, rpn_targets=rpn_targets)
+        utils.check_mold(mold, cfg.IMAGE_PADDING)
+        train_generator = data_generator(train_dataset, cfg, shuffle=True, batch_size=cfg.BATCH_SIZE, rpn_targets=rpn_targets, mold=mold)
+        val_generator = data_generator(val_dataset, cfg, shuffle=True, batch_size=cfg.BATCH_SIZE, augment=False, rpn_targets=rpn_targets, mold=mold)
+        # (the validation batch is drawn BEFORE the prefetch thread starts: both generators draw from np.random, and the order of their
+        # draws must not depend on a thread's timing)
+        val_batch = next(val_generator)[0]
+        if prefetch:
+            with utils.Prefetcher(train_generator, prefetch) as ahead:
+                return self._fit(ahead, val_batch, learning_rate, epochs, layers)
+        return self._fit(train_generator, val_batch, learning_rate, epochs, layers)
+
+    def _fit(self, train_generator, val_batch, learning_rate, epochs, layers):
+        """train()'s loop over the training generator, validating on the one fixed batch."""
+        cfg = self.config
         self.set_trainable(layers)
         self.compile(learning_rate)
-        val_batch = next(val_generator)[0]
         names = ("loss",) + self.LOSS_NAMES
         history = []
         # Frozen ResNet (the script's layers: 'heads'-like sets): the backbone pass of batch i + 1 runs beside the rest of batch i's step

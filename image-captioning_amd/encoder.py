@@ -557,18 +557,32 @@ class EncoderPlan:
         self._run_part("all", self._run_ops)
         return self.P
 
-    def mold_images(self, images, min_dim, max_dim, padding=True):
+    def mold_images(self, images, min_dim, max_dim, padding=True, flips=None):
         """mold='device': the raw uint8 [h,w,3] images of one batch (any sizes) resized and zero-padded as utils.resize_image does it,
-        straight into self.images (ops.resize_pad_images: one upload of the raw bytes, every byte of the buffer written); follow
-        with forward() / forward_rois(None, ...).  Returns utils.resize_geometry's tuple per image."""
+        straight into self.images (one upload of the raw bytes, every byte of the buffer written); follow with forward() /
+        forward_rois(None, ...).  flips: one boolean per image (None: none) -- a flagged image's padded square is mirrored left to
+        right, load_image_gt's augmentation.  Returns utils.resize_geometry's tuple per image (the unflipped window)."""
+        packed, records, geo = self.pack_images(images, min_dim, max_dim, padding, flips)
+        self.mold_packed(torch.from_numpy(packed).to(self.images.device), records, flips)
+        return geo
+
+    # mold_images() in two halves, for a caller that uploads on one stream and resamples on another (pipeline.JointTrainPipeline):
+    # pack_images() touches the host only; mold_packed() enqueues the three resize launches on the current stream and nothing else.
+    def pack_images(self, images, min_dim, max_dim, padding=True, flips=None):
+        """-> (packed uint8 host buffer, records, geometry): ops.pack_resize_batch for this plan's image buffer."""
         from . import utils
         utils.check_mold("device", padding)
         if len(images) != self.B or max_dim != self.H or max_dim != self.W:
             raise ValueError("mold_images: this plan reads %d images of %d x %d, got %d images for max_dim %r; pass mold=\"host\""
                              % (self.B, self.H, self.W, len(images), max_dim))
         geo = [utils.resize_geometry(utils.check_device_mold_image(im).shape, min_dim, max_dim, True) for im in images]
-        ops.resize_pad_images(images, placements=[(g[0], g[1], g[2][0], g[2][1]) for g in geo], out=self.images)
-        return geo
+        packed, records = ops.pack_resize_batch(images, [(g[0], g[1], g[2][0], g[2][1]) for g in geo], flips)
+        return packed, records, geo
+
+    def mold_packed(self, packed_dev, records, flips=None):
+        """The device copy of pack_images()' buffer resampled into self.images on the CURRENT stream.  The scratch is ops.WORKSPACE's
+        buffer of that stream (one per stream): no other stream's launches can be using it."""
+        ops.resize_pad_packed(packed_dev, records, out=self.images, flips=flips)
 
     # The pass in two halves, for a caller that runs the frozen backbone of the NEXT batch beside the rest of this batch's step
     # (pipeline.JointTrainPipeline): forward_trunk() = image -> C2..C5 (reads nothing a train step changes when no ResNet stage is

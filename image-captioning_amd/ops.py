@@ -532,18 +532,32 @@ def mold_image_padded(img_u8, mean_pixel, out):
     return out
 
 
-def pack_resize_batch(images, placements):
+def _resize_flips(flips, B, who):
+    """flips= of the resize wrappers: None, or one boolean per image -> int32 [B] of 0 / 1."""
+    if flips is None:
+        return None
+    f = np.asarray(flips)
+    if f.ndim != 1 or f.shape[0] != B:
+        raise ValueError("%s: flips must hold one flag per image (%d), got shape %s" % (who, B, tuple(f.shape)))
+    return np.ascontiguousarray(f.astype(bool), np.int32)
+
+
+def pack_resize_batch(images, placements, flips=None):
     """The one host buffer of a resize_pad_packed() call: `images` (uint8 [h,w,3] arrays of any sizes) and, per image, its placement
     (new_h, new_w, top, left) -> (packed uint8 [bytes], records int32 [B,_lib.RESIZE_RECORD_INTS]).  `packed` starts with the records
     {byte offset, h, w, new_h, new_w, top, left, the intermediate's byte offset in the workspace} and holds the raw bytes end to
-    end behind them; `records` is the host's own copy.  Anything but a uint8 [h,w,3] array is refused (ValueError: mold="host")."""
+    end behind them; `records` is the host's own copy.  Anything but a uint8 [h,w,3] array is refused (ValueError: mold="host").
+    flips (one boolean per image, or None: today's buffer): the flags of dc_resize_pad_flip_u8 travel as an int32 [B] block between
+    the records and the first image, at byte B * _lib.RESIZE_RECORD_INTS * 4."""
     from . import utils
     images = [utils.check_device_mold_image(im) for im in images]
     B, R = len(images), _lib.RESIZE_RECORD_INTS
     if B < 1 or len(placements) != B:
         raise ValueError("pack_resize_batch: one placement (new_h, new_w, top, left) per image and at least one image")
+    flags = _resize_flips(flips, B, "pack_resize_batch")
     records = np.zeros((B, R), np.int32)
-    pos, mid = B * R * 4, 0
+    head = B * R * 4
+    pos, mid = head + (0 if flags is None else B * 4), 0
     for b, (im, (new_h, new_w, top, left)) in enumerate(zip(images, placements)):
         h, w = im.shape[:2]
         if max(pos + h * w * 3, mid + h * int(new_w) * 3) >= 1 << 31:
@@ -552,21 +566,26 @@ def pack_resize_batch(images, placements):
         pos += h * w * 3
         mid += h * int(new_w) * 3
     packed = np.empty(pos, np.uint8)
-    packed[:B * R * 4] = records.view(np.uint8).reshape(-1)
+    packed[:head] = records.view(np.uint8).reshape(-1)
+    if flags is not None:
+        packed[head:head + B * 4] = flags.view(np.uint8)
     for im, r in zip(images, records):
         packed[r[0]:r[0] + im.size].reshape(im.shape)[...] = im
     return packed, records
 
 
-def resize_pad_packed(packed, records, canvas=None, out=None):
+def resize_pad_packed(packed, records, canvas=None, out=None, flips=None):
     """dc_resize_pad_u8 on an already uploaded batch: `packed` the device copy of pack_resize_batch()'s buffer, `records` its host
     records.  Writes EVERY byte of out (uint8 [B,H,W,3], contiguous; made from canvas=(H, W) when not given): image b resampled as
-    PIL.Image.resize(BILINEAR) does it, at its (top, left), zeros elsewhere.  Enqueue-only on the current stream."""
+    PIL.Image.resize(BILINEAR) does it, at its (top, left), zeros elsewhere.  Enqueue-only on the current stream.
+    flips (the sequence pack_resize_batch(flips=) was given; None: the call above): dc_resize_pad_flip_u8 -- a flagged image's canvas
+    is mirrored left to right, padding included (load_image_gt's image[:, ::-1])."""
     lib = _lib.load()
     records = np.ascontiguousarray(records, np.int32)
     B = records.shape[0]
     if _chk(packed, torch.uint8, "packed").dim() != 1 or records.ndim != 2 or records.shape[1] != _lib.RESIZE_RECORD_INTS:
         raise _lib.DcapError("resize_pad_packed: packed must be a 1-D uint8 tensor and records int32 [B,%d]" % _lib.RESIZE_RECORD_INTS)
+    flags = _resize_flips(flips, B, "resize_pad_packed")
     if out is None:
         out = torch.empty((B, int(canvas[0]), int(canvas[1]), 3), dtype=torch.uint8, device=packed.device)
     if not _chk(out, torch.uint8, "out").is_contiguous() or out.dim() != 4 or out.shape[0] != B or out.shape[3] != 3 or out.device != packed.device:
@@ -576,15 +595,20 @@ def resize_pad_packed(packed, records, canvas=None, out=None):
     d.out, d.H, d.W = out.data_ptr(), out.shape[1], out.shape[2]
     need = lib.dc_resize_pad_u8_workspace_bytes(C.byref(d))
     ws, wsb = WORKSPACE.get(need, packed.device)
-    check(lib.dc_resize_pad_u8(C.byref(d), _ptr(ws), wsb, _stream()), "dc_resize_pad_u8")
+    if flags is None:
+        check(lib.dc_resize_pad_u8(C.byref(d), _ptr(ws), wsb, _stream()), "dc_resize_pad_u8")
+    else:
+        check(lib.dc_resize_pad_flip_u8(C.byref(d), flags.ctypes.data, B * _lib.RESIZE_RECORD_INTS * 4, _ptr(ws), wsb, _stream()),
+              "dc_resize_pad_flip_u8")
     return out
 
 
-def resize_pad_images(images, min_dim=None, max_dim=None, padding=True, placements=None, canvas=None, out=None, device=None):
+def resize_pad_images(images, min_dim=None, max_dim=None, padding=True, placements=None, canvas=None, out=None, device=None, flips=None):
     """utils.resize_image + np.pad + np.stack on the device, bit for bit: `images` (a list of uint8 [h,w,3] arrays of any sizes) are
     packed (pack_resize_batch), uploaded in ONE blocking copy and resampled into a uint8 [B,H,W,3] device tensor (returned; `out`
     is filled when given, every byte of it).  The geometry is utils.resize_geometry's for (min_dim, max_dim) with the canvas
     max_dim x max_dim, or explicit: placements [(new_h, new_w, top, left)] and canvas (H, W) or out.
+    flips: one boolean per image (None: none) -- a flagged image's square is mirrored left to right (resize_pad_packed).
     Refused with a ValueError that names mold="host": images that are not uint8 [h,w,3], and padding=False."""
     from . import utils
     utils.check_mold("device", padding)
@@ -592,9 +616,9 @@ def resize_pad_images(images, min_dim=None, max_dim=None, padding=True, placemen
     if placements is None:
         geo = [utils.resize_geometry(im.shape, min_dim, max_dim, True) for im in images]
         placements, canvas = [(g[0], g[1], g[2][0], g[2][1]) for g in geo], (max_dim, max_dim)
-    packed, records = pack_resize_batch(images, placements)
+    packed, records = pack_resize_batch(images, placements, flips)
     dev = out.device if out is not None else torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
-    return resize_pad_packed(torch.from_numpy(packed).to(dev), records, canvas, out)
+    return resize_pad_packed(torch.from_numpy(packed).to(dev), records, canvas, out, flips)
 
 
 def roi_align_pyramid(maps, boxes, image_area, pool=7, out=None, levels_out=None):

@@ -12,6 +12,8 @@ import os
 
 import torch
 
+from . import utils
+
 
 class CaptionTrainPipeline(object):
     def __init__(self, plan, decoder, rois_per_image):
@@ -161,6 +163,8 @@ class JointTrainPipeline(object):
     def _trunk(self, j, images):
         dev = self.inner.device
         cur = torch.cuda.current_stream(dev)
+        if isinstance(images, utils.RawImageBatch):
+            return self._trunk_raw(j, images, cur)
         u8 = self.inner._images_u8(images)
         if not u8.is_cuda:
             # A host batch (the data generator's): a copy from pageable memory blocks the host until the stream it is issued on has drained.
@@ -177,6 +181,24 @@ class JointTrainPipeline(object):
         self.s_trunk.wait_stream(cur)
         with torch.cuda.stream(self.s_trunk):
             self.plans[j].forward_trunk(u8)
+            self.ev_trunk[j].record(self.s_trunk)
+
+    def _trunk_raw(self, j, batch, cur):
+        """A data_generator(mold="device") batch: the raw images' packed bytes go up on the copy stream exactly as a host batch does
+        (the host waits for its own bytes only, the device tensor lives in _hold), and the three resize launches that write plan j's
+        image buffer run on the backbone stream in front of its backbone pass.  Their scratch is ops.WORKSPACE's buffer of that
+        stream (one per stream), which nothing on the caller's stream touches."""
+        cfg, plan = self.inner.config, self.plans[j]
+        packed, records, _ = plan.pack_images(batch.images, cfg.IMAGE_MIN_DIM, cfg.IMAGE_MAX_DIM, cfg.IMAGE_PADDING, batch.flips)
+        with torch.cuda.stream(self.s_copy):
+            packed = torch.from_numpy(packed).to(self.inner.device)
+        self.s_trunk.wait_stream(self.s_copy)
+        packed.record_stream(self.s_trunk)
+        self._hold.append(packed)
+        self.s_trunk.wait_stream(cur)                      # (the last reader of plan j's buffers: see _trunk)
+        with torch.cuda.stream(self.s_trunk):
+            plan.mold_packed(packed, records, batch.flips)
+            plan.forward_trunk(None)
             self.ev_trunk[j].record(self.s_trunk)
 
     def _rest(self, inputs, j):

@@ -12,10 +12,10 @@ import time
 import numpy as np
 
 from .config import Config
-from .dense_model import DenseImageCapRCNN, check_rpn_targets_mode
+from .dense_model import DenseImageCapRCNN, check_prefetch, check_rpn_targets_mode
 from .preprocess import encode_caption, load_corpus, load_embeddings, tokenize_corpus
 from .text_generation_model_v2 import pad_sequences
-from .utils import Dataset
+from .utils import Dataset, check_mold
 
 
 class DenseCapConfig(Config):
@@ -93,9 +93,12 @@ def load_vocabulary(cache_dir, embeddings_file, data_file, train_image_ids):
     return id_to_word, word_to_id, matrix
 
 
-def main(root_dir=None, init_with='coco', epochs=100, rpn_targets="host"):
-    """rpn_targets="device": the RPN targets of every step are built on the GPU (DenseImageCapRCNN.train)."""
+def main(root_dir=None, init_with='coco', epochs=100, rpn_targets="host", mold="host", prefetch=0):
+    """rpn_targets="device": the RPN targets of every step are built on the GPU; mold="device": the raw images are resized, padded and
+    flipped on the GPU; prefetch=n: the training generator runs n batches ahead in a thread (DenseImageCapRCNN.train)."""
     check_rpn_targets_mode(rpn_targets)
+    check_mold(mold)
+    check_prefetch(prefetch)
     from .parallel_model import ParallelModel, init_process_group_from_env
     rank, world, _ = init_process_group_from_env()
     root_dir = root_dir or os.getcwd()
@@ -129,7 +132,8 @@ def main(root_dir=None, init_with='coco', epochs=100, rpn_targets="host"):
     if rank == 0:
         print(model.summary())
     start_time = time.time()
-    model.train(datasets[0], datasets[1], learning_rate=config.LEARNING_RATE, epochs=epochs, layers="no_backbone", rpn_targets=rpn_targets)
+    model.train(datasets[0], datasets[1], learning_rate=config.LEARNING_RATE, epochs=epochs, layers="no_backbone", rpn_targets=rpn_targets,
+                mold=mold, prefetch=prefetch)
     print(time.time() - start_time)
 
 

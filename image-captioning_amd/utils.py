@@ -139,13 +139,98 @@ def check_mold(mold, padding=True):
     return mold
 
 
+class DeviceMoldError(ValueError):
+    """An image mold='device' cannot take: a configuration error (the data generator hands it on; it is not a bad sample to skip)."""
+
+
 def check_device_mold_image(image):
     """What mold='device' resamples: a uint8 [h,w,3] array.  The host path byte-scales other dtypes (imresize) and takes whatever
     channel count PIL does, a road the device kernel does not have."""
     a = np.asarray(image)
     if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.shape[0] < 1 or a.shape[1] < 1:
-        raise ValueError("mold='device' resamples uint8 [h,w,3] images only, got %s %s: pass mold=\"host\"" % (a.dtype, tuple(a.shape)))
+        raise DeviceMoldError("mold='device' resamples uint8 [h,w,3] images only, got %s %s: pass mold=\"host\"" % (a.dtype, tuple(a.shape)))
     return a
+
+
+class RawImageBatch(object):
+    """Position 0 of a data_generator(mold="device") batch: the B raw uint8 [h,w,3] images as the dataset loaded them (any sizes) and
+    one flip flag per image.  The step resizes, pads and mirrors them on the device (EncoderPlan.mold_images).  len() and slicing by a
+    slice are all parallel_model.shard needs to split it over the towers."""
+
+    def __init__(self, images, flips):
+        self.images, self.flips = list(images), [bool(f) for f in flips]
+        if len(self.images) != len(self.flips):
+            raise ValueError("RawImageBatch: %d images and %d flip flags" % (len(self.images), len(self.flips)))
+
+    def __len__(self):
+        return len(self.images)
+
+    def __getitem__(self, index):
+        if not isinstance(index, slice):
+            raise TypeError("RawImageBatch is sliced by a slice (a sub-batch), not indexed by %r" % (index,))
+        return RawImageBatch(self.images[index], self.flips[index])
+
+
+class Prefetcher(object):
+    """`generator` run in ONE daemon thread, at most `depth` items ahead of the consumer: an iterator that yields exactly the
+    generator's sequence and re-raises whatever the generator raises at the position where it occurred.  The thread takes a slot
+    BEFORE it asks the generator for an item and the consumer gives the slot back when it takes one, so never more than `depth`
+    items exist that the consumer has not taken.  close() (or leaving the with block) stops the thread and closes the generator.
+    The thread runs the generator and nothing else: give it a generator that stays on the host."""
+
+    def __init__(self, generator, depth):
+        import queue
+        import threading
+        if int(depth) < 1:
+            raise ValueError("Prefetcher: depth must be at least 1, got %r" % (depth,))
+        self._gen, self._items, self._done = generator, queue.Queue(), False
+        self._slots, self._stop = threading.Semaphore(int(depth)), threading.Event()
+        self.thread = threading.Thread(target=self._produce, name="dcap-prefetch", daemon=True)
+        self.thread.start()
+
+    def _produce(self):
+        try:
+            while True:
+                self._slots.acquire()
+                if self._stop.is_set():
+                    break
+                try:
+                    item = (next(self._gen), None)
+                except BaseException as e:                   # (StopIteration included: the consumer's next() ends the same way)
+                    item = (None, e)
+                self._items.put(item)
+                if item[1] is not None:
+                    break
+        finally:
+            close = getattr(self._gen, "close", None)
+            if close is not None:
+                close()
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        if self._done:
+            raise StopIteration
+        value, error = self._items.get()
+        if error is not None:
+            self._done = True
+            raise error
+        self._slots.release()
+        return value
+
+    def close(self, timeout=None):
+        self._done = True
+        self._stop.set()
+        self._slots.release()
+        self.thread.join(timeout)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
 
 
 def compose_image_meta(image_id, image_shape, window):

@@ -328,6 +328,21 @@ typedef struct {
 size_t dc_resize_pad_u8_workspace_bytes(const dc_resize_pad_desc* d);
 int    dc_resize_pad_u8(const dc_resize_pad_desc* d, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The same with load_image_gt's augmentation (dense_model.py:953-984: image[:, ::-1] on the resized AND padded square), per image:
+ * with flag 1, out[b][y][x][c] is byte [y][W - 1 - x][c] of what dc_resize_pad_u8 writes for image b -- the window moves to columns
+ * [W - left - new_w, W - left), and when W - new_w is odd the padding's odd column changes sides.  No mirrored source is resampled:
+ * the vertical kernel (shared with dc_resize_pad_u8) computes the unflipped canvas' byte with the unflipped pass's coefficients and
+ * stores it at the mirrored column, so the bytes are PIL's by construction.  With every flag 0 the canvas is dc_resize_pad_u8's.
+ *   The flags travel in the one packed upload: B int32 at byte `flips_offset` of d->packed (e.g. between the records and the first
+ *   image; such a buffer is still valid for dc_resize_pad_u8, which only wants image offsets >= B * DC_RESIZE_RECORD_INTS * 4).
+ *   flips: the HOST's copy of the B flags, checked with the records before anything is launched: a null pointer, a value other than
+ *   0 or 1, a block off a 4-byte boundary, one that overlaps the records or an image or leaves `packed` is DC_EINVAL and the canvas
+ *   stays untouched.  The device never reads the host copy.
+ * Workspace, launches (three, whatever B is) and every other rule are dc_resize_pad_u8's; size the workspace with
+ * dc_resize_pad_u8_workspace_bytes (the layout is the same). */
+int    dc_resize_pad_flip_u8(const dc_resize_pad_desc* d, const int32_t* flips, size_t flips_offset, void* workspace,
+                             size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * PyramidROIAlign forward (feature_generation/dense_model.py:317-418): level routing
  * k = clamp(4 + round_half_even(log2(sqrt(h*w) / (224/sqrt(image_area)))), 2, 5) and
