@@ -1086,44 +1086,8 @@ def test_bn_bwd_recovers_the_normalised_activation_and_survives_dead_channels(op
     close(dzn, want, 2e-5)
 
 
-def _philox2x32(c0, c1, key):
-    """NumPy restatement of the library's counter-based generator (csrc/dcap_internal.h philox2x32: Philox-2x32-10)."""
-    c0 = np.asarray(c0, np.uint64) & 0xFFFFFFFF
-    c1 = np.full_like(c0, int(c1) & 0xFFFFFFFF)
-    key = int(key) & 0xFFFFFFFF
-    for _ in range(10):
-        p = (np.uint64(0xD256D193) * c0) & np.uint64(0xFFFFFFFFFFFFFFFF)
-        hi, lo = p >> np.uint64(32), p & np.uint64(0xFFFFFFFF)
-        c0 = (hi ^ np.uint64(key) ^ c1) & np.uint64(0xFFFFFFFF)
-        c1 = lo
-        key = (key + 0x9E3779B9) & 0xFFFFFFFF
-    return c0.astype(np.uint32)
-
-
-def _dt_case(seed, n_props, n_gt, pad_props, pad_gt, T=6, jitter=0.08):
-    """Proposals scattered around GT boxes (some close: IoU above 0.5, some far), zero padding rows in both lists, one all-zero
-    proposal in the middle of the list and a degenerate (zero-area) proposal."""
-    rng = np.random.default_rng(seed)
-    gt = np.zeros((n_gt + pad_gt, 4), np.float32)
-    y1, x1 = rng.uniform(0, 0.6, n_gt), rng.uniform(0, 0.6, n_gt)
-    gt[:n_gt] = np.stack([y1, x1, y1 + rng.uniform(0.1, 0.4, n_gt), x1 + rng.uniform(0.1, 0.4, n_gt)], 1)
-    caps = np.zeros((n_gt + pad_gt, T), np.int32)
-    caps[:n_gt] = rng.integers(1, 1000, (n_gt, T))
-    props = np.zeros((n_props + pad_props, 4), np.float32)
-    src = rng.integers(0, max(n_gt, 1), n_props)
-    noise = rng.normal(0, jitter, (n_props, 4)) * (rng.random((n_props, 1)) < 0.6)
-    base = gt[src] if n_gt else rng.uniform(0.1, 0.5, (n_props, 4)).astype(np.float32)
-    props[:n_props] = np.clip(base + noise, 0, 1)
-    far = rng.random(n_props) < 0.3
-    fy, fx = rng.uniform(0, 0.9, n_props), rng.uniform(0, 0.9, n_props)
-    props[:n_props][far] = np.stack([fy, fx, fy + 0.05, fx + 0.05], 1)[far]
-    if n_props > 10:
-        props[5] = 0                                         # a zero row that is NOT trailing padding: later indices shift when compacted
-        props[7] = [0.3, 0.3, 0.3, 0.6]                      # zero area, non-zero row
-    if pad_gt and n_gt > 2:
-        gt[[1, n_gt]] = gt[[n_gt, 1]]                        # a zero GT row in the middle
-        caps[[1, n_gt]] = caps[[n_gt, 1]]
-    return props.astype(np.float32), gt, caps
+# the counter-based generator and the proposal / GT box builder live with the other RoI / RPN inputs (test_gpu_roi_rpn_edges.py shares them)
+from _roi_rpn_cases import philox2x32 as _philox2x32, dt_case as _dt_case  # noqa: E402
 
 
 @pytest.mark.parametrize("case", [(0, 2000, 40, 0, 60), (1, 1500, 7, 500, 3), (2, 300, 1, 0, 0), (3, 2000, 100, 48, 0), (4, 64, 0, 6, 4), (5, 3000, 12, 100, 0),
