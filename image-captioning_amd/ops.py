@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import (RpnTargetsDesc, PwChainDesc, ConvBf16Desc, AmsgradDesc, DetectionTargetsDesc, BnReluDesc, ConvDesc, ConvWgradBf16Desc, GemmBf16Desc, VocabCeDesc, ProposalDesc, RpnLossDesc, GemmDesc, LstmBwdDesc, LstmFwdDesc, RoiAlignDesc, RoiGroupsDesc,
+from ._lib import (RpnTargetsDesc, PwChainDesc, ConvBf16Desc, AmsgradDesc, DetectionTargetsDesc, BnReluDesc, ConvDesc, ConvWgradBf16Desc, GemmBf16Desc, VocabCeDesc, ProposalDesc, RpnLossDesc, GemmDesc, LstmBwdDesc, LstmFwdDesc, RoialignDesc, RoiGroupsDesc,
                    SoftmaxCeDesc, VocabTop1Desc, VocabTopkDesc, VocabTop1Bf16Desc, VocabTopkBf16Desc, VocabSampleDesc, VocabSampleBf16Desc, BeamSelectDesc, BeamStepDesc, LstmStepDesc, RefineDesc, ResizePadDesc, check)
 
 
@@ -107,11 +107,28 @@ class _Workspace:
 WORKSPACE = _Workspace()
 
 
-def gemm(A, B, out=None, a_trans=False, b_trans=False, gather=None, scale=None, shift=None,
-         residual=None, res_rows=0, relu=False, accumulate=False, split_k=0):
-    """out[M,N] = epilogue(op(A) @ op(B)); see dc_gemm_f32."""
-    lib = _lib.load()
-    _chk(A, name="A"), _chk(B, name="B")
+def _launch_ws(nbytes, device, fn, *args):
+    """fn(*args, workspace, workspace_bytes, stream) on the current stream, with its scratch buffer of at least nbytes (what the
+    entry point's own dc_*_workspace_bytes call returned)."""
+    ws, wsb = WORKSPACE.get(nbytes, device)
+    check(fn(*args, _ptr(ws), wsb, _stream()), fn.__name__)
+
+
+def _tile_info(info, tile_fn, d):
+    """info= of the bf16 wrappers (tests / benches): which block tile and how many split-K slices run the problem `d`."""
+    if info is not None:
+        sk = C.c_int(0)
+        info["tile"] = int(tile_fn(C.byref(d), C.byref(sk)))
+        info["split_k"] = int(sk.value)
+
+
+def _scale_shift(d, scale, shift):
+    d.scale = None if scale is None else _chk(scale, name="scale").data_ptr()
+    d.shift = None if shift is None else _chk(shift, name="shift").data_ptr()
+
+
+def _gemm_shape(fn, A, B, a_trans, b_trans, gather):
+    """(M, N, K) of op(A) @ op(B), A's rows (a_trans: its K rows) picked by `gather` when given."""
     if a_trans:
         K, M = (gather.numel() if gather is not None else A.shape[0]), A.shape[1]
     elif gather is not None:
@@ -121,26 +138,43 @@ def gemm(A, B, out=None, a_trans=False, b_trans=False, gather=None, scale=None, 
     N = B.shape[0] if b_trans else B.shape[1]
     kb = B.shape[1] if b_trans else B.shape[0]
     if kb != K:
-        raise _lib.DcapError("gemm: inner dimensions differ (%d vs %d)" % (K, kb))
+        raise _lib.DcapError("%s: inner dimensions differ (%d vs %d)" % (fn, K, kb))
+    return M, N, K
+
+
+def _gemm_operands(d, M, N, K, A, B, a_trans, b_trans, gather):
+    """The problem and the A / B operand fields dc_gemm_desc and dc_gemm_bf16_desc share."""
+    d.M, d.N, d.K = M, N, K
+    d.A, d.lda, d.a_trans = A.data_ptr(), A.stride(0), int(a_trans)
+    d.a_gather = None if gather is None else _chk(gather, torch.int32, "gather").data_ptr()
+    d.B, d.ldb, d.b_trans = B.data_ptr(), B.stride(0), int(b_trans)
+
+
+def _gemm_epilogue(d, scale, shift, residual, res_rows, relu, accumulate, split_k):
+    """The epilogue and split_k fields the two GEMM descriptors share."""
+    _scale_shift(d, scale, shift)
+    if residual is not None:
+        _chk(residual, name="residual")
+        d.residual, d.ldr, d.res_rows = residual.data_ptr(), residual.stride(0), int(res_rows)
+    d.relu, d.accumulate, d.split_k = int(relu), int(accumulate), int(split_k)
+
+
+def gemm(A, B, out=None, a_trans=False, b_trans=False, gather=None, scale=None, shift=None,
+         residual=None, res_rows=0, relu=False, accumulate=False, split_k=0):
+    """out[M,N] = epilogue(op(A) @ op(B)); see dc_gemm_f32."""
+    lib = _lib.load()
+    _chk(A, name="A"), _chk(B, name="B")
+    M, N, K = _gemm_shape("gemm", A, B, a_trans, b_trans, gather)
     if out is None:
         out = torch.empty((M, N), dtype=torch.float32, device=A.device)
     _chk(out, name="out")
     if tuple(out.shape) != (M, N):
         raise _lib.DcapError("gemm: out has shape %s, expected %s" % (tuple(out.shape), (M, N)))
     d = GemmDesc()
-    d.M, d.N, d.K = M, N, K
-    d.A, d.lda, d.a_trans = A.data_ptr(), A.stride(0), int(a_trans)
-    d.a_gather = None if gather is None else _chk(gather, torch.int32, "gather").data_ptr()
-    d.B, d.ldb, d.b_trans = B.data_ptr(), B.stride(0), int(b_trans)
+    _gemm_operands(d, M, N, K, A, B, a_trans, b_trans, gather)
     d.C, d.ldc = out.data_ptr(), out.stride(0)
-    d.scale = None if scale is None else _chk(scale, name="scale").data_ptr()
-    d.shift = None if shift is None else _chk(shift, name="shift").data_ptr()
-    if residual is not None:
-        _chk(residual, name="residual")
-        d.residual, d.ldr, d.res_rows = residual.data_ptr(), residual.stride(0), int(res_rows)
-    d.relu, d.accumulate, d.split_k = int(relu), int(accumulate), int(split_k)
-    ws, wsb = WORKSPACE.get(lib.dc_gemm_workspace_bytes(C.byref(d)), A.device)
-    check(lib.dc_gemm_f32(C.byref(d), _ptr(ws), wsb, _stream()), "dc_gemm_f32")
+    _gemm_epilogue(d, scale, shift, residual, res_rows, relu, accumulate, split_k)
+    _launch_ws(lib.dc_gemm_workspace_bytes(C.byref(d)), A.device, lib.dc_gemm_f32, C.byref(d))
     return out
 
 
@@ -182,24 +216,13 @@ def gemm_bf16(A, B, out=None, out_bf16=None, a_trans=False, b_trans=False, gathe
     out nor out_bf16 is given); out_bf16: optional bf16 [M,N] copy of the result.  Returns out if present else out_bf16."""
     lib = _lib.load()
     _chk(A, BF16, "A"), _chk(B, BF16, "B")
-    if a_trans:
-        K, M = (gather.numel() if gather is not None else A.shape[0]), A.shape[1]
-    elif gather is not None:
-        M, K = gather.numel(), A.shape[1]
-    else:
-        M, K = A.shape
-    N = B.shape[0] if b_trans else B.shape[1]
-    kb = B.shape[1] if b_trans else B.shape[0]
-    if kb != K:
-        raise _lib.DcapError("gemm_bf16: inner dimensions differ (%d vs %d)" % (K, kb))
+    M, N, K = _gemm_shape("gemm_bf16", A, B, a_trans, b_trans, gather)
     if out is None and out_bf16 is None:
         out = torch.empty((M, N), dtype=torch.float32, device=A.device)
     d = GemmBf16Desc()
-    d.M, d.N, d.K = M, N, K
-    d.A, d.lda, d.a_trans = A.data_ptr(), A.stride(0), int(a_trans)
+    _gemm_operands(d, M, N, K, A, B, a_trans, b_trans, gather)
     if gather is not None:
-        d.a_gather, d.a_gather_rows = _chk(gather, torch.int32, "gather").data_ptr(), A.shape[0]
-    d.B, d.ldb, d.b_trans = B.data_ptr(), B.stride(0), int(b_trans)
+        d.a_gather_rows = A.shape[0]
     for t, name, dt in ((out, "out", torch.float32), (out_bf16, "out_bf16", BF16)):
         if t is not None and tuple(_chk(t, dt, name).shape) != (M, N):
             raise _lib.DcapError("gemm_bf16: %s has shape %s, expected %s" % (name, tuple(t.shape), (M, N)))
@@ -207,19 +230,16 @@ def gemm_bf16(A, B, out=None, out_bf16=None, a_trans=False, b_trans=False, gathe
         d.C, d.ldc = out.data_ptr(), out.stride(0)
     if out_bf16 is not None:
         d.Cb, d.ldcb = out_bf16.data_ptr(), out_bf16.stride(0)
-    d.scale = None if scale is None else _chk(scale, name="scale").data_ptr()
-    d.shift = None if shift is None else _chk(shift, name="shift").data_ptr()
-    if residual is not None:
-        _chk(residual, name="residual")
-        d.residual, d.ldr, d.res_rows = residual.data_ptr(), residual.stride(0), int(res_rows)
-    d.relu, d.accumulate, d.split_k = int(relu), int(accumulate), int(split_k)
-    if info is not None:                      # tests / benches: which kernel runs this problem
-        sk = C.c_int(0)
-        info["tile"] = int(lib.dc_gemm_bf16_tile(C.byref(d), C.byref(sk)))
-        info["split_k"] = int(sk.value)
-    ws, wsb = WORKSPACE.get(lib.dc_gemm_bf16_workspace_bytes(C.byref(d)), A.device)
-    check(lib.dc_gemm_bf16(C.byref(d), _ptr(ws), wsb, _stream()), "dc_gemm_bf16")
+    _gemm_epilogue(d, scale, shift, residual, res_rows, relu, accumulate, split_k)
+    _tile_info(info, lib.dc_gemm_bf16_tile, d)
+    _launch_ws(lib.dc_gemm_bf16_workspace_bytes(C.byref(d)), A.device, lib.dc_gemm_bf16, C.byref(d))
     return out if out is not None else out_bf16
+
+
+def _conv_geometry(d, x, Cout, kh, kw, stride, pad_t, pad_l, Ho, Wo):
+    """The twelve geometry fields every convolution descriptor starts with; x [N,H,W,Cin]."""
+    d.N, d.H, d.W, d.Cin = x.shape
+    d.Cout, d.kh, d.kw, d.stride, d.pad_t, d.pad_l, d.Ho, d.Wo = Cout, kh, kw, stride, pad_t, pad_l, Ho, Wo
 
 
 def conv2d(x, w_packed, kh, kw, stride, pad_t, pad_l, Ho, Wo, scale=None, shift=None, residual=None,
@@ -235,11 +255,9 @@ def conv2d(x, w_packed, kh, kw, stride, pad_t, pad_l, Ho, Wo, scale=None, shift=
     if out is None:
         out = torch.empty((N, Ho, Wo, Cout), dtype=torch.float32, device=x.device)
     d = ConvDesc()
-    d.N, d.H, d.W, d.Cin = N, H, W, Cin
-    d.Cout, d.kh, d.kw, d.stride, d.pad_t, d.pad_l, d.Ho, d.Wo = Cout, kh, kw, stride, pad_t, pad_l, Ho, Wo
+    _conv_geometry(d, x, Cout, kh, kw, stride, pad_t, pad_l, Ho, Wo)
     d.x, d.w, d.y = x.data_ptr(), w_packed.data_ptr(), _chk(out, name="out").data_ptr()
-    d.scale = None if scale is None else scale.data_ptr()
-    d.shift = None if shift is None else shift.data_ptr()
+    _scale_shift(d, scale, shift)
     d.residual = None if residual is None else _chk(residual, name="residual").data_ptr()
     d.res_mode, d.relu, d.split_k, d.math = int(res_mode), int(relu), int(split_k), int(math)
     if w_wino is not None:
@@ -254,8 +272,7 @@ def conv2d(x, w_packed, kh, kw, stride, pad_t, pad_l, Ho, Wo, scale=None, shift=
         buf = C.create_string_buffer(128)
         check(lib.dc_conv2d_kernel_name(C.byref(d), buf, 128), "dc_conv2d_kernel_name")
         return buf.value.decode()
-    ws, wsb = WORKSPACE.get(lib.dc_conv2d_workspace_bytes(C.byref(d)), x.device)
-    check(lib.dc_conv2d_nhwc_f32(C.byref(d), _ptr(ws), wsb, _stream()), "dc_conv2d_nhwc_f32")
+    _launch_ws(lib.dc_conv2d_workspace_bytes(C.byref(d)), x.device, lib.dc_conv2d_nhwc_f32, C.byref(d))
     return out
 
 
@@ -268,29 +285,25 @@ def pw_chain_supported(k1, n1, n2):
     return bool(_lib.load().dc_pw_chain_supported(int(k1), int(n1), int(n2)))
 
 
-def pw_chain_pack(w_packed, out=None):
-    """A packed 1x1 kernel [Cout, Cin] in the fragment order dc_pw_chain_f32 reads (same size)."""
-    lib = _lib.load()
+def _pw_chain_pack(fn, w_packed, out, pack, dtype, pieces):
     _chk(w_packed, name="w")
     if w_packed.dim() != 2 or not w_packed.is_contiguous():
-        raise _lib.DcapError("pw_chain_pack: w must be the contiguous packed 1x1 kernel [Cout, Cin]")
+        raise _lib.DcapError("%s: w must be the contiguous packed 1x1 kernel [Cout, Cin]" % fn)
     if out is None:
-        out = torch.empty_like(w_packed)
-    check(lib.dc_pw_chain_pack_f32(_ptr(w_packed), _ptr(out), w_packed.shape[0], w_packed.shape[1], _stream()), "dc_pw_chain_pack_f32")
+        out = torch.empty((w_packed.shape[0], pieces * w_packed.shape[1]), dtype=dtype, device=w_packed.device)
+    check(pack(_ptr(w_packed), _ptr(out), w_packed.shape[0], w_packed.shape[1], _stream()), pack.__name__)
     return out
+
+
+def pw_chain_pack(w_packed, out=None):
+    """A packed 1x1 kernel [Cout, Cin] in the fragment order dc_pw_chain_f32 reads (same size)."""
+    return _pw_chain_pack("pw_chain_pack", w_packed, out, pack=_lib.load().dc_pw_chain_pack_f32, dtype=torch.float32, pieces=1)
 
 
 def pw_chain_pack_b3(w_packed, out=None):
     """A packed 1x1 kernel [Cout, Cin] as three bf16 pieces per element in the fragment order of the split-bf16 chain kernel:
     int16 [Cout, 3 * Cin] (dc_pw_chain_pack_b3)."""
-    lib = _lib.load()
-    _chk(w_packed, name="w")
-    if w_packed.dim() != 2 or not w_packed.is_contiguous():
-        raise _lib.DcapError("pw_chain_pack_b3: w must be the contiguous packed 1x1 kernel [Cout, Cin]")
-    if out is None:
-        out = torch.empty((w_packed.shape[0], 3 * w_packed.shape[1]), dtype=torch.int16, device=w_packed.device)
-    check(lib.dc_pw_chain_pack_b3(_ptr(w_packed), _ptr(out), w_packed.shape[0], w_packed.shape[1], _stream()), "dc_pw_chain_pack_b3")
-    return out
+    return _pw_chain_pack("pw_chain_pack_b3", w_packed, out, pack=_lib.load().dc_pw_chain_pack_b3, dtype=torch.int16, pieces=3)
 
 
 def pw_chain(x, w1f, shift1, w2f, shift2, scale1=None, scale2=None, residual=None, relu1=True, relu2=True, y=None, z=None):
@@ -329,35 +342,32 @@ def pw_chain(x, w1f, shift1, w2f, shift2, scale1=None, scale2=None, residual=Non
     return y, z
 
 
+def _winograd_pack(fn, w_packed, cin, cout, out, weight_bytes, pack, dtype):
+    _chk(w_packed, name="w")
+    if not w_packed.is_contiguous() or w_packed.numel() != 9 * cin * cout:
+        raise _lib.DcapError("%s: w must be the contiguous packed 3x3 kernel [Cout, 9*Cin]" % fn)
+    nbytes = weight_bytes(cin, cout)
+    if nbytes == 0:
+        raise _lib.DcapError("%s: Cin and Cout must be multiples of 32" % fn)
+    if out is None:
+        out = torch.empty((nbytes // dtype.itemsize,), dtype=dtype, device=w_packed.device)
+    check(pack(_ptr(w_packed), _ptr(out), cin, cout, _stream()), pack.__name__)
+    return out
+
+
 def winograd_pack_b3(w_packed, cin, cout, out=None):
     """U = G g G^T of a packed 3x3 kernel [Cout, 9*Cin], every element as three bf16 pieces, in the fragment order of the split-bf16
     Winograd kernel: int16 [48*Cin*Cout] (dc_conv2d_winograd_pack_b3)."""
     lib = _lib.load()
-    _chk(w_packed, name="w")
-    if not w_packed.is_contiguous() or w_packed.numel() != 9 * cin * cout:
-        raise _lib.DcapError("winograd_pack_b3: w must be the contiguous packed 3x3 kernel [Cout, 9*Cin]")
-    nbytes = lib.dc_conv2d_winograd_b3_weight_bytes(cin, cout)
-    if nbytes == 0:
-        raise _lib.DcapError("winograd_pack_b3: Cin and Cout must be multiples of 32")
-    if out is None:
-        out = torch.empty((nbytes // 2,), dtype=torch.int16, device=w_packed.device)
-    check(lib.dc_conv2d_winograd_pack_b3(_ptr(w_packed), _ptr(out), cin, cout, _stream()), "dc_conv2d_winograd_pack_b3")
-    return out
+    return _winograd_pack("winograd_pack_b3", w_packed, cin, cout, out, dtype=torch.int16,
+                          weight_bytes=lib.dc_conv2d_winograd_b3_weight_bytes, pack=lib.dc_conv2d_winograd_pack_b3)
 
 
 def winograd_pack(w_packed, cin, cout, out=None):
     """U = G g G^T of a packed 3x3 kernel [Cout, 9*Cin] in the fragment order the Winograd kernel reads: fp32 [16*Cin*Cout]."""
     lib = _lib.load()
-    _chk(w_packed, name="w")
-    if not w_packed.is_contiguous() or w_packed.numel() != 9 * cin * cout:
-        raise _lib.DcapError("winograd_pack: w must be the contiguous packed 3x3 kernel [Cout, 9*Cin]")
-    nbytes = lib.dc_conv2d_winograd_weight_bytes(cin, cout)
-    if nbytes == 0:
-        raise _lib.DcapError("winograd_pack: Cin and Cout must be multiples of 32")
-    if out is None:
-        out = torch.empty((nbytes // 4,), dtype=torch.float32, device=w_packed.device)
-    check(lib.dc_conv2d_winograd_pack_f32(_ptr(w_packed), _ptr(out), cin, cout, _stream()), "dc_conv2d_winograd_pack_f32")
-    return out
+    return _winograd_pack("winograd_pack", w_packed, cin, cout, out, dtype=torch.float32,
+                          weight_bytes=lib.dc_conv2d_winograd_weight_bytes, pack=lib.dc_conv2d_winograd_pack_f32)
 
 
 def split_bf16x3(x, out=None):
@@ -383,12 +393,10 @@ def conv2d_wgrad(x, dy, kh, kw, stride, pad_t, pad_l, out=None, split_k=0, accum
     if out is None:
         out = torch.empty((Cout, kh * kw * Cin), dtype=torch.float32, device=x.device)
     d = ConvDesc()
-    d.N, d.H, d.W, d.Cin = N, H, W, Cin
-    d.Cout, d.kh, d.kw, d.stride, d.pad_t, d.pad_l, d.Ho, d.Wo = Cout, kh, kw, stride, pad_t, pad_l, Ho, Wo
+    _conv_geometry(d, x, Cout, kh, kw, stride, pad_t, pad_l, Ho, Wo)
     d.x, d.y, d.w, d.split_k = x.data_ptr(), dy.data_ptr(), _chk(out, name="dw").data_ptr(), int(split_k)
     d.accumulate = int(accumulate)
-    ws, wsb = WORKSPACE.get(lib.dc_conv2d_wgrad_workspace_bytes(C.byref(d)), x.device)
-    check(lib.dc_conv2d_wgrad_f32(C.byref(d), _ptr(ws), wsb, _stream()), "dc_conv2d_wgrad_f32")
+    _launch_ws(lib.dc_conv2d_wgrad_workspace_bytes(C.byref(d)), x.device, lib.dc_conv2d_wgrad_f32, C.byref(d))
     return out
 
 
@@ -403,16 +411,11 @@ def conv2d_wgrad_bf16(x, dy, kh, kw, stride, pad_t, pad_l, out=None, split_k=0, 
     if out is None:
         out = torch.empty((Cout, kh * kw * Cin), dtype=torch.float32, device=x.device)
     d = ConvWgradBf16Desc()
-    d.N, d.H, d.W, d.Cin = N, H, W, Cin
-    d.Cout, d.kh, d.kw, d.stride, d.pad_t, d.pad_l, d.Ho, d.Wo = Cout, kh, kw, stride, pad_t, pad_l, Ho, Wo
+    _conv_geometry(d, x, Cout, kh, kw, stride, pad_t, pad_l, Ho, Wo)
     d.x, d.dy, d.dw = x.data_ptr(), dy.data_ptr(), _chk(out, name="dw").data_ptr()
     d.accumulate, d.split_k = int(accumulate), int(split_k)
-    if info is not None:
-        sk = C.c_int(0)
-        info["tile"] = int(lib.dc_conv2d_wgrad_bf16_tile(C.byref(d), C.byref(sk)))
-        info["split_k"] = int(sk.value)
-    ws, wsb = WORKSPACE.get(lib.dc_conv2d_wgrad_bf16_workspace_bytes(C.byref(d)), x.device)
-    check(lib.dc_conv2d_wgrad_bf16(C.byref(d), _ptr(ws), wsb, _stream()), "dc_conv2d_wgrad_bf16")
+    _tile_info(info, lib.dc_conv2d_wgrad_bf16_tile, d)
+    _launch_ws(lib.dc_conv2d_wgrad_bf16_workspace_bytes(C.byref(d)), x.device, lib.dc_conv2d_wgrad_bf16, C.byref(d))
     return out
 
 
@@ -431,21 +434,15 @@ def conv2d_bf16(x, w, kh, kw, stride, pad_t, pad_l, Ho, Wo, scale=None, shift=No
     if out_bf16 is None and want_bf16:
         out_bf16 = torch.empty((N, Ho, Wo, Cout), dtype=BF16, device=x.device)
     d = ConvBf16Desc()
-    d.N, d.H, d.W, d.Cin = N, H, W, Cin
-    d.Cout, d.kh, d.kw, d.stride, d.pad_t, d.pad_l, d.Ho, d.Wo = Cout, kh, kw, stride, pad_t, pad_l, Ho, Wo
+    _conv_geometry(d, x, Cout, kh, kw, stride, pad_t, pad_l, Ho, Wo)
     d.x, d.w = x.data_ptr(), w.data_ptr()
     d.y = None if out is None else _chk(out, name="out").data_ptr()
     d.y_bf16 = None if out_bf16 is None else _chk(out_bf16, BF16, "out_bf16").data_ptr()
-    d.scale = None if scale is None else _chk(scale, name="scale").data_ptr()
-    d.shift = None if shift is None else _chk(shift, name="shift").data_ptr()
+    _scale_shift(d, scale, shift)
     d.residual = None if residual is None else _chk(residual, name="residual").data_ptr()
     d.res_mode, d.relu, d.split_k, d.tile = int(res_mode), int(relu), int(split_k), int(tile)
-    if info is not None:                      # tests / benches: which kernel runs this layer
-        sk = C.c_int(0)
-        info["tile"] = int(lib.dc_conv2d_bf16_tile(C.byref(d), C.byref(sk)))
-        info["split_k"] = int(sk.value)
-    ws, wsb = WORKSPACE.get(lib.dc_conv2d_bf16_workspace_bytes(C.byref(d)), x.device)
-    check(lib.dc_conv2d_bf16(C.byref(d), _ptr(ws), wsb, _stream()), "dc_conv2d_bf16")
+    _tile_info(info, lib.dc_conv2d_bf16_tile, d)
+    _launch_ws(lib.dc_conv2d_bf16_workspace_bytes(C.byref(d)), x.device, lib.dc_conv2d_bf16, C.byref(d))
     return out, out_bf16
 
 
@@ -473,7 +470,7 @@ def roi_align_pyramid_bwd(dmaps, boxes, image_area, dout, pool=7):
     """dmaps: four zero-initialised gradient maps [B,H,W,C] (accumulated into); dout [B,R,pool,pool,C]."""
     lib = _lib.load()
     B, R, _ = boxes.shape
-    d = RoiAlignDesc()
+    d = RoialignDesc()
     d.B, d.R, d.C, d.pool = B, R, dmaps[0].shape[-1], pool
     for i, m in enumerate(dmaps):
         if not _chk(m, name="dmap").is_contiguous():
@@ -594,12 +591,10 @@ def resize_pad_packed(packed, records, canvas=None, out=None, flips=None):
     d.B, d.packed, d.packed_bytes, d.records = B, packed.data_ptr(), packed.numel(), records.ctypes.data
     d.out, d.H, d.W = out.data_ptr(), out.shape[1], out.shape[2]
     need = lib.dc_resize_pad_u8_workspace_bytes(C.byref(d))
-    ws, wsb = WORKSPACE.get(need, packed.device)
     if flags is None:
-        check(lib.dc_resize_pad_u8(C.byref(d), _ptr(ws), wsb, _stream()), "dc_resize_pad_u8")
+        _launch_ws(need, packed.device, lib.dc_resize_pad_u8, C.byref(d))
     else:
-        check(lib.dc_resize_pad_flip_u8(C.byref(d), flags.ctypes.data, B * _lib.RESIZE_RECORD_INTS * 4, _ptr(ws), wsb, _stream()),
-              "dc_resize_pad_flip_u8")
+        _launch_ws(need, packed.device, lib.dc_resize_pad_flip_u8, C.byref(d), flags.ctypes.data, B * _lib.RESIZE_RECORD_INTS * 4)
     return out
 
 
@@ -631,7 +626,7 @@ def roi_align_pyramid(maps, boxes, image_area, pool=7, out=None, levels_out=None
         raise _lib.DcapError("roi_align: boxes must be contiguous")
     if out is None:
         out = torch.empty((B, R, pool, pool, Cc), dtype=torch.float32, device=boxes.device)
-    d = RoiAlignDesc()
+    d = RoialignDesc()
     d.B, d.R, d.C, d.pool = B, R, Cc, pool
     for i, m in enumerate(maps):
         _chk(m, name="map")
@@ -710,15 +705,32 @@ def conv2d_tiles(x, w_packed, tile_list, count, out, scale=None, shift=None, res
     if residual is not None and (not _chk(residual, name="residual").is_contiguous() or tuple(residual.shape) != (N, H // 2, W // 2, Cout)):
         raise _lib.DcapError("conv2d_tiles: the upsample-add operand must be contiguous [N,H/2,W/2,Cout]")
     d = ConvDesc()
-    d.N, d.H, d.W, d.Cin = N, H, W, Cin
-    d.Cout, d.kh, d.kw, d.stride, d.pad_t, d.pad_l, d.Ho, d.Wo = Cout, 1, 1, 1, 0, 0, H, W
+    _conv_geometry(d, x, Cout, 1, 1, 1, 0, 0, H, W)
     d.x, d.w, d.y = x.data_ptr(), w_packed.data_ptr(), out.data_ptr()
-    d.scale = None if scale is None else _chk(scale, name="scale").data_ptr()
-    d.shift = None if shift is None else _chk(shift, name="shift").data_ptr()
+    _scale_shift(d, scale, shift)
     d.residual = None if residual is None else residual.data_ptr()
     d.res_mode, d.relu, d.split_k, d.math = int(res_mode), int(relu), int(split_k), int(math)
     check(lib.dc_conv2d_nhwc_tiles_f32(C.byref(d), _ptr(tile_list), _ptr(count), _stream()), "dc_conv2d_nhwc_tiles_f32")
     return out
+
+
+def _nhwc_same_out(fn, x, w, out):
+    """The operand checks of the list-driven Winograd wrappers: x [N,H,W,Cin], packed kernel w, out [N,H,W,Cout] -> (N, H, W, Cin, Cout)."""
+    _chk(x, name="x"), _chk(w, name="w"), _chk(out, name="out")
+    N, H, W, Cin = x.shape
+    Cout = w.shape[0]
+    if not x.is_contiguous() or not out.is_contiguous() or tuple(out.shape) != (N, H, W, Cout):
+        raise _lib.DcapError("%s: x and out must be contiguous [N,H,W,C]" % fn)
+    return N, H, W, Cin, Cout
+
+
+def _wino_b3_fill(d, x, w, u, out, scale, shift, relu):
+    """d: the 3x3 / stride 1 / 'same' layer the split-bf16 Winograd kernel runs on listed tile groups (u: its winograd_pack_b3)."""
+    _conv_geometry(d, x, w.shape[0], 3, 3, 1, 1, 1, x.shape[1], x.shape[2])
+    d.x, d.w, d.y = x.data_ptr(), w.data_ptr(), out.data_ptr()
+    _scale_shift(d, scale, shift)
+    d.relu = int(relu)
+    d.w_wino_b3 = _chk(u, torch.int16, "w_wino_b3").data_ptr()
 
 
 def conv2d_winograd_groups(x, w_packed, w_wino_b3, group_list, count, out, scale=None, shift=None, relu=False):
@@ -726,24 +738,14 @@ def conv2d_winograd_groups(x, w_packed, w_wino_b3, group_list, count, out, scale
     `count`: int32 device tensor whose first element is the list's length).  Listed groups of `out` get conv2d's values bit for bit,
     nothing else of it is written.  dc_conv2d_winograd_groups_f32."""
     lib = _lib.load()
-    _chk(x, name="x"), _chk(w_packed, name="w"), _chk(out, name="out")
     _chk(group_list, torch.int32, "group_list"), _chk(count, torch.int32, "count")
-    N, H, W, Cin = x.shape
-    Cout = w_packed.shape[0]
-    if not x.is_contiguous() or not out.is_contiguous() or tuple(out.shape) != (N, H, W, Cout):
-        raise _lib.DcapError("conv2d_winograd_groups: x and out must be contiguous [N,H,W,C]")
+    N, H, W, Cin, Cout = _nhwc_same_out("conv2d_winograd_groups", x, w_packed, out)
     if not w_wino_b3.is_contiguous() or w_wino_b3.numel() != 48 * Cin * Cout:
         raise _lib.DcapError("conv2d_winograd_groups: w_wino_b3 must be the contiguous winograd_pack_b3() of this layer's kernel")
     if group_list.numel() < N * lib.dc_conv2d_winograd_group_count(H, W) or count.numel() < 1:
         raise _lib.DcapError("conv2d_winograd_groups: the list must have room for every tile group of the layer")
     d = ConvDesc()
-    d.N, d.H, d.W, d.Cin = N, H, W, Cin
-    d.Cout, d.kh, d.kw, d.stride, d.pad_t, d.pad_l, d.Ho, d.Wo = Cout, 3, 3, 1, 1, 1, H, W
-    d.x, d.w, d.y = x.data_ptr(), w_packed.data_ptr(), out.data_ptr()
-    d.scale = None if scale is None else scale.data_ptr()
-    d.shift = None if shift is None else shift.data_ptr()
-    d.relu = int(relu)
-    d.w_wino_b3 = _chk(w_wino_b3, torch.int16, "w_wino_b3").data_ptr()
+    _wino_b3_fill(d, x, w_packed, w_wino_b3, out, scale, shift, relu)
     check(lib.dc_conv2d_winograd_groups_f32(C.byref(d), _ptr(group_list), _ptr(count), _stream()), "dc_conv2d_winograd_groups_f32")
     return out
 
@@ -762,23 +764,14 @@ def conv2d_winograd_levels(xs, ws_packed, ws_wino_b3, lists, counts, outs, scale
     descs, ptrs = (ConvDesc * n)(), (C.c_void_p * n)()
     for l in range(n):
         x, w, u, out = xs[l], ws_packed[l], ws_wino_b3[l], outs[l]
-        _chk(x, name="x"), _chk(w, name="w"), _chk(out, name="out"), _chk(lists[l], torch.int32, "list")
-        N, H, W, Cin = x.shape
-        Cout = w.shape[0]
-        if not x.is_contiguous() or not out.is_contiguous() or tuple(out.shape) != (N, H, W, Cout):
-            raise _lib.DcapError("conv2d_winograd_levels: x and out must be contiguous [N,H,W,C]")
+        _chk(lists[l], torch.int32, "list")
+        N, H, W, Cin, Cout = _nhwc_same_out("conv2d_winograd_levels", x, w, out)
         if not u.is_contiguous() or u.numel() != 48 * Cin * Cout:
             raise _lib.DcapError("conv2d_winograd_levels: w_wino_b3 must be the contiguous winograd_pack_b3() of the layer's kernel")
         if lists[l].numel() < N * lib.dc_conv2d_winograd_group_count(H, W):
             raise _lib.DcapError("conv2d_winograd_levels: a list must have room for every tile group of its layer")
-        d = descs[l]
-        d.N, d.H, d.W, d.Cin = N, H, W, Cin
-        d.Cout, d.kh, d.kw, d.stride, d.pad_t, d.pad_l, d.Ho, d.Wo = Cout, 3, 3, 1, 1, 1, H, W
-        d.x, d.w, d.y = x.data_ptr(), w.data_ptr(), out.data_ptr()
-        d.scale = None if scales is None or scales[l] is None else _chk(scales[l], name="scale").data_ptr()
-        d.shift = None if shifts is None or shifts[l] is None else _chk(shifts[l], name="shift").data_ptr()
-        d.relu = int(relu[l] if isinstance(relu, (list, tuple)) else relu)
-        d.w_wino_b3 = _chk(u, torch.int16, "w_wino_b3").data_ptr()
+        _wino_b3_fill(descs[l], x, w, u, out, None if scales is None else scales[l], None if shifts is None else shifts[l],
+                      relu[l] if isinstance(relu, (list, tuple)) else relu)
         ptrs[l] = lists[l].data_ptr()
     check(lib.dc_conv2d_winograd_levels_f32(descs, n, ptrs, _ptr(counts), _stream()), "dc_conv2d_winograd_levels_f32")
     return outs
@@ -824,8 +817,7 @@ def rpn_proposals(heads, anchors, image_hw, proposal_count, nms_threshold, std_d
                  torch.empty((B, k), dtype=torch.int32, device=dev),
                  torch.empty((B, proposal_count), dtype=torch.int32, device=dev))
         d.scores_out, d.order_out, d.keep_out = (t.data_ptr() for t in extra)
-    ws, wsb = WORKSPACE.get(lib.dc_proposals_workspace_bytes(C.byref(d)), dev)
-    check(lib.dc_proposals_f32(C.byref(d), _ptr(ws), wsb, _stream()), "dc_proposals_f32")
+    _launch_ws(lib.dc_proposals_workspace_bytes(C.byref(d)), dev, lib.dc_proposals_f32, C.byref(d))
     return (out, extra) if debug else out
 
 
@@ -872,8 +864,7 @@ def refine_generations(rois, image_consts, threshold, max_instances, word_scores
     count = torch.empty((B,), dtype=torch.int32, device=dev)
     d.B, d.N, d.rois, d.image_consts, d.threshold, d.max_instances = B, N, rois.data_ptr(), image_consts.data_ptr(), float(threshold), M
     d.boxes_out, d.keep_out, d.count_out, d.scores_out = boxes.data_ptr(), keep.data_ptr(), count.data_ptr(), scores.data_ptr()
-    ws, wsb = WORKSPACE.get(lib.dc_refine_generations_workspace_bytes(C.byref(d)), dev)
-    check(lib.dc_refine_generations_f64(C.byref(d), _ptr(ws), wsb, _stream()), "dc_refine_generations_f64")
+    _launch_ws(lib.dc_refine_generations_workspace_bytes(C.byref(d)), dev, lib.dc_refine_generations_f64, C.byref(d))
     return boxes, keep, count, scores
 
 
@@ -903,8 +894,7 @@ def lstm_seq_fwd(z, U_rec, mask, B, T, h_seq=None, c_seq=None, rec_masks=None):
     d.mask = None if mask is None else _chk(mask, torch.uint8, "mask").data_ptr()
     d.h_seq, d.c_seq = h_seq.data_ptr(), c_seq.data_ptr()
     d.rec_masks = _rec_masks(rec_masks, B, U)
-    ws, wsb = WORKSPACE.get(lib.dc_lstm_seq_workspace_bytes(B, T, U), z.device)
-    check(lib.dc_lstm_seq_fwd_f32(C.byref(d), _ptr(ws), wsb, _stream()), "dc_lstm_seq_fwd_f32")
+    _launch_ws(lib.dc_lstm_seq_workspace_bytes(B, T, U), z.device, lib.dc_lstm_seq_fwd_f32, C.byref(d))
     return h_seq, c_seq
 
 
@@ -952,8 +942,7 @@ def lstm_step(z, U_rec, h_prev=None, c_prev=None, mask=None, h=None, c=None, U_p
     d.z, d.U_rec, d.U_packed = z.data_ptr(), U_rec.data_ptr(), _ptr(U_packed)
     d.h_prev, d.c_prev, d.mask = _ptr(h_prev), _ptr(c_prev), _ptr(mask)
     d.h, d.c = h.data_ptr(), c.data_ptr()
-    ws, wsb = WORKSPACE.get(lib.dc_lstm_step_workspace_bytes(B, U), z.device)
-    check(lib.dc_lstm_step_f32(C.byref(d), _ptr(ws), wsb, _stream()), "dc_lstm_step_f32")
+    _launch_ws(lib.dc_lstm_step_workspace_bytes(B, U), z.device, lib.dc_lstm_step_f32, C.byref(d))
     return h, c
 
 
@@ -978,8 +967,7 @@ def lstm_seq_bwd(z, U_rec, mask, h_seq, c_seq, B, T, dh_seq=None, dh_last=None, 
     d.dh_last = None if dh_last is None else dh_last.data_ptr()
     d.dz, d.dU_rec, d.accumulate_dU = dz.data_ptr(), (None if dU is None else _chk(dU, name="dU").data_ptr()), int(accumulate_dU)
     d.rec_masks = _rec_masks(rec_masks, B, U)
-    ws, wsb = WORKSPACE.get(lib.dc_lstm_seq_workspace_bytes(B, T, U), z.device)
-    check(lib.dc_lstm_seq_bwd_f32(C.byref(d), _ptr(ws), wsb, _stream()), "dc_lstm_seq_bwd_f32")
+    _launch_ws(lib.dc_lstm_seq_workspace_bytes(B, T, U), z.device, lib.dc_lstm_seq_bwd_f32, C.byref(d))
     return dz, dU
 
 
@@ -1039,8 +1027,7 @@ def vocab_ce(X, W, bias, targets, loss_rows=None, dlogits=None, dbias=None, grad
     if materialize_bf16 is None:
         materialize_bf16 = os.environ.get("DCAP_VOCAB_MATERIALIZE", "1") != "0"
     d.materialize_bf16 = int(bool(materialize_bf16) and bf and dlogits is not None and dlogits.dtype == BF16)
-    ws, wsb = WORKSPACE.get(lib.dc_vocab_ce_workspace_bytes(C.byref(d)), X.device)
-    check(lib.dc_vocab_ce(C.byref(d), _ptr(ws), wsb, _stream()), "dc_vocab_ce")
+    _launch_ws(lib.dc_vocab_ce_workspace_bytes(C.byref(d)), X.device, lib.dc_vocab_ce, C.byref(d))
 
 
 def _row_out(t, M, dtype, name):
@@ -1127,11 +1114,9 @@ def vocab_top1(X, W, bias=None, tokens=None, ids=None, probs=None, mask=None, ti
     d.mask = _ptr(mask)
     if bf:
         d.tile = int(tile or 0)
-        ws, wsb = WORKSPACE.get(lib.dc_vocab_top1_bf16_workspace_bytes(M, V, K, d.tile), X.device)
-        check(lib.dc_vocab_top1_bf16(C.byref(d), _ptr(ws), wsb, _stream()), "dc_vocab_top1_bf16")
-        return tokens
-    ws, wsb = WORKSPACE.get(lib.dc_vocab_top1_workspace_bytes(M, V), X.device)
-    check(lib.dc_vocab_top1_f32(C.byref(d), _ptr(ws), wsb, _stream()), "dc_vocab_top1_f32")
+        _launch_ws(lib.dc_vocab_top1_bf16_workspace_bytes(M, V, K, d.tile), X.device, lib.dc_vocab_top1_bf16, C.byref(d))
+    else:
+        _launch_ws(lib.dc_vocab_top1_workspace_bytes(M, V), X.device, lib.dc_vocab_top1_f32, C.byref(d))
     return tokens
 
 
@@ -1165,11 +1150,9 @@ def vocab_topk(X, W, bias, k, ids=None, probs=None, tile=None):
     d.ids, d.probs = ids.data_ptr(), probs.data_ptr()
     if bf:
         d.tile = int(tile or 0)
-        ws, wsb = WORKSPACE.get(lib.dc_vocab_topk_bf16_workspace_bytes(M, V, K, k, d.tile), X.device)
-        check(lib.dc_vocab_topk_bf16(C.byref(d), _ptr(ws), wsb, _stream()), "dc_vocab_topk_bf16")
-        return ids, probs
-    ws, wsb = WORKSPACE.get(lib.dc_vocab_topk_workspace_bytes(M, V, k), X.device)
-    check(lib.dc_vocab_topk_f32(C.byref(d), _ptr(ws), wsb, _stream()), "dc_vocab_topk_f32")
+        _launch_ws(lib.dc_vocab_topk_bf16_workspace_bytes(M, V, K, k, d.tile), X.device, lib.dc_vocab_topk_bf16, C.byref(d))
+    else:
+        _launch_ws(lib.dc_vocab_topk_workspace_bytes(M, V, k), X.device, lib.dc_vocab_topk_f32, C.byref(d))
     return ids, probs
 
 
@@ -1222,11 +1205,9 @@ def vocab_sample(X, W, bias=None, *, temperature=1.0, top_k=None, seed, offset=0
     d.inv_t, d.seed, d.offset, d.top_k = inv_t, int(seed), int(offset), int(top_k or 0)
     if bf:
         d.tile = int(tile or 0)
-        ws, wsb = WORKSPACE.get(lib.dc_vocab_sample_bf16_workspace_bytes(M, V, K, d.top_k, d.tile), X.device)
-        check(lib.dc_vocab_sample_bf16(C.byref(d), _ptr(ws), wsb, _stream()), "dc_vocab_sample_bf16")
-        return tokens
-    ws, wsb = WORKSPACE.get(lib.dc_vocab_sample_workspace_bytes(M, V, d.top_k), X.device)
-    check(lib.dc_vocab_sample_f32(C.byref(d), _ptr(ws), wsb, _stream()), "dc_vocab_sample_f32")
+        _launch_ws(lib.dc_vocab_sample_bf16_workspace_bytes(M, V, K, d.top_k, d.tile), X.device, lib.dc_vocab_sample_bf16, C.byref(d))
+    else:
+        _launch_ws(lib.dc_vocab_sample_workspace_bytes(M, V, d.top_k), X.device, lib.dc_vocab_sample_f32, C.byref(d))
     return tokens
 
 
@@ -1497,8 +1478,7 @@ def rpn_targets(anchors, gt_boxes, gt_counts, level_sizes, anchors_per_image_bud
     d.seed, d.offset = int(seed) & 0xFFFFFFFF, int(offset) & 0xFFFFFFFF
     d.offset_dev = None if offset_dev is None else _chk(offset_dev, torch.int32, "offset_dev").data_ptr()
     d.counts, d.sel_level, d.sel_index, d.sel_match, d.deltas = counts.data_ptr(), lvl.data_ptr(), idx.data_ptr(), mt.data_ptr(), deltas.data_ptr()
-    ws, wsb = WORKSPACE.get(lib.dc_rpn_targets_workspace(C.byref(d)), anchors.device)
-    check(lib.dc_rpn_targets_f64(C.byref(d), _ptr(ws), wsb, _stream()), "dc_rpn_targets_f64")
+    _launch_ws(lib.dc_rpn_targets_workspace(C.byref(d)), anchors.device, lib.dc_rpn_targets_f64, C.byref(d))
     return counts, lvl, idx, mt, deltas
 
 
@@ -1527,10 +1507,9 @@ def scatter2_add(coarse, fine):
 def l2_reg(w, coef, grad=None, loss=None, mask=None):
     """grad = grad * mask + 2 coef w (mask None: all ones); loss[0] = sum coef w^2 in a fixed order."""
     lib = _lib.load()
-    ws, wsb = WORKSPACE.get(lib.dc_l2_reg_workspace_bytes(w.numel()), w.device) if loss is not None else (None, 0)
-    check(lib.dc_l2_reg_f32(_ptr(_chk(w, name="w")), _ptr(_chk(coef, name="coef")), None if mask is None else _ptr(_chk(mask, name="mask")),
-                            None if grad is None else _ptr(grad), w.numel(), None if loss is None else _ptr(loss),
-                            None if ws is None else _ptr(ws), wsb, _stream()), "dc_l2_reg_f32")
+    _launch_ws(lib.dc_l2_reg_workspace_bytes(w.numel()) if loss is not None else 0, w.device, lib.dc_l2_reg_f32,
+               _ptr(_chk(w, name="w")), _ptr(_chk(coef, name="coef")), None if mask is None else _ptr(_chk(mask, name="mask")),
+               None if grad is None else _ptr(grad), w.numel(), None if loss is None else _ptr(loss))
     return loss
 
 
@@ -1585,8 +1564,8 @@ def colsum(x, out=None, accumulate=False):
     _chk(x, name="x")
     if out is None:
         out = torch.empty((x.shape[1],), dtype=torch.float32, device=x.device)
-    ws, wsb = WORKSPACE.get(lib.dc_colsum_workspace_bytes(x.shape[0], x.shape[1], x.stride(0)), x.device)
-    check(lib.dc_colsum_f32(_ptr(x), x.shape[0], x.shape[1], x.stride(0), _ptr(out), int(accumulate), _ptr(ws), wsb, _stream()), "dc_colsum_f32")
+    M, N, ld = x.shape[0], x.shape[1], x.stride(0)
+    _launch_ws(lib.dc_colsum_workspace_bytes(M, N, ld), x.device, lib.dc_colsum_f32, _ptr(x), M, N, ld, _ptr(out), int(accumulate))
     return out
 
 
@@ -1594,8 +1573,7 @@ def sumsq(x, out=None, accumulate=False):
     lib = _lib.load()
     if out is None:
         out = torch.empty((1,), dtype=torch.float32, device=x.device)
-    ws, wsb = WORKSPACE.get(lib.dc_sumsq_workspace_bytes(x.numel()), x.device)
-    check(lib.dc_sumsq_f32(_ptr(_chk(x, name="x")), x.numel(), _ptr(out), int(accumulate), _ptr(ws), wsb, _stream()), "dc_sumsq_f32")
+    _launch_ws(lib.dc_sumsq_workspace_bytes(x.numel()), x.device, lib.dc_sumsq_f32, _ptr(_chk(x, name="x")), x.numel(), _ptr(out), int(accumulate))
     return out
 
 
@@ -1677,9 +1655,8 @@ def reg_sumsq(w, g, segs, loss=None, gnorm_sq=None):
     lib = _lib.load()
     if segs.n != w.numel() or g.numel() != w.numel():
         raise _lib.DcapError("reg_sumsq: the segment table covers %d elements, the bucket has %d" % (segs.n, w.numel()))
-    ws, wsb = WORKSPACE.get(lib.dc_reg_sumsq_workspace_bytes(w.numel()), w.device)
-    check(lib.dc_reg_sumsq_f32(_ptr(_chk(w, name="w")), _ptr(_chk(g, name="g")), C.byref(segs.c), w.numel(), None if loss is None else _ptr(loss),
-                               None if gnorm_sq is None else _ptr(gnorm_sq), _ptr(ws), wsb, _stream()), "dc_reg_sumsq_f32")
+    _launch_ws(lib.dc_reg_sumsq_workspace_bytes(w.numel()), w.device, lib.dc_reg_sumsq_f32, _ptr(_chk(w, name="w")), _ptr(_chk(g, name="g")),
+               C.byref(segs.c), w.numel(), None if loss is None else _ptr(loss), None if gnorm_sq is None else _ptr(gnorm_sq))
     return loss, gnorm_sq
 
 
