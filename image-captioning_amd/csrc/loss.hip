@@ -510,6 +510,89 @@ __global__ __launch_bounds__(256) void amsgrad_kernel(dc_amsgrad_desc d, dc_reg_
     }
 }
 
+// keras.optimizers.Adam (amsgrad=False) / SGD over the same bucket (dc_optimizer_step_f32): amsgrad_kernel's layout -- float4 grid-stride
+// body, scalar tail, the segment table in LDS -- with one update per instantiation, so that each one loads and stores only the streams
+// its optimizer has: Adam p, g, m, v (4 reads + 3 writes against AMSGrad's 5 + 4), SGD with momentum p, g, velocity (3 + 2), plain
+// SGD p, g (2 + 1).
+enum { kOptAdam = 0, kOptSgdMomentum = 1, kOptSgdPlain = 2 };
+struct OptConsts {
+    float gscale, step, b1, b2, eps, clipvalue;
+    bool nesterov;
+};
+// one element: gg = g' * gscale, clipped by value (Keras' get_gradients clips by norm first, then by value), then the update.
+// s0: Adam's m / SGD's velocity, s1: Adam's v (the kinds without them are handed dummies the compiler drops)
+template <int KIND>
+__device__ __forceinline__ void opt_update(float& p, float g, float& s0, float& s1, const OptConsts& k) {
+    float gg = g * k.gscale;
+    if (k.clipvalue > 0.f) gg = fminf(fmaxf(gg, -k.clipvalue), k.clipvalue);
+    if constexpr (KIND == kOptAdam) {
+        s0 = k.b1 * s0 + (1.f - k.b1) * gg;
+        s1 = k.b2 * s1 + (1.f - k.b2) * gg * gg;
+        p -= k.step * s0 / (sqrtf(s1) + k.eps);
+    } else if constexpr (KIND == kOptSgdMomentum) {
+        const float u = k.step * gg;
+        s0 = k.b1 * s0 - u;
+        p += k.nesterov ? k.b1 * s0 - u : s0;
+    } else {
+        p -= k.step * gg;
+    }
+}
+
+template <int KIND, bool REG>
+__global__ __launch_bounds__(256) void optimizer_kernel(dc_optimizer_desc d, dc_reg_segments r) {
+    __shared__ typename std::conditional<REG, RegLds, int>::type t;
+    if constexpr (REG) reg_load(r, t);
+    OptConsts k;
+    k.gscale = d.grad_scale;
+    if (d.gnorm_sq && d.clipnorm > 0.f) {
+        const float norm = sqrtf(d.gnorm_sq[0]) * fabsf(d.grad_scale);
+        if (norm >= d.clipnorm) k.gscale *= d.clipnorm / norm;
+    }
+    k.step = d.step_dev ? d.step_dev[0] : d.step;
+    k.b1 = d.beta1, k.b2 = d.beta2, k.eps = d.eps, k.clipvalue = d.clipvalue, k.nesterov = d.nesterov != 0;
+    const size_t n4 = d.n >> 2;
+    RegCursor cur;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
+        float4 g = reinterpret_cast<const float4*>(d.g)[i], p = reinterpret_cast<float4*>(d.p)[i];
+        float4 s0 = make_float4(0.f, 0.f, 0.f, 0.f), s1 = s0;
+        if constexpr (KIND != kOptSgdPlain) s0 = reinterpret_cast<float4*>(d.state0)[i];
+        if constexpr (KIND == kOptAdam) s1 = reinterpret_cast<float4*>(d.state1)[i];
+        if constexpr (REG) {
+            float c[4], m[4];
+            reg_vec4(t, r.nseg, i, c, m, cur);
+            g.x = g.x * m[0] + 2.f * c[0] * p.x;
+            g.y = g.y * m[1] + 2.f * c[1] * p.y;
+            g.z = g.z * m[2] + 2.f * c[2] * p.z;
+            g.w = g.w * m[3] + 2.f * c[3] * p.w;
+        }
+        opt_update<KIND>(p.x, g.x, s0.x, s1.x, k);
+        opt_update<KIND>(p.y, g.y, s0.y, s1.y, k);
+        opt_update<KIND>(p.z, g.z, s0.z, s1.z, k);
+        opt_update<KIND>(p.w, g.w, s0.w, s1.w, k);
+        if constexpr (KIND != kOptSgdPlain) reinterpret_cast<float4*>(d.state0)[i] = s0;
+        if constexpr (KIND == kOptAdam) reinterpret_cast<float4*>(d.state1)[i] = s1;
+        reinterpret_cast<float4*>(d.p)[i] = p;
+        if (d.p_bf16 && 4 * i < d.n_bf16) {
+            typedef unsigned short us4 __attribute__((ext_vector_type(4)));
+            auto bits = [](float v) { return __builtin_bit_cast(unsigned short, (__bf16)v); };
+            reinterpret_cast<us4*>(d.p_bf16)[i] = us4{bits(p.x), bits(p.y), bits(p.z), bits(p.w)};
+        }
+    }
+    for (size_t i = (n4 << 2) + (size_t)blockIdx.x * 256 + threadIdx.x; i < d.n; i += (size_t)gridDim.x * 256) {
+        float g0 = d.g[i], p = d.p[i], s0 = 0.f, s1 = 0.f;
+        if constexpr (KIND != kOptSgdPlain) s0 = d.state0[i];
+        if constexpr (KIND == kOptAdam) s1 = d.state1[i];
+        if constexpr (REG) {
+            const int sgm = reg_find(t, r.nseg, (int)i);
+            g0 = g0 * t.mask[sgm] + 2.f * t.coef[sgm] * p;
+        }
+        opt_update<KIND>(p, g0, s0, s1, k);
+        if constexpr (KIND != kOptSgdPlain) d.state0[i] = s0;
+        if constexpr (KIND == kOptAdam) d.state1[i] = s1;
+        d.p[i] = p;
+    }
+}
+
 }  // namespace dcap
 
 using namespace dcap;
@@ -834,4 +917,38 @@ extern "C" int dc_amsgrad_step_f32(const dc_amsgrad_desc* d, void* stream) {
         hipLaunchKernelGGL(amsgrad_kernel<false>, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), *d, dc_reg_segments{});
     }
     return check_launch("amsgrad_kernel");
+}
+
+template <int KIND>
+static void optimizer_launch(const dc_optimizer_desc* d, int blocks, hipStream_t s) {
+    if (d->reg)
+        hipLaunchKernelGGL((optimizer_kernel<KIND, true>), dim3(blocks), dim3(256), 0, s, *d, *d->reg);
+    else
+        hipLaunchKernelGGL((optimizer_kernel<KIND, false>), dim3(blocks), dim3(256), 0, s, *d, dc_reg_segments{});
+}
+
+extern "C" int dc_optimizer_step_f32(const dc_optimizer_desc* d, void* stream) {
+    DC_REQUIRE(d && d->p && d->g && d->n > 0 && (d->kind == DC_OPT_ADAM || d->kind == DC_OPT_SGD), DC_EINVAL, "dc_optimizer_step: bad arguments");
+    DC_REQUIRE(d->kind != DC_OPT_ADAM || (d->state0 && d->state1), DC_EINVAL, "dc_optimizer_step: Adam needs both moment buffers (m, v)");
+    DC_REQUIRE(d->kind != DC_OPT_SGD || d->state0 || d->beta1 == 0.f, DC_EINVAL, "dc_optimizer_step: SGD with momentum needs its velocity buffer");
+    DC_REQUIRE(d->clipvalue >= 0.f, DC_EINVAL, "dc_optimizer_step: clipvalue must be >= 0 (0 = off)");
+    if (!aligned16(d->p) || !aligned16(d->g) || !aligned16(d->state0) || !aligned16(d->state1)) {      // (a NULL state pointer is aligned)
+        set_error("dc_optimizer_step: buffers must be 16-byte aligned");
+        return DC_EALIGN;
+    }
+    DC_REQUIRE(!d->p_bf16 || ((d->n_bf16 & 3) == 0 && d->n_bf16 <= (d->n & ~(size_t)3) && (reinterpret_cast<uintptr_t>(d->p_bf16) & 7u) == 0), DC_EINVAL,
+               "dc_optimizer_step: the bf16 shadow must be 8-byte aligned and cover a multiple of 4 elements inside the vectorised part of p");
+    if (d->reg) {
+        int rc = reg_check(d->reg, d->n, "dc_optimizer_step");
+        if (rc) return rc;
+    }
+    const int blocks = (int)std::min<size_t>((d->n / 4 + 255) / 256 + 1, (size_t)kNumCU * opt_blocks_per_cu());
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (d->kind == DC_OPT_ADAM)
+        optimizer_launch<kOptAdam>(d, blocks, s);
+    else if (d->state0)
+        optimizer_launch<kOptSgdMomentum>(d, blocks, s);
+    else
+        optimizer_launch<kOptSgdPlain>(d, blocks, s);
+    return check_launch("optimizer_kernel");
 }

@@ -18,7 +18,6 @@ The detection-target sampling uses tf.random_shuffle in the reference (order is 
 numpy permutation on the host, the only host round trip of the step (2000x4 floats down, 200x4 up).
 """
 import datetime
-import math
 import os
 import re
 
@@ -30,7 +29,7 @@ from .encoder import EncoderPlan, fuse_rpn_head
 from .layers import resnet_fpn_convs
 from .modified_dense_model import load_weight_file, save_weight_file
 from .packing import pack_conv_kernel, pack_stem_kernel
-from .params import Adam
+from .params import Adam, get as get_optimizer
 from .text_generation_model import CaptionModelV1, caption_targets
 
 FPN_CONVS = (("fpn_c5p5", 1, 2048), ("fpn_c4p4", 1, 1024), ("fpn_c3p3", 1, 512), ("fpn_c2p2", 1, 256),
@@ -727,10 +726,14 @@ class DenseImageCapRCNN(object):
         self._invalidate_graphs()
 
     # ---- compile ----------------------------------------------------------------------------
-    def compile(self, learning_rate):
-        """Adam(lr, clipnorm=0.5, amsgrad=True); losses = the three graph losses + L2(WEIGHT_DECAY)(w)/size(w) over the
-        trainable non-BN weights (:1694-1730)."""
-        self.optimizer = Adam(lr=learning_rate, clipnorm=0.5, amsgrad=True)
+    def compile(self, learning_rate, optimizer=None):
+        """Adam(lr, clipnorm=0.5, amsgrad=True), or `optimizer` (a params.Adam / params.SGD instance, "adam", "sgd") with its lr set to
+        learning_rate; losses = the three graph losses + L2(WEIGHT_DECAY)(w)/size(w) over the trainable non-BN weights (:1694-1730)."""
+        if optimizer is None:
+            self.optimizer = Adam(lr=learning_rate, clipnorm=0.5, amsgrad=True)
+        else:
+            self.optimizer = get_optimizer(optimizer)
+            self.optimizer.lr = learning_rate
         self.caption_model.compile(self.optimizer)          # (drops the caption model's own captured steps: they hold the old m / v / vhat)
         self._invalidate_graphs()
 
@@ -899,8 +902,7 @@ class DenseImageCapRCNN(object):
         opt = self.optimizer
         lr_next = 0.0
         if training and opt is not None:
-            t = opt.iterations + 1                          # the update at the end of THIS step
-            lr_next = opt.lr * math.sqrt(1.0 - opt.beta_2 ** t) / (1.0 - opt.beta_1 ** t)
+            lr_next = opt.step_word(opt.iterations + 1)     # the update at the end of THIS step
         cm = self.caption_model
         scal = np.zeros(4, np.int32)
         scal[0:1] = np.array([lr_next], np.float32).view(np.int32)
@@ -1318,7 +1320,7 @@ class DenseImageCapRCNN(object):
             scale = self.grad_sync(self.store.flat_grad) if self.grad_sync is not None else 1.0
             self.optimizer.apply(self.store, grad_scale=scale)
             return losses
-        # ---- single GPU: [one async upload] -> [encoder hipGraph] -> [step hipGraph: proposals .. losses .. gradients .. AMSGrad]
+        # ---- single GPU: [one async upload] -> [encoder hipGraph] -> [step hipGraph: proposals .. losses .. gradients .. optimizer]
         p, rpn_up, images, gt_caps, gt_norm = self._begin_step(inputs, True)
         path = self._path
         self._choose_step_path()
@@ -1513,14 +1515,15 @@ class DenseImageCapRCNN(object):
         return [{"rois": rois[b, :n[b]].copy(), "ids": ids[b, :n[b]].copy()} for b in range(B)]
 
     # ---- training loop ----------------------------------------------------------------------
-    def train(self, train_dataset, val_dataset, learning_rate, epochs, layers, rpn_targets="host", mold="host", prefetch=0):
+    def train(self, train_dataset, val_dataset, learning_rate, epochs, layers, rpn_targets="host", mold="host", prefetch=0, optimizer=None):
         """fit_generator over data_generator with a checkpoint per epoch (:1810-1888).  rpn_targets="device": the generators hand on the
         images' boxes and every step builds its RPN targets on the device (data_generator, ops.rpn_targets) instead of in NumPy on this
         thread; opt-in, because the subsample is then drawn from Philox keys, not from np.random.choice.
         mold="device" (uint8 [h,w,3] images, IMAGE_PADDING on): the generators hand on the raw images and their flip flags, and every
         step resizes, pads and mirrors them on the device (EncoderPlan.mold_images) -- the same bytes, so the same run bit for bit.
         prefetch=n > 0: the training generator runs in one daemon thread, at most n batches ahead (utils.Prefetcher); the thread is
-        stopped when train() returns or raises.  0: next() on this thread."""
+        stopped when train() returns or raises.  0: next() on this thread.
+        optimizer: compile()'s -- None keeps Adam(clipnorm=0.5, amsgrad=True); e.g. params.SGD(momentum=config.LEARNING_MOMENTUM, clipnorm=5.0)."""
         check_rpn_targets_mode(rpn_targets)
         utils.check_mold(mold)
         prefetch = check_prefetch(prefetch)
@@ -1535,14 +1538,14 @@ class DenseImageCapRCNN(object):
         val_batch = next(val_generator)[0]
         if prefetch:
             with utils.Prefetcher(train_generator, prefetch) as ahead:
-                return self._fit(ahead, val_batch, learning_rate, epochs, layers)
-        return self._fit(train_generator, val_batch, learning_rate, epochs, layers)
+                return self._fit(ahead, val_batch, learning_rate, epochs, layers, optimizer)
+        return self._fit(train_generator, val_batch, learning_rate, epochs, layers, optimizer)
 
-    def _fit(self, train_generator, val_batch, learning_rate, epochs, layers):
+    def _fit(self, train_generator, val_batch, learning_rate, epochs, layers, optimizer=None):
         """train()'s loop over the training generator, validating on the one fixed batch."""
         cfg = self.config
         self.set_trainable(layers)
-        self.compile(learning_rate)
+        self.compile(learning_rate, optimizer)
         names = ("loss",) + self.LOSS_NAMES
         history = []
         # Frozen ResNet (the script's layers: 'heads'-like sets): the backbone pass of batch i + 1 runs beside the rest of batch i's step

@@ -9,6 +9,7 @@ import numpy as np
 import torch
 
 from . import ops, step_graph
+from .params import get as get_optimizer
 from .modified_dense_model import load_weight_file, save_weight_file
 
 
@@ -55,7 +56,8 @@ class KerasLikeModel(object):
     use_step_graph = True      # (one GPU) replay the train step from a hipGraph; DCAP_STEP_GRAPH=0 overrides
 
     def compile(self, optimizer, loss=None):
-        self.optimizer, self.loss = optimizer, loss
+        """optimizer: a params.Adam / params.SGD instance, or "adam" / "sgd" (Keras' defaults)."""
+        self.optimizer, self.loss = (get_optimizer(optimizer) if isinstance(optimizer, str) else optimizer), loss
         self._invalidate_graphs()              # captured train steps hold the previous optimizer's state tensors
 
     def _invalidate_graphs(self):
@@ -97,7 +99,7 @@ class KerasLikeModel(object):
             self._bufs = own
 
     def _train_step_eager(self, *batch):
-        """The step launch by launch: forward (batch: what the sub-class's _forward_train takes), loss, backward, (all-reduce), AMSGrad."""
+        """The step launch by launch: forward (batch: what the sub-class's _forward_train takes), loss, backward, (all-reduce), the optimizer's launch."""
         loss_rows, _ = self._forward_train(*batch, want_grad=True)
         loss = ops.mean(loss_rows, out=self._buf('loss', (1,)))
         self._backward()

@@ -1679,3 +1679,42 @@ def amsgrad_step(p, g, m, v, vhat, lr_t, beta1=0.9, beta2=0.999, eps=1e-7, grad_
             raise _lib.DcapError("amsgrad_step: the segment table covers %d elements, the bucket has %d" % (reg.n, p.numel()))
         d.reg = C.pointer(reg.c)
     check(lib.dc_amsgrad_step_f32(C.byref(d), _stream()), "dc_amsgrad_step_f32")
+
+
+OPTIMIZER_KINDS = {"adam": _lib.OPT_ADAM, "sgd": _lib.OPT_SGD}
+
+
+def optimizer_step(kind, p, g, state, step, beta1=0.9, beta2=0.999, eps=1e-7, nesterov=False, grad_scale=1.0, gnorm_sq=None, clipnorm=0.0,
+                   clipvalue=0.0, p_bf16=None, step_dev=None, reg=None):
+    """One fused update of the bucket p from g (dc_optimizer_step_f32).  kind "adam": state = (m, v), step = Keras' lr_t; kind "sgd":
+    state = (velocity,), or () with beta1 (the momentum) == 0 -- then nothing but p is written --, step = lr.  gnorm_sq / clipnorm,
+    p_bf16, step_dev (a device word that overrides step) and reg (RegSegmentTable) as amsgrad_step takes them; clipvalue clips the
+    scaled gradient after the norm clip."""
+    lib = _lib.load()
+    if kind not in OPTIMIZER_KINDS:
+        raise _lib.DcapError("optimizer_step: kind must be one of %s, got %r" % (sorted(OPTIMIZER_KINDS), kind))
+    state = tuple(state or ())
+    if len(state) > 2:
+        raise _lib.DcapError("optimizer_step: at most two state buckets, got %d" % len(state))
+    d = _lib.OptimizerDesc()
+    d.kind, d.nesterov = OPTIMIZER_KINDS[kind], int(bool(nesterov))
+    d.n = p.numel()
+    for t in (g,) + state:
+        if t.numel() != p.numel():
+            raise _lib.DcapError("optimizer_step: a bucket of %d elements beside p's %d" % (t.numel(), p.numel()))
+    d.p, d.g = _chk(p, name="optimizer buffer").data_ptr(), _chk(g, name="optimizer buffer").data_ptr()
+    ptrs = [_chk(t, name="optimizer state").data_ptr() for t in state] + [None, None]
+    d.state0, d.state1 = ptrs[0], ptrs[1]
+    d.step, d.beta1, d.beta2, d.eps = float(step), float(beta1), float(beta2), float(eps)
+    d.grad_scale = float(grad_scale)
+    d.gnorm_sq = None if gnorm_sq is None else gnorm_sq.data_ptr()
+    d.clipnorm, d.clipvalue = float(clipnorm or 0.0), float(clipvalue or 0.0)
+    if p_bf16 is not None:
+        d.p_bf16, d.n_bf16 = _chk(p_bf16, BF16, "p_bf16").data_ptr(), p_bf16.numel()
+    if step_dev is not None:
+        d.step_dev = _chk(step_dev, name="step_dev").data_ptr()
+    if reg is not None:
+        if reg.n != p.numel():
+            raise _lib.DcapError("optimizer_step: the segment table covers %d elements, the bucket has %d" % (reg.n, p.numel()))
+        d.reg = C.pointer(reg.c)
+    check(lib.dc_optimizer_step_f32(C.byref(d), _stream()), "dc_optimizer_step_f32")

@@ -1,7 +1,7 @@
-"""Flat parameter storage and the Keras-compatible AMSGrad optimizer.
+"""Flat parameter storage and the Keras-compatible optimizers (Adam with and without amsgrad, SGD).
 
 All trainable weights of a model live in ONE contiguous fp32 buffer (and so do their gradients and
-the Adam moments): the optimizer is a single fused kernel launch over the bucket, and data-parallel
+the optimizer's state): the optimizer is a single fused kernel launch over the bucket, and data-parallel
 training all-reduces the gradient bucket directly (RCCL) with no flatten/unflatten copies.
 Per-weight tensors are views into the buckets; every offset is 16-byte aligned.
 """
@@ -93,44 +93,45 @@ class ParamStore:
             self.refresh_shadow()
 
 
-class Adam:
-    """keras.optimizers.Adam(lr=0.001, beta_1=0.9, beta_2=0.999, epsilon=None -> K.epsilon()=1e-7,
-    decay=0., amsgrad=False, clipnorm=None) -- the reference uses amsgrad=True everywhere
-    (text_generation_model.py:425; _v2.py:266; dense_img_cap/dense_model.py:1699 adds clipnorm=0.5).
-    Semantics (SURVEY 9.7): t = iterations+1; lr_t = lr*sqrt(1-b2^t)/(1-b1^t); m, v as usual;
-    vhat = max(vhat, v); p -= lr_t*m/(sqrt(vhat)+eps)."""
+class Optimizer(object):
+    """What the Keras optimizers here share (keras/optimizers.py, 2.1): lr, `decay` (lr_d = lr / (1 + decay * iterations), iterations =
+    the number of completed updates), clipnorm / clipvalue (get_gradients: by global norm first, then by value), the state buckets and
+    ONE fused launch per update.  A sub-class names its kind, its state buckets, what its launch bakes, its step word and its launch."""
+    N_STATE = 0
 
-    def __init__(self, lr=0.001, beta_1=0.9, beta_2=0.999, epsilon=None, decay=0.0, amsgrad=False, clipnorm=None):
-        if not amsgrad:
-            raise NotImplementedError("only the amsgrad=True variant the reference trains with is implemented")
-        if decay:
-            raise NotImplementedError("lr decay is not used by the reference")
-        self.lr, self.beta_1, self.beta_2 = lr, beta_1, beta_2
-        self.epsilon = 1e-7 if epsilon is None else epsilon
-        self.clipnorm = clipnorm
+    def __init__(self, lr, decay=0.0, clipnorm=None, clipvalue=None):
+        if decay < 0 or (clipvalue is not None and clipvalue < 0):
+            raise ValueError("decay and clipvalue must be >= 0")
+        self.lr, self.decay = lr, decay
+        self.clipnorm, self.clipvalue = clipnorm, clipvalue
         self.iterations = 0
         self._state = None
 
+    def _baked(self):
+        raise NotImplementedError
+
     def baked_key(self):
-        """What a captured train step bakes of this optimizer as kernel arguments (only lr reaches a replay, through the lr_t device
-        word): part of every step-graph key, so that changing any of them after a capture takes a fresh capture instead of being
-        silently ignored."""
-        return (id(self), float(self.beta_1), float(self.beta_2), float(self.epsilon), float(self.clipnorm or 0.0))
+        """What a captured train step bakes of this optimizer as kernel arguments (only lr and decay reach a replay, through the step
+        device word): part of every step-graph key, so that changing any of them after a capture takes a fresh capture instead of being
+        silently ignored -- and a step captured under one optimizer is never replayed with another's."""
+        return (id(self),) + tuple(self._baked()) + (float(self.clipnorm or 0.0), float(self.clipvalue or 0.0))
+
+    def lr_decayed(self, t):
+        """lr of update t (1-based): `t - 1` updates are complete when it runs."""
+        return self.lr / (1.0 + self.decay * (t - 1)) if self.decay else self.lr
+
+    def step_word(self, t):
+        """The float32 word update t's launch multiplies with: computed in Python floats, rounded once."""
+        return np.float32(self._step(t))
 
     def _init(self, store):
-        z = lambda: torch.zeros_like(store.flat)
-        self._state = (z(), z(), z())
+        self._state = tuple(torch.zeros_like(store.flat) for _ in range(self.N_STATE))
         self._gnorm = torch.zeros(1, dtype=torch.float32, device=store.device)
-
-    def lr_t(self):
-        t = self.iterations
-        return self.lr * math.sqrt(1.0 - self.beta_2 ** t) / (1.0 - self.beta_1 ** t)
 
     def apply(self, store, grad_scale=1.0, lr_t_dev=None, reg=None, reg_loss=None):
         """One update of every trainable weight from store.flat_grad (scaled by grad_scale, e.g.
-        1/world_size after a summing all-reduce).  lr_t_dev: a float32 device word holding this step's lr_t (the caller wrote
-        lr * sqrt(1 - b2^t) / (1 - b1^t) for t = iterations + 1 there): the launch then carries no per-step host value and can be
-        replayed from a captured hipGraph.
+        1/world_size after a summing all-reduce).  lr_t_dev: a float32 device word holding this step's step word (the caller wrote
+        step_word(iterations + 1) there): the launch then carries no per-step host value and can be replayed from a captured hipGraph.
         reg (ops.RegSegmentTable): the joint model's L2 regulariser and trainable mask are applied INSIDE the update -- store.flat_grad
         holds the plain loss gradient and is left alone; one read-only pass over (weights, gradient) gives the clip norm of the
         regularised gradient and the regulariser's loss term (-> reg_loss[0]) -- instead of a pass that rewrites the gradient bucket
@@ -138,7 +139,6 @@ class Adam:
         if self._state is None:
             self._init(store)
         self.iterations += 1
-        m, v, vh = self._state
         gn = None
         if reg is not None:
             if self.clipnorm or reg_loss is not None:
@@ -146,6 +146,73 @@ class Adam:
             gn = self._gnorm if self.clipnorm else None
         elif self.clipnorm:
             gn = ops.sumsq(store.flat_grad, out=self._gnorm)
-        ops.amsgrad_step(store.flat, store.flat_grad, m, v, vh, self.lr_t(), self.beta_1, self.beta_2, self.epsilon,
-                         grad_scale=grad_scale, gnorm_sq=gn, clipnorm=self.clipnorm or 0.0, p_bf16=getattr(store, "flat_bf16", None),
-                         lr_t_dev=lr_t_dev, reg=reg)
+        self._launch(store, float(self.step_word(self.iterations)), grad_scale, gn, lr_t_dev, reg)
+
+
+class Adam(Optimizer):
+    """keras.optimizers.Adam(lr=0.001, beta_1=0.9, beta_2=0.999, epsilon=None -> K.epsilon()=1e-7,
+    decay=0., amsgrad=False, clipnorm=None, clipvalue=None) -- the reference uses amsgrad=True everywhere
+    (text_generation_model.py:425; _v2.py:266; dense_img_cap/dense_model.py:1699 adds clipnorm=0.5).
+    Semantics (SURVEY 9.7): t = iterations+1; lr_t = lr_d*sqrt(1-b2^t)/(1-b1^t); m, v as usual;
+    amsgrad: vhat = max(vhat, v); p -= lr_t*m/(sqrt(vhat)+eps) (dc_amsgrad_step_f32, three state buckets);
+    else p -= lr_t*m/(sqrt(v)+eps) (dc_optimizer_step_f32, two)."""
+
+    def __init__(self, lr=0.001, beta_1=0.9, beta_2=0.999, epsilon=None, decay=0.0, amsgrad=False, clipnorm=None, clipvalue=None):
+        if amsgrad and clipvalue:
+            raise NotImplementedError("clipvalue is not implemented for amsgrad=True (the AMSGrad launch clips by norm only)")
+        Optimizer.__init__(self, lr, decay, clipnorm, clipvalue)
+        self.beta_1, self.beta_2 = beta_1, beta_2
+        self.epsilon = 1e-7 if epsilon is None else epsilon
+        self.amsgrad = bool(amsgrad)
+        self.N_STATE = 3 if amsgrad else 2
+
+    def _baked(self):
+        return ("amsgrad" if self.amsgrad else "adam", float(self.beta_1), float(self.beta_2), float(self.epsilon))
+
+    def _step(self, t):
+        return self.lr_decayed(t) * math.sqrt(1.0 - self.beta_2 ** t) / (1.0 - self.beta_1 ** t)
+
+    def _launch(self, store, step, grad_scale, gn, step_dev, reg):
+        shadow = getattr(store, "flat_bf16", None)
+        if self.amsgrad:
+            m, v, vh = self._state
+            ops.amsgrad_step(store.flat, store.flat_grad, m, v, vh, step, self.beta_1, self.beta_2, self.epsilon, grad_scale=grad_scale,
+                             gnorm_sq=gn, clipnorm=self.clipnorm or 0.0, p_bf16=shadow, lr_t_dev=step_dev, reg=reg)
+        else:
+            ops.optimizer_step("adam", store.flat, store.flat_grad, self._state, step, self.beta_1, self.beta_2, self.epsilon,
+                               grad_scale=grad_scale, gnorm_sq=gn, clipnorm=self.clipnorm or 0.0, clipvalue=self.clipvalue or 0.0,
+                               p_bf16=shadow, step_dev=step_dev, reg=reg)
+
+
+class SGD(Optimizer):
+    """keras.optimizers.SGD(lr=0.01, momentum=0., decay=0., nesterov=False, clipnorm=None, clipvalue=None) (the reference's
+    parallel_model.py self-test compiles SGD(lr=0.01, momentum=0.9, clipnorm=5.0); Mask R-CNN's usual fine-tuning optimizer).
+    Keras 2.1: v = momentum*m - lr_d*g; m := v; p += momentum*v - lr_d*g if nesterov else v.  One state bucket (the velocity), none
+    with momentum == 0: that launch reads p and g and writes p."""
+
+    def __init__(self, lr=0.01, momentum=0.0, decay=0.0, nesterov=False, clipnorm=None, clipvalue=None):
+        if momentum < 0:
+            raise ValueError("momentum must be >= 0")
+        Optimizer.__init__(self, lr, decay, clipnorm, clipvalue)
+        self.momentum, self.nesterov = momentum, bool(nesterov)
+        self.N_STATE = 1 if momentum else 0
+
+    def _baked(self):
+        return ("sgd", float(self.momentum), self.nesterov)
+
+    def _step(self, t):
+        return self.lr_decayed(t)
+
+    def _launch(self, store, step, grad_scale, gn, step_dev, reg):
+        ops.optimizer_step("sgd", store.flat, store.flat_grad, self._state, step, beta1=self.momentum, nesterov=self.nesterov,
+                           grad_scale=grad_scale, gnorm_sq=gn, clipnorm=self.clipnorm or 0.0, clipvalue=self.clipvalue or 0.0,
+                           p_bf16=getattr(store, "flat_bf16", None), step_dev=step_dev, reg=reg)
+
+
+def get(optimizer):
+    """keras.optimizers.get: an instance as it is, "adam" / "sgd" with Keras' defaults."""
+    if isinstance(optimizer, Optimizer):
+        return optimizer
+    if isinstance(optimizer, str) and optimizer.lower() in ("adam", "sgd"):
+        return {"adam": Adam, "sgd": SGD}[optimizer.lower()]()
+    raise ValueError("unknown optimizer %r: an Adam / SGD instance, 'adam' or 'sgd'" % (optimizer,))

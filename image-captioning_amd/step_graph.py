@@ -4,7 +4,8 @@ encoder pass, whole or as trunk + top) and the joint model's choice between repl
 
 The decoder-only configurations (BASELINE configs[0] / configs[1]) are chains of 60 - 150 kernels of 5 - 20 us each: issued one by one
 from Python the host is the bottleneck (10 us per launch through ctypes), not the GPU.  Here the step is enqueued once into a hipGraph
--- forward, loss, backward, AMSGrad -- and replayed; what changes from step to step reaches the kernels through persistent device
+-- forward, loss, backward, the optimizer's launch (ops.amsgrad_step, or ops.optimizer_step
+for Adam without amsgrad and SGD) -- and replayed; what changes from step to step reaches the kernels through persistent device
 buffers:
 
   * PackedInputs: the host's per-step words (token ids, masks, targets, index tables, Keras' lr_t, the dropout stream position) packed
@@ -14,7 +15,6 @@ buffers:
 Values that Python computed while the capture ran (optimizer.iterations, the dropout step counter) are advanced by hand on every replay.
 Replays are bit-identical to the eager step: the same launches with the same arguments (tests/test_gpu_models.py).
 """
-import math
 import os
 import warnings
 
@@ -193,7 +193,6 @@ class PathChooser(object):
 
 
 def lr_word(opt):
-    """Keras' lr_t = lr * sqrt(1 - b2^t) / (1 - b1^t) of the update the NEXT step ends with (t = iterations + 1), as the float32 word
-    the eager launch would carry as its argument."""
-    t = opt.iterations + 1
-    return np.array([opt.lr * math.sqrt(1.0 - opt.beta_2 ** t) / (1.0 - opt.beta_1 ** t)], np.float32)
+    """The step word of the update the NEXT step ends with (t = iterations + 1; Adam / AMSGrad: Keras' lr_t = lr_d * sqrt(1 - b2^t) /
+    (1 - b1^t), SGD: lr_d -- params.Optimizer.step_word), as the float32 word the eager launch would carry as its argument."""
+    return np.array([opt.step_word(opt.iterations + 1)], np.float32)

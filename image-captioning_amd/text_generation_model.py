@@ -22,7 +22,7 @@ import torch
 from . import decoding, ops, step_graph, synth, utils
 from .config import Config
 from .keras_like import KerasLikeModel, ModelCheckpoint, CSVLogger  # noqa: F401
-from .params import ParamStore, Adam  # noqa: F401
+from .params import ParamStore, Adam, SGD  # noqa: F401
 from .text_generation_model_v2 import pad_sequences
 from .utils import Dataset
 
@@ -512,7 +512,7 @@ class CaptionModelV1(KerasLikeModel):
         return None
 
     def train_step(self, feat, caps, targets):
-        """forward + roi_caption_loss + backward + (all-reduce) + AMSGrad; the loss as a DEVICE scalar (no sync).
+        """forward + roi_caption_loss + backward + (all-reduce) + the optimizer's update; the loss as a DEVICE scalar (no sync).
         One GPU, one mask set per RoI: the whole step is replayed from a hipGraph captured on the third call with the same batch
         shape (step_graph.py); captions, targets, lr_t and the dropout stream position travel in ONE upload, the features in one copy."""
         if self.optimizer is None:

@@ -20,7 +20,7 @@ from .config import Config
 from .keras_like import KerasLikeModel, ModelCheckpoint, CSVLogger  # noqa: F401  (re-exported for scripts)
 from .layers import V2_WORD_LSTM
 from .packing import fold_bn
-from .params import ParamStore, Adam  # noqa: F401
+from .params import ParamStore, Adam, SGD  # noqa: F401
 from .utils import Dataset
 
 
@@ -496,7 +496,7 @@ class CaptionModelV2(KerasLikeModel):
     use_step_graph = False
 
     def train_step(self, feat, tb):
-        """forward + backward + (all-reduce) + AMSGrad; returns the loss as a DEVICE scalar (no sync).
+        """forward + backward + (all-reduce) + the optimizer's update; returns the loss as a DEVICE scalar (no sync).
         use_step_graph (one GPU): the whole step is replayed from a hipGraph captured on the third call with the same batch shape
         (step_graph.py); the batch reaches it through two device-to-device copies (features, packed tables) and one word (lr_t)."""
         if self.optimizer is None:

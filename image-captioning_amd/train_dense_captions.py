@@ -93,9 +93,10 @@ def load_vocabulary(cache_dir, embeddings_file, data_file, train_image_ids):
     return id_to_word, word_to_id, matrix
 
 
-def main(root_dir=None, init_with='coco', epochs=100, rpn_targets="host", mold="host", prefetch=0):
+def main(root_dir=None, init_with='coco', epochs=100, rpn_targets="host", mold="host", prefetch=0, optimizer=None):
     """rpn_targets="device": the RPN targets of every step are built on the GPU; mold="device": the raw images are resized, padded and
-    flipped on the GPU; prefetch=n: the training generator runs n batches ahead in a thread (DenseImageCapRCNN.train)."""
+    flipped on the GPU; prefetch=n: the training generator runs n batches ahead in a thread; optimizer: a params.Adam / params.SGD
+    instance, "adam" or "sgd" in place of Adam(clipnorm=0.5, amsgrad=True) (DenseImageCapRCNN.train)."""
     check_rpn_targets_mode(rpn_targets)
     check_mold(mold)
     check_prefetch(prefetch)
@@ -133,7 +134,7 @@ def main(root_dir=None, init_with='coco', epochs=100, rpn_targets="host", mold="
         print(model.summary())
     start_time = time.time()
     model.train(datasets[0], datasets[1], learning_rate=config.LEARNING_RATE, epochs=epochs, layers="no_backbone", rpn_targets=rpn_targets,
-                mold=mold, prefetch=prefetch)
+                mold=mold, prefetch=prefetch, optimizer=optimizer)
     print(time.time() - start_time)
 
 

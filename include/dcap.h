@@ -1094,6 +1094,42 @@ typedef struct {
 
 int dc_amsgrad_step_f32(const dc_amsgrad_desc* d, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * keras.optimizers.Adam (amsgrad=False) and keras.optimizers.SGD (momentum, nesterov) fused over one flat parameter bucket: the
+ * siblings of the launch above that read and write only the streams their update needs (Adam: p, g, m, v -- no vhat; SGD with
+ * momentum: p, g, velocity; plain SGD: p, g).  fp32, per element, in this order:
+ *   g' = g * mask + 2 * coef * p (reg given, else g) ; gg = g' * grad_scale * clip (clip as dc_amsgrad_step_f32 takes it from
+ *   gnorm_sq / clipnorm) ; clipvalue > 0: gg = min(max(gg, -clipvalue), clipvalue)   (Keras' get_gradients: by norm, then by value)
+ *   DC_OPT_ADAM: m = beta1*m + (1-beta1)*gg ; v = beta2*v + (1-beta2)*gg*gg ; p -= step * m / (sqrt(v) + eps)
+ *                (step = lr*sqrt(1-beta2^t)/(1-beta1^t), computed by the caller)
+ *   DC_OPT_SGD:  u = step*gg ; vel = beta1*vel - u ; p += nesterov ? beta1*vel - u : vel      (beta1 = the momentum, step = lr)
+ *                beta1 == 0 and state0 == NULL: p -= u, no state is read or written
+ * ------------------------------------------------------------------------------------------------ */
+#define DC_OPT_ADAM 0
+#define DC_OPT_SGD 1
+typedef struct {
+    int kind;                 /* DC_OPT_ADAM | DC_OPT_SGD */
+    int nesterov;             /* DC_OPT_SGD only */
+    size_t n;
+    float* p;
+    const float* g;
+    float* state0;            /* Adam: m; SGD: the velocity (NULL with beta1 == 0) */
+    float* state1;            /* Adam: v; SGD: NULL */
+    float step;               /* the word the update multiplies with */
+    const float* step_dev;    /* optional: a device word that overrides step (as lr_t_dev above: a captured hipGraph replays with this
+                                 step's value) */
+    float beta1, beta2, eps;
+    float grad_scale;
+    const float* gnorm_sq;    /* as above */
+    float clipnorm;
+    float clipvalue;          /* 0 = off */
+    uint16_t* p_bf16;         /* as above: the bf16 shadow of p[0 .. n_bf16), refreshed in the same pass */
+    size_t n_bf16;
+    const dc_reg_segments* reg; /* as above: HOST pointer, read during the call; gnorm_sq then comes from dc_reg_sumsq_f32 */
+} dc_optimizer_desc;
+
+int dc_optimizer_step_f32(const dc_optimizer_desc* d, void* stream);
+
 /* One READ-ONLY pass over (w, g) in front of the fused update above (round 5: replaces dc_l2_reg_f32 + dc_sumsq_f32 = three reads and
  * one write of the bucket + one more read, by two reads): loss[0] = sum coef * w^2 (the L2 term of dense_img_cap/dense_model.py:1715-1718),
  * gnorm_sq[0] = sum (g * mask + 2 * coef * w)^2 (what Adam(clipnorm=0.5), :1699, clips by), both as block partials in block order
