@@ -1,5 +1,5 @@
 // loss.hip -- vocabulary softmax + Keras categorical cross-entropy (forward + d/dlogits), greedy
-// argmax, column sums (bias gradients), reductions and the fused AMSGrad update.
+// argmax, column sums (bias gradients), reductions, the fused AMSGrad update and the RoI tag head's focal loss.
 // All of these are HBM-bandwidth kernels: 16-byte accesses, wavefront (64-lane) shuffles for the
 // row reductions, one pass over the data wherever the maths allows.
 #include <type_traits>
@@ -593,6 +593,122 @@ __global__ __launch_bounds__(256) void optimizer_kernel(dc_optimizer_desc d, dc_
     }
 }
 
+// RoI tag head (dc_tag_focal_f32): sigmoid + focal loss + gradient of one logit, from the logit.  e = exp(-|z|) gives p and 1 - p both
+// without cancellation; the clip of Keras' binary_crossentropy is decided on p (low side) and on 1 - p (high side, where p itself has
+// no digits left), and inside it x = log(q / (1 - q)) is z itself.
+struct TagConsts {
+    float lo, omhi;           // (float)1e-7 and 1 - (float)(1 - 1e-7)
+    float x_lo, x_hi;         // log(q / (1 - q)) at the two clip values
+};
+__device__ __forceinline__ void tag_focal_elem(float z, int t, float alpha, int gamma, const TagConsts& k, float& L, float& g) {
+    const float e = expf(-fabsf(z)), r = 1.f / (1.f + e), s = e * r;
+    const bool pos = z >= 0.f, one = t == 1;
+    const float p = pos ? r : s, omp = pos ? s : r;
+    const bool in = p >= k.lo && omp >= k.omhi;
+    const float x = in ? z : (pos ? k.x_hi : k.x_lo);
+    const float ex = in ? e : expf(-fabsf(x));
+    const float tf = (float)t;
+    const float bce = fmaxf(x, 0.f) - x * tf + log1pf(ex);
+    const float fw = one ? omp : p, dfw = one ? -(p * omp) : p * omp;
+    const float a = one ? alpha : 1.f - alpha;
+    const float fwg = gamma == 0 ? 1.f : gamma == 1 ? fw : fw * fw;
+    const float dfwg = gamma == 0 ? 0.f : gamma == 1 ? 1.f : 2.f * fw;
+    L = a * fwg * bce;
+    const float dq = one ? -omp : p - tf;                // sigmoid(x) - t, the derivative of bce in x, times dx/dz = 1 inside the clip
+    g = a * (dfwg * dfw * bce + (in ? fwg * dq : 0.f));
+}
+
+// One 256-thread block per row.  Columns go to threads in groups of four in BOTH instantiations (VEC only chooses 16-byte or 4-byte
+// accesses), so a row's sum is added in one order whatever its alignment: a row computed alone equals the same row inside a batch.
+template <bool VEC>
+__global__ __launch_bounds__(256) void tag_focal_kernel(dc_tag_focal_desc d, int gamma, TagConsts k) {
+    __shared__ float red[4];
+    const int row = blockIdx.x, tid = threadIdx.x, C = d.C, C4 = C >> 2;
+    const float* z = d.z + (long)row * d.ldz;
+    const int32_t* t = d.t + (long)row * d.ldt;
+    float* dz = d.dz ? d.dz + (long)row * d.lddz : nullptr;
+    int any = 0;
+    for (int i = tid; i < C4; i += 256) {
+        int4 v;
+        if constexpr (VEC) v = reinterpret_cast<const int4*>(t)[i];
+        else v = make_int4(t[4 * i], t[4 * i + 1], t[4 * i + 2], t[4 * i + 3]);
+        any |= (v.x == 1) | (v.y == 1) | (v.z == 1) | (v.w == 1);
+    }
+    for (int i = 4 * C4 + tid; i < C; i += 256) any |= t[i] == 1;
+    // every thread has read its targets and (below) reads its own logits before it overwrites them: dz may alias z
+    if (!__syncthreads_or(any)) {                          // a dead row: zeros, its logits are never read
+        if (dz) {
+            for (int i = tid; i < C4; i += 256) {
+                if constexpr (VEC) reinterpret_cast<float4*>(dz)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+                else dz[4 * i] = dz[4 * i + 1] = dz[4 * i + 2] = dz[4 * i + 3] = 0.f;
+            }
+            for (int i = 4 * C4 + tid; i < C; i += 256) dz[i] = 0.f;
+        }
+        if (tid == 0 && d.loss_rows) d.loss_rows[row] = 0.f;
+        return;
+    }
+    float sum = 0.f;
+    for (int i = tid; i < C4; i += 256) {
+        float4 v;
+        int4 w;
+        if constexpr (VEC) {
+            v = reinterpret_cast<const float4*>(z)[i];
+            w = reinterpret_cast<const int4*>(t)[i];
+        } else {
+            v = make_float4(z[4 * i], z[4 * i + 1], z[4 * i + 2], z[4 * i + 3]);
+            w = make_int4(t[4 * i], t[4 * i + 1], t[4 * i + 2], t[4 * i + 3]);
+        }
+        float L0, L1, L2, L3;
+        float4 g;
+        tag_focal_elem(v.x, w.x, d.alpha, gamma, k, L0, g.x);
+        tag_focal_elem(v.y, w.y, d.alpha, gamma, k, L1, g.y);
+        tag_focal_elem(v.z, w.z, d.alpha, gamma, k, L2, g.z);
+        tag_focal_elem(v.w, w.w, d.alpha, gamma, k, L3, g.w);
+        sum += L0; sum += L1; sum += L2; sum += L3;
+        if (dz) {
+            g.x *= d.grad_scale; g.y *= d.grad_scale; g.z *= d.grad_scale; g.w *= d.grad_scale;
+            if constexpr (VEC) reinterpret_cast<float4*>(dz)[i] = g;
+            else { dz[4 * i] = g.x; dz[4 * i + 1] = g.y; dz[4 * i + 2] = g.z; dz[4 * i + 3] = g.w; }
+        }
+    }
+    for (int i = 4 * C4 + tid; i < C; i += 256) {
+        float L, g;
+        tag_focal_elem(z[i], t[i], d.alpha, gamma, k, L, g);
+        sum += L;
+        if (dz) dz[i] = g * d.grad_scale;
+    }
+    if (!d.loss_rows) return;
+    sum = block_reduce<false>(sum, red);
+    if (tid == 0) d.loss_rows[row] = sum;
+}
+
+// dc_tag_scores_f32: one block per row; the float64 partial sums of log p meet in lane order, then in wave order
+__global__ __launch_bounds__(256) void tag_scores_kernel(const float* __restrict__ z, int ldz, int C, float min_confidence, float* __restrict__ probs,
+                                                         int ldp, float* __restrict__ scores) {
+    __shared__ double red[4];
+    const int row = blockIdx.x, tid = threadIdx.x;
+    const float* zr = z + (long)row * ldz;
+    float* P = probs ? probs + (long)row * ldp : nullptr;
+    double s = 0.0;
+    int any = 0;
+    for (int i = tid; i < C; i += 256) {
+        const float v = zr[i], e = expf(-fabsf(v)), r = 1.f / (1.f + e);
+        const float p = v >= 0.f ? r : e * r;
+        if (P) P[i] = p;
+        if (p > min_confidence) {
+            s += log((double)p);
+            any = 1;
+        }
+    }
+    any = __syncthreads_or(any);
+    if (!scores) return;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    if ((tid & 63) == 0) red[tid >> 6] = s;
+    __syncthreads();
+    if (tid == 0) scores[row] = any ? (float)((red[0] + red[1]) + (red[2] + red[3])) : -3.4e38f;
+}
+
 }  // namespace dcap
 
 using namespace dcap;
@@ -951,4 +1067,34 @@ extern "C" int dc_optimizer_step_f32(const dc_optimizer_desc* d, void* stream) {
     else
         optimizer_launch<kOptSgdPlain>(d, blocks, s);
     return check_launch("optimizer_kernel");
+}
+
+extern "C" int dc_tag_focal_f32(const dc_tag_focal_desc* d, void* stream) {
+    DC_REQUIRE(d && d->z && d->t && d->M >= 1 && d->C >= 1 && (d->loss_rows || d->dz), DC_EINVAL, "dc_tag_focal: bad arguments");
+    DC_REQUIRE(d->M == 1 || (d->ldz >= d->C && d->ldt >= d->C && (!d->dz || d->lddz >= d->C)), DC_EINVAL, "dc_tag_focal: a row stride is shorter than C");
+    DC_REQUIRE(d->alpha >= 0.f && d->alpha <= 1.f, DC_EINVAL, "dc_tag_focal: alpha must lie in [0, 1], got %g", (double)d->alpha);
+    DC_REQUIRE(d->gamma == 0.f || d->gamma == 1.f || d->gamma == 2.f, DC_EINVAL, "dc_tag_focal: gamma must be 0, 1 or 2 (exact products, no powf), got %g",
+               (double)d->gamma);
+    const float lo = 1e-7f, hi = 1.f - 1e-7f;            // Keras casts epsilon and 1 - epsilon to the tensor's dtype
+    TagConsts k;
+    k.lo = lo;
+    k.omhi = 1.f - hi;                                    // exact (2^-23)
+    k.x_lo = (float)log((double)lo / (1.0 - (double)lo));
+    k.x_hi = (float)log((double)hi / (1.0 - (double)hi));
+    const bool one = d->M == 1;
+    const bool vec = aligned16(d->z) && aligned16(d->t) && (one || ((d->ldz & 3) == 0 && (d->ldt & 3) == 0)) &&
+                     (!d->dz || (aligned16(d->dz) && (one || (d->lddz & 3) == 0)));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (vec)
+        hipLaunchKernelGGL(tag_focal_kernel<true>, dim3(d->M), dim3(256), 0, s, *d, (int)d->gamma, k);
+    else
+        hipLaunchKernelGGL(tag_focal_kernel<false>, dim3(d->M), dim3(256), 0, s, *d, (int)d->gamma, k);
+    return check_launch("tag_focal_kernel");
+}
+
+extern "C" int dc_tag_scores_f32(const float* z, int ldz, int M, int C, float min_confidence, float* probs, int ldp, float* scores, void* stream) {
+    DC_REQUIRE(z && M >= 1 && C >= 1 && (probs || scores), DC_EINVAL, "dc_tag_scores: bad arguments");
+    DC_REQUIRE(M == 1 || (ldz >= C && (!probs || ldp >= C)), DC_EINVAL, "dc_tag_scores: a row stride is shorter than C");
+    hipLaunchKernelGGL(tag_scores_kernel, dim3(M), dim3(256), 0, static_cast<hipStream_t>(stream), z, ldz, C, min_confidence, probs, ldp, scores);
+    return check_launch("tag_scores_kernel");
 }

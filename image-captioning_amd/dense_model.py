@@ -190,16 +190,17 @@ def refine_constants(window, config, image_shape):
     return np.array([window[0], window[1], window[2], window[3], h, w, window[0], window[1], scale, 0.0], np.float64)
 
 
-def load_image_gt(dataset, config, image_id, augment=False, rng=np.random, mold="host"):
+def load_image_gt(dataset, config, image_id, augment=False, rng=np.random, mold="host", loader=None):
     """image (resized + padded), image_meta, gt_captions [G,T], gt_boxes [G,4] (dense_model.py:953-984).
     As in the reference the boxes are handed on exactly as the dataset stores them: they are NOT rescaled or padded
     with the image, and the horizontal flip mirrors only the image (quirk kept so that the same dataset yields the
     same training inputs).
     mold="device": no pixel is touched.  `image` is a utils.RawImageBatch of one -- the array dataset.load_image returned and the flip
     flag, drawn from `rng` where the host mode draws it -- and image_meta is the host mode's (utils.resize_geometry: the unflipped
-    window).  An image that is not uint8 [h,w,3] raises utils.DeviceMoldError."""
+    window).  An image that is not uint8 [h,w,3] raises utils.DeviceMoldError.
+    loader(dataset, image_id) -> (boxes [G,4], targets [G,W]) stands in for dataset.load_captions_and_rois (see data_generator)."""
     image = dataset.load_image(image_id)
-    boxes, captions = dataset.load_captions_and_rois(image_id)
+    boxes, captions = dataset.load_captions_and_rois(image_id) if loader is None else loader(dataset, image_id)
     shape = image.shape
     if mold == "device":
         window = utils.resize_geometry(utils.check_device_mold_image(image).shape, config.IMAGE_MIN_DIM, config.IMAGE_MAX_DIM, True)[2]
@@ -227,7 +228,7 @@ def check_prefetch(prefetch):
     return int(prefetch)
 
 
-def data_generator(dataset, config, shuffle=True, augment=True, batch_size=1, rng=np.random, rpn_targets="host", mold="host"):
+def data_generator(dataset, config, shuffle=True, augment=True, batch_size=1, rng=np.random, rpn_targets="host", mold="host", loader=None):
     """Infinite generator of ([images f32 molded, image_meta, rpn_match [B,A,1], rpn_bbox [B,256,4], gt_captions
     [B,MAX_GT,T], gt_boxes [B,MAX_GT,4]], []) -- the six training inputs of the reference's generator (:1260-1403).
     rpn_targets="device": build_rpn_targets is not called; position 2 is a list of the B images' FULL box arrays (every box of the
@@ -237,7 +238,10 @@ def data_generator(dataset, config, shuffle=True, augment=True, batch_size=1, rn
     second epoch's shuffle on its image order differs from the host mode's.
     mold="device" (uint8 [h,w,3] images, IMAGE_PADDING on): no pixel is resampled, converted or copied on the host.  Position 0 is a
     utils.RawImageBatch -- the B arrays as the dataset loaded them and the B flip flags -- that the step resizes, pads and mirrors on
-    the device into the same bytes; positions 1 - 5 and every draw from `rng` are the host mold's."""
+    the device into the same bytes; positions 1 - 5 and every draw from `rng` are the host mold's.
+    loader(dataset, image_id) -> (boxes [G,4], targets [G,W]): the per-box targets of a model with another top (roi_tag_model: multi-hot
+    tag rows) in place of dataset.load_captions_and_rois; position 4 is then [B,MAX_GT,W] with the loader's own width W.  None (default):
+    captions, PADDING_SIZE wide."""
     check_rpn_targets_mode(rpn_targets)
     raw = utils.check_mold(mold, config.IMAGE_PADDING) == "device"
     molded_shape = (config.IMAGE_MAX_DIM, config.IMAGE_MAX_DIM, 3)          # (device mold: what image.shape is on the host)
@@ -252,7 +256,7 @@ def data_generator(dataset, config, shuffle=True, augment=True, batch_size=1, rn
             rng.shuffle(image_ids)
         image_id = image_ids[index]
         try:
-            image, meta, caps, boxes = load_image_gt(dataset, config, image_id, augment, rng, mold)
+            image, meta, caps, boxes = load_image_gt(dataset, config, image_id, augment, rng, mold, loader)
             if not on_device:
                 match, deltas = build_rpn_targets(molded_shape if raw else image.shape, anchors, caps, boxes, config, rng)
             elif boxes.shape[0] == 0:
@@ -277,7 +281,7 @@ def data_generator(dataset, config, shuffle=True, augment=True, batch_size=1, rn
             if not on_device:
                 matches = np.zeros((batch_size, anchors.shape[0], 1), match.dtype)
                 bboxes = np.zeros((batch_size, config.RPN_TRAIN_ANCHORS_PER_IMAGE, 4), deltas.dtype)
-            gt_caps = np.zeros((batch_size, config.MAX_GT_INSTANCES, config.PADDING_SIZE), caps.dtype)
+            gt_caps = np.zeros((batch_size, config.MAX_GT_INSTANCES, config.PADDING_SIZE if loader is None else caps.shape[1]), caps.dtype)
             gt_boxes = np.zeros((batch_size, config.MAX_GT_INSTANCES, 4), boxes.dtype)
             rpn_boxes = []
         if raw:
@@ -386,6 +390,8 @@ class DenseImageCapRCNN(object):
         "all": ".*",
         "caption_only": r"imgcap\_.*",
     }
+    GT_LOADER = None                      # data_generator's loader: None = the dataset's captions
+    PIPELINED_FIT = True                  # _fit may run pipeline.JointTrainPipeline (a sub-class that cannot: False, the serial loop)
 
     def __init__(self, mode, config, model_dir, device=None, stage4_blocks=22, seed=0, lstm_units=512, conv_math=None,
                  compute_dtype="f32", backbone_from=None):
@@ -501,10 +507,7 @@ class DenseImageCapRCNN(object):
         hk, hb = fuse_rpn_head(W, HEAD_PAD)
         extra.append(("rpn_head/kernel", pack_conv_kernel(hk), True))
         extra.append(("rpn_head/bias", hb, True))
-        self.caption_model = CaptionModelV1([cfg.POOL_SIZE, cfg.POOL_SIZE, 256], cfg, self.units, 'training', dev, seed,
-                                            extra_params=extra, compute_dtype=self.compute_dtype)
-        self.caption_model.recurrent_dropout = float(getattr(cfg, "RECURRENT_DROPOUT", 0.2))    # dense_img_cap/dense_model.py:769-770: recurrent_dropout=0.2
-        self.caption_model.dropout_rows = str(getattr(cfg, "DROPOUT_ROWS", "roi"))
+        self.caption_model = self._make_top(cfg, dev, seed, extra)
         self.store = self.caption_model.store
         self._plan = None                                    # the encoder plan the step runs on
         self._plans = []                                     # ... and its siblings (pipeline.JointTrainPipeline alternates between two)
@@ -514,6 +517,16 @@ class DenseImageCapRCNN(object):
         self._invalidate_graphs()
         if weights is not None:
             self.set_weights({k: v for k, v in weights.items() if k not in self._backbone})
+
+    def _make_top(self, cfg, dev, seed, extra):
+        """What sits on the pooled RoI features and owns the parameter bucket (self.caption_model).  The step asks of it: store,
+        compile(optimizer), _forward_train / _backward (through _top_forward_device / _top_forward_host below), _prefix_rows,
+        recurrent_dropout and _drop_step.  A sub-class with another top (roi_tag_model.ROITagRCNN) overrides this and those two."""
+        top = CaptionModelV1([cfg.POOL_SIZE, cfg.POOL_SIZE, 256], cfg, self.units, 'training', dev, seed,
+                             extra_params=extra, compute_dtype=self.compute_dtype)
+        top.recurrent_dropout = float(getattr(cfg, "RECURRENT_DROPOUT", 0.2))    # dense_img_cap/dense_model.py:769-770: recurrent_dropout=0.2
+        top.dropout_rows = str(getattr(cfg, "DROPOUT_ROWS", "roi"))
+        return top
 
     def _invalidate_graphs(self):
         """Captured step graphs bake buffer addresses, the plan's outputs, the trainable subset and the optimizer state: anything
@@ -1199,9 +1212,14 @@ class DenseImageCapRCNN(object):
                                   out=(rois_d[b], caps_d[b], counts_d[b]))
         self._last_targets = (rois_d, caps_d, counts_d)
         feats = p.roi_features(boxes_norm=rois_d, out=self._buf("feats", (B, R, cfg.POOL_SIZE, cfg.POOL_SIZE, 256))).view(B * R, cfg.POOL_SIZE, cfg.POOL_SIZE, 256)
+        return rois_d, self._top_forward_device(feats, caps_d, B * R, T, backward, rpn_up)
+
+    def _top_forward_device(self, feats, caps_d, R_all, T, backward, rpn_up):
+        """The top's forward on the sampled RoIs' features [R_all,7,7,256] and their device-resident targets caps_d [B,R,T]; returns
+        loss_rows (the step's third loss is their mean times their count)."""
+        cm = self.caption_model
         # the caption loss is the mean over every live position of the BATCH (imgcap_caption_loss_graph gathers over all images,
         # dense_model.py:936-946): the tables' row weights are 1 / (live positions of all B * R captions)
-        R_all = B * R
         tables = ops.caption_tables(caps_d.view(R_all, T), out=(self._buf("ct_ids", (T * R_all,), torch.int32), self._buf("ct_mask", (T * R_all,), torch.uint8),
                                                                 self._buf("ct_tg", (T * R_all,), torch.int32), self._buf("ct_rw", (T * R_all,))))
         if cm._prefix_rows(backward):
@@ -1210,9 +1228,9 @@ class DenseImageCapRCNN(object):
             caps_h = caps_d.view(R_all, T).cpu().numpy()
             tg_h = caption_targets(caps_h)
             live = (tg_h > 0).astype(np.float32)
-            return rois_d, cm._forward_train(feats, caps_h, tg_h, want_grad=backward, row_weights=live / max(float(live.sum()), 1.0), keras_sparse=True)[0]
-        return rois_d, cm._forward_train(feats, None, want_grad=backward, keras_sparse=True, device_tables=tables + (R_all, T),
-                                         drop_offset_dev=rpn_up["drop_offset"])[0]
+            return cm._forward_train(feats, caps_h, tg_h, want_grad=backward, row_weights=live / max(float(live.sum()), 1.0), keras_sparse=True)[0]
+        return cm._forward_train(feats, None, want_grad=backward, keras_sparse=True, device_tables=tables + (R_all, T),
+                                 drop_offset_dev=rpn_up["drop_offset"])[0]
 
     def _host_sample(self, p, proposals, shuffle, given, rpn, gt_caps, gt_norm):
         """A caller-supplied permutation (shuffle = callable) or sample (given): drawn on the host, as until round 3.  The proposals start their
@@ -1225,7 +1243,7 @@ class DenseImageCapRCNN(object):
             if rpn is not None:
                 rpn.run()
             rois, caps = given
-            npos = int((np.asarray(caps)[:, 1:] > 0).any(axis=1).sum())
+            npos = self._given_positive_rows(caps)
             nneg = int((np.abs(rois).sum(axis=1) > 0).sum()) - npos
         else:
             if rpn is not None:
@@ -1242,10 +1260,19 @@ class DenseImageCapRCNN(object):
         self._last_targets = dict(rois=rois, caps=caps, npos=npos, nneg=nneg)
         boxes = torch.tensor(np.ascontiguousarray(rois[None]), dtype=torch.float32, device=self.device)
         feats = p.roi_features(boxes_norm=boxes, out=self._buf("feats", (1, cfg.TRAIN_ROIS_PER_IMAGE, cfg.POOL_SIZE, cfg.POOL_SIZE, 256)))
+        return boxes, self._top_forward_host(feats[0], caps, rpn is not None)
+
+    @staticmethod
+    def _given_positive_rows(caps):
+        """Rows of a caller-supplied sample that carry a target (last_targets' npos)."""
+        return int((np.asarray(caps)[:, 1:] > 0).any(axis=1).sum())
+
+    def _top_forward_host(self, feats, caps, want_grad):
+        """_top_forward_device for a sample that was drawn on the host: feats [R,7,7,256], caps a host array [R,T]."""
         tg = caption_targets(caps)
         live = (tg > 0).astype(np.float32)
-        return boxes, self.caption_model._forward_train(feats[0], caps, tg, want_grad=rpn is not None, row_weights=live / max(float(live.sum()), 1.0),
-                                                        keras_sparse=True)[0]
+        return self.caption_model._forward_train(feats, caps, tg, want_grad=want_grad, row_weights=live / max(float(live.sum()), 1.0),
+                                                 keras_sparse=True)[0]
 
     def _validation_tail(self, p, rpn_up, losses):
         """Forward-only pass: the RPN losses need the heads only (their gradient goes to zeroed scratch), the regulariser loss the weights only."""
@@ -1296,13 +1323,14 @@ class DenseImageCapRCNN(object):
     def _loss_list(self, losses):
         """losses: the step's raw loss terms [rpn_class, rpn_bbox, imgcap (unscaled), reg], a device tensor or its host copy."""
         v = (losses.cpu().numpy() if isinstance(losses, torch.Tensor) else np.asarray(losses)).astype(np.float64)
-        out = dict(rpn_class_loss=v[0], rpn_bbox_loss=v[1], imgcap_loss=v[2] * self._loss_scale, reg_loss=v[3])
-        out["loss"] = out["rpn_class_loss"] + out["rpn_bbox_loss"] + out["imgcap_loss"] + out["reg_loss"]
+        top = self.LOSS_NAMES[2]                             # imgcap_loss
+        out = {"rpn_class_loss": v[0], "rpn_bbox_loss": v[1], top: v[2] * self._loss_scale, "reg_loss": v[3]}
+        out["loss"] = out["rpn_class_loss"] + out["rpn_bbox_loss"] + out[top] + out["reg_loss"]
         return out
 
     def _losses_to_api(self, v):
         self.last_losses = d = self._loss_list(v)
-        return [d["loss"], d["rpn_class_loss"], d["rpn_bbox_loss"], d["imgcap_loss"]]
+        return [d["loss"], d["rpn_class_loss"], d["rpn_bbox_loss"], d[self.LOSS_NAMES[2]]]
 
     def train_on_batch_device(self, inputs, targets=None, trunk_done=False):
         """One optimizer step; the raw loss terms as a float32 device tensor [4] (the loss all-reduce of ParallelModel and the
@@ -1531,8 +1559,9 @@ class DenseImageCapRCNN(object):
         layers = self.LAYER_REGEX.get(layers, layers)
         cfg = self.config
         utils.check_mold(mold, cfg.IMAGE_PADDING)
-        train_generator = data_generator(train_dataset, cfg, shuffle=True, batch_size=cfg.BATCH_SIZE, rpn_targets=rpn_targets, mold=mold)
-        val_generator = data_generator(val_dataset, cfg, shuffle=True, batch_size=cfg.BATCH_SIZE, augment=False, rpn_targets=rpn_targets, mold=mold)
+        train_generator = data_generator(train_dataset, cfg, shuffle=True, batch_size=cfg.BATCH_SIZE, rpn_targets=rpn_targets, mold=mold, loader=self.GT_LOADER)
+        val_generator = data_generator(val_dataset, cfg, shuffle=True, batch_size=cfg.BATCH_SIZE, augment=False, rpn_targets=rpn_targets, mold=mold,
+                                       loader=self.GT_LOADER)
         # (the validation batch is drawn BEFORE the prefetch thread starts: both generators draw from np.random, and the order of their
         # draws must not depend on a thread's timing)
         val_batch = next(val_generator)[0]
@@ -1545,13 +1574,13 @@ class DenseImageCapRCNN(object):
         """train()'s loop over the training generator, validating on the one fixed batch."""
         cfg = self.config
         self.set_trainable(layers)
-        self.compile(learning_rate, optimizer)
+        self.compile(learning_rate, optimizer=optimizer)
         names = ("loss",) + self.LOSS_NAMES
         history = []
         # Frozen ResNet (the script's layers: 'heads'-like sets): the backbone pass of batch i + 1 runs beside the rest of batch i's step
         # (pipeline.JointTrainPipeline: same updates bit for bit, tests/test_gpu_models.py; DCAP_JOINT_PIPELINE=0 keeps the serial loop).
         pipe = None
-        if self.backbone_from is None and os.environ.get("DCAP_JOINT_PIPELINE", "1") != "0":
+        if self.PIPELINED_FIT and self.backbone_from is None and os.environ.get("DCAP_JOINT_PIPELINE", "1") != "0":
             from .pipeline import JointTrainPipeline
             pipe = JointTrainPipeline(self._outer)
         for epoch in range(self.epoch, epochs):

@@ -12,7 +12,7 @@ import torch
 
 from . import _lib
 from ._lib import (RpnTargetsDesc, PwChainDesc, ConvBf16Desc, AmsgradDesc, DetectionTargetsDesc, BnReluDesc, ConvDesc, ConvWgradBf16Desc, GemmBf16Desc, VocabCeDesc, ProposalDesc, RpnLossDesc, GemmDesc, LstmBwdDesc, LstmFwdDesc, RoialignDesc, RoiGroupsDesc,
-                   SoftmaxCeDesc, VocabTop1Desc, VocabTopkDesc, VocabTop1Bf16Desc, VocabTopkBf16Desc, VocabSampleDesc, VocabSampleBf16Desc, BeamSelectDesc, BeamStepDesc, LstmStepDesc, RefineDesc, ResizePadDesc, check)
+                   SoftmaxCeDesc, TagFocalDesc, VocabTop1Desc, VocabTopkDesc, VocabTop1Bf16Desc, VocabTopkBf16Desc, VocabSampleDesc, VocabSampleBf16Desc, BeamSelectDesc, BeamStepDesc, LstmStepDesc, RefineDesc, ResizePadDesc, check)
 
 
 def _stream():
@@ -989,6 +989,58 @@ def softmax_ce(logits, targets=None, probs=None, loss_rows=None, dlogits=None, g
     d.row_weights = None if row_weights is None else _chk(row_weights, name="row_weights").data_ptr()
     d.keras_sparse = int(keras_sparse)
     check(lib.dc_softmax_ce_f32(C.byref(d), _stream()), "dc_softmax_ce_f32")
+
+
+def _tag_rows(fn, name, t, dtype, M, C):
+    """A [M,C] device matrix with any row stride -> its stride as the kernels take it (a single row has none)."""
+    if _chk(t, dtype, name).dim() != 2 or tuple(t.shape) != (M, C):
+        raise _lib.DcapError("%s: %s must be a %s [%d,%d] matrix, got %s" % (fn, name, dtype, M, C, tuple(t.shape)))
+    return t.stride(0) if M > 1 else C
+
+
+def tag_focal(logits, targets, alpha=0.25, gamma=2.0, grad_scale=1.0, loss_rows=None, dlogits=None):
+    """Sigmoid + focal loss + gradient of the RoI tag head in one launch (dc_tag_focal_f32): logits float32 [M,C] and targets int32 [M,C]
+    (multi-hot), any row strides.  loss_rows float32 [M] receives each live row's summed loss (a row is live when it has a target equal
+    to 1; dead rows give exact zeros), dlogits float32 [M,C] (may be logits) grad_scale * d(sum of loss_rows)/d(logits).  Both are
+    optional; with neither given, loss_rows is allocated.  Returns (loss_rows, dlogits).  alpha in [0, 1], gamma 0, 1 or 2."""
+    lib = _lib.load()
+    if _chk(logits, name="logits").dim() != 2 or logits.shape[0] < 1 or logits.shape[1] < 1:
+        raise _lib.DcapError("tag_focal: logits must be a float32 [M,C] matrix with M, C >= 1, got %s" % (tuple(logits.shape),))
+    M, Cn = logits.shape
+    d = TagFocalDesc()
+    d.M, d.C, d.z, d.ldz = M, Cn, logits.data_ptr(), _tag_rows("tag_focal", "logits", logits, torch.float32, M, Cn)
+    d.t, d.ldt = targets.data_ptr(), _tag_rows("tag_focal", "targets", targets, torch.int32, M, Cn)
+    if loss_rows is None and dlogits is None:
+        loss_rows = torch.empty((M,), dtype=torch.float32, device=logits.device)
+    if loss_rows is not None:
+        if not _chk(loss_rows, name="loss_rows").is_contiguous() or tuple(loss_rows.shape) != (M,):
+            raise _lib.DcapError("tag_focal: loss_rows must be a contiguous float32 [%d] vector" % M)
+        d.loss_rows = loss_rows.data_ptr()
+    if dlogits is not None:
+        d.dz, d.lddz = dlogits.data_ptr(), _tag_rows("tag_focal", "dlogits", dlogits, torch.float32, M, Cn)
+    d.alpha, d.gamma, d.grad_scale = float(alpha), float(gamma), float(grad_scale)
+    check(lib.dc_tag_focal_f32(C.byref(d), _stream()), "dc_tag_focal_f32")
+    return loss_rows, dlogits
+
+
+def tag_scores(logits, min_confidence, probs=None, scores=None):
+    """The RoI tag head at inference (dc_tag_scores_f32): probs float32 [M,C] = sigmoid(logits) and scores float32 [M] = the sum of log p
+    over the classes with p > min_confidence (float64 accumulation, rounded once), float32(-3.4e38) for a row with none.  Both are
+    allocated when not given.  Returns (probs, scores)."""
+    lib = _lib.load()
+    if _chk(logits, name="logits").dim() != 2 or logits.shape[0] < 1 or logits.shape[1] < 1:
+        raise _lib.DcapError("tag_scores: logits must be a float32 [M,C] matrix with M, C >= 1, got %s" % (tuple(logits.shape),))
+    M, Cn = logits.shape
+    if probs is None:
+        probs = torch.empty((M, Cn), dtype=torch.float32, device=logits.device)
+    if scores is None:
+        scores = torch.empty((M,), dtype=torch.float32, device=logits.device)
+    if not _chk(scores, name="scores").is_contiguous() or tuple(scores.shape) != (M,):
+        raise _lib.DcapError("tag_scores: scores must be a contiguous float32 [%d] vector" % M)
+    check(lib.dc_tag_scores_f32(_ptr(logits), _tag_rows("tag_scores", "logits", logits, torch.float32, M, Cn), M, Cn, float(min_confidence),
+                                _ptr(probs), _tag_rows("tag_scores", "probs", probs, torch.float32, M, Cn), _ptr(scores), _stream()),
+          "dc_tag_scores_f32")
+    return probs, scores
 
 
 def vocab_ce_supported(X, W):

@@ -84,6 +84,14 @@ def rpn_weights(seed=4, anchors_per_loc=3, depth=256):
     return W
 
 
+def tag_head_weights(seed=6, num_classes=1000, width=1024):
+    """roitag_class_logits with the reference's initialisers (roi_tag_classification/model.py:795-797): kernel N(0, 0.01), bias
+    PriorProbability(0.01) = -log(99)."""
+    rng = np.random.default_rng(seed)
+    return {"roitag_class_logits/kernel": (0.01 * rng.standard_normal((width, num_classes))).astype(F32),
+            "roitag_class_logits/bias": np.full(num_classes, -np.log((1.0 - 0.01) / 0.01), F32)}
+
+
 def head_weights(seed=1, pool=7, cin=256, width=1024):
     rng = np.random.default_rng(seed)
     W = {}

@@ -159,10 +159,86 @@ class _Act(object):
         return self._b
 
 
-class CaptionModelV1(KerasLikeModel):
+class RoiHead(KerasLikeModel):
+    """The trainable RoI head mrcnn_class_conv1/bn1/conv2/bn2 (frozen BN statistics) on pooled features, forward and backward, and the
+    GEMM engine it runs on -- what the models that put a top on it share (CaptionModelV1 below, roi_tag_model.TagTop).  Sub-classes
+    provide store, compute_dtype, device and _bufs."""
     FEAT = 1024
-    D1 = 1024
     HEAD = (("mrcnn_class_conv1", "mrcnn_class_bn1"), ("mrcnn_class_conv2", "mrcnn_class_bn2"))
+
+    # ---------------------------------------------------------------------------------- engine
+    def _act(self, key, f):
+        return _Act(self, key, f)
+
+    def _wview(self, name, rows=None):
+        """(fp32 view, bf16 view or None) of a 2-D weight (conv kernels flattened to [k*k*cin, cout]), optionally a row range."""
+        w = self.store.w[name]
+        w = w.view(-1, w.shape[-1])
+        wb = self.store.wb.get(name)
+        if wb is not None:
+            wb = wb.view(-1, wb.shape[-1])
+        if rows is not None:
+            w = w[rows[0]:rows[1]]
+            wb = None if wb is None else wb[rows[0]:rows[1]]
+        return w, wb
+
+    def _mm(self, A, W, key=None, out=None, a_trans=False, b_trans=False, want_b=False, **ep):
+        """op(A) @ op(W) with the fused epilogue `ep`.  A: _Act; W: (fp32, bf16-or-None) weight views or an _Act.  Runs on
+        the bf16 matrix pipe when this model computes in bf16 and the shapes fit dc_gemm_bf16 (16-byte chunks along K),
+        else on the fp32 MFMA path.  Returns an _Act of the fp32 result (with its bf16 copy when want_b)."""
+        wf, wb = (W.f, None) if isinstance(W, _Act) else W
+        Af = A.f
+        M = Af.shape[1] if a_trans else Af.shape[0]
+        K = Af.shape[0] if a_trans else Af.shape[1]
+        N = wf.shape[0] if b_trans else wf.shape[1]
+        if out is None:
+            out = self._buf(key, (M, N))
+        use_b = (self.compute_dtype == "bf16" and K % 8 == 0 and Af.stride(0) % 8 == 0 and wf.stride(0) % 8 == 0 and
+                 (not a_trans or M % 8 == 0) and (b_trans or N % 8 == 0) and (isinstance(W, _Act) or wb is not None))
+        if use_b:
+            if isinstance(W, _Act):
+                wb = W.b
+            ob = self._buf((key or 'mm') + ':outb', (M, N), torch.bfloat16) if want_b else None
+            ops.gemm_bf16(A.b, wb, out=out, out_bf16=ob, a_trans=a_trans, b_trans=b_trans, **ep)
+            return _Act(self, key or 'mm', out, ob)
+        ops.gemm(Af, wf, out=out, a_trans=a_trans, b_trans=b_trans, **ep)
+        return _Act(self, key or 'mm', out)
+
+    def _head_forward(self, X):
+        w = self.store.w
+        R = X.shape[0]
+        x = self._act('X', X)
+        self._head_in = []
+        for li, (conv, bn) in enumerate(self.HEAD):
+            self._head_in.append(x)
+            acc = self._mm(x, self._wview(conv + '/kernel'), key='acc%d' % li).f
+            y = ops.bn_relu_fwd(acc, w[conv + '/bias'], w[bn + '/gamma'], w[bn + '/beta'], w[bn + '/moving_mean'],
+                                w[bn + '/moving_variance'], self._buf('hact%d' % li, (R, self.FEAT)))
+            x = self._act('hact%d' % li, y)
+        return x
+
+    def _head_backward(self, dy, B, ready, want_dx):
+        """The head's backward from dy = d(loss)/d(its output) [B, FEAT]: kernels, biases, BN gamma / beta (statistics frozen) into the
+        bucket, ready(conv, bn) as each pair is final; with want_dx returns the gradient w.r.t. the flattened RoI features."""
+        w, g, bf = self.store.w, self.store.grad, self._bufs
+        for li in (1, 0):
+            conv, bn = self.HEAD[li]
+            dacc = ops.bn_relu_bwd(bf['acc%d' % li], w[conv + '/bias'], w[bn + '/gamma'], w[bn + '/beta'], w[bn + '/moving_mean'],
+                                   w[bn + '/moving_variance'], dy, self._buf('dacc%d' % li, (B, self.FEAT)),
+                                   g[bn + '/gamma'], g[bn + '/beta'], g[conv + '/bias'])
+            dacc = self._act('dacc%d' % li, dacc)
+            gk = g[conv + '/kernel']
+            self._mm(self._head_in[li], dacc, a_trans=True, out=gk.view(-1, gk.shape[-1]))
+            ready(conv, bn)
+            if li == 1:
+                dy = self._mm(dacc, self._wview(conv + '/kernel'), key='dhact0', b_trans=True).f
+            elif want_dx:
+                return self._mm(dacc, self._wview(conv + '/kernel'), key='dX', b_trans=True).f
+        return None
+
+
+class CaptionModelV1(RoiHead):
+    D1 = 1024
     # Keras recurrent_dropout of imgcap_lstm1 / imgcap_lstm2 (:141-142; dense_img_cap/dense_model.py:769-770).  Default = the
     # reference's 0.2: every train step (train_on_batch / fit_generator / train()) draws four inverted-dropout masks [B, units]
     # per LSTM (one per gate i,f,c,o), fixed over the timesteps, from a seeded counter-based generator ON THE DEVICE
@@ -252,57 +328,6 @@ class CaptionModelV1(KerasLikeModel):
             for layer in layers:
                 lo, hi = self.store.layer_range(layer)
                 self.grad_sync.ready(self.store.flat_grad, lo, hi)
-
-    # ---------------------------------------------------------------------------------- engine
-    def _act(self, key, f):
-        return _Act(self, key, f)
-
-    def _wview(self, name, rows=None):
-        """(fp32 view, bf16 view or None) of a 2-D weight (conv kernels flattened to [k*k*cin, cout]), optionally a row range."""
-        w = self.store.w[name]
-        w = w.view(-1, w.shape[-1])
-        wb = self.store.wb.get(name)
-        if wb is not None:
-            wb = wb.view(-1, wb.shape[-1])
-        if rows is not None:
-            w = w[rows[0]:rows[1]]
-            wb = None if wb is None else wb[rows[0]:rows[1]]
-        return w, wb
-
-    def _mm(self, A, W, key=None, out=None, a_trans=False, b_trans=False, want_b=False, **ep):
-        """op(A) @ op(W) with the fused epilogue `ep`.  A: _Act; W: (fp32, bf16-or-None) weight views or an _Act.  Runs on
-        the bf16 matrix pipe when this model computes in bf16 and the shapes fit dc_gemm_bf16 (16-byte chunks along K),
-        else on the fp32 MFMA path.  Returns an _Act of the fp32 result (with its bf16 copy when want_b)."""
-        wf, wb = (W.f, None) if isinstance(W, _Act) else W
-        Af = A.f
-        M = Af.shape[1] if a_trans else Af.shape[0]
-        K = Af.shape[0] if a_trans else Af.shape[1]
-        N = wf.shape[0] if b_trans else wf.shape[1]
-        if out is None:
-            out = self._buf(key, (M, N))
-        use_b = (self.compute_dtype == "bf16" and K % 8 == 0 and Af.stride(0) % 8 == 0 and wf.stride(0) % 8 == 0 and
-                 (not a_trans or M % 8 == 0) and (b_trans or N % 8 == 0) and (isinstance(W, _Act) or wb is not None))
-        if use_b:
-            if isinstance(W, _Act):
-                wb = W.b
-            ob = self._buf((key or 'mm') + ':outb', (M, N), torch.bfloat16) if want_b else None
-            ops.gemm_bf16(A.b, wb, out=out, out_bf16=ob, a_trans=a_trans, b_trans=b_trans, **ep)
-            return _Act(self, key or 'mm', out, ob)
-        ops.gemm(Af, wf, out=out, a_trans=a_trans, b_trans=b_trans, **ep)
-        return _Act(self, key or 'mm', out)
-
-    def _head_forward(self, X):
-        w = self.store.w
-        R = X.shape[0]
-        x = self._act('X', X)
-        self._head_in = []
-        for li, (conv, bn) in enumerate(self.HEAD):
-            self._head_in.append(x)
-            acc = self._mm(x, self._wview(conv + '/kernel'), key='acc%d' % li).f
-            y = ops.bn_relu_fwd(acc, w[conv + '/bias'], w[bn + '/gamma'], w[bn + '/beta'], w[bn + '/moving_mean'],
-                                w[bn + '/moving_variance'], self._buf('hact%d' % li, (R, self.FEAT)))
-            x = self._act('hact%d' % li, y)
-        return x
 
     def _hidden(self, f, ids_tm, mask, B, T, Bl=None):
         """word_generation_model up to the Dense-1024 layer, over time-major token ids: a1 [T*B, 1024] (row t*B+b = the
@@ -494,22 +519,7 @@ class CaptionModelV1(KerasLikeModel):
         self._mm(f, dzf, a_trans=True, out=gW1[self.E:])
         ready('imgcap_lstm1')
         self._mm(dzf, self._wview('imgcap_lstm1/kernel', (self.E, self.E + self.FEAT)), out=df, b_trans=True, accumulate=True)
-        # trainable head (kernels, biases, BN gamma/beta; statistics frozen)
-        dy = df
-        for li in (1, 0):
-            conv, bn = self.HEAD[li]
-            dacc = ops.bn_relu_bwd(bf['acc%d' % li], w[conv + '/bias'], w[bn + '/gamma'], w[bn + '/beta'], w[bn + '/moving_mean'],
-                                   w[bn + '/moving_variance'], dy, self._buf('dacc%d' % li, (B, self.FEAT)),
-                                   g[bn + '/gamma'], g[bn + '/beta'], g[conv + '/bias'])
-            dacc = self._act('dacc%d' % li, dacc)
-            gk = g[conv + '/kernel']
-            self._mm(self._head_in[li], dacc, a_trans=True, out=gk.view(-1, gk.shape[-1]))
-            ready(conv, bn)
-            if li == 1:
-                dy = self._mm(dacc, self._wview(conv + '/kernel'), key='dhact0', b_trans=True).f
-            elif want_dx:
-                return self._mm(dacc, self._wview(conv + '/kernel'), key='dX', b_trans=True).f
-        return None
+        return self._head_backward(df, B, ready, want_dx)
 
     def train_step(self, feat, caps, targets):
         """forward + roi_caption_loss + backward + (all-reduce) + the optimizer's update; the loss as a DEVICE scalar (no sync).

@@ -1138,6 +1138,43 @@ size_t dc_reg_sumsq_workspace_bytes(size_t n);
 int dc_reg_sumsq_f32(const float* w, const float* g, const dc_reg_segments* reg, size_t n, float* loss, float* gnorm_sq, void* workspace,
                      size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * RoI tag head: sigmoid + focal loss + d/dlogits in one launch (roi_tag_classification/model.py:48-66 focal_loss, :877-887
+ * roi_tag_classes_loss_graph, on Keras 2.1's K.binary_crossentropy over probabilities).
+ *   z [M][ldz] float32 logits (C valid columns; the projection GEMM's output, bias added); t [M][ldt] int32 multi-hot targets.
+ *   per element:  p = sigmoid(z) ; q = clip(p, lo, hi), lo = (float)1e-7, hi = (float)(1 - 1e-7) ; x = log(q / (1 - q)) ;
+ *                 bce = max(x, 0) - x t + log(1 + exp(-|x|)) ; fw = t == 1 ? 1 - p : p (the UNCLIPPED p) ;
+ *                 a = t == 1 ? alpha : 1 - alpha ; L = a * fw^gamma * bce
+ *   A row is live when one of its targets is 1.  loss_rows[m] = sum_c L (live) or 0 (dead); the model's loss is the SUM of loss_rows.
+ *   dz [M][lddz] = grad_scale * dL/dz as TensorFlow differentiates the above: through fw's unclipped p, and through the clip only
+ *   where lo <= p <= hi.  Dead rows are exact zeros in both outputs whatever their logits hold (the reference gathers them away
+ *   before any arithmetic).  dz may alias z.
+ *   Evaluated from the logit (exp(-|z|), log1p; p and 1 - p both without cancellation): any finite z gives finite results.
+ *   alpha in [0, 1]; gamma 0, 1 or 2 (exact products), anything else DC_EINVAL.  Strides are free: 16-byte accesses when every base and
+ *   stride allows them, 4-byte accesses otherwise -- no alignment refusal.  loss_rows and dz are each optional.
+ *   One 256-thread block per row: the liveness reduction, then the element pass, then a fixed-order wave / LDS reduction of the row
+ *   loss -- no atomics, a row's result does not depend on M or on scheduling.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct {
+    int M, C;
+    const float* z;
+    int ldz;
+    const int32_t* t;
+    int ldt;
+    float alpha, gamma, grad_scale;
+    float* loss_rows;         /* optional [M] */
+    float* dz;                /* optional [M][lddz] */
+    int lddz;
+} dc_tag_focal_desc;
+
+int dc_tag_focal_f32(const dc_tag_focal_desc* d, void* stream);
+
+/* Inference side of the same head: probs [M][ldp] = sigmoid(z) in float32 and scores [M] = the reference's classes_scores
+ * (model.py:644-646): the sum over the classes with p > min_confidence of log p -- decided on the float32 p that is written,
+ * log((double)p) accumulated in float64 in a fixed order and rounded once -- or (float)-3.4e38 when no class qualifies.
+ * One block per row; either output may be NULL; no alignment rule. */
+int dc_tag_scores_f32(const float* z, int ldz, int M, int C, float min_confidence, float* probs, int ldp, float* scores, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
