@@ -350,6 +350,16 @@ extern "C" size_t dc_conv2d_wgrad_workspace_bytes(const dc_conv_desc* d) {
     return t.split > 1 ? (size_t)t.split * d->Cout * d->kh * d->kw * d->Cin * sizeof(float) : 0;
 }
 
+extern "C" int dc_conv2d_wgrad_tile_config(const dc_conv_desc* d, int* bm, int* bn, int* split_k) {
+    int rc = wgrad_validate(d);
+    if (rc) return rc;
+    const TileChoice t = wgrad_tile(d);
+    if (bm) *bm = t.bm;
+    if (bn) *bn = t.bn;
+    if (split_k) *split_k = t.split;
+    return DC_OK;
+}
+
 extern "C" int dc_conv2d_wgrad_f32(const dc_conv_desc* d, void* workspace, size_t workspace_bytes, void* stream) {
     int rc = wgrad_validate(d);
     if (rc) return rc;

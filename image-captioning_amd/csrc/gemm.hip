@@ -72,6 +72,9 @@ static bool gemm_is_fast(const dc_gemm_desc* d) {
            (d->a_gather || a_span < lim) && b_span < lim;
 }
 
+// the tile / split rule of one launch: what gemm_run launches, dc_gemm_workspace_bytes sizes and dc_gemm_tile_config reports
+static TileChoice gemm_tile(const dc_gemm_desc* d) { return choose_tile(d->M, d->N, d->K, d->split_k, gemm_is_fast(d)); }
+
 static int gemm_validate(const dc_gemm_desc* d) {
     DC_REQUIRE(d != nullptr, DC_EINVAL, "dc_gemm_f32: null descriptor");
     DC_REQUIRE(d->M > 0 && d->N > 0 && d->K > 0, DC_EINVAL, "dc_gemm_f32: M,N,K must be positive (got %d,%d,%d)", d->M, d->N,
@@ -118,8 +121,20 @@ extern "C" size_t dc_gemm_workspace_bytes(const dc_gemm_desc* d) {
     if (!d || d->M <= 0 || d->N <= 0 || d->K <= 0) return 0;
     dc_gemm_desc bulk, tail;
     if (gemm_split_tail(d, &bulk, &tail)) d = &bulk;
-    const TileChoice t = choose_tile(d->M, d->N, d->K, d->split_k, gemm_is_fast(d));
+    const TileChoice t = gemm_tile(d);
     return t.split > 1 ? (size_t)t.split * d->M * d->N * sizeof(float) : 0;
+}
+
+extern "C" int dc_gemm_tile_config(const dc_gemm_desc* d, int* bm, int* bn, int* split_k) {
+    int rc = gemm_validate(d);
+    if (rc) return rc;
+    dc_gemm_desc bulk, tail;
+    if (gemm_split_tail(d, &bulk, &tail)) d = &bulk;      // the range-checked tail launch always runs 64x64 unsplit
+    const TileChoice t = gemm_tile(d);
+    if (bm) *bm = t.bm;
+    if (bn) *bn = t.bn;
+    if (split_k) *split_k = t.split;
+    return DC_OK;
 }
 
 static int gemm_run(const dc_gemm_desc* d, void* workspace, size_t workspace_bytes, hipStream_t s);
@@ -138,7 +153,7 @@ extern "C" int dc_gemm_f32(const dc_gemm_desc* d, void* workspace, size_t worksp
 
 static int gemm_run(const dc_gemm_desc* d, void* workspace, size_t workspace_bytes, hipStream_t s) {
     const bool fast = gemm_is_fast(d);
-    const TileChoice t = choose_tile(d->M, d->N, d->K, d->split_k, fast);
+    const TileChoice t = gemm_tile(d);
     Epilogue ep{d->C, d->ldc, d->scale, d->shift, d->residual, d->ldr, d->residual ? (d->res_rows > 0 ? 3 : 1) : 0, d->res_rows, 0, d->relu, d->accumulate, 0};
     ep.vec4 = (d->N & 3) == 0 && (d->ldc & 3) == 0 && aligned16(d->C) && (!d->residual || ((d->ldr & 3) == 0 && aligned16(d->residual))) &&
               (!d->scale || aligned16(d->scale)) && (!d->shift || aligned16(d->shift));

@@ -122,6 +122,16 @@ def _tile_info(info, tile_fn, d):
         info["split_k"] = int(sk.value)
 
 
+def _tile_config_info(info, config_fn, d):
+    """info= of the fp32 wrappers (tests / benches): the block tile (bm, bn) and the split-K factor the library's own rule picks for the
+    problem `d` (dc_gemm_tile_config, dc_conv2d_tile_config, dc_conv2d_wgrad_tile_config: host-only queries, nothing is launched)."""
+    if info is not None:
+        bm, bn, sk = C.c_int(0), C.c_int(0), C.c_int(0)
+        check(config_fn(C.byref(d), C.byref(bm), C.byref(bn), C.byref(sk)), config_fn.__name__)
+        info["tile"] = (int(bm.value), int(bn.value))
+        info["split_k"] = int(sk.value)
+
+
 def _scale_shift(d, scale, shift):
     d.scale = None if scale is None else _chk(scale, name="scale").data_ptr()
     d.shift = None if shift is None else _chk(shift, name="shift").data_ptr()
@@ -160,8 +170,8 @@ def _gemm_epilogue(d, scale, shift, residual, res_rows, relu, accumulate, split_
 
 
 def gemm(A, B, out=None, a_trans=False, b_trans=False, gather=None, scale=None, shift=None,
-         residual=None, res_rows=0, relu=False, accumulate=False, split_k=0):
-    """out[M,N] = epilogue(op(A) @ op(B)); see dc_gemm_f32."""
+         residual=None, res_rows=0, relu=False, accumulate=False, split_k=0, info=None):
+    """out[M,N] = epilogue(op(A) @ op(B)); see dc_gemm_f32.  info: a dict that receives "tile" (bm, bn) and "split_k" of the launch."""
     lib = _lib.load()
     _chk(A, name="A"), _chk(B, name="B")
     M, N, K = _gemm_shape("gemm", A, B, a_trans, b_trans, gather)
@@ -174,6 +184,7 @@ def gemm(A, B, out=None, a_trans=False, b_trans=False, gather=None, scale=None, 
     _gemm_operands(d, M, N, K, A, B, a_trans, b_trans, gather)
     d.C, d.ldc = out.data_ptr(), out.stride(0)
     _gemm_epilogue(d, scale, shift, residual, res_rows, relu, accumulate, split_k)
+    _tile_config_info(info, lib.dc_gemm_tile_config, d)
     _launch_ws(lib.dc_gemm_workspace_bytes(C.byref(d)), A.device, lib.dc_gemm_f32, C.byref(d))
     return out
 
@@ -243,9 +254,10 @@ def _conv_geometry(d, x, Cout, kh, kw, stride, pad_t, pad_l, Ho, Wo):
 
 
 def conv2d(x, w_packed, kh, kw, stride, pad_t, pad_l, Ho, Wo, scale=None, shift=None, residual=None,
-           res_mode=0, relu=False, out=None, split_k=0, math=0, w_wino=None, w_wino_b3=None, _name_only=False):
+           res_mode=0, relu=False, out=None, split_k=0, math=0, w_wino=None, w_wino_b3=None, _name_only=False, info=None):
     """NHWC conv forward with fused epilogue; see dc_conv2d_nhwc_f32.  x [N,H,W,Cin] contiguous.  w_wino: winograd_pack(w_packed)
-    of a frozen 3x3 / stride 1 / pad 1 kernel -> the layer runs in the Winograd F(2x2, 3x3) form (fp32, math=0 only)."""
+    of a frozen 3x3 / stride 1 / pad 1 kernel -> the layer runs in the Winograd F(2x2, 3x3) form (fp32, math=0 only).
+    info: a dict that receives "tile" (bm, bn), "split_k" and "kernel" (dc_conv2d_kernel_name's answer) of the launch."""
     lib = _lib.load()
     _chk(x, name="x"), _chk(w_packed, name="w")
     N, H, W, Cin = x.shape
@@ -268,10 +280,13 @@ def conv2d(x, w_packed, kh, kw, stride, pad_t, pad_l, Ho, Wo, scale=None, shift=
         if not w_wino_b3.is_contiguous() or w_wino_b3.numel() != 48 * Cin * Cout:
             raise _lib.DcapError("conv2d: w_wino_b3 must be the contiguous winograd_pack_b3() of this layer's kernel (48*Cin*Cout bf16)")
         d.w_wino_b3 = _chk(w_wino_b3, torch.int16, "w_wino_b3").data_ptr()
-    if _name_only:
+    if _name_only or info is not None:
         buf = C.create_string_buffer(128)
         check(lib.dc_conv2d_kernel_name(C.byref(d), buf, 128), "dc_conv2d_kernel_name")
-        return buf.value.decode()
+        if _name_only:
+            return buf.value.decode()
+        info["kernel"] = buf.value.decode()
+    _tile_config_info(info, lib.dc_conv2d_tile_config, d)
     _launch_ws(lib.dc_conv2d_workspace_bytes(C.byref(d)), x.device, lib.dc_conv2d_nhwc_f32, C.byref(d))
     return out
 
@@ -382,8 +397,9 @@ def split_bf16x3(x, out=None):
     return out
 
 
-def conv2d_wgrad(x, dy, kh, kw, stride, pad_t, pad_l, out=None, split_k=0, accumulate=False):
-    """dw packed [Cout][kh*kw*Cin] = sum_pixels dy (x) im2col(x); x [N,H,W,Cin], dy [N,Ho,Wo,Cout] contiguous."""
+def conv2d_wgrad(x, dy, kh, kw, stride, pad_t, pad_l, out=None, split_k=0, accumulate=False, info=None):
+    """dw packed [Cout][kh*kw*Cin] = sum_pixels dy (x) im2col(x); x [N,H,W,Cin], dy [N,Ho,Wo,Cout] contiguous.
+    info: a dict that receives "tile" (bm, bn) and "split_k" of the launch."""
     lib = _lib.load()
     _chk(x, name="x"), _chk(dy, name="dy")
     N, H, W, Cin = x.shape
@@ -396,6 +412,7 @@ def conv2d_wgrad(x, dy, kh, kw, stride, pad_t, pad_l, out=None, split_k=0, accum
     _conv_geometry(d, x, Cout, kh, kw, stride, pad_t, pad_l, Ho, Wo)
     d.x, d.y, d.w, d.split_k = x.data_ptr(), dy.data_ptr(), _chk(out, name="dw").data_ptr(), int(split_k)
     d.accumulate = int(accumulate)
+    _tile_config_info(info, lib.dc_conv2d_wgrad_tile_config, d)
     _launch_ws(lib.dc_conv2d_wgrad_workspace_bytes(C.byref(d)), x.device, lib.dc_conv2d_wgrad_f32, C.byref(d))
     return out
 

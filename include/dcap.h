@@ -72,6 +72,12 @@ typedef struct {
 
 size_t dc_gemm_workspace_bytes(const dc_gemm_desc* d);
 int    dc_gemm_f32(const dc_gemm_desc* d, void* workspace, size_t workspace_bytes, void* stream);
+/* Test / profiling aid (host only, launches nothing): the block tile (bm x bn: 128 x 128, 128 x 64 or 64 x 64) and the split-K factor
+ * dc_gemm_f32 picks for `d`, from the rule the launch itself applies.  For a K that is not a multiple of 32 and is run as a bulk launch
+ * plus a range-checked tail launch, the answer is the bulk launch's (the tail accumulates onto it on 64 x 64 tiles, unsplit).
+ * *split_k is the factor the rule hands to the launch, which then cuts K into slices of whole 32-deep K-tiles: 28 asked of 256 K-tiles
+ * run as 26 slices (25 of 10 K-tiles, one of 6).  dc_conv2d_tile_config and dc_conv2d_wgrad_tile_config report it the same way. */
+int    dc_gemm_tile_config(const dc_gemm_desc* d, int* bm, int* bn, int* split_k);
 
 /* ------------------------------------------------------------------------------------------------
  * GEMM with bf16 operands (bit patterns in uint16_t), fp32 accumulate on the bf16 matrix pipe -- the arithmetic BASELINE
@@ -278,6 +284,9 @@ int    dc_get_persistent_cus(void);
  * ------------------------------------------------------------------------------------------------ */
 size_t dc_conv2d_wgrad_workspace_bytes(const dc_conv_desc* d);
 int    dc_conv2d_wgrad_f32(const dc_conv_desc* d, void* workspace, size_t workspace_bytes, void* stream);
+/* Test / profiling aid (host only, launches nothing): the block tile (bm x bn over Cout x kh*kw*Cin) and the split-K factor (over the
+ * N*Ho*Wo pixels) dc_conv2d_wgrad_f32 picks for `d`, from the rule the launch itself applies. */
+int    dc_conv2d_wgrad_tile_config(const dc_conv_desc* d, int* bm, int* bn, int* split_k);
 
 /* KL.MaxPooling2D((3,3), strides 2, 'same') (dense_model.py:150); C % 4 == 0. */
 int dc_maxpool3x3s2_same_f32(const float* x, float* y, int N, int H, int W, int C, void* stream);
