@@ -104,7 +104,7 @@ __global__ __launch_bounds__(256) void lstm_pack_urec_kernel(const float* __rest
 
 // RT = 32-row MFMA blocks per workgroup, NW = waves that split K = U.  The gate phase's operands (zx, h, c of the block's own
 // (row, unit) items) are requested before the K loop, so their latency hides behind it.  LDS: NW/2 partial tiles (waves
-// NW/2.. publish, waves 0..NW/2-1 add theirs on top): 16.9 KB at <1,8> and <2,4> -- in the training pipeline this kernel runs
+// NW/2.. publish, waves 0..NW/2-1 add theirs on top): 16.9 KB at <2,4> (and at <1,8>, which no (B, U) selects: not instantiated) -- in the training pipeline this kernel runs
 // beside the encoder's convolutions, whose two resident blocks leave ~19 KB of a CU's LDS; with 33.8 KB its blocks could only
 // start at conv-kernel boundaries (78-100 us per step in the pipeline against 18 us alone).
 // (The recurrent-dropout variant of the step is lstm_step_masked_kernel below.)
@@ -553,17 +553,42 @@ static dc_gemm_desc dU_desc(int B, int T, int U, const float* h_seq, const float
     return g;
 }
 
+// Which instance of the three step kernels runs a (B, U) problem: rows = batch rows per block, waves = waves per block; rows == 0: the
+// step is not fused at this U (split-K GEMM + gate kernel, with masks the per-gate GEMMs).  The launches below take their template
+// arguments and grids from these helpers and dc_lstm_step_tile_config reports them, so a test sees what the library really runs.
+struct StepTile { int rows, waves; };
+
+// lstm_step_fused_kernel<rows / 32, waves> (U % 32 == 0)
+static StepTile fwd_step_tile(int B, int U) {
+    if ((U & 31) != 0) return {0, 0};
+    const int frt = ((U / 8) * ((B + 31) / 32) <= 2 * kNumCU) ? 1 : 2;      // 32- or 64-row blocks (measured again in round 5 at 200 x 512: 12.3 vs 13.2 us)
+    const int fnw = (frt == 2 && (U & 63) == 0) ? 8 : 4;                     // measured: 4 waves at 32 rows, 8 at 64
+    return {32 * frt, fnw};
+}
+
+// lstm_step_masked_kernel<rows / 16> (U % 32 == 0): always 8 waves (4 gates x 2 halves of K)
+static StepTile fwd_masked_step_tile(int B, int U) {
+    if ((U & 31) != 0) return {0, 0};
+    const bool two = (U / 16) * ((B + 15) / 16) > kNumCU;                    // 32-row blocks once 16-row blocks no longer fit the chip at once (measured: B = 200)
+    return {two ? 32 : 16, 8};
+}
+
+// lstm_bwd_step_fused_kernel<rows / 16, waves> (U % 16 == 0), with or without rec_masks
+static StepTile bwd_step_tile(int B, int U) {
+    if ((U & 15) != 0) return {0, 0};
+    const int rows = ((U / 16) * ((B + 15) / 16) <= kNumCU) ? 16 : 32;       // measured: 200 x 512 is 1.2x faster with 32-row blocks
+    return {rows, (U & 31) == 0 ? 8 : 4};
+}
+
 // One fused forward timestep (U % 32 == 0, h_prev / c_prev given), the block shape chosen from (B, U) alone: dc_lstm_seq_fwd_f32 and
 // dc_lstm_step_f32 run the same kernel instance at the same batch, so a decode step by step reproduces the sequence bit for bit.
 static int launch_fused_fwd_step(float* z_t, const float* Upk, const float* hp, const float* cp, const uint8_t* mk, float* h_t, float* c_t,
                                  int B, int U, hipStream_t s) {
-    const int frt = ((U / 8) * ((B + 31) / 32) <= 2 * kNumCU) ? 1 : 2;      // 32- or 64-row blocks (measured again in round 5 at 200 x 512: 12.3 vs 13.2 us)
-    const int fnw = (frt == 2 && (U & 63) == 0) ? 8 : 4;                     // measured: 4 waves at 32 rows, 8 at 64
-    const dim3 grid(U / 8, (B + 32 * frt - 1) / (32 * frt));
+    const StepTile tile = fwd_step_tile(B, U);
+    const dim3 grid(U / 8, (B + tile.rows - 1) / tile.rows);
 #define LAUNCH_FWD_STEP(RT_, NW_) hipLaunchKernelGGL((lstm_step_fused_kernel<RT_, NW_>), grid, dim3(NW_ * 64), 0, s, z_t, Upk, hp, cp, mk, h_t, c_t, B, U)
-    if (frt == 1 && fnw == 8) LAUNCH_FWD_STEP(1, 8);
-    else if (frt == 1) LAUNCH_FWD_STEP(1, 4);
-    else if (fnw == 8) LAUNCH_FWD_STEP(2, 8);
+    if (tile.rows == 32) LAUNCH_FWD_STEP(1, 4);          // (8 waves only ever come with 64 rows)
+    else if (tile.waves == 8) LAUNCH_FWD_STEP(2, 8);
     else LAUNCH_FWD_STEP(2, 4);
 #undef LAUNCH_FWD_STEP
     return check_launch("lstm_step_fused_kernel");
@@ -648,9 +673,9 @@ extern "C" int dc_lstm_seq_fwd_f32(const dc_lstm_fwd_desc* d, void* workspace, s
             float* h_t = d->h_seq + (long)t * n;
             float* c_t = d->c_seq + (long)t * n;
             if (d->rec_masks) {                        // recurrent dropout: one wave per gate, masks applied to the A fragments (lstm_step_masked_kernel)
-                const bool two = (U / 16) * ((B + 15) / 16) > kNumCU;              // 32-row blocks once 16-row blocks no longer fit the chip at once (measured: B = 200)
-                const dim3 gridm(U / 16, (B + (two ? 31 : 15)) / (two ? 32 : 16));
-                if (two) hipLaunchKernelGGL((lstm_step_masked_kernel<2>), gridm, dim3(512), 0, s, z_t, Upk, hp, cp, mk, h_t, c_t, B, U, d->rec_masks);
+                const StepTile tile = fwd_masked_step_tile(B, U);
+                const dim3 gridm(U / 16, (B + tile.rows - 1) / tile.rows);
+                if (tile.rows == 32) hipLaunchKernelGGL((lstm_step_masked_kernel<2>), gridm, dim3(512), 0, s, z_t, Upk, hp, cp, mk, h_t, c_t, B, U, d->rec_masks);
                 else hipLaunchKernelGGL((lstm_step_masked_kernel<1>), gridm, dim3(512), 0, s, z_t, Upk, hp, cp, mk, h_t, c_t, B, U, d->rec_masks);
                 int rc = check_launch("lstm_step_masked_kernel");
                 if (rc) return rc;
@@ -716,8 +741,8 @@ extern "C" int dc_lstm_seq_bwd_f32(const dc_lstm_bwd_desc* d, void* workspace, s
     int zrc = zero_fill_async(wsp, 2 * state_bytes, s);
     if (zrc) return zrc;
     const bool fused = (U & 15) == 0;
-    int rt_rows = ((U / 16) * ((B + 15) / 16) <= kNumCU) ? 16 : 32;      // measured: 200 x 512 is 1.2x faster with 32-row blocks
-    int nw = (U & 31) == 0 ? 8 : 4;
+    const StepTile tile = bwd_step_tile(B, U);
+    const int rt_rows = tile.rows, nw = tile.waves;
     for (int t = T - 1; t >= 0; --t) {
         const float* z_t = d->z + (long)t * B * 4 * U;
         float* dz_t = d->dz + (long)t * B * 4 * U;
@@ -787,6 +812,17 @@ extern "C" int dc_lstm_seq_bwd_f32(const dc_lstm_bwd_desc* d, void* workspace, s
         zrc = zero_fill_async(d->dU_rec, (size_t)U * 4 * U * sizeof(float), s);
         if (zrc) return zrc;
     }
+    return DC_OK;
+}
+
+// Host-only: the block (batch rows, waves) of the fused step kernel that runs a (B, U) problem; rows = waves = 0 where the step is not fused.
+extern "C" int dc_lstm_step_tile_config(int B, int U, int direction, int rec_masks, int* rows, int* waves) {
+    DC_REQUIRE(rows && waves, DC_EINVAL, "dc_lstm_step_tile_config: null pointer");
+    DC_REQUIRE(B > 0 && U > 0 && (U & 3) == 0, DC_EINVAL, "dc_lstm_step_tile_config: bad B/U (U %% 4 == 0)");
+    DC_REQUIRE(direction == 0 || direction == 1, DC_EINVAL, "dc_lstm_step_tile_config: direction is 0 (forward) or 1 (backward)");
+    const StepTile t = direction ? bwd_step_tile(B, U) : rec_masks ? fwd_masked_step_tile(B, U) : fwd_step_tile(B, U);
+    *rows = t.rows;
+    *waves = t.waves;
     return DC_OK;
 }
 

@@ -893,9 +893,20 @@ def _rec_masks(rec_masks, B, U):
     return rec_masks.data_ptr()
 
 
-def lstm_seq_fwd(z, U_rec, mask, B, T, h_seq=None, c_seq=None, rec_masks=None):
+def _lstm_step_info(info, B, U, direction, rec_masks):
+    """info= of the LSTM wrappers (tests / benches): the block of the fused step kernel the library's own rule picks for (B, U) --
+    "rows" batch rows and "waves" waves per block, both 0 where the step is not fused (dc_lstm_step_tile_config: a host-only query)."""
+    if info is not None:
+        rows, waves = C.c_int(0), C.c_int(0)
+        check(_lib.load().dc_lstm_step_tile_config(B, U, direction, int(rec_masks), C.byref(rows), C.byref(waves)), "dc_lstm_step_tile_config")
+        info["rows"] = int(rows.value)
+        info["waves"] = int(waves.value)
+
+
+def lstm_seq_fwd(z, U_rec, mask, B, T, h_seq=None, c_seq=None, rec_masks=None, info=None):
     """z [T*B,4U] (x-projection + bias, overwritten with the full pre-activation) -> h_seq, c_seq [T*B,U].
-    rec_masks [4,B,U]: Keras recurrent_dropout masks (training phase); None = no dropout."""
+    rec_masks [4,B,U]: Keras recurrent_dropout masks (training phase); None = no dropout.
+    info: a dict that receives "rows" and "waves" of the fused step's block (0, 0: not fused at this U)."""
     lib = _lib.load()
     U = U_rec.shape[0]
     _chk(z, name="z"), _chk(U_rec, name="U_rec")
@@ -911,6 +922,7 @@ def lstm_seq_fwd(z, U_rec, mask, B, T, h_seq=None, c_seq=None, rec_masks=None):
     d.mask = None if mask is None else _chk(mask, torch.uint8, "mask").data_ptr()
     d.h_seq, d.c_seq = h_seq.data_ptr(), c_seq.data_ptr()
     d.rec_masks = _rec_masks(rec_masks, B, U)
+    _lstm_step_info(info, B, U, 0, rec_masks is not None)
     _launch_ws(lib.dc_lstm_seq_workspace_bytes(B, T, U), z.device, lib.dc_lstm_seq_fwd_f32, C.byref(d))
     return h_seq, c_seq
 
@@ -931,10 +943,11 @@ def lstm_pack_urec(U_rec, out=None):
     return out
 
 
-def lstm_step(z, U_rec, h_prev=None, c_prev=None, mask=None, h=None, c=None, U_packed=None):
+def lstm_step(z, U_rec, h_prev=None, c_prev=None, mask=None, h=None, c=None, U_packed=None, info=None):
     """ONE LSTM timestep with carried state (dc_lstm_step_f32): z [B,4U] (x-projection + bias, overwritten with the full pre-activation),
     h_prev / c_prev [B,U] (None: zeros), mask uint8 [B] (None: every row live; rows with 0 copy h_prev / c_prev) -> h, c [B,U].
-    U_packed: lstm_pack_urec(U_rec) (None: repacked on every call when U % 32 == 0)."""
+    U_packed: lstm_pack_urec(U_rec) (None: repacked on every call when U % 32 == 0).
+    info: a dict that receives "rows" and "waves" of the fused step's block, as lstm_seq_fwd's does at the same B."""
     _chk(z, name="z"), _chk(U_rec, name="U_rec")
     lib = _lib.load()
     U = U_rec.shape[0]
@@ -959,11 +972,13 @@ def lstm_step(z, U_rec, h_prev=None, c_prev=None, mask=None, h=None, c=None, U_p
     d.z, d.U_rec, d.U_packed = z.data_ptr(), U_rec.data_ptr(), _ptr(U_packed)
     d.h_prev, d.c_prev, d.mask = _ptr(h_prev), _ptr(c_prev), _ptr(mask)
     d.h, d.c = h.data_ptr(), c.data_ptr()
+    _lstm_step_info(info, B, U, 0, False)
     _launch_ws(lib.dc_lstm_step_workspace_bytes(B, U), z.device, lib.dc_lstm_step_f32, C.byref(d))
     return h, c
 
 
-def lstm_seq_bwd(z, U_rec, mask, h_seq, c_seq, B, T, dh_seq=None, dh_last=None, dz=None, dU=None, accumulate_dU=False, rec_masks=None):
+def lstm_seq_bwd(z, U_rec, mask, h_seq, c_seq, B, T, dh_seq=None, dh_last=None, dz=None, dU=None, accumulate_dU=False, rec_masks=None, info=None):
+    """info: a dict that receives "rows" and "waves" of the fused backward step's block (0, 0: not fused at this U)."""
     lib = _lib.load()
     U = U_rec.shape[0]
     if dz is None:
@@ -984,6 +999,7 @@ def lstm_seq_bwd(z, U_rec, mask, h_seq, c_seq, B, T, dh_seq=None, dh_last=None, 
     d.dh_last = None if dh_last is None else dh_last.data_ptr()
     d.dz, d.dU_rec, d.accumulate_dU = dz.data_ptr(), (None if dU is None else _chk(dU, name="dU").data_ptr()), int(accumulate_dU)
     d.rec_masks = _rec_masks(rec_masks, B, U)
+    _lstm_step_info(info, B, U, 1, rec_masks is not None)
     _launch_ws(lib.dc_lstm_seq_workspace_bytes(B, T, U), z.device, lib.dc_lstm_seq_bwd_f32, C.byref(d))
     return dz, dU
 

@@ -561,6 +561,13 @@ typedef struct {
 
 int dc_lstm_seq_bwd_f32(const dc_lstm_bwd_desc* d, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Host-only (nothing is launched): which instance of the fused step kernels runs a (B, U) problem -- direction 0: the forward step of
+ * dc_lstm_seq_fwd_f32 / dc_lstm_step_f32 (rec_masks != 0: the recurrent-dropout step), 1: the backward step of dc_lstm_seq_bwd_f32 (one
+ * rule with and without masks).  rows = batch rows per block, waves = waves per block, from the helpers the launches themselves call;
+ * rows = waves = 0 where the step is not fused (U % 32 != 0 forward, U % 16 != 0 backward).  DC_EINVAL: B <= 0, U <= 0, U % 4 != 0, a
+ * direction other than 0 / 1, a null rows / waves. */
+int dc_lstm_step_tile_config(int B, int U, int direction, int rec_masks, int* rows, int* waves);
+
 /* ------------------------------------------------------------------------------------------------
  * ONE timestep of the recurrence above with carried state: incremental greedy decoding feeds one token per call instead of
  * re-running the whole zero-padded prefix (ROICaptionInferenceLayer, text_generation_model.py:192-232; dense_img_cap/dense_model.py:820).

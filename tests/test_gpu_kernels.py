@@ -1,6 +1,6 @@
 """Kernel-level parity: the C-ABI entry points against the NumPy oracle on seeded inputs (-m gpu).  The ones that are not here --
 pooling backward, BatchNorm + ReLU, ReLU backward, time folding, row gathers, the elementwise helpers, zero fill, image molding, the bf16
-casts -- are in test_gpu_kernel_edges.py; test_kernel_coverage.py checks that every launching entry point is called by a GPU test file.
+casts -- are in test_gpu_kernel_edges.py; every instantiation of the fused LSTM step kernels is in test_gpu_lstm_steps.py; test_kernel_coverage.py checks that every launching entry point is called by a GPU test file.
 Tolerances: fp32 MFMA accumulation vs float64 oracle => 2e-5 of the output scale unless stated
 (index outputs -- argmax, pyramid levels -- are bit-exact)."""
 import os
