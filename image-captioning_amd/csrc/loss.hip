@@ -709,9 +709,38 @@ __global__ __launch_bounds__(256) void tag_scores_kernel(const float* __restrict
     if (tid == 0) scores[row] = any ? (float)((red[0] + red[1]) + (red[2] + red[3])) : -3.4e38f;
 }
 
+// dc_embedding_grad_f32: the gradient of a trainable KL.Embedding -- demb[v] = sum of the rows m of dx with ids[m] == v, added in
+// ascending m (one fixed order: bit-reproducible, no float atomics), zeros for a word the batch does not hold, so EVERY row of demb is
+// written and the gradient bucket needs no clearing.  One block per word, a wave per 64 columns: the lanes test 64 ids at a time, the
+// hits are visited in ascending order (wave-uniform), each adding its dx row's piece.
+__global__ __launch_bounds__(256) void embedding_grad_kernel(const float* dx, int ld, const int32_t* ids, int n, float* demb, int ld_e, int W) {
+    const int v = blockIdx.x, lane = threadIdx.x & 63;
+    const int col = (blockIdx.y * 4 + (threadIdx.x >> 6)) * 64 + lane;
+    if (col - lane >= W) return;                       // (wave-uniform: the whole wave lies past the last column)
+    float acc = 0.f;
+    for (int m0 = 0; m0 < n; m0 += 64) {
+        const int m = m0 + lane;
+        unsigned long long hits = __ballot(m < n && ids[m] == v);
+        while (hits) {
+            const int j = __ffsll((long long)hits) - 1;
+            hits &= hits - 1;
+            if (col < W) acc += dx[(long)(m0 + j) * ld + col];
+        }
+    }
+    if (col < W) demb[(long)v * ld_e + col] = acc;
+}
+
 }  // namespace dcap
 
 using namespace dcap;
+
+extern "C" int dc_embedding_grad_f32(const float* dx, int ld, const int32_t* ids, int n, float* demb, int ld_e, int V, int W, void* stream) {
+    DC_REQUIRE(dx && ids && demb, DC_EINVAL, "dc_embedding_grad: null pointer");
+    DC_REQUIRE(n > 0 && V > 0 && W > 0 && ld >= W && ld_e >= W && (W + 255) / 256 <= 65535, DC_EINVAL, "dc_embedding_grad: bad n/V/W/ld");
+    hipLaunchKernelGGL(embedding_grad_kernel, dim3((unsigned)V, (unsigned)((W + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), dx, ld, ids, n,
+                       demb, ld_e, W);
+    return check_launch("embedding_grad_kernel");
+}
 
 extern "C" int dc_softmax_ce_f32(const dc_softmax_ce_desc* d, void* stream) {
     DC_REQUIRE(d && d->logits && d->M > 0 && d->V > 0 && d->ld >= d->V, DC_EINVAL, "dc_softmax_ce: bad arguments");

@@ -309,9 +309,81 @@ __global__ __launch_bounds__(RG_THREADS) void roi_tile_groups_kernel(RoiGroupsAr
     if (tid == 0) a.lat_count[0] = listed;
 }
 
+// ------------------------------------------------------------------------------------------------------------------------
+// dc_row_mean_f32: out[b][c] = (((x[b][0][c] + x[b][1][c]) + x[b][2][c]) + ...) / K -- the image-level feature vector, the mean of the
+// RoIAlign block over its RoIs, in the order np.mean(float32[K, ...], axis=0) adds: sequentially over k, then ONE correctly rounded
+// division.  Only the columns are parallel (12 544 of them, 1000 dependent adds each), so a block owns RM_COLS = 64 columns (196 blocks
+// at C = 12 544: one per CU on most of the chip) and separates the two jobs: all four waves LOAD -- 16 lanes x float4 cover the block's
+// 256-byte piece of a row, a wave instruction fetches four rows, the block RM_ROWS = 128 rows (32 KiB) per tile, every load of a tile
+// issued before the first is waited for -- and stage the tile in LDS; wave 0 then ADDS, lane = column, row after row out of LDS, while
+// the loads of the next tile are already in flight (two LDS tiles, one barrier per tile).  VEC: the float4 loads, where x, ld and the
+// batch stride keep every quad on a 16-byte boundary; otherwise (and for a quad that crosses C) the same walk with four guarded scalar
+// loads per lane.  Rows past K are staged as zeros and never added.
+// ------------------------------------------------------------------------------------------------------------------------
+constexpr int RM_COLS = 64, RM_ROWS = 128, RM_THREADS = 256, RM_LOADS = RM_ROWS * (RM_COLS / 4) / RM_THREADS;      // 8 quads per lane and tile
+
+template <bool VEC>
+__device__ __forceinline__ void row_mean_load(const float* xb, long ld, int K, int C, int t0, int c, int r0, float4 (&v)[RM_LOADS]) {
+#pragma unroll
+    for (int j = 0; j < RM_LOADS; ++j) {
+        const int row = t0 + r0 + 16 * j;
+        v[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (row >= K || c >= C) continue;
+        const float* p = xb + (long)row * ld + c;
+        if (VEC && c + 3 < C) {
+            v[j] = *reinterpret_cast<const float4*>(p);
+        } else {
+            v[j].x = p[0];
+            if (c + 1 < C) v[j].y = p[1];
+            if (c + 2 < C) v[j].z = p[2];
+            if (c + 3 < C) v[j].w = p[3];
+        }
+    }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(RM_THREADS) void row_mean_kernel(const float* x, int K, int C, long ld, long batch_stride, float* out, long ld_out) {
+    __shared__ float4 tile[2][RM_ROWS][RM_COLS / 4];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int c0 = blockIdx.x * RM_COLS;
+    const float* xb = x + (long)blockIdx.y * batch_stride;
+    const int r0 = wave * 4 + (lane >> 4), q = lane & 15;      // this lane's row within a round of 16, its quad of columns
+    const int c = c0 + 4 * q;
+    float4 v[RM_LOADS];
+    row_mean_load<VEC>(xb, ld, K, C, 0, c, r0, v);
+    float acc = 0.f;
+    int buf = 0;
+    for (int t0 = 0; t0 < K; t0 += RM_ROWS, buf ^= 1) {
+#pragma unroll
+        for (int j = 0; j < RM_LOADS; ++j) tile[buf][r0 + 16 * j][q] = v[j];
+        __syncthreads();                                         // the tile is whole; wave 0 is done with the other one
+        if (t0 + RM_ROWS < K) row_mean_load<VEC>(xb, ld, K, C, t0 + RM_ROWS, c, r0, v);
+        if (wave == 0) {
+            const float* col = reinterpret_cast<const float*>(&tile[buf][0][0]) + lane;
+            const int rows = min(RM_ROWS, K - t0);
+#pragma unroll 8
+            for (int r = 0; r < rows; ++r) acc = add_rn(acc, col[r * RM_COLS]);
+        }
+    }
+    if (wave == 0 && c0 + lane < C) out[(long)blockIdx.y * ld_out + c0 + lane] = div_rn(acc, (float)K);
+}
+
 }  // namespace dcap
 
 using namespace dcap;
+
+extern "C" int dc_row_mean_f32(const float* x, int B, int K, int C, long ld, long batch_stride, float* out, long ld_out, void* stream) {
+    DC_REQUIRE(x && out, DC_EINVAL, "dc_row_mean: null pointer");
+    DC_REQUIRE(B > 0 && B <= 65535 && K > 0 && K < (1 << 24) && C > 0, DC_EINVAL, "dc_row_mean: bad B/K/C (1 <= B <= 65535, 1 <= K < 2^24, C >= 1)");
+    DC_REQUIRE(ld >= C && ld_out >= C && (B == 1 || batch_stride >= 0), DC_EINVAL, "dc_row_mean: a row stride below C or a negative batch stride");
+    const dim3 grid((unsigned)((C + RM_COLS - 1) / RM_COLS), (unsigned)B);
+    const bool vec = aligned16(x) && ld % 4 == 0 && (B == 1 || batch_stride % 4 == 0);
+    if (vec)
+        hipLaunchKernelGGL(row_mean_kernel<true>, grid, dim3(RM_THREADS), 0, static_cast<hipStream_t>(stream), x, K, C, ld, batch_stride, out, ld_out);
+    else
+        hipLaunchKernelGGL(row_mean_kernel<false>, grid, dim3(RM_THREADS), 0, static_cast<hipStream_t>(stream), x, K, C, ld, batch_stride, out, ld_out);
+    return check_launch("row_mean_kernel");
+}
 
 static int roi_tile_groups_launch(const dc_roi_groups_desc* d, int32_t* lat_list, int32_t* lat_count, void* stream) {
     DC_REQUIRE(d && d->boxes && d->marks && d->counts, DC_EINVAL, "dc_roi_tile_groups: null pointer");

@@ -1,6 +1,7 @@
 """Image-level features of the reference's feature_generation/ package
 (feature_generation/generate_roi_features.py:60-75): ResNet-101 + FPN + RPN + ProposalLayer, PyramidROIAlign on
 the POST_NMS_ROIS_INFERENCE proposals, mean over RoIs, flattened to 12 544 floats."""
+import inspect
 import os
 
 import numpy as np
@@ -31,9 +32,17 @@ def load_model(weights=None, model_path=None, **kw):
     return model
 
 
-def generate_features(image, model, mold="host"):
+def generate_features(image, model, mold="host", device_features=False):
     """image: [H,W,3] uint8 array (the reference reads a JPEG path with skimage, which is absent here).
-    mold='device': the image is resized on the GPU (DenseImageCapRCNN.generate_captions), the same features bit for bit."""
+    mold='device': the image is resized on the GPU (DenseImageCapRCNN.generate_captions), the same features bit for bit.
+    device_features=True: the same 12 544 floats as a float32 DEVICE tensor, reduced on the GPU (generate_captions(image_level=True),
+    ops.row_mean: NumPy's summation order, the same bits) -- the [1000,7,7,256] block (50 MB) is not copied to the host to hand
+    back 50 KB.  The feature model must take image_level= (ValueError otherwise: there is no host detour behind this switch)."""
     kw = {"mold": utils.check_mold(mold)} if mold != "host" else {}      # (feature models with the reference's plain signature keep working)
+    if device_features:
+        if "image_level" not in inspect.signature(model.generate_captions).parameters:
+            raise ValueError("device_features=True needs a feature model whose generate_captions takes image_level= "
+                             "(DenseImageCapRCNN); %s has none: use the default host path" % type(model).__name__)
+        return model.generate_captions([np.asarray(image)], verbose=0, image_level=True, **kw)[0]['image_features']
     results = model.generate_captions([np.asarray(image)], verbose=0, **kw)
     return np.mean(results[0]['features'], axis=0).flatten()

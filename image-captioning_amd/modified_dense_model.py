@@ -11,7 +11,7 @@ is a SURVEY.md section 8(f) "next" row and raises NotImplementedError.
 import numpy as np
 import torch
 
-from . import utils
+from . import ops, utils
 from .encoder import EncoderPlan
 from .layers import resnet_fpn_convs
 
@@ -147,7 +147,7 @@ class DenseImageCapRCNN(object):
             windows.append(window)
         return np.stack(molded), np.stack(metas), np.stack(windows)
 
-    def generate_captions(self, images, rois=None, verbose=0, device_features=False, mold="host"):
+    def generate_captions(self, images, rois=None, verbose=0, device_features=False, mold="host", image_level=False):
         """images: list of [H,W,3] uint8; rois: [len(images), N, 4] (y1,x1,y2,x2) pixels.
         Returns [{'features': float32 [N,7,7,256]}] like the reference (whose slice
         features[i][1000*i:1000*(i+1)] only works for BATCH_SIZE == 1; image i > 0 gets its own RoIs here).
@@ -155,7 +155,10 @@ class DenseImageCapRCNN(object):
         feeds them back to the decoder then never moves [N,7,7,256] floats through host memory.
         mold='host' (default): mold_inputs -- utils.resize_image on the host, the molded batch uploaded.  'device' (uint8 [h,w,3]
         images, IMAGE_PADDING on): the raw images are uploaded and resampled into the plan's image buffer with PIL's integer
-        arithmetic (EncoderPlan.mold_images): the same bytes, so the same features bit for bit."""
+        arithmetic (EncoderPlan.mold_images): the same bytes, so the same features bit for bit.
+        image_level=True: returns [{'image_features': float32 device tensor [7*7*256]}] instead -- per image the mean of its RoI
+        features over the RoIs (ops.row_mean: np.mean(features, axis=0).flatten() bit for bit), one launch for the batch; the
+        [N,7,7,256] block itself never leaves the GPU."""
         utils.check_mold(mold)
         if mold == "device":
             images = [utils.check_device_mold_image(im) for im in images]
@@ -170,8 +173,11 @@ class DenseImageCapRCNN(object):
         else:
             molded, metas, windows = self.mold_inputs(images)
             feats = self.extract_features(molded, rois, sparse=True)      # (only the features leave this call: nothing reads the maps whole)
-        feats = feats.clone() if device_features else feats.cpu().numpy()
         n = self.config.POST_NMS_ROIS_INFERENCE
+        if image_level:
+            vecs = ops.row_mean(feats.reshape(feats.shape[0], feats.shape[1], -1)[:, :n])      # (a view: rows and blocks keep their strides)
+            return [{"image_features": vecs[i]} for i in range(len(images))]
+        feats = feats.clone() if device_features else feats.cpu().numpy()
         results = [{"features": feats[i][:n]} for i in range(len(images))]
         if self.use_generated_rois:
             # evaluate_models/modified_dense_model.py:1922-1929: the evaluation's copy also hands back the proposals the features were

@@ -1644,6 +1644,39 @@ def fold_time(x, T, B, out):
     return out
 
 
+def embedding_grad(dx, ids, out):
+    """out[v] = the sum, in ascending m, of the rows dx[m] with ids[m] == v (dc_embedding_grad_f32): the gradient of a trainable embedding
+    table out [V,W] from d(embedded tokens) dx [n,W] and the int32 ids [n].  Every row of out is written (zeros for absent words)."""
+    lib = _lib.load()
+    _chk(dx, name="dx"), _chk(out, name="out"), _chk(ids, torch.int32, "ids")
+    if dx.dim() != 2 or out.dim() != 2 or dx.shape[1] != out.shape[1] or ids.numel() != dx.shape[0] or not ids.is_contiguous():
+        raise _lib.DcapError("embedding_grad: dx [n,W], contiguous ids [n], out [V,W]; got %s, %s, %s" % (tuple(dx.shape), tuple(ids.shape), tuple(out.shape)))
+    n, W = dx.shape
+    check(lib.dc_embedding_grad_f32(_ptr(dx), dx.stride(0) if n > 1 else W, _ptr(ids), n, _ptr(out), out.stride(0) if out.shape[0] > 1 else W,
+                                    out.shape[0], W, _stream()), "dc_embedding_grad_f32")
+    return out
+
+
+def row_mean(x, out=None):
+    """np.mean(x, axis=0) of a float32 x [K,C] -> out [C], or of every block of x [B,K,C] -> out [B,C] in the same launch, bit for bit
+    (dc_row_mean_f32: the additions sequential over k, one correctly rounded division).  Rows and blocks may have any stride and the
+    base any alignment; out (allocated when None) needs unit stride along C.  K = 0 or C = 0 is the library's DC_EINVAL."""
+    lib = _lib.load()
+    if _chk(x, name="x").dim() not in (2, 3):
+        raise _lib.DcapError("row_mean: x must be a float32 [K,C] or [B,K,C] tensor, got %s" % (tuple(x.shape),))
+    B, (K, Cn) = (x.shape[0] if x.dim() == 3 else 1), x.shape[-2:]
+    shape = (B, Cn) if x.dim() == 3 else (Cn,)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    if tuple(_chk(out, name="out").shape) != shape or out.device != x.device:
+        raise _lib.DcapError("row_mean: out must be a float32 %s tensor on x's device" % (shape,))
+    ld = x.stride(-2) if K > 1 else max(Cn, 1)
+    bs = x.stride(0) if x.dim() == 3 and B > 1 else 0
+    ld_out = out.stride(0) if x.dim() == 3 and B > 1 else max(Cn, 1)
+    check(lib.dc_row_mean_f32(_ptr(x), B, K, Cn, ld, bs, _ptr(out), ld_out, _stream()), "dc_row_mean_f32")
+    return out
+
+
 def colsum(x, out=None, accumulate=False):
     lib = _lib.load()
     _chk(x, name="x")

@@ -134,6 +134,26 @@ def v1_weights(seed, vocab, emb_dim=300, units=512, feat_dim=1024):
     return W
 
 
+def embedding_uniform(rng, vocab, dim):
+    """keras.layers.Embedding's default initialiser: RandomUniform(-0.05, 0.05)."""
+    return rng.uniform(-0.05, 0.05, (vocab, dim)).astype(F32)
+
+
+def whole_image_weights(seed, vocab, embedding_dim=128, input_dim=12544, word_dim=256, language_units=256, merged_units=1000):
+    """The whole-image captioner (image captioning/model.py:7-91) under the reference's layer names with Keras 2.1's default
+    initialisers: glorot-uniform kernels, orthogonal recurrent kernels, zero biases with unit_forget_bias, uniform(-0.05, 0.05)
+    embeddings.  In Keras' own shapes (no padding); insertion order = the order of Keras' model.weights."""
+    rng = np.random.default_rng(seed)
+    W = {}
+    W["language_model_embedding/embeddings"] = embedding_uniform(rng, vocab, word_dim)
+    dense_weights(rng, "image_model_fc", input_dim, embedding_dim, W)
+    lstm_weights(rng, "language_model_lstm", word_dim, language_units, W)
+    dense_weights(rng, "language_model_td", language_units, embedding_dim, W)
+    lstm_weights(rng, "merged_model_lstm", 2 * embedding_dim, merged_units, W)
+    dense_weights(rng, "merged_model_softmax", merged_units, vocab, W)
+    return W
+
+
 def images(seed, n, h=1024, w=1024):
     return np.random.default_rng(seed).integers(0, 256, (n, h, w, 3), dtype=np.uint8)
 

@@ -1024,6 +1024,22 @@ int dc_relu_bwd_dual_f32(const float* dy, const float* y, float* out, uint16_t* 
  * over timesteps -- RepeatVector(feature), text_generation_model.py:146). */
 int dc_fold_time_f32(const float* x, int T, int B, int N, int ld, float* out, int ld_out, void* stream);
 
+/* demb[v][w] = sum over the rows m (ascending) with ids[m] == v of dx[m][w]: the gradient of a trainable KL.Embedding(V, W)
+ * (image captioning/model.py:36-39) from d(embedded tokens) dx [n][W] (rows ld apart) and the n token ids.  EVERY row of demb [V][W]
+ * (rows ld_e apart) is written -- zeros for a word the batch does not hold -- in one fixed order without atomics: bit-reproducible.
+ * An id outside [0, V) contributes nothing.  DC_EINVAL: a null pointer, n / V / W < 1, ld or ld_e below W. */
+int dc_embedding_grad_f32(const float* dx, int ld, const int32_t* ids, int n, float* demb, int ld_e, int V, int W, void* stream);
+
+/* out[b][c] = (((x[b][0][c] + x[b][1][c]) + x[b][2][c]) + ... + x[b][K-1][c]) / K in float32: the additions sequential over k, then one
+ * correctly rounded division -- what np.mean(float32[K, ...], axis=0) computes, bit for bit (the image-level feature vector of
+ * feature_generation/generate_roi_features.py:60-75: the mean of the [1000,7,7,256] RoIAlign block over its RoIs).  A tree or split-K
+ * sum (dc_colsum_f32) or a multiplication by 1 / K gives other bits from K = 3 on.
+ * x: B blocks of K rows of C floats, rows ld floats apart (ld >= C), blocks batch_stride floats apart; out: B rows, ld_out floats
+ * apart.  One launch, grid over (columns, B).  Any pointer alignment and any C: rows are read 16 bytes at a time where x, ld and
+ * batch_stride keep them on 16-byte boundaries, element by element otherwise -- the same values either way.
+ * DC_EINVAL before anything is launched: a null pointer, B outside 1..65535, K outside 1..2^24 - 1, C < 1, ld or ld_out below C. */
+int dc_row_mean_f32(const float* x, int B, int K, int C, long ld, long batch_stride, float* out, long ld_out, void* stream);
+
 /* out[n] (+)= sum_m x[m][n]  -- bias gradients (K.sum over batch/time inside the Dense/Conv backward of Keras).
  * Tall matrices are summed in row chunks through `workspace` (dc_colsum_workspace_bytes) and combined in a fixed
  * order: bit-reproducible.  Without workspace the kernel falls back to one chunk. */
