@@ -1076,6 +1076,74 @@ def tag_scores(logits, min_confidence, probs=None, scores=None):
     return probs, scores
 
 
+def _caption_rows(fn, name, t, rows=None, dim=2):
+    """A caption-metric operand: int32 on the GPU, `dim` dimensions, unit stride along the last.  Returns the row stride."""
+    if _chk(t, torch.int32, name).dim() != dim or (rows is not None and t.shape[0] != rows):
+        raise _lib.DcapError("%s: %s must be an int32 %s, got shape %s" % (fn, name, "[%s]" % ", ".join(
+            ["%d" % rows if rows is not None else "rows"] + ["width"] * (dim - 1)), tuple(t.shape)))
+    if dim == 1:
+        return 1
+    if t.shape[1] < 1 or (t.shape[0] > 1 and t.stride(0) < 1):
+        raise _lib.DcapError("%s: %s needs a width and a row stride of at least 1" % (fn, name))
+    return t.stride(0) if t.shape[0] > 1 else t.shape[1]
+
+
+def caption_metrics(cand, cand_len, refs, ref_len, ref_start, lcs=False):
+    """BLEU-1..4 and ROUGE-L of N caption records in one launch (dc_caption_metrics_f64): cand int32 [N,Tc] + cand_len [N], refs int32
+    [M,Tr] + ref_len [M], ref_start int32 [N+1] (CSR: the references of record i are rows ref_start[i]..ref_start[i+1]-1).  Returns
+    (stats int32 [N,12], bleu float64 [4,N], rouge float64 [N]).  lcs=False: ROUGE on what the reference fork's my_lcs returns;
+    lcs=True: on the true longest common subsequence.  A sentence holds at most CAPTION_MAX_TOKENS tokens (the kernel reads a longer
+    length as that many: caption_metrics.score refuses it by name before it gets here).  N = 0 gives empty results without a launch."""
+    lib = _lib.load()
+    fn = "caption_metrics"
+    N, M = cand.shape[0], refs.shape[0]
+    d = _lib.CaptionMetricsDesc()
+    d.N, d.M, d.Tc, d.Tr, d.lcs = N, M, cand.shape[1], refs.shape[1], int(bool(lcs))
+    d.ld_cand, d.ld_refs = _caption_rows(fn, "cand", cand), _caption_rows(fn, "refs", refs)
+    for name, t, rows in (("cand_len", cand_len, N), ("ref_len", ref_len, M), ("ref_start", ref_start, N + 1)):
+        _caption_rows(fn, name, t, rows, dim=1)
+    stats = torch.empty((N, 12), dtype=torch.int32, device=cand.device)
+    bleu = torch.empty((4, N), dtype=torch.float64, device=cand.device)
+    rouge = torch.empty((N,), dtype=torch.float64, device=cand.device)
+    if N == 0:
+        return stats, bleu, rouge
+    d.cand, d.cand_len, d.refs, d.ref_len, d.ref_start = cand.data_ptr(), cand_len.data_ptr(), refs.data_ptr(), ref_len.data_ptr(), ref_start.data_ptr()
+    d.stats, d.bleu, d.rouge = stats.data_ptr(), bleu.data_ptr(), rouge.data_ptr()
+    check(lib.dc_caption_metrics_f64(C.byref(d), _stream()), "dc_caption_metrics_f64")
+    return stats, bleu, rouge
+
+
+def caption_cider(grams, sent_len, ref_start, df, df_off, group_n):
+    """CIDEr of N records in one launch (dc_caption_cider_f64) from dense n-gram ids: grams int32 [4,S,T] (sentences 0..N-1 the
+    candidates, then the references; -1 where no n-gram starts), sent_len int32 [S], ref_start int32 [N+1], df int32 (the orders'
+    document-frequency tables one after the other, order k's at df_off[k-1]), group_n int32 [N] (the size of the record's group).
+    caption_metrics.cider_gram_tables builds these.  Returns cider float64 [N]."""
+    lib = _lib.load()
+    fn = "caption_cider"
+    N = group_n.shape[0]
+    if _chk(grams, torch.int32, "grams").dim() != 3 or grams.shape[0] != 4 or not grams.is_contiguous() or grams.shape[2] < 1:
+        raise _lib.DcapError("%s: grams must be a contiguous int32 [4,S,T] tensor, got shape %s" % (fn, tuple(grams.shape)))
+    S, T = grams.shape[1], grams.shape[2]
+    for name, t, rows in (("sent_len", sent_len, S), ("ref_start", ref_start, N + 1), ("df", df, None), ("group_n", group_n, N)):
+        _caption_rows(fn, name, t, rows, dim=1)
+    df_off = [int(o) for o in df_off]
+    if len(df_off) != 4 or df_off[0] != 0 or sorted(df_off) != df_off or df_off[3] > df.shape[0]:
+        raise _lib.DcapError("%s: df_off must be four offsets into df that start at 0 and do not decrease, got %s" % (fn, df_off))
+    cider = torch.empty((N,), dtype=torch.float64, device=grams.device)
+    if N == 0:
+        return cider
+    if S <= N:
+        raise _lib.DcapError("%s: grams holds %d sentences for %d records: every record needs a reference" % (fn, S, N))
+    d = _lib.CaptionCiderDesc()
+    d.N, d.S, d.T, d.df_len = N, S, T, df.shape[0]
+    for k in range(4):
+        d.df_off[k] = df_off[k]
+    d.grams, d.sent_len, d.ref_start, d.df, d.group_n, d.cider = (grams.data_ptr(), sent_len.data_ptr(), ref_start.data_ptr(), df.data_ptr(),
+                                                                  group_n.data_ptr(), cider.data_ptr())
+    check(lib.dc_caption_cider_f64(C.byref(d), _stream()), "dc_caption_cider_f64")
+    return cider
+
+
 def vocab_ce_supported(X, W):
     """Shapes the fused vocabulary softmax / cross-entropy takes (otherwise: gemm + softmax_ce)."""
     K, V = W.shape

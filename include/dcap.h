@@ -1207,6 +1207,64 @@ int dc_tag_focal_f32(const dc_tag_focal_desc* d, void* stream);
  * One block per row; either output may be NULL; no alignment rule. */
 int dc_tag_scores_f32(const float* z, int ldz, int M, int C, float min_confidence, float* probs, int ldp, float* scores, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Caption metrics on token ids (eval/bleu, eval/rouge, eval/cider of the reference; caption_metrics.py states the formulas).
+ * A sentence is a row of int32 ids >= 0 and a length; what lies past the length is never read as a token.  One 64-lane wave per
+ * record with the candidate's positions on the lanes: a sentence holds at most DC_CAPTION_MAX_TOKENS tokens (a longer length is
+ * read as that many; the Python side refuses it by name).  Any number of references per record, any base alignment.
+ *   cand [N][ld_cand] of Tc valid columns, cand_len [N]; refs [M][ld_refs] of Tr valid columns, ref_len [M] (lengths are clamped
+ *   into 0..min(width, DC_CAPTION_MAX_TOKENS)); ref_start [N+1] the CSR index of a record's references (clamped into 0..M).
+ *   stats [N][12] int32, exact: correct_1..4 (sum over the candidate's distinct k-grams of min(count, max over references of count)),
+ *     guess_1..4 = max(0, len - k + 1), testlen, reflen (the reference length closest to testlen, the shorter on a tie), lcs_max, 0.
+ *   bleu [4][N] float64: (prod_{j<=k} (correct_j + 1e-15) / (guess_j + 1e-9))^(1/k), times exp(1 - 1/ratio) when
+ *     ratio = (testlen + 1e-15) / (reflen + 1e-9) < 1.
+ *   rouge [N] float64: (1 + b^2) P R / (R + b^2 P), b = 1.2, P = max_r l / max(1, len cand), R = max_r l / max(1, len ref), 0 when
+ *     either is 0.  lcs = 0: l = the positions of the shorter sentence (the candidate on equal lengths) whose token occurs in the
+ *     longer one -- what the reference fork's my_lcs returns; lcs = 1: l = the longest common subsequence.
+ * N-gram equality compares the ids (up to four int32), nothing is hashed; float64 in a fixed order, no atomics: identical bits from
+ * call to call.  DC_EINVAL: a null pointer, N < 1, M < 1, a width below 1 or above its row stride, lcs not 0 / 1.
+ * ------------------------------------------------------------------------------------------------ */
+#define DC_CAPTION_MAX_TOKENS 64
+typedef struct {
+    int N, M, Tc, Tr;
+    const int32_t* cand;
+    int ld_cand;
+    const int32_t* cand_len;
+    const int32_t* refs;
+    int ld_refs;
+    const int32_t* ref_len;
+    const int32_t* ref_start;
+    int lcs;
+    int32_t* stats;
+    double* bleu;
+    double* rouge;
+} dc_caption_metrics_desc;
+
+int dc_caption_metrics_f64(const dc_caption_metrics_desc* d, void* stream);
+
+/* CIDEr (n = 4, sigma = 6) per record from dense n-gram ids.  Sentences 0..N-1 are the candidates, N..S-1 the references in
+ * ref_start's order.  grams [4][S][T] int32: grams[k-1][s][i] = the id of the k-gram that starts at position i of sentence s, ids of
+ * order k in 0..G_k-1 with equal ids exactly for equal n-grams OF ONE GROUP (the caller numbers them; a value outside 0..G_k-1 is
+ * "no n-gram").  df [df_len] int32: the document frequency of id g of order k at df[df_off[k-1] + g] (G_k = the next offset, or
+ * df_len, minus this one).  group_n [N]: the size of the record's group.  sent_len [S] (clamped to min(T, DC_CAPTION_MAX_TOKENS)).
+ *   weight of g = tf * (log group_n - log max(1, df)); per order and reference sum over the candidate's distinct grams of
+ *   min(w_c, w_r) w_r / (|c| |r|) (no division when a norm is 0), times exp(-delta^2 / 72), delta the difference of max(len - 1, 0);
+ *   cider [N] float64 = mean over the orders of the sum over the references, / references, * 10.
+ * One wave per record, float64 in a fixed order, no atomics.  DC_EINVAL: a null pointer, N < 1, S <= N, T < 1, bad df_off. */
+typedef struct {
+    int N, S, T;
+    const int32_t* grams;
+    const int32_t* sent_len;
+    const int32_t* ref_start;
+    const int32_t* df;
+    int df_off[4];
+    int df_len;
+    const int32_t* group_n;
+    double* cider;
+} dc_caption_cider_desc;
+
+int dc_caption_cider_f64(const dc_caption_cider_desc* d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
