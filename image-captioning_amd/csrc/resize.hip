@@ -18,24 +18,18 @@
 // sum -- and stores it at (x, c).  Nothing is resampled from a mirrored source, so the mirrored bytes are the unflipped pass's by
 // construction.  The flags are an int32 [B] block inside the packed buffer (one upload); the old entry point passes none.
 #include "dcap_internal.h"
+#include "resize_core.h"
 #include <math.h>
 
-// The coefficients are the host C code's only if every operation rounds once: no fused multiply-add.
+// The coefficients are the host C code's only if every operation rounds once: no fused multiply-add (resize_core.h, shared with
+// detect.hip, says so for its own body; this keeps the whole file that way).
 #pragma clang fp contract(off)
 
 namespace dcap {
 
-constexpr int RS_PRECISION_BITS = 32 - 8 - 2;      // PIL's PRECISION_BITS: coefficients carry 22 fractional bits
 constexpr int RS_THREADS = 256;
 constexpr int RS_MAX_GRID_Y = 65535;
 constexpr size_t RS_LIMIT = (size_t)1 << 31;       // every byte count and offset fits int32
-
-// bilinear support is 1.0: the taps of one output index never exceed this (precompute_coeffs' ksize)
-static inline int resize_ksize(int in_size, int out_size) {
-    const double scale = (double)in_size / (double)out_size;
-    const double fs = scale < 1.0 ? 1.0 : scale;
-    return (int)ceil(1.0 * fs) * 2 + 1;
-}
 
 // One axis' table in the workspace: bounds [out][2] = (xmin, n), then coefficients tap-major [tap][out] so that neighbouring output
 // indices read neighbouring words.
@@ -57,33 +51,7 @@ __global__ __launch_bounds__(RS_THREADS) void resize_coef_kernel(const int* __re
     if (xx >= out_size) return;
     int* bounds = resize_axis_table(tables, B, b, axis, ax, ay);
     int* coefs = bounds + 2 * (size_t)out_size;
-    const double scale = (double)in_size / (double)out_size;
-    const double fs = scale < 1.0 ? 1.0 : scale;
-    const double support = 1.0 * fs, ss = 1.0 / fs;
-    const double center = (xx + 0.5) * scale;
-    int xmin = (int)(center - support + 0.5);
-    if (xmin < 0) xmin = 0;
-    int xmax = (int)(center + support + 0.5);
-    if (xmax > in_size) xmax = in_size;
-    const int n = xmax - xmin;
-    double ww = 0.0;
-    for (int x = 0; x < n; ++x) {
-        const double a = fabs((x + xmin - center + 0.5) * ss);
-        ww += a < 1.0 ? 1.0 - a : 0.0;
-    }
-    for (int x = 0; x < n; ++x) {                    // the same weights again (same operations, same values), now normalised
-        const double a = fabs((x + xmin - center + 0.5) * ss);
-        double w = a < 1.0 ? 1.0 - a : 0.0;
-        if (ww != 0.0) w /= ww;
-        coefs[(size_t)x * out_size + xx] = (int)(0.5 + w * (double)(1 << RS_PRECISION_BITS));
-    }
-    bounds[2 * xx] = xmin;
-    bounds[2 * xx + 1] = n;
-}
-
-__device__ __forceinline__ uint8_t resize_clip8(int acc) {
-    const int v = acc >> RS_PRECISION_BITS;
-    return (uint8_t)(v < 0 ? 0 : v > 255 ? 255 : v);
+    resize_axis_coefs(in_size, out_size, xx, bounds, coefs);
 }
 
 // mid[y][xx][c] = clip8((1 << 21) + sum_t k[t][xx] * src[y][xmin + t][c]); thread = byte j = xx * 3 + c of the row, rows grid-strided

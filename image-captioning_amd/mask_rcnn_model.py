@@ -1,0 +1,417 @@
+"""Mask R-CNN at inference behind the reference's module interface (mask_rcnn/mask_rcnn_model.py: MaskRCNN :1760, the inference branch of
+build :1915-1942, fpn_classifier_graph :854-905, build_fpn_mask_graph :908-956, refine_detections :669-738, DetectionLayer :741-779,
+unmold_detections :2253-2312, detect :2314-2354; mask_rcnn/utils.py: apply_box_deltas, non_max_suppression, unmold_mask).
+
+  ResNet-101 -> FPN -> RPN -> ProposalLayer (POST_NMS_ROIS_INFERENCE)
+  -> PyramidROIAlign(7) -> mrcnn_class_conv1/bn1/conv2/bn2 -> mrcnn_class_logits, mrcnn_bbox_fc (two GEMMs, bias in the epilogue)
+  -> ops.class_select: per RoI the winning class, its softmax probability and its four deltas -- 6 words per RoI to the host
+  -> refine_detections + the box part of unmold_detections on the host in NumPy (the reference runs the former in a py_func)
+  -> ONE packed upload: the detection boxes normalised, their class ids, their boxes in the original image
+  -> PyramidROIAlign(MASK_POOL_SIZE) -> mrcnn_mask_conv1..4 + frozen BN + ReLU (four dc_conv2d_nhwc_f32 launches)
+  -> ops.mask_head_tail: mrcnn_mask_deconv + ReLU + mrcnn_mask + sigmoid for each detection's OWN class: [M,28,28]
+  -> utils.unmold_mask: postprocess="host" in NumPy / PIL, "device" ops.mask_paste and one copy of the [M,H,W] bytes.
+
+Everything below the heads is DenseImageCapRCNN's, unchanged: MaskRCNN sub-classes it and puts DetectTop where the caption model sits.
+
+Not in this class (each is refused with a ValueError that names it): mode="training" and the parent's training surface -- train, compile,
+train_on_batch(_device), test_on_batch(_device), forward_backward, set_trainable, plan_pair, use_step_graph, grad_sync -- (the detection
+targets and the class, box and mask losses are not built), compute_dtype="bf16", GPU_COUNT > 1 and generate_captions."""
+import os
+
+import numpy as np
+import torch
+
+from . import dense_model, ops, synth, utils
+from .config import Config
+from .dense_model import DenseImageCapRCNN
+from .packing import pack_conv_kernel, pack_mask_tail
+from .params import ParamStore
+from .text_generation_model import RoiHead
+
+MASK_CONVS = tuple(("mrcnn_mask_conv%d" % i, "mrcnn_mask_bn%d" % i) for i in (1, 2, 3, 4))
+MASK_CHANNELS = 256
+
+
+class MaskRCNNConfig(Config):
+    """mask_rcnn/config.py's fields that config.Config (the captioning models' copy) does not carry."""
+    NAME = "mask_rcnn"
+    NUM_CLASSES = 1                       # background + the dataset's classes (COCO: 81); the reference's default
+    USE_MINI_MASK = True                  # training-side fields, kept for scripts that set them
+    MINI_MASK_SHAPE = (56, 56)
+
+    def __init__(self, num_classes=None):
+        super(MaskRCNNConfig, self).__init__()
+        if num_classes is not None:
+            self.NUM_CLASSES = int(num_classes)
+
+
+# ------------------------------------------------------------------------------------------------ the host side, restated
+def apply_box_deltas(boxes, deltas):
+    """utils.apply_box_deltas with the reference's number formats: float32 boxes, sizes and centres; the deltas arrive as float64
+    (refine_detections multiplies them by the float64 BBOX_STD_DEV) and enter through IN-PLACE updates, i.e. each update is computed in
+    float64 and rounded to float32 once; np.exp is NumPy's, on the host, as in the reference."""
+    boxes = boxes.astype(np.float32)
+    height = boxes[:, 2] - boxes[:, 0]
+    width = boxes[:, 3] - boxes[:, 1]
+    center_y = boxes[:, 0] + 0.5 * height
+    center_x = boxes[:, 1] + 0.5 * width
+    center_y += deltas[:, 0] * height
+    center_x += deltas[:, 1] * width
+    height *= np.exp(deltas[:, 2])
+    width *= np.exp(deltas[:, 3])
+    y1 = center_y - 0.5 * height
+    x1 = center_x - 0.5 * width
+    return np.stack([y1, x1, y1 + height, x1 + width], axis=1)
+
+
+def clip_to_window(window, boxes):
+    """In place, in the boxes' own dtype: the window is the float32 row of image_meta the DetectionLayer reads."""
+    window = np.asarray(window, boxes.dtype)
+    for col, lo, hi in ((0, 0, 2), (1, 1, 3), (2, 0, 2), (3, 1, 3)):
+        boxes[:, col] = np.maximum(np.minimum(boxes[:, col], window[hi]), window[lo])
+    return boxes
+
+
+def refine_detections(rois, class_ids, class_scores, deltas_specific, window, config):
+    """refine_detections (:689-738) for one image from line :689 on: what comes before it -- the argmax, the winner's probability and
+    the winner's deltas (:684-688) -- is ops.class_select's output.  rois float32 [N,4] normalised, class_ids int [N], class_scores
+    float32 [N], deltas_specific float32 [N,4], window (y1, x1, y2, x2) of the molded image.
+    Returns (boxes int32 [K,4] in the molded image, class_ids int32 [K], scores float32 [K], the kept RoIs' indices [K]), best first."""
+    class_ids = np.asarray(class_ids).astype(np.int64)
+    class_scores = np.asarray(class_scores, np.float32)
+    refined = apply_box_deltas(np.asarray(rois, np.float32), np.asarray(deltas_specific, np.float32) * config.BBOX_STD_DEV)
+    height, width = config.IMAGE_SHAPE[:2]
+    refined *= np.array([height, width, height, width])
+    refined = clip_to_window(window, refined)
+    refined = np.rint(refined).astype(np.int32)
+    keep = np.where(class_ids > 0)[0]
+    if config.DETECTION_MIN_CONFIDENCE:
+        keep = np.intersect1d(keep, np.where(class_scores >= config.DETECTION_MIN_CONFIDENCE)[0])
+    pre_ids, pre_scores, pre_rois = class_ids[keep], class_scores[keep], refined[keep]
+    nms_keep = []
+    for class_id in np.unique(pre_ids):
+        ixs = np.where(pre_ids == class_id)[0]
+        class_keep = utils.non_max_suppression(pre_rois[ixs], pre_scores[ixs], config.DETECTION_NMS_THRESHOLD)
+        nms_keep = np.union1d(nms_keep, keep[ixs[class_keep]])
+    keep = np.intersect1d(keep, nms_keep).astype(np.int32)
+    top = np.argsort(class_scores[keep])[::-1][:config.DETECTION_MAX_INSTANCES]
+    keep = keep[top]
+    return refined[keep], class_ids[keep].astype(np.int32), class_scores[keep], keep
+
+
+def unmold_boxes(boxes, image_shape, window):
+    """The box part of unmold_detections (:2281-2301): shift by the window, scale to the original image in float64, truncate to int32.
+    Returns (boxes int32 [K,4], mask of the boxes with a positive area: the others are deleted there)."""
+    return dense_model.unmold_generations(boxes, image_shape, window)
+
+
+def bytescale(mask):
+    """scipy 1.0's misc.bytescale(mask) as imresize calls it (cmin / cmax the mask's own, low 0, high 255), with NumPy 1.x's arithmetic on
+    a float32 array: the scale is 255.0 / range in float64, then cast to the array's float32 by the multiplication."""
+    m = np.asarray(mask, np.float32)
+    cmin, cmax = m.min(), m.max()
+    rng = np.float32(cmax - cmin)
+    if rng == 0:
+        rng = np.float32(1.0)
+    scale = np.float32(255.0 / float(rng))
+    out = np.clip((m - cmin) * scale, np.float32(0.0), np.float32(255.0)) + np.float32(0.5)
+    return out.astype(np.uint8)
+
+
+def resize_mask(mask, bh, bw):
+    """imresize(mask, (bh, bw), interp='bilinear') >= 128: uint8 [bh,bw] of 0 / 1 (byte / 255 >= 0.5 exactly when byte >= 128)."""
+    from PIL import Image
+    small = Image.fromarray(bytescale(mask), mode="L").resize((int(bw), int(bh)), resample=Image.BILINEAR)
+    return (np.asarray(small) >= 128).astype(np.uint8)
+
+
+def unmold_mask(mask, bbox, image_shape):
+    """utils.unmold_mask: the [h,w] float mask of one detection -> uint8 [H,W] of the original image, 1 inside the box where the
+    resized mask reaches 0.5.  A box without area or one that leaves the image gives zeros (the reference deletes the former before it
+    gets here and cannot produce the latter)."""
+    y1, x1, y2, x2 = (int(v) for v in bbox)
+    full = np.zeros(tuple(image_shape[:2]), np.uint8)
+    if 0 <= y1 < y2 <= full.shape[0] and 0 <= x1 < x2 <= full.shape[1]:
+        full[y1:y2, x1:x2] = resize_mask(mask, y2 - y1, x2 - x1)
+    return full
+
+
+# ------------------------------------------------------------------------------------------------ the heads
+class DetectTop(RoiHead):
+    """What sits on the pooled RoI features: the shared head, the class / box GEMMs and the mask head's weights.  Owns the parameter
+    store like TagTop; the detection layers are frozen entries (this class only runs inference).  Stored shapes: mrcnn_class_logits
+    padded to a multiple of 4 columns (16-byte rows for the GEMM), the mask convolutions packed like every 3x3 kernel here,
+    mrcnn_mask transposed to [C][256] (packing.pack_mask_tail); get_keras_weights / set_keras_weights speak Keras' shapes."""
+    compute_dtype = "f32"
+
+    def __init__(self, features_input, num_classes, device, seed=0, extra_params=(), mask_pool=14):
+        self.C = int(num_classes)
+        if self.C < 2:
+            raise ValueError("NUM_CLASSES must be at least 2 (background and one class), got %r" % (num_classes,))
+        self.Cp = (self.C + 3) // 4 * 4
+        self.mask_pool = int(mask_pool)
+        self.device = torch.device(device)
+        pool, cin = features_input[0], features_input[2]
+        st = ParamStore(self.device)
+        W = synth.head_weights(seed + 1, pool, cin, self.FEAT)
+        for k in sorted(W):
+            st.add(k, W[k], 'moving_' not in k)
+        for k, v in self.to_stored(synth.detect_head_weights(seed + 6, self.C, self.FEAT)).items():
+            st.add(k, v, False)
+        for name, array, trainable in extra_params:
+            st.add(name, array, trainable)
+        self.store = st.finalize()
+        self._bufs = {}
+        self._folded = None
+
+    def to_stored(self, W):
+        """Keras-shaped detection-head weights -> the shapes the store holds (any subset)."""
+        out = {}
+        for k, v in W.items():
+            layer, wname = k.split("/")
+            v = np.asarray(v, np.float32)
+            if layer == "mrcnn_class_logits":
+                want = (self.FEAT, self.C) if wname == "kernel" else (self.C,)
+                if tuple(v.shape) != want:
+                    raise ValueError("shape mismatch for %s: %s vs %s" % (k, v.shape, want))
+                pad = np.zeros(want[:-1] + (self.Cp,), np.float32)
+                pad[..., :self.C] = v
+                v = pad
+            elif layer.startswith("mrcnn_mask_conv") and wname == "kernel":
+                v = pack_conv_kernel(v)
+            elif layer == "mrcnn_mask" and wname == "kernel":
+                v = pack_mask_tail(v)
+            out[k] = v
+        return out
+
+    def from_stored(self, k, v):
+        layer, wname = k.split("/")
+        if layer == "mrcnn_class_logits":
+            return np.ascontiguousarray(v[..., :self.C])
+        if layer.startswith("mrcnn_mask_conv") and wname == "kernel":
+            return np.ascontiguousarray(v.reshape(v.shape[0], 3, 3, -1).transpose(1, 2, 3, 0))
+        if layer == "mrcnn_mask" and wname == "kernel":
+            return np.ascontiguousarray(v.T)[None, None]
+        return v
+
+    def heads(self, feat):
+        """feat [R,7,7,256] -> (logits [R,C] (a view of the padded [R,Cp] buffer), box deltas [R,4C])."""
+        w = self.store.w
+        R = feat.shape[0]
+        f = self._head_forward(feat.reshape(R, -1))
+        z = ops.gemm(f.f, w['mrcnn_class_logits/kernel'], shift=w['mrcnn_class_logits/bias'], out=self._buf('logits', (R, self.Cp)))
+        d = ops.gemm(f.f, w['mrcnn_bbox_fc/kernel'], shift=w['mrcnn_bbox_fc/bias'], out=self._buf('bbox', (R, 4 * self.C)))
+        return z[:, :self.C], d
+
+    def folded(self):
+        """The four mask convolutions' epilogue operands: frozen BN statistics and the convolution's bias folded on the device
+        (dc_bn_fold_f32), once per set of weights."""
+        if self._folded is None:
+            w = self.store.w
+            self._folded = []
+            for conv, bn in MASK_CONVS:
+                scale, shift = (torch.empty(MASK_CHANNELS, dtype=torch.float32, device=self.device) for _ in range(2))
+                ops.bn_fold(w[bn + '/gamma'], w[bn + '/beta'], w[conv + '/bias'], w[bn + '/moving_mean'], w[bn + '/moving_variance'], scale, shift)
+                self._folded.append((scale, shift))
+        return self._folded
+
+    def mask_layer(self, i, x, out=None):
+        """mrcnn_mask_conv<i+1> + mrcnn_mask_bn<i+1> (frozen) + ReLU on x [M,P,P,256], one dc_conv2d_nhwc_f32 launch."""
+        conv = MASK_CONVS[i][0]
+        scale, shift = self.folded()[i]
+        P = x.shape[1]
+        return ops.conv2d(x, self.store.w[conv + '/kernel'], 3, 3, 1, 1, 1, P, P, scale=scale, shift=shift, relu=True, out=out)
+
+    def mask_trunk(self, x):
+        """x [M,P,P,256] -> the fourth convolution's output (conv + frozen BN + ReLU, four times, two buffers in turn)."""
+        for i in range(len(MASK_CONVS)):
+            x = self.mask_layer(i, x, out=self._buf('mask_act%d' % (i & 1), tuple(x.shape[:3]) + (MASK_CHANNELS,)))
+        return x
+
+    def class_masks(self, x, class_ids, out=None):
+        """x [M,P,P,256] (RoIAlign at MASK_POOL_SIZE), class_ids int32 [M] on the device -> [M,2P,2P]: each detection's own class mask."""
+        w = self.store.w
+        return ops.mask_head_tail(self.mask_trunk(x), w['mrcnn_mask_deconv/kernel'], w['mrcnn_mask_deconv/bias'], w['mrcnn_mask/kernel'],
+                                  w['mrcnn_mask/bias'], class_ids, out=out)
+
+
+def _no_training(name):
+    """A method of the parent's training surface as this inference-only class has it: refused by name."""
+    def refuse(self, *args, **kw):
+        raise ValueError("MaskRCNN.%s: training is not built (mode=\"training\": detection targets and the class, box and mask losses)" % name)
+    refuse.__name__ = name
+    return refuse
+
+
+class MaskRCNN(DenseImageCapRCNN):
+    LOSS_NAMES = ()
+
+    def __init__(self, mode, config, model_dir, device=None, stage4_blocks=22, seed=0, conv_math=None, compute_dtype="f32"):
+        if mode != "inference":
+            raise ValueError("MaskRCNN: mode=%r: only mode=\"inference\" is built (mode=\"training\" needs the class-id, box-delta and mask "
+                             "detection targets and the class, box and mask losses)" % (mode,))
+        if compute_dtype != "f32":
+            raise ValueError("MaskRCNN: compute_dtype=%r is not available for the detection heads (compute_dtype=\"bf16\" is out of scope): "
+                             "use 'f32'" % (compute_dtype,))
+        if int(config.GPU_COUNT) > 1:
+            raise ValueError("MaskRCNN: GPU_COUNT = %d: data-parallel runs (GPU_COUNT > 1 / ParallelModel) are not available for this class"
+                             % config.GPU_COUNT)
+        if int(getattr(config, "NUM_CLASSES", 0)) < 2:
+            raise ValueError("MaskRCNN: NUM_CLASSES must be at least 2 (background and one class), got %r" % (getattr(config, "NUM_CLASSES", None),))
+        DenseImageCapRCNN.__init__(self, mode, config, model_dir, device=device, stage4_blocks=stage4_blocks, seed=seed, conv_math=conv_math,
+                                   compute_dtype="f32")
+        self._path.pin(False)
+        self.last_heads = self.last_selection = self.last_detections = self.last_class_masks = None
+
+    def _make_top(self, cfg, dev, seed, extra):
+        return DetectTop([cfg.POOL_SIZE, cfg.POOL_SIZE, 256], cfg.NUM_CLASSES, dev, seed, extra_params=extra, mask_pool=cfg.MASK_POOL_SIZE)
+
+    # ---- what this class refuses -------------------------------------------------------------
+    train, compile, train_on_batch, train_on_batch_device = (_no_training(n) for n in ("train", "compile", "train_on_batch", "train_on_batch_device"))
+    test_on_batch, test_on_batch_device, forward_backward = (_no_training(n) for n in ("test_on_batch", "test_on_batch_device", "forward_backward"))
+    set_trainable, plan_pair = _no_training("set_trainable"), _no_training("plan_pair")
+
+    @property
+    def use_step_graph(self):
+        return False
+
+    @use_step_graph.setter
+    def use_step_graph(self, value):
+        if value:
+            raise ValueError("MaskRCNN: captured step graphs belong to training, which is not built for this class")
+
+    @property
+    def grad_sync(self):
+        return None
+
+    @grad_sync.setter
+    def grad_sync(self, value):
+        if value is not None:
+            raise ValueError("MaskRCNN: a gradient exchange (ParallelModel / GPU_COUNT > 1) is not available for this class")
+
+    def generate_captions(self, *args, **kw):
+        raise ValueError("MaskRCNN has no caption decoder: use detect")
+
+    # ---- weights -------------------------------------------------------------------------------
+    def get_weights_dict(self):
+        """'<layer>/<weight>' -> ndarray under the reference's layer names, in Keras' shapes (mrcnn_class_logits [1024,C],
+        mrcnn_mask_conv* HWIO, mrcnn_mask_deconv [2,2,256,256], mrcnn_mask [1,1,256,C])."""
+        out = DenseImageCapRCNN.get_weights_dict(self)
+        top = self.caption_model
+        return {k: top.from_stored(k, v) if k.startswith("mrcnn_") else v for k, v in out.items()}
+
+    def set_weights(self, weights):
+        top = self.caption_model
+        W = dict(weights)
+        W.update(top.to_stored({k: v for k, v in W.items() if k.split("/")[0] in ("mrcnn_class_logits", "mrcnn_mask") or
+                                k.startswith("mrcnn_mask_conv")}))
+        DenseImageCapRCNN.set_weights(self, W)
+        top._folded = None
+
+    def save_weights(self, path):
+        """Atomic like DenseImageCapRCNN.save_weights; every layer of this model is a top-level Keras layer (TimeDistributed wrappers
+        carry their inner layer's name)."""
+        tmp = path + (".tmp.h5" if path.endswith((".h5", ".hdf5")) else ".tmp.npz")
+        dense_model.save_weight_file(tmp, self.get_weights_dict())
+        os.replace(tmp, path)
+
+    # ---- inference -----------------------------------------------------------------------------
+    def detect(self, images, verbose=0, postprocess="host", mold="host", device_masks=False):
+        """The inference graph + detect (:2314-2354).  Returns, per image, {"rois": int32 [N,4] in the original image, "class_ids": int32
+        [N], "scores": float32 [N], "masks": uint8 [H,W,N] (a transposed view of [N,H,W]); (0,28,28) floats when nothing is detected, as
+        the reference returns it}.  postprocess="host": the [N,28,28] class masks come to the host and utils.unmold_mask runs in NumPy /
+        PIL; "device": ops.mask_paste and one copy of the finished bytes -- the same bytes.  mold: as DenseImageCapRCNN.generate_captions.
+        device_masks=True (postprocess="device"): "masks" stays a uint8 [N,H,W] tensor on the device."""
+        if postprocess not in ("host", "device"):
+            raise ValueError("postprocess must be 'host' or 'device', got %r" % (postprocess,))
+        if device_masks and postprocess != "device":
+            raise ValueError("device_masks=True needs postprocess='device'")
+        utils.check_mold(mold, self.config.IMAGE_PADDING)
+        assert self.mode == "inference", "Create model in inference mode."
+        assert len(images) == self.config.BATCH_SIZE, "len(images) must be equal to BATCH_SIZE"
+        cfg, top, B = self.config, self.caption_model, len(images)
+        if verbose:
+            print("Processing %d images" % B)
+        if mold == "device":
+            images = [utils.check_device_mold_image(im) for im in images]
+        p = self.plan()
+        if mold == "device":
+            molded, windows = None, self._mold_device(p, images)
+        else:
+            molded, _, windows = self.mold_inputs(images)
+            molded = torch.as_tensor(molded)
+        p.forward(molded)
+        proposals = p.proposals()
+        self.last_proposals = proposals
+        K, C = proposals.shape[1], top.C
+        feats = p.roi_features(boxes_norm=proposals)
+        z, d = top.heads(feats.view(B * K, cfg.POOL_SIZE, cfg.POOL_SIZE, 256))
+        self.last_heads = (z, d)
+        # proposals, ids, scores and deltas leave in one buffer of 10 words per RoI: ids as their bits
+        sel = self._buf("selection", (B * K, 10))
+        sel[:, :4].copy_(proposals.view(B * K, 4))
+        ids, scores, deltas = ops.class_select(z, d, class_ids=self._buf("sel_ids", (B * K,), torch.int32), scores=self._buf("sel_scores", (B * K,)),
+                                               deltas_out=self._buf("sel_deltas", (B * K, 4)))
+        sel[:, 4].copy_(ids.view(torch.float32))
+        sel[:, 5].copy_(scores)
+        sel[:, 6:].copy_(deltas)
+        host = sel.cpu().numpy().reshape(B, K, 10)          # the one device-to-host copy of step 4
+        self.last_selection = [(host[b, :, :4].copy(), host[b, :, 4].copy().view(np.int32), host[b, :, 5].copy(), host[b, :, 6:].copy())
+                               for b in range(B)]
+        h, w = cfg.IMAGE_SHAPE[:2]
+        norm = np.array([h, w, h, w])
+        dets, counts = [], []
+        for b in range(B):
+            rois_b, ids_b, scores_b, deltas_b = self.last_selection[b]
+            boxes, cls, sc, _ = refine_detections(rois_b, ids_b, scores_b, deltas_b, np.asarray(windows[b], np.float32), cfg)
+            final, ok = unmold_boxes(boxes, images[b].shape, windows[b])
+            dets.append(dict(boxes=boxes[ok], class_ids=cls[ok], scores=sc[ok], rois=final[ok]))
+            counts.append(int(ok.sum()))
+        self.last_detections = dets
+        M = max(counts)
+        self.last_class_masks = [np.zeros((0, 2 * top.mask_pool, 2 * top.mask_pool), np.float32) for _ in range(B)]
+        results = [{"rois": dt["rois"], "class_ids": dt["class_ids"], "scores": dt["scores"],
+                    "masks": np.empty((0, 2 * top.mask_pool, 2 * top.mask_pool))} for dt in dets]
+        if M == 0:
+            if device_masks:
+                for b in range(B):
+                    results[b]["masks"] = torch.empty((0,) + tuple(images[b].shape[:2]), dtype=torch.uint8, device=self.device)
+            return results
+        # one packed upload: per image M rows of (normalised detection box as float32 bits, class id, box in the original image);
+        # padding rows carry a zero box and class id -1, which gives zero masks
+        pack = np.zeros((B, M, 9), np.int32)
+        pack[:, :, 4] = -1
+        for b, dt in enumerate(dets):
+            n = counts[b]
+            pack[b, :n, :4] = (dt["boxes"].astype(np.float32) / norm).astype(np.float32).view(np.int32)
+            pack[b, :n, 4] = dt["class_ids"]
+            pack[b, :n, 5:] = dt["rois"]
+        up = torch.from_numpy(pack).to(self.device)
+        det_norm = up[:, :, :4].contiguous().view(torch.float32)
+        det_ids = up[:, :, 4].contiguous().view(B * M)
+        P = top.mask_pool
+        x = ops.roi_align_pyramid(list(p.P), det_norm, float(p.H * p.W), P, out=self._buf("mask_rois", (B, M, P, P, 256)))
+        masks = top.class_masks(x.view(B * M, P, P, 256), det_ids, out=self._buf("class_masks", (B * M, 2 * P, 2 * P))).view(B, M, 2 * P, 2 * P)
+        if postprocess == "host":
+            masks_h = masks.cpu().numpy()
+            for b in range(B):
+                n = counts[b]
+                self.last_class_masks[b] = masks_h[b, :n].copy()
+                if n:
+                    full = np.stack([unmold_mask(masks_h[b, i], dets[b]["rois"][i], images[b].shape) for i in range(n)])
+                    results[b]["masks"] = full.transpose(1, 2, 0)
+            return results
+        keep = []
+        for b in range(B):
+            n = counts[b]
+            if not n:
+                if device_masks:
+                    results[b]["masks"] = torch.empty((0,) + tuple(images[b].shape[:2]), dtype=torch.uint8, device=self.device)
+                continue
+            H0, W0 = images[b].shape[:2]
+            full = ops.mask_paste(masks[b, :n], up[b, :n, 5:].contiguous(), H0, W0)
+            keep.append((b, full))
+        for b, full in keep:
+            results[b]["masks"] = full if device_masks else full.cpu().numpy().transpose(1, 2, 0)
+        self.last_class_masks = [masks[b, :counts[b]] for b in range(B)]     # (device views of a buffer the next call reuses)
+        return results

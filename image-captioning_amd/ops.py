@@ -12,7 +12,7 @@ import torch
 
 from . import _lib
 from ._lib import (RpnTargetsDesc, PwChainDesc, ConvBf16Desc, AmsgradDesc, DetectionTargetsDesc, BnReluDesc, ConvDesc, ConvWgradBf16Desc, GemmBf16Desc, VocabCeDesc, ProposalDesc, RpnLossDesc, GemmDesc, LstmBwdDesc, LstmFwdDesc, RoialignDesc, RoiGroupsDesc,
-                   SoftmaxCeDesc, TagFocalDesc, VocabTop1Desc, VocabTopkDesc, VocabTop1Bf16Desc, VocabTopkBf16Desc, VocabSampleDesc, VocabSampleBf16Desc, BeamSelectDesc, BeamStepDesc, LstmStepDesc, RefineDesc, ResizePadDesc, check)
+                   SoftmaxCeDesc, TagFocalDesc, VocabTop1Desc, VocabTopkDesc, VocabTop1Bf16Desc, VocabTopkBf16Desc, VocabSampleDesc, VocabSampleBf16Desc, BeamSelectDesc, BeamStepDesc, LstmStepDesc, RefineDesc, ResizePadDesc, MaskHeadTailDesc, MaskPasteDesc, check)
 
 
 def _stream():
@@ -1074,6 +1074,121 @@ def tag_scores(logits, min_confidence, probs=None, scores=None):
                                 _ptr(probs), _tag_rows("tag_scores", "probs", probs, torch.float32, M, Cn), _ptr(scores), _stream()),
           "dc_tag_scores_f32")
     return probs, scores
+
+
+def _on_gpu(fn, **tensors):
+    """The detection wrappers' last check before the library is loaded: every tensor lives on the device."""
+    for name, t in tensors.items():
+        if not t.is_cuda:
+            raise _lib.DcapError("%s: %s must live on the GPU (no CPU path exists)" % (fn, name))
+
+
+def class_select(logits, deltas, class_ids=None, scores=None, deltas_out=None):
+    """The detection head's per-RoI selection (dc_class_select_f32): logits float32 [R,C] and box deltas float32 [R,4C] (or [R,C,4]
+    contiguous), each with any row stride -> (class_ids int32 [R]: the lowest index of the maximal logit; scores float32 [R]: that
+    class's softmax probability 1 / sum exp(z - z_max); deltas float32 [R,4]: the class's four words, copied).  C >= 2, any value.
+    Outputs are allocated when not given.  The shapes are checked before the library is loaded."""
+    if logits.dim() != 2 or logits.shape[0] < 1 or logits.shape[1] < 2:
+        raise _lib.DcapError("class_select: logits must be a float32 [R,C] matrix with R >= 1 and C >= 2, got %s" % (tuple(logits.shape),))
+    R, Cn = logits.shape
+    if deltas.dim() == 3:
+        if tuple(deltas.shape) != (R, Cn, 4) or not deltas.is_contiguous():
+            raise _lib.DcapError("class_select: 3-D deltas must be a contiguous [%d,%d,4] tensor, got %s" % (R, Cn, tuple(deltas.shape)))
+        deltas = deltas.view(R, 4 * Cn)
+    if deltas.dim() != 2 or tuple(deltas.shape) != (R, 4 * Cn):
+        raise _lib.DcapError("class_select: deltas must be a float32 [%d,%d] matrix, got %s" % (R, 4 * Cn, tuple(deltas.shape)))
+    for name, t in (("logits", logits), ("deltas", deltas)):
+        if t.dtype != torch.float32:
+            raise _lib.DcapError("class_select: %s must be torch.float32, got %s" % (name, t.dtype))
+        if t.stride(1) != 1 or (R > 1 and t.stride(0) < t.shape[1]):
+            raise _lib.DcapError("class_select: %s must be contiguous along its rows with a row stride of at least %d, got strides %s"
+                                 % (name, t.shape[1], tuple(t.stride())))
+    dev = logits.device
+    if class_ids is None:
+        class_ids = torch.empty((R,), dtype=torch.int32, device=dev)
+    if scores is None:
+        scores = torch.empty((R,), dtype=torch.float32, device=dev)
+    if deltas_out is None:
+        deltas_out = torch.empty((R, 4), dtype=torch.float32, device=dev)
+    for name, t, dtype, shape in (("class_ids", class_ids, torch.int32, (R,)), ("scores", scores, torch.float32, (R,)),
+                                  ("deltas_out", deltas_out, torch.float32, (R, 4))):
+        if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
+            raise _lib.DcapError("class_select: %s must be a contiguous %s %s tensor, got %s %s" % (name, dtype, list(shape), t.dtype, tuple(t.shape)))
+    _on_gpu("class_select", logits=logits, deltas=deltas, class_ids=class_ids, scores=scores, deltas_out=deltas_out)
+    lib = _lib.load()
+    check(lib.dc_class_select_f32(_ptr(logits), logits.stride(0) if R > 1 else Cn, _ptr(deltas), deltas.stride(0) if R > 1 else 4 * Cn, R, Cn,
+                                  _ptr(class_ids), _ptr(scores), _ptr(deltas_out), _stream()), "dc_class_select_f32")
+    return class_ids, scores, deltas_out
+
+
+def mask_head_tail(x, wd, bd, wm_t, bm, class_ids, out=None):
+    """mrcnn_mask_deconv + ReLU + mrcnn_mask + sigmoid for each RoI's own class (dc_mask_head_tail_f32).  x float32 [N,P,P,Cin]
+    contiguous (P <= 16); wd the Keras Conv2DTranspose kernel [2,2,Cmid,Cin]; bd [Cmid]; wm_t [C,Cmid], the mrcnn_mask kernel
+    transposed (packing.pack_mask_tail); bm [C]; class_ids int32 [N] on the device.  Cin a multiple of 32 up to 256, Cmid a multiple
+    of 32.  Returns out float32 [N,2P,2P]; a class id outside [0,C) gives that RoI zeros.  No alignment rule beyond float32's own (bases off
+    a 16-byte boundary are read 4 bytes at a time).  Shapes, dtypes and strides are checked before the library is loaded."""
+    if x.dim() != 4 or x.shape[0] < 1 or x.shape[1] != x.shape[2] or not 1 <= x.shape[1] <= 16:
+        raise _lib.DcapError("mask_head_tail: x must be [N,P,P,Cin] with N >= 1 and P in 1..16, got %s" % (tuple(x.shape),))
+    N, P, _, Cin = x.shape
+    if Cin % 32 or not 32 <= Cin <= 256:
+        raise _lib.DcapError("mask_head_tail: Cin must be a multiple of 32 in 32..256, got %d" % Cin)
+    if wd.dim() != 4 or tuple(wd.shape[:2]) != (2, 2) or wd.shape[3] != Cin or wd.shape[2] % 32 or wd.shape[2] < 32:
+        raise _lib.DcapError("mask_head_tail: wd must be the Keras deconvolution kernel [2,2,Cmid,%d] with Cmid a multiple of 32, got %s"
+                             % (Cin, tuple(wd.shape)))
+    Cmid = wd.shape[2]
+    if wm_t.dim() != 2 or wm_t.shape[1] != Cmid or wm_t.shape[0] < 1:
+        raise _lib.DcapError("mask_head_tail: wm_t must be [C,%d] (the mrcnn_mask kernel transposed), got %s" % (Cmid, tuple(wm_t.shape)))
+    Cn = wm_t.shape[0]
+    if out is None:
+        out = torch.empty((N, 2 * P, 2 * P), dtype=torch.float32, device=x.device)
+    for name, t, dtype, shape in (("x", x, torch.float32, (N, P, P, Cin)), ("wd", wd, torch.float32, (2, 2, Cmid, Cin)),
+                                  ("bd", bd, torch.float32, (Cmid,)), ("wm_t", wm_t, torch.float32, (Cn, Cmid)),
+                                  ("bm", bm, torch.float32, (Cn,)), ("class_ids", class_ids, torch.int32, (N,)),
+                                  ("out", out, torch.float32, (N, 2 * P, 2 * P))):
+        if t.dtype != dtype:
+            raise _lib.DcapError("mask_head_tail: %s must be %s, got %s" % (name, dtype, t.dtype))
+        if tuple(t.shape) != shape or not t.is_contiguous():
+            raise _lib.DcapError("mask_head_tail: %s must be a contiguous %s tensor, got shape %s strides %s"
+                                 % (name, list(shape), tuple(t.shape), tuple(t.stride())))
+    _on_gpu("mask_head_tail", x=x, wd=wd, bd=bd, wm_t=wm_t, bm=bm, class_ids=class_ids, out=out)
+    lib = _lib.load()
+    d = MaskHeadTailDesc()
+    d.N, d.P, d.Cin, d.Cmid, d.C = N, P, Cin, Cmid, Cn
+    d.x, d.wd, d.bd, d.wm_t, d.bm, d.class_ids, d.out = (x.data_ptr(), wd.data_ptr(), bd.data_ptr(), wm_t.data_ptr(), bm.data_ptr(),
+                                                         class_ids.data_ptr(), out.data_ptr())
+    check(lib.dc_mask_head_tail_f32(C.byref(d), _stream()), "dc_mask_head_tail_f32")
+    return out
+
+
+def mask_paste(masks, boxes, H, W, out=None):
+    """utils.unmold_mask for the M detections of one image (dc_mask_paste_u8): masks float32 [M,h,w] (h, w <= 64), boxes int32 [M,4]
+    (y1, x1, y2, x2) in the original H x W image, both on the device -> uint8 [M,H,W]: scipy's bytescale on each mask's own range,
+    PIL's 8-bit bilinear resize to the box, 1 where the byte is >= 128, 0 elsewhere -- every byte written.  An empty box or one that
+    leaves the image gives zeros.  M = 0 returns an empty tensor.  Shapes and dtypes are checked before the library is loaded."""
+    H, W = int(H), int(W)
+    if masks.dim() != 3 or not (1 <= masks.shape[1] <= 64 and 1 <= masks.shape[2] <= 64):
+        raise _lib.DcapError("mask_paste: masks must be [M,h,w] with h, w in 1..64, got %s" % (tuple(masks.shape),))
+    M, h, w = masks.shape
+    if H < 1 or W < 1 or max(H, W) > 1 << 24 or H * W >= 1 << 31 or M > 65535:
+        raise _lib.DcapError("mask_paste: an image of at least 1 x 1 and below 2^31 pixels and at most 65535 detections, got %d x %d, M %d" % (H, W, M))
+    if out is None:
+        out = torch.empty((M, H, W), dtype=torch.uint8, device=masks.device)
+    for name, t, dtype, shape in (("masks", masks, torch.float32, (M, h, w)), ("boxes", boxes, torch.int32, (M, 4)),
+                                  ("out", out, torch.uint8, (M, H, W))):
+        if t.dtype != dtype:
+            raise _lib.DcapError("mask_paste: %s must be %s, got %s" % (name, dtype, t.dtype))
+        if tuple(t.shape) != shape or not t.is_contiguous():
+            raise _lib.DcapError("mask_paste: %s must be a contiguous %s tensor, got shape %s strides %s"
+                                 % (name, list(shape), tuple(t.shape), tuple(t.stride())))
+    _on_gpu("mask_paste", masks=masks, boxes=boxes, out=out)
+    if M == 0:
+        return out
+    lib = _lib.load()
+    d = MaskPasteDesc()
+    d.M, d.h, d.w, d.H, d.W = M, h, w, H, W
+    d.masks, d.boxes, d.out = masks.data_ptr(), boxes.data_ptr(), out.data_ptr()
+    _launch_ws(lib.dc_mask_paste_u8_workspace_bytes(C.byref(d)), masks.device, lib.dc_mask_paste_u8, C.byref(d))
+    return out
 
 
 def _caption_rows(fn, name, t, rows=None, dim=2):

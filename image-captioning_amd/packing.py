@@ -33,3 +33,10 @@ def pack_conv_kernel_dgrad(k_hwio):
     kh, kw, cin, cout = k_hwio.shape
     rot = k_hwio[::-1, ::-1]                                   # [kh,kw,cin,cout] rotated
     return np.ascontiguousarray(np.transpose(rot, (2, 0, 1, 3)).reshape(cin, kh * kw * cout), dtype=np.float32)
+
+
+def pack_mask_tail(k_mask):
+    """mrcnn_mask's 1x1 kernel ([1,1,Cmid,C] as Keras stores it, or [Cmid,C]) -> [C][Cmid]: dc_mask_head_tail_f32 reads ONE class's
+    column per RoI, which this makes a contiguous row."""
+    k = np.asarray(k_mask, np.float32)
+    return np.ascontiguousarray(k.reshape(k.shape[-2], k.shape[-1]).T)

@@ -92,6 +92,32 @@ def tag_head_weights(seed=6, num_classes=1000, width=1024):
             "roitag_class_logits/bias": np.full(num_classes, -np.log((1.0 - 0.01) / 0.01), F32)}
 
 
+def mask_head_weights(seed=7, num_classes=81, channels=256):
+    """build_fpn_mask_graph's layers under the reference's names, in Keras' shapes: four 3x3 convolutions with BatchNorm,
+    mrcnn_mask_deconv (Conv2DTranspose kernel [2,2,out,in]) and the 1x1 mrcnn_mask."""
+    rng = np.random.default_rng(seed)
+    W = {}
+    for i in (1, 2, 3, 4):
+        conv_weights(rng, "mrcnn_mask_conv%d" % i, 3, channels, channels, W)
+        bn_weights(rng, "mrcnn_mask_bn%d" % i, channels, W)
+    W["mrcnn_mask_deconv/kernel"] = glorot(rng, (2, 2, channels, channels), 4 * channels, 4 * channels)
+    W["mrcnn_mask_deconv/bias"] = (0.01 * rng.standard_normal(channels)).astype(F32)
+    conv_weights(rng, "mrcnn_mask", 1, channels, num_classes, W)
+    return W
+
+
+def detect_head_weights(seed=6, num_classes=81, width=1024, channels=256):
+    """Everything Mask R-CNN puts behind the shared RoI head: mrcnn_class_logits, mrcnn_bbox_fc (fpn_classifier_graph) and the mask
+    head, glorot-uniform kernels as Keras initialises them."""
+    rng = np.random.default_rng(seed)
+    W = {}
+    dense_weights(rng, "mrcnn_class_logits", width, num_classes, W)
+    dense_weights(rng, "mrcnn_bbox_fc", width, 4 * num_classes, W)
+    W["mrcnn_bbox_fc/bias"] = (0.01 * rng.standard_normal(4 * num_classes)).astype(F32)
+    W.update(mask_head_weights(seed + 1, num_classes, channels))
+    return W
+
+
 def head_weights(seed=1, pool=7, cin=256, width=1024):
     rng = np.random.default_rng(seed)
     W = {}

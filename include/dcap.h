@@ -1265,6 +1265,71 @@ typedef struct {
 
 int dc_caption_cider_f64(const dc_caption_cider_desc* d, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Mask R-CNN inference behind the shared RoI head (mask_rcnn/mask_rcnn_model.py; detect.hip).  None of the three allocates,
+ * synchronises or reads back; all are capturable and give identical bits from call to call.
+ *
+ * dc_class_select_f32: per RoI r of logits [R][ld_logits] (C valid columns) and deltas [R][ld_deltas] (4 C valid columns):
+ *   class_ids[r] = the LOWEST index of the maximal logit (the argmax of the logits, not of rounded probabilities);
+ *   scores[r]    = 1 / sum_j exp(z_j - z_max) in float32: accurate expf, the terms of a lane added in index order (j = lane, lane + 64,
+ *                  ...), the 64 lane sums by an xor butterfly -- an order C alone fixes;
+ *   deltas_out[r][0..3] = deltas[r][4 class .. 4 class + 3], the words copied.
+ *   This is mrcnn_class (softmax) + the first three lines of refine_detections (:684-688).  Logits are expected finite.  One wave per
+ *   row.  C is any value from 2 up; strides are free (every access is 4 bytes).  DC_EINVAL: a null pointer, R < 1, C < 2, a stride
+ *   below its row length, a pointer off a 4-byte boundary.
+ * ------------------------------------------------------------------------------------------------ */
+int dc_class_select_f32(const float* logits, int ld_logits, const float* deltas, int ld_deltas, int R, int C, int32_t* class_ids,
+                        float* scores, float* deltas_out, void* stream);
+
+/* dc_mask_head_tail_f32: mrcnn_mask_deconv (Conv2DTranspose 2x2, stride 2, ReLU) fused with mrcnn_mask (1x1, sigmoid) for each RoI's
+ * own class k = class_ids[n] only:
+ *   out[n][2y+dy][2x+dx] = sigmoid(bm[k] + sum_c' relu(bd[c'] + sum_c x[n][y][x][c] * wd[dy][dx][c'][c]) * wm_t[k][c'])
+ *   x [N][P][P][Cin] (the fourth mask convolution's output); wd [2][2][Cmid][Cin], the Keras kernel as it is stored; bd [Cmid];
+ *   wm_t [C][Cmid], the mrcnn_mask kernel [Cmid][C] TRANSPOSED (a class column becomes one contiguous row: packing.pack_mask_tail);
+ *   bm [C]; class_ids int32 [N] in device memory; out [N][2P][2P].
+ * The [N P P, Cin] x [Cin, 4 Cmid] product runs on v_mfma_f32_32x32x2_f32 (exact fp32 products, fp32 accumulation in k order, as
+ * DC_MATH_F32); ReLU, the dot with the class row and the sigmoid are the tile's epilogue, so neither the [N][2P][2P][Cmid] map nor an
+ * all-class map is ever written.  A 128-row tile may hold rows of several RoIs: the class is looked up per row.  The dot over c' is
+ * summed in a fixed order (per lane in channel order, then the two lane halves).  A class id outside [0, C) writes zeros for that
+ * RoI and reads nothing with it.  The sigmoid is evaluated from exp(-|z|): finite and monotone for any finite z.
+ * x, wd and wm_t are read 16 bytes at a time when all three bases sit on 16-byte boundaries and 4 bytes at a time otherwise (the same
+ * products in the same order, so the same bits): no alignment refusal.
+ * DC_EINVAL: a null pointer, N < 1, P outside 1..16, C < 1, Cin not a multiple of 32 in 32..256 (a lane keeps half a pixel's inputs
+ * in registers), Cmid not a multiple of 32 in 32..4096, a pointer off a 4-byte boundary. */
+typedef struct {
+    int N, P, Cin, Cmid, C;
+    const float* x;
+    const float* wd;
+    const float* bd;
+    const float* wm_t;
+    const float* bm;
+    const int32_t* class_ids;
+    float* out;
+} dc_mask_head_tail_desc;
+
+int dc_mask_head_tail_f32(const dc_mask_head_tail_desc* d, void* stream);
+
+/* dc_mask_paste_u8: utils.unmold_mask for the M detections of one image.  masks [M][h][w] float32 (h, w in 1..64), boxes int32 [M][4]
+ * (y1, x1, y2, x2) in the original image, in DEVICE memory (the host need not know them), out uint8 [M][H][W].  Per detection:
+ *   1. scipy 1.0's bytescale with the mask's own minimum and maximum, in float32: scale = (float)(255.0 / (double)(cmax - cmin)) with
+ *      a zero range read as 1; byte = (uint8) trunc(clip((m - cmin) * scale, 0, 255) + 0.5f), one rounding per operation;
+ *   2. PIL.Image.resize((x2 - x1, y2 - y1), BILINEAR) of that 8-bit image: the horizontal-then-vertical integer arithmetic of
+ *      dc_resize_pad_u8, with the same coefficient code;
+ *   3. out[m][y1 + y][x1 + x] = byte >= 128; every byte outside the box is written as 0, so the buffer may be reused.
+ * A box with non-positive area, or one that leaves the image (y1 < 0, x1 < 0, y2 > H, x2 > W), gives a plane of zeros; nothing is
+ * written outside out[m].  Workspace (16-byte aligned): the byte images, the horizontal intermediates (h x W each) and per
+ * detection a coefficient table sized for the largest box the image allows.  Four launches whatever M is; M = 0 launches nothing.
+ * DC_EINVAL: a null pointer (with M > 0), M outside 0..65535, a mask side outside 1..64, H or W outside 1..2^24 or H W >= 2^31. */
+typedef struct {
+    int M, h, w, H, W;
+    const float* masks;
+    const int32_t* boxes;
+    uint8_t* out;
+} dc_mask_paste_desc;
+
+size_t dc_mask_paste_u8_workspace_bytes(const dc_mask_paste_desc* d);
+int    dc_mask_paste_u8(const dc_mask_paste_desc* d, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

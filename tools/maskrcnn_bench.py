@@ -1,0 +1,195 @@
+"""What Mask R-CNN inference costs on the device, and what the fused mask-head tail buys.
+
+1. detect() per image at the reference's inference shape -- 1024 x 1024 molded image (a 768 x 1024 original), ResNet-101, 1000 proposals,
+   81 classes, up to 100 detections, synthetic weights (mrcnn_class_logits spread so that foreground classes win; the count of
+   detections that results is reported) -- with postprocess="host", "device" and "device" with device_masks=True (the masks stay on the device), alternating call by call: wall clock around each call
+   (detect ends in device-to-host copies, so the call is complete when it returns), median of the calls of a repeat, median of the repeats.
+2. The three kernels alone at that shape: ops.class_select (1000 x 81), ops.mask_head_tail (100 RoIs), ops.mask_paste (100 detections
+   into 768 x 1024): device events around each launch, median per repeat, median of the repeats.
+3. The fused tail against the same mathematics composed from what existed before it: ops.gemm to [N 196, 1024] with the bias in its
+   epilogue, torch ReLU, ops.gemm of the [N 784, 256] view (a quadrant's channels are contiguous, so no shuffle is needed in front) to
+   all classes (81 padded to 84 columns), torch sigmoid, gather of each RoI's class, pixel shuffle of the small result.  The two
+   alternate call by call in one process.  fused_wins: composed - fused > the run-to-run spread of the composition's repeats.
+
+    python tools/maskrcnn_bench.py --out profiles/maskrcnn_bench.json
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def emit(rows, **row):
+    rows.append(row)
+    print(json.dumps(row), flush=True)
+
+
+def timed_alternating(call, launches, repeats, warmup):
+    """{name: per-repeat medians (ms)}: device events around every call, the variants alternating call by call."""
+    for _ in range(warmup):
+        for k in call:
+            call[k]()
+    torch.cuda.synchronize()
+    per_repeat = {k: [] for k in call}
+    for _ in range(repeats):
+        ev = {k: [] for k in call}
+        for _ in range(launches):
+            for k in call:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                call[k]()
+                e1.record()
+                ev[k].append((e0, e1))
+        torch.cuda.synchronize()
+        for k in call:
+            per_repeat[k].append(float(np.median([a.elapsed_time(b) for a, b in ev[k]])))
+    return per_repeat
+
+
+def summary(v):
+    return dict(ms=round(float(np.median(v)), 4), repeats_ms=[round(x, 4) for x in v], spread_ms=round(max(v) - min(v), 4))
+
+
+def kernels(own, rows):
+    from image_captioning_amd import ops
+    from image_captioning_amd.packing import pack_mask_tail
+    dev = torch.device("cuda", 0)
+    rng = np.random.RandomState(0)
+    t = lambda a, dt=torch.float32: torch.tensor(np.ascontiguousarray(a), dtype=dt, device=dev)
+    R, C, N, P, Cc = own.proposals, own.classes, own.detections, 14, 256
+    note = "device events around each call, median of %d calls per repeat, variants alternating call by call, median of %d repeats" % (own.launches, own.repeats)
+    # ---- class_select
+    z, d = t(rng.randn(R, C) * 3.0), t(rng.randn(R, 4 * C))
+    ids, sc, dl = torch.empty(R, dtype=torch.int32, device=dev), torch.empty(R, device=dev), torch.empty(R, 4, device=dev)
+    r = timed_alternating({"class_select": lambda: ops.class_select(z, d, class_ids=ids, scores=sc, deltas_out=dl)}, own.launches, own.repeats, own.warmup)
+    emit(rows, what="kernel", kernel="dc_class_select_f32", R=R, C=C, bytes=R * C * 4 + R * 24, timing=note, **summary(r["class_select"]))
+    # ---- the tail, fused and composed
+    x = t(np.maximum(rng.randn(N, P, P, Cc), 0.0))
+    wd, bd = t(rng.randn(2, 2, Cc, Cc) / np.sqrt(Cc)), t(0.1 * rng.randn(Cc))
+    wm, bm = (rng.randn(Cc, C) * 2.0 / np.sqrt(Cc)).astype(np.float32), (0.1 * rng.randn(C)).astype(np.float32)
+    cls = t(rng.randint(1, C, N), torch.int32)
+    wm_t, bm_d = t(pack_mask_tail(wm)), t(bm)
+    out = torch.empty(N, 2 * P, 2 * P, device=dev)
+    Cp = (C + 3) // 4 * 4
+    wm_pad, bm_pad = np.zeros((Cc, Cp), np.float32), np.zeros(Cp, np.float32)
+    wm_pad[:, :C], bm_pad[:C] = wm, bm
+    wm_pad, bm_pad = t(wm_pad), t(bm_pad)
+    wd_flat, bd4 = wd.view(4 * Cc, Cc), bd.repeat(4)
+    g1, g2 = torch.empty(N * P * P, 4 * Cc, device=dev), torch.empty(N * P * P * 4, Cp, device=dev)
+    index = cls.long().view(N, 1, 1).expand(N, P * P * 4, 1)
+
+    def composed():
+        ops.gemm(x.view(N * P * P, Cc), wd_flat, b_trans=True, shift=bd4, out=g1)
+        torch.relu_(g1)
+        ops.gemm(g1.view(N * P * P * 4, Cc), wm_pad, shift=bm_pad, out=g2)
+        torch.sigmoid_(g2)
+        picked = g2.view(N, P * P * 4, Cp).gather(2, index)                      # [N, (y, x, dy, dx), 1]
+        return picked.view(N, P, P, 2, 2).permute(0, 1, 3, 2, 4).reshape(N, 2 * P, 2 * P)
+
+    fused = lambda: ops.mask_head_tail(x, wd, bd, wm_t, bm_d, cls, out=out)
+    diff = float((fused() - composed()).abs().max().item())
+    r = timed_alternating({"fused": fused, "composed": composed}, own.launches, own.repeats, own.warmup)
+    f, c = summary(r["fused"]), summary(r["composed"])
+    flop = 2.0 * N * P * P * Cc * 4 * Cc
+    wins = bool(c["ms"] - f["ms"] > c["spread_ms"])
+    emit(rows, what="mask_tail", variant="fused", kernel="dc_mask_head_tail_f32", N=N, P=P, Cin=Cc, Cmid=Cc, C=C, gemm_flop=flop,
+         tflops=round(flop / (f["ms"] * 1e-3) / 1e12, 2), max_abs_difference_to_composed=diff, fused_wins=wins, timing=note, **f)
+    emit(rows, what="mask_tail", variant="composed", N=N, C=C, intermediate_bytes=int(g1.numel() * 4 + g2.numel() * 4), over_fused=round(c["ms"] / f["ms"], 2),
+         timing=note, **c)
+    # ---- mask_paste
+    H, W = own.image
+    hh, ww = rng.randint(20, H // 2, N), rng.randint(20, W // 2, N)
+    y1, x1 = (rng.rand(N) * (H - hh)).astype(np.int64), (rng.rand(N) * (W - ww)).astype(np.int64)
+    boxes = t(np.stack([y1, x1, y1 + hh, x1 + ww], axis=1), torch.int32)
+    masks = torch.sigmoid(t(rng.randn(N, 2 * P, 2 * P) * 3.0))
+    full = torch.empty(N, H, W, dtype=torch.uint8, device=dev)
+    r = timed_alternating({"mask_paste": lambda: ops.mask_paste(masks, boxes, H, W, out=full)}, max(own.launches // 4, 10), own.repeats, own.warmup)
+    s = summary(r["mask_paste"])
+    emit(rows, what="kernel", kernel="dc_mask_paste_u8", M=N, H=H, W=W, bytes_written=N * H * W, gbytes_per_s=round(N * H * W / (s["ms"] * 1e-3) / 1e9, 1),
+         timing=note, **s)
+    return wins
+
+
+def detect(own, rows):
+    from image_captioning_amd import synth
+    from image_captioning_amd.mask_rcnn_model import MaskRCNN, MaskRCNNConfig
+    S = own.side
+
+    class Cfg(MaskRCNNConfig):
+        IMAGES_PER_GPU = 1
+        IMAGE_MIN_DIM = S
+        IMAGE_MAX_DIM = S
+        POST_NMS_ROIS_INFERENCE = own.proposals
+        DETECTION_MAX_INSTANCES = own.detections
+        DETECTION_MIN_CONFIDENCE = 0
+    cfg = Cfg(own.classes)
+    model = MaskRCNN("inference", cfg, "logs", stage4_blocks=own.stage4_blocks)
+    W = model.get_weights_dict()
+    scaled = {"rpn_conv_shared/kernel": 0.05, "rpn_bbox_pred/kernel": 0.3, "mrcnn_class_conv1/kernel": 0.05, "mrcnn_class_logits/kernel": 10.0,
+              "mrcnn_bbox_fc/kernel": 0.3}
+    model.set_weights({k: W[k] * np.float32(f) for k, f in scaled.items()})
+    img = synth.images(7, 1, own.image[0], own.image[1])[0]
+    modes = {"host": dict(postprocess="host"), "device": dict(postprocess="device"),
+             "device_masks": dict(postprocess="device", device_masks=True)}      # the last leaves the [N,H,W] bytes on the device
+    res = {}
+    for post, kw in modes.items():
+        for _ in range(own.detect_warmup):
+            res[post] = model.detect([img], **kw)[0]
+    same = bool(np.array_equal(res["host"]["masks"], res["device"]["masks"]) and np.array_equal(res["host"]["rois"], res["device"]["rois"]))
+    wall = {k: [] for k in modes}
+    for _ in range(own.repeats):
+        ts = {k: [] for k in modes}
+        for _ in range(own.detect_calls):
+            for post in ts:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                model.detect([img], **modes[post])
+                torch.cuda.synchronize()
+                ts[post].append((time.perf_counter() - t0) * 1e3)
+        for post in ts:
+            wall[post].append(float(np.median(ts[post])))
+    for post in wall:
+        emit(rows, what="detect", postprocess=post, image=list(img.shape[:2]), molded=S, proposals=own.proposals, classes=own.classes,
+             detections=int(len(res[post]["rois"])), mask_pixels=int(res[post]["masks"].sum()), same_results_both_modes=same,
+             mask_bytes=int(len(res[post]["rois"]) * img.shape[0] * img.shape[1]),
+             conv_math=model.conv_math_name, stage4_blocks=own.stage4_blocks,
+             timing="wall clock around each detect() call (it returns host arrays), the modes alternating call by call, median of %d calls per "
+                    "repeat, median of %d repeats" % (own.detect_calls, own.repeats), **summary(wall[post]))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--side", type=int, default=1024)
+    ap.add_argument("--image", type=int, nargs=2, default=[768, 1024], help="the original image's height and width")
+    ap.add_argument("--proposals", type=int, default=1000)
+    ap.add_argument("--classes", type=int, default=81)
+    ap.add_argument("--detections", type=int, default=100)
+    ap.add_argument("--stage4-blocks", type=int, default=22)
+    ap.add_argument("--launches", type=int, default=100)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--detect-calls", type=int, default=10)
+    ap.add_argument("--detect-warmup", type=int, default=3)
+    ap.add_argument("--no-detect", action="store_true")
+    ap.add_argument("--out", default=None)
+    own = ap.parse_args()
+    torch.cuda.set_device(0)
+    rows = []
+    kernels(own, rows)
+    if not own.no_detect:
+        detect(own, rows)
+    if own.out:
+        os.makedirs(os.path.dirname(own.out) or ".", exist_ok=True)
+        with open(own.out, "w") as f:
+            json.dump(dict(device=torch.cuda.get_device_name(0), rows=rows), f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
