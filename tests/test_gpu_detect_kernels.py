@@ -6,6 +6,8 @@ import pytest
 import torch
 
 import _maskrcnn_ref as R
+from _detect_cases import select_case, tail_case
+from _detect_device import dev, run_tail
 
 pytestmark = pytest.mark.gpu
 U = 2.0 ** -24
@@ -20,25 +22,7 @@ def ops():
     return _ops
 
 
-def dev(a, dtype=torch.float32):
-    return torch.tensor(np.ascontiguousarray(a), dtype=dtype, device="cuda")
-
-
 # ---- class_select ------------------------------------------------------------------------------------------------------------------
-def select_case(R_, C, seed=0):
-    """Logits normal * 3 with +-80 planted; ties between equal maximal logits planted in the first rows: two lanes (3 and 70 -> lanes 3
-    and 6 when C = 81), one lane's two passes (5 and 69), neighbours (0 and 1)."""
-    rng = np.random.RandomState(100 * R_ + C + seed)
-    z = (rng.randn(R_, C) * 3.0).astype(np.float32)
-    z.reshape(-1)[rng.permutation(z.size)[:max(2, z.size // 50)]] = rng.choice([80.0, -80.0], max(2, z.size // 50))
-    ties = [(0, 1), (C - 2, C - 1)] + ([(3, 70), (5, 69)] if C > 70 else [])
-    for r, (a, b) in enumerate(ties):
-        if r < R_:
-            z[r, a] = z[r, b] = np.float32(max(81.0, z[r].max() + 1.0)) if r % 2 == 0 else z[r].max() + np.float32(0.5)
-    d = rng.randn(R_, 4 * C).astype(np.float32)
-    return z, d
-
-
 @pytest.mark.parametrize("C", [2, 5, 81])
 @pytest.mark.parametrize("R_", [1, 7, 1000])
 def test_class_select(ops, R_, C):
@@ -76,35 +60,6 @@ def test_class_select_3d_deltas_and_given_outputs(ops):
 
 
 # ---- mask_head_tail ------------------------------------------------------------------------------------------------------------------
-def tail_case(N, Cin, Cmid, C, big=False):
-    rng = np.random.RandomState(N * 1000 + Cin + Cmid + C + (7 if big else 0))
-    P = 14
-    x = np.maximum(rng.randn(N, P, P, Cin), 0.0).astype(np.float32)      # what a ReLU hands over
-    wd = (rng.randn(2, 2, Cmid, Cin) / np.sqrt(Cin)).astype(np.float32)
-    bd = (0.1 * rng.randn(Cmid)).astype(np.float32)
-    wm = (rng.randn(Cmid, C) * 2.0 / np.sqrt(Cmid)).astype(np.float32)
-    bm = (0.1 * rng.randn(C)).astype(np.float32)
-    ids = rng.randint(0, C, N).astype(np.int32)
-    ids[-1] = C - 1
-    if N >= 3:
-        ids[0], ids[1] = 0, (C if N == 3 else -1)                        # one id out of range, between two valid neighbours
-    if big:
-        bm[0], bm[C - 1] = 200.0, -200.0
-    return x, wd, bd, wm, bm, ids
-
-
-def run_tail(ops, case):
-    x, wd, bd, wm, bm, ids = case
-    out = torch.full((x.shape[0], 28, 28), float("nan"), device="cuda")
-    args = (dev(x), dev(wd), dev(bd), dev(np.ascontiguousarray(wm.T)), dev(bm), dev(ids, torch.int32))
-    got = ops.mask_head_tail(*args, out=out)
-    assert got is out
-    first = out.cpu().numpy().copy()
-    again = ops.mask_head_tail(*args).cpu().numpy()
-    assert np.array_equal(first.view(np.int32), again.view(np.int32)), "two calls differ"
-    return first
-
-
 @pytest.mark.parametrize("C", [5, 81])
 @pytest.mark.parametrize("Cin,Cmid", [(256, 256), (64, 32)])
 @pytest.mark.parametrize("N", [1, 3, 101])

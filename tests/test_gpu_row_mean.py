@@ -96,6 +96,32 @@ def test_row_mean_scalar_path(ops):
     assert torch.equal(ops.row_mean(xs), ops.row_mean(torch.tensor(x, device="cuda")))
 
 
+@pytest.mark.parametrize("path", ["vector", "scalar"])
+@pytest.mark.parametrize("C_", [68, 64])
+@pytest.mark.parametrize("K", [127, 128, 129, 256, 257])
+def test_row_mean_tile_edges(ops, K, C_, path):
+    """The double-buffered tile is 128 rows and the next one is fetched while t0 + 128 < K: one row short of a tile, a whole tile
+    (nothing to prefetch), one row into a second tile, two whole tiles, one row into a third.  C = 64 is one block of columns, 68 a
+    second block with one live quad.  scalar: the base 4 bytes past a 16-byte boundary, as in test_row_mean_scalar_path."""
+    x = _x((K, C_), seed=K * 1009 + C_)
+    want = _sequential(x) / np.float32(K)
+    # what these cases are for is the order of the sum across tiles, which 64 columns always show; the division (multiplying by 1 / 128
+    # or 1 / 256 IS dividing, and 1 / 257 differs in a column of a hundred) is told apart on the wider cases above
+    assert not np.array_equal(_pairwise(x) / np.float32(K), want), "this case cannot tell a pairwise sum from the sequential one"
+    assert np.array_equal(want, np.mean(x, axis=0))
+    if path == "vector":
+        xs = torch.tensor(x, device="cuda")
+        assert xs.data_ptr() % 16 == 0
+    else:
+        flat = torch.zeros(K * C_ + 1, dtype=torch.float32, device="cuda")
+        assert flat.data_ptr() % 16 == 0
+        xs = flat[1:].view(K, C_)
+        xs.copy_(torch.tensor(x))
+        assert xs.data_ptr() % 16 == 4
+    got = ops.row_mean(xs).cpu().numpy()
+    assert got.shape == (C_,) and np.array_equal(got.view(np.int32), want.view(np.int32))
+
+
 def test_row_mean_production_size_and_out_reuse(ops):
     x = _x((1000, 12544), seed=8)                 # the RoIAlign block of one image: 50 MB, one launch
     _assert_orders_differ(x[:, :260])
