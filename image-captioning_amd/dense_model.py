@@ -190,6 +190,20 @@ def refine_constants(window, config, image_shape):
     return np.array([window[0], window[1], window[2], window[3], h, w, window[0], window[1], scale, 0.0], np.float64)
 
 
+def pack_survivors(count, boxes, keep, K, parts):
+    """The tail of postprocess='device': ops.refine_generations' count [B], boxes [B,M,4] and keep [B,M] (RoI indices, -1 behind the
+    last survivor) and, of every tensor in `parts` ([B*K, ...] per-RoI rows of 4-byte elements on the device), the survivors' rows, as
+    ONE int32 buffer and ONE device-to-host copy.  Returns (n [B], rois [B,M,4], [each part's rows as int32 [B,M,...]]) on the host:
+    image b's first n[b] rows count, and float payloads are the caller's to view as float32."""
+    B, M = keep.shape
+    rows = (keep.clamp(min=0).long() + torch.arange(B, device=keep.device).unsqueeze(1) * K).reshape(-1)
+    packed = torch.cat([count, boxes.reshape(-1)] + [t.index_select(0, rows).view(torch.int32).reshape(-1) for t in parts])
+    host = packed.cpu().numpy()                          # the one device-to-host copy
+    cuts = np.cumsum([0, B, B * M * 4] + [B * M * int(np.prod(t.shape[1:])) for t in parts])
+    blocks = [host[lo:hi].reshape((B, M) + tuple(t.shape[1:])) for lo, hi, t in zip(cuts[2:], cuts[3:], parts)]
+    return host[:B], host[B:cuts[2]].reshape(B, M, 4), blocks
+
+
 def load_image_gt(dataset, config, image_id, augment=False, rng=np.random, mold="host", loader=None):
     """image (resized + padded), image_meta, gt_captions [G,T], gt_boxes [G,4] (dense_model.py:953-984).
     As in the reference the boxes are handed on exactly as the dataset stores them: they are NOT rescaled or padded
@@ -380,6 +394,22 @@ class _RpnBranch(object):
         torch.cuda.current_stream(self.model.device).wait_stream(self.model._side_stream)
 
 
+def _refuse_step_graph(self, value):
+    if value:
+        raise ValueError("%s: %s" % (type(self).__name__, self.NO_STEP_GRAPH))
+
+
+def _refuse_grad_sync(self, value):
+    if value is not None:
+        raise ValueError("%s: a gradient exchange (ParallelModel / GPU_COUNT > 1) is not available for this class" % type(self).__name__)
+
+
+# use_step_graph and grad_sync as the sub-classes with another top have them (roi_tag_model.ROITagRCNN, mask_rcnn_model.MaskRCNN): always
+# False / None, and assigning anything else is refused by name -- the step graph with the class's own reason, its NO_STEP_GRAPH
+REFUSED_STEP_GRAPH = property(lambda self: False, _refuse_step_graph)
+REFUSED_GRAD_SYNC = property(lambda self: None, _refuse_grad_sync)
+
+
 class DenseImageCapRCNN(object):
     LOSS_NAMES = ("rpn_class_loss", "rpn_bbox_loss", "imgcap_loss")
     LAYER_REGEX = {                       # dense_img_cap/dense_model.py:1829-1845
@@ -390,6 +420,13 @@ class DenseImageCapRCNN(object):
         "all": ".*",
         "caption_only": r"imgcap\_.*",
     }
+    # save_weights' layer_groups: the reference keeps the caption decoder inside TimeDistributed(caption_model, name='imgcap_caption_td'): a
+    # Keras-layout file stores those layers under that group, where its load_weights(by_name=True) finds them (None: every layer of the
+    # model is a top-level Keras layer)
+    SAVE_LAYER_GROUPS = {l: "imgcap_caption_td" for l in ("imgcap_embedding_layer", "imgcap_lstm1", "imgcap_lstm2", "imgcap_lstm_d1", "imgcap_lstm_d2")}
+    # ... in the order of TimeDistributed(Model).weights, which Keras' by-name loader assigns BY POSITION: the wrapped model's
+    # trainable weights in layer order (word_generation_model, dense_model.py:758-784: lstm1, lstm2, d1, d2), then the frozen embedding
+    SAVE_GROUP_MEMBER_ORDER = {"imgcap_caption_td": ["imgcap_lstm1", "imgcap_lstm2", "imgcap_lstm_d1", "imgcap_lstm_d2", "imgcap_embedding_layer"]}
     GT_LOADER = None                      # data_generator's loader: None = the dataset's captions
     PIPELINED_FIT = True                  # _fit may run pipeline.JointTrainPipeline (a sub-class that cannot: False, the serial loop)
 
@@ -416,7 +453,6 @@ class DenseImageCapRCNN(object):
         self.A = len(config.RPN_ANCHOR_RATIOS)
         if 6 * self.A > HEAD_PAD:
             raise ValueError("at most 3 anchors per location")
-        self._seed = int(seed)
         # DCAP_STEP_GRAPH: 0 = every step eagerly, 1 = the captured step graph, unset / auto (round 6) = capture, then KEEP whichever of the
         # two measured faster on this machine over the first steps (HIP events around whole steps: step_graph.PathChooser) -- on the pool's
         # boxes the eager step has been 1 - 2.5 % faster in two rounds of measurements (the replay of a two-branch graph costs more than
@@ -663,13 +699,7 @@ class DenseImageCapRCNN(object):
     def save_weights(self, path):
         """Atomic: written beside the target and renamed, so a reader (or a second rank) never sees a torn file."""
         tmp = path + (".tmp.h5" if path.endswith((".h5", ".hdf5")) else ".tmp.npz")
-        # the reference keeps the caption decoder inside TimeDistributed(caption_model, name='imgcap_caption_td'): a Keras-layout
-        # file stores those layers under that group, where its load_weights(by_name=True) finds them
-        nested = {l: "imgcap_caption_td" for l in ("imgcap_embedding_layer", "imgcap_lstm1", "imgcap_lstm2", "imgcap_lstm_d1", "imgcap_lstm_d2")}
-        # ... in the order of TimeDistributed(Model).weights, which Keras' by-name loader assigns BY POSITION: the wrapped model's
-        # trainable weights in layer order (word_generation_model, dense_model.py:758-784: lstm1, lstm2, d1, d2), then the frozen embedding
-        order = {"imgcap_caption_td": ["imgcap_lstm1", "imgcap_lstm2", "imgcap_lstm_d1", "imgcap_lstm_d2", "imgcap_embedding_layer"]}
-        save_weight_file(tmp, self.get_weights_dict(), layer_groups=nested, group_member_order=order)
+        save_weight_file(tmp, self.get_weights_dict(), layer_groups=self.SAVE_LAYER_GROUPS, group_member_order=self.SAVE_GROUP_MEMBER_ORDER)
         os.replace(tmp, path)
 
     def set_log_dir(self, model_path=None):
@@ -1413,20 +1443,39 @@ class DenseImageCapRCNN(object):
 
     # ---- inference -------------------------------------------------------------------------
     def mold_inputs(self, images):
-        molded, metas, windows = [], [], []
-        for image in images:
-            m, window, scale, padding = utils.resize_image(image, min_dim=self.config.IMAGE_MIN_DIM, max_dim=self.config.IMAGE_MAX_DIM,
-                                                           padding=self.config.IMAGE_PADDING)
-            molded.append(m)                                # mean subtraction happens on the GPU
-            metas.append(utils.compose_image_meta(0, image.shape, window))
-            windows.append(window)
-        return np.stack(molded), np.stack(metas), np.stack(windows)
+        return utils.mold_inputs(images, self.config)
 
     def _mold_device(self, p, images):
         """mold='device': the plan's image buffer written by EncoderPlan.mold_images; returns mold_inputs' windows."""
         cfg = self.config
         geo = p.mold_images(images, cfg.IMAGE_MIN_DIM, cfg.IMAGE_MAX_DIM, cfg.IMAGE_PADDING)
         return np.stack([g[2] for g in geo])
+
+    def _proposal_features(self, images, mold, want_consts):
+        """The front of every inference entry point (generate_captions, roi_tag_model's generate_roi_tags, mask_rcnn_model's detect):
+        images -> the plan's image buffer -> encoder pass -> RPN proposals (kept as last_proposals) -> pooled RoI features.
+        Returns (plan, images, windows, consts, proposals, feats); consts (want_consts: postprocess='device') are the images'
+        refine_constants rows on the device, else None.
+        Order of the checks, the same for every entry point: with mold='device' each image (utils.check_device_mold_image), then the
+        mode and the batch size.  A call that is wrong in both ways raises the image's DeviceMoldError."""
+        if mold == "device":
+            images = [utils.check_device_mold_image(im) for im in images]
+        assert self.mode == "inference", "Create model in inference mode."
+        assert len(images) == self.config.BATCH_SIZE, "len(images) must be equal to BATCH_SIZE"
+        p = self.plan()
+        if mold == "device":
+            molded, windows = None, self._mold_device(p, images)
+        else:
+            molded, _, windows = self.mold_inputs(images)
+            molded = torch.as_tensor(molded)
+        consts = None
+        if want_consts:
+            consts = np.stack([refine_constants(windows[b], self.config, images[b].shape) for b in range(len(images))])
+            consts = torch.as_tensor(consts).to(p.device)   # before the image upload: the stream is idle, nothing waits on this copy
+        p.forward(molded)                                   # (mold='device': None, the plan's image buffer is already written)
+        proposals = p.proposals()
+        self.last_proposals = proposals
+        return p, images, windows, consts, proposals, p.roi_features(boxes_norm=proposals)
 
     def generate_captions(self, images, verbose=0, return_probabilities=True, decoder="prefix", vocab_math=None, beam_size=None, score="logprob",
                           end_id=None, postprocess="host", temperature=None, top_k=None, seed=None, mold="host"):
@@ -1460,22 +1509,11 @@ class DenseImageCapRCNN(object):
         sampling = CaptionModelV1.check_decoder(decoder, return_probabilities, vocab_math,
                                                 getattr(self, "compute_dtype", None) if vocab_math == "bf16" else None, beam_size=beam_size, score=score,
                                                 end_id=end_id, postprocess=postprocess, temperature=temperature, top_k=top_k, seed=seed, mold=mold)
-        if mold == "device":
-            images = [utils.check_device_mold_image(im) for im in images]
-        assert self.mode == "inference", "Create model in inference mode."
-        assert len(images) == self.config.BATCH_SIZE, "len(images) must be equal to BATCH_SIZE"
-        p = self.plan()
-        if mold == "device":
-            molded, windows = None, self._mold_device(p, images)
-        else:
-            molded, metas, windows = self.mold_inputs(images)
-            molded = torch.as_tensor(molded)
+        # (through the class: the front's image check reads nothing of self, and refuses a bad image whatever self is)
+        front = DenseImageCapRCNN._proposal_features(self, images, mold, want_consts=postprocess == "device")
         if postprocess == "device":
-            return self._generate_captions_device(p, images, molded, windows, decoder, vocab_math, beam_size, score, end_id, sampling)
-        p.forward(molded)
-        proposals = p.proposals()
-        self.last_proposals = proposals
-        feats = p.roi_features(boxes_norm=proposals)
+            return self._generate_captions_device(front, decoder, vocab_math, beam_size, score, end_id, sampling)
+        p, images, windows, _, proposals, feats = front
         results = []
         for b in range(len(images)):
             if decoder == "beam":
@@ -1502,16 +1540,11 @@ class DenseImageCapRCNN(object):
             results.append(out)
         return results
 
-    def _generate_captions_device(self, p, images, molded, windows, decoder, vocab_math, beam_size, score, end_id, sampling=None):
-        """generate_captions(postprocess='device'): see there.  The packed int32 result buffer holds, for the batch, the survivor
-        counts [B], the boxes [B,M,4], the survivors' ids [B,M,T] (greedy) or beam tokens [B,M,k,T] and beam scores' bits [B,M,k]."""
+    def _generate_captions_device(self, front, decoder, vocab_math, beam_size, score, end_id, sampling=None):
+        """generate_captions(postprocess='device') behind the front (_proposal_features' results): see there.  pack_survivors' buffer
+        holds the survivors' ids [B,M,T] (greedy) or beam tokens [B,M,k,T] and beam scores' bits [B,M,k]."""
+        _, images, _, consts, proposals, feats = front
         cfg, cm, B = self.config, self.caption_model, len(images)
-        consts = np.stack([refine_constants(windows[b], cfg, images[b].shape) for b in range(B)])
-        consts = torch.as_tensor(consts).to(p.device)       # before the image upload: the stream is idle, nothing waits on this copy
-        p.forward(molded)                                   # (mold='device': None, the plan's image buffer is already written)
-        proposals = p.proposals()
-        self.last_proposals = proposals
-        feats = p.roi_features(boxes_norm=proposals)
         K, M = proposals.shape[1], int(cfg.DETECTION_MAX_INSTANCES)
         # One decode call per image, each into its own output buffer, none of them waited for.  The per-image calls are the host
         # path's, so the scores are its scores bit for bit: one call over the B * K rows chooses the same words, but its GEMMs run at
@@ -1521,25 +1554,15 @@ class DenseImageCapRCNN(object):
             k, T = outs[0][1], outs[0][2]
             views = [decoding.beam_views(o[3], K, k, T) for o in outs]
             toks, sc = (views[0] if B == 1 else tuple(torch.cat([v[i] for v in views]) for i in range(2)))
-            parts = [toks, sc]
             boxes, keep, count, _ = ops.refine_generations(proposals, consts, cfg.DETECTION_NMS_THRESHOLD, M, caption_scores=sc[:, 0])
-        else:
-            views = [decoding.greedy_views(cm._decode_greedy(feats[b], vocab_math, sampling, b * cm.T * K)) for b in range(B)]   # (sampling None: greedy)
-            ids, word_scores = (views[0] if B == 1 else tuple(torch.cat([v[i] for v in views]) for i in range(2)))
-            T, parts = ids.shape[1], [ids]
-            boxes, keep, count, _ = ops.refine_generations(proposals, consts, cfg.DETECTION_NMS_THRESHOLD, M, word_scores=word_scores)
-        rows = (keep.clamp(min=0).long() + torch.arange(B, device=keep.device).unsqueeze(1) * K).reshape(-1)
-        packed = torch.cat([count, boxes.reshape(-1)] + [t.index_select(0, rows).view(torch.int32).reshape(-1) for t in parts])
-        host = packed.cpu().numpy()                          # the one device-to-host copy
-        n, cut = host[:B], B
-        rois = host[cut:cut + B * M * 4].reshape(B, M, 4)
-        cut += B * M * 4
-        if decoder == "beam":
-            beam_ids = host[cut:cut + B * M * k * T].reshape(B, M, k, T)
-            beam_scores = host[cut + B * M * k * T:].view(np.float32).reshape(B, M, k)
+            n, rois, (beam_ids, beam_scores) = pack_survivors(count, boxes, keep, K, [toks, sc])
+            beam_scores = beam_scores.view(np.float32)
             return [{"rois": rois[b, :n[b]].copy(), "ids": beam_ids[b, :n[b], 0].copy(), "beam_ids": beam_ids[b, :n[b]].copy(),
                      "beam_scores": beam_scores[b, :n[b]].copy()} for b in range(B)]
-        ids = host[cut:].reshape(B, M, T)
+        views = [decoding.greedy_views(cm._decode_greedy(feats[b], vocab_math, sampling, b * cm.T * K)) for b in range(B)]   # (sampling None: greedy)
+        ids, word_scores = (views[0] if B == 1 else tuple(torch.cat([v[i] for v in views]) for i in range(2)))
+        boxes, keep, count, _ = ops.refine_generations(proposals, consts, cfg.DETECTION_NMS_THRESHOLD, M, word_scores=word_scores)
+        n, rois, (ids,) = pack_survivors(count, boxes, keep, K, [ids])
         return [{"rois": rois[b, :n[b]].copy(), "ids": ids[b, :n[b]].copy()} for b in range(B)]
 
     # ---- training loop ----------------------------------------------------------------------

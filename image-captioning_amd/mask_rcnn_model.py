@@ -12,12 +12,12 @@ unmold_detections :2253-2312, detect :2314-2354; mask_rcnn/utils.py: apply_box_d
   -> utils.unmold_mask: postprocess="host" in NumPy / PIL, "device" ops.mask_paste and one copy of the [M,H,W] bytes.
 
 Everything below the heads is DenseImageCapRCNN's, unchanged: MaskRCNN sub-classes it and puts DetectTop where the caption model sits.
+detect() starts with the parent's inference front (_proposal_features: mold, encoder pass, proposals, RoIAlign(7)); save_weights is the
+parent's (no layer groups), and the use_step_graph / grad_sync refusals are dense_model's shared properties.
 
 Not in this class (each is refused with a ValueError that names it): mode="training" and the parent's training surface -- train, compile,
 train_on_batch(_device), test_on_batch(_device), forward_backward, set_trainable, plan_pair, use_step_graph, grad_sync -- (the detection
 targets and the class, box and mask losses are not built), compute_dtype="bf16", GPU_COUNT > 1 and generate_captions."""
-import os
-
 import numpy as np
 import torch
 
@@ -25,7 +25,6 @@ from . import dense_model, ops, synth, utils
 from .config import Config
 from .dense_model import DenseImageCapRCNN
 from .packing import pack_conv_kernel, pack_mask_tail
-from .params import ParamStore
 from .text_generation_model import RoiHead
 
 MASK_CONVS = tuple(("mrcnn_mask_conv%d" % i, "mrcnn_mask_bn%d" % i) for i in (1, 2, 3, 4))
@@ -152,15 +151,9 @@ class DetectTop(RoiHead):
         self.mask_pool = int(mask_pool)
         self.device = torch.device(device)
         pool, cin = features_input[0], features_input[2]
-        st = ParamStore(self.device)
-        W = synth.head_weights(seed + 1, pool, cin, self.FEAT)
-        for k in sorted(W):
-            st.add(k, W[k], 'moving_' not in k)
-        for k, v in self.to_stored(synth.detect_head_weights(seed + 6, self.C, self.FEAT)).items():
-            st.add(k, v, False)
-        for name, array, trainable in extra_params:
-            st.add(name, array, trainable)
-        self.store = st.finalize()
+        # the detection layers: frozen entries in front of extra_params, in synth.detect_head_weights' order
+        detect = [(k, v, False) for k, v in self.to_stored(synth.detect_head_weights(seed + 6, self.C, self.FEAT)).items()]
+        self.store = self._build_store(synth.head_weights(seed + 1, pool, cin, self.FEAT), lambda k: 'moving_' in k, detect + list(extra_params))
         self._bufs = {}
         self._folded = None
 
@@ -245,6 +238,8 @@ def _no_training(name):
 
 class MaskRCNN(DenseImageCapRCNN):
     LOSS_NAMES = ()
+    # every layer of this model is a top-level Keras layer (TimeDistributed wrappers carry their inner layer's name)
+    SAVE_LAYER_GROUPS = SAVE_GROUP_MEMBER_ORDER = None
 
     def __init__(self, mode, config, model_dir, device=None, stage4_blocks=22, seed=0, conv_math=None, compute_dtype="f32"):
         if mode != "inference":
@@ -271,23 +266,8 @@ class MaskRCNN(DenseImageCapRCNN):
     test_on_batch, test_on_batch_device, forward_backward = (_no_training(n) for n in ("test_on_batch", "test_on_batch_device", "forward_backward"))
     set_trainable, plan_pair = _no_training("set_trainable"), _no_training("plan_pair")
 
-    @property
-    def use_step_graph(self):
-        return False
-
-    @use_step_graph.setter
-    def use_step_graph(self, value):
-        if value:
-            raise ValueError("MaskRCNN: captured step graphs belong to training, which is not built for this class")
-
-    @property
-    def grad_sync(self):
-        return None
-
-    @grad_sync.setter
-    def grad_sync(self, value):
-        if value is not None:
-            raise ValueError("MaskRCNN: a gradient exchange (ParallelModel / GPU_COUNT > 1) is not available for this class")
+    NO_STEP_GRAPH = "captured step graphs belong to training, which is not built for this class"
+    use_step_graph, grad_sync = dense_model.REFUSED_STEP_GRAPH, dense_model.REFUSED_GRAD_SYNC
 
     def generate_captions(self, *args, **kw):
         raise ValueError("MaskRCNN has no caption decoder: use detect")
@@ -308,13 +288,6 @@ class MaskRCNN(DenseImageCapRCNN):
         DenseImageCapRCNN.set_weights(self, W)
         top._folded = None
 
-    def save_weights(self, path):
-        """Atomic like DenseImageCapRCNN.save_weights; every layer of this model is a top-level Keras layer (TimeDistributed wrappers
-        carry their inner layer's name)."""
-        tmp = path + (".tmp.h5" if path.endswith((".h5", ".hdf5")) else ".tmp.npz")
-        dense_model.save_weight_file(tmp, self.get_weights_dict())
-        os.replace(tmp, path)
-
     # ---- inference -----------------------------------------------------------------------------
     def detect(self, images, verbose=0, postprocess="host", mold="host", device_masks=False):
         """The inference graph + detect (:2314-2354).  Returns, per image, {"rois": int32 [N,4] in the original image, "class_ids": int32
@@ -327,24 +300,11 @@ class MaskRCNN(DenseImageCapRCNN):
         if device_masks and postprocess != "device":
             raise ValueError("device_masks=True needs postprocess='device'")
         utils.check_mold(mold, self.config.IMAGE_PADDING)
-        assert self.mode == "inference", "Create model in inference mode."
-        assert len(images) == self.config.BATCH_SIZE, "len(images) must be equal to BATCH_SIZE"
         cfg, top, B = self.config, self.caption_model, len(images)
         if verbose:
             print("Processing %d images" % B)
-        if mold == "device":
-            images = [utils.check_device_mold_image(im) for im in images]
-        p = self.plan()
-        if mold == "device":
-            molded, windows = None, self._mold_device(p, images)
-        else:
-            molded, _, windows = self.mold_inputs(images)
-            molded = torch.as_tensor(molded)
-        p.forward(molded)
-        proposals = p.proposals()
-        self.last_proposals = proposals
-        K, C = proposals.shape[1], top.C
-        feats = p.roi_features(boxes_norm=proposals)
+        p, images, windows, _, proposals, feats = self._proposal_features(images, mold, want_consts=False)
+        K = proposals.shape[1]
         z, d = top.heads(feats.view(B * K, cfg.POOL_SIZE, cfg.POOL_SIZE, 256))
         self.last_heads = (z, d)
         # proposals, ids, scores and deltas leave in one buffer of 10 words per RoI: ids as their bits

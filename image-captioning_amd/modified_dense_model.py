@@ -137,15 +137,7 @@ class DenseImageCapRCNN(object):
 
     # ---- reference API -------------------------------------------------------------------
     def mold_inputs(self, images):
-        molded, metas, windows = [], [], []
-        for image in images:
-            m, window, scale, padding = utils.resize_image(image, min_dim=self.config.IMAGE_MIN_DIM,
-                                                           max_dim=self.config.IMAGE_MAX_DIM,
-                                                           padding=self.config.IMAGE_PADDING)
-            molded.append(m)                                # mean subtraction happens on the GPU
-            metas.append(compose_image_meta(0, image.shape, window))
-            windows.append(window)
-        return np.stack(molded), np.stack(metas), np.stack(windows)
+        return utils.mold_inputs(images, self.config)
 
     def generate_captions(self, images, rois=None, verbose=0, device_features=False, mold="host", image_level=False):
         """images: list of [H,W,3] uint8; rois: [len(images), N, 4] (y1,x1,y2,x2) pixels.

@@ -12,18 +12,18 @@ The joint dense-captioning graph (dense_model.DenseImageCapRCNN) with the captio
 Everything below the top is DenseImageCapRCNN's step, unchanged: ROITagRCNN sub-classes it and puts TagTop where the caption model
 sits (DenseImageCapRCNN._make_top).  The detection-target kernel gathers any int32 [n_gt, T] rows, so it runs as it is with
 T = NUM_CLASSES; negatives and padding come out as all-zero rows, which the loss kernel treats as dead: no count, no row weights.
+Inference shares the parent's pieces too: generate_roi_tags starts with its front (_proposal_features: mold, encoder pass, proposals,
+RoIAlign) and packs postprocess='device' results with dense_model.pack_survivors; save_weights is the parent's (no layer groups).
 
 Not in this class (each is refused with a ValueError that names it): compute_dtype="bf16", GPU_COUNT > 1 / ParallelModel,
 pipeline.JointTrainPipeline (train() runs the serial loop) and captured step graphs -- every step is issued eagerly and
 DCAP_STEP_GRAPH does not apply."""
-import os
-
 import numpy as np
 import torch
 
 from . import dense_model, ops, synth, utils
 from .dense_model import DenseImageCapRCNN
-from .params import SGD, ParamStore
+from .params import SGD
 from .text_generation_model import RoiHead
 
 def load_rois_and_tags(dataset, image_id):
@@ -70,12 +70,7 @@ class TagTop(RoiHead):
         pool, cin = features_input[0], features_input[2]
         W = dict(synth.head_weights(seed + 1, pool, cin, self.FEAT))
         W.update(synth.tag_head_weights(seed + 6, self.C, self.FEAT))
-        st = ParamStore(self.device)
-        for k in sorted(W):
-            st.add(k, W[k], 'moving_' not in k)
-        for name, array, trainable in extra_params:
-            st.add(name, array, trainable)
-        self.store = st.finalize()
+        self.store = self._build_store(W, lambda k: 'moving_' in k, extra_params)
         self.grad_sync = None
         self._bufs = {}
         self._steps = {}
@@ -122,6 +117,7 @@ class ROITagRCNN(DenseImageCapRCNN):
         "5+": r"(res5.*)|(bn5.*)|(roitag\_.*)|(rpn\_.*)|(fpn\_.*)|(mrcnn\_.*)",
         "all": ".*",
     }
+    SAVE_LAYER_GROUPS = SAVE_GROUP_MEMBER_ORDER = None       # every layer of this model is a top-level Keras layer
     GT_LOADER = staticmethod(load_rois_and_tags)
     PIPELINED_FIT = False
     FOCAL_ALPHA, FOCAL_GAMMA = 0.25, 2.0  # focal_loss' defaults (model.py:48)
@@ -142,23 +138,8 @@ class ROITagRCNN(DenseImageCapRCNN):
                       gamma=self.FOCAL_GAMMA)
 
     # ---- what this class refuses -------------------------------------------------------------
-    @property
-    def use_step_graph(self):
-        return False
-
-    @use_step_graph.setter
-    def use_step_graph(self, value):
-        if value:
-            raise ValueError("ROITagRCNN: captured step graphs are not available for this class (its steps are issued eagerly)")
-
-    @property
-    def grad_sync(self):
-        return None
-
-    @grad_sync.setter
-    def grad_sync(self, value):
-        if value is not None:
-            raise ValueError("ROITagRCNN: a gradient exchange (ParallelModel / GPU_COUNT > 1) is not available for this class")
+    NO_STEP_GRAPH = "captured step graphs are not available for this class (its steps are issued eagerly)"
+    use_step_graph, grad_sync = dense_model.REFUSED_STEP_GRAPH, dense_model.REFUSED_GRAD_SYNC
 
     def plan_pair(self):
         raise ValueError("ROITagRCNN: pipeline.JointTrainPipeline is not available for this class: train() runs the serial loop")
@@ -186,12 +167,6 @@ class ROITagRCNN(DenseImageCapRCNN):
             optimizer = SGD(lr=learning_rate, momentum=self.config.LEARNING_MOMENTUM if momentum is None else momentum, clipnorm=5.0)
         DenseImageCapRCNN.compile(self, learning_rate, optimizer)
 
-    def save_weights(self, path):
-        """Atomic like DenseImageCapRCNN.save_weights; every layer of this model is a top-level Keras layer."""
-        tmp = path + (".tmp.h5" if path.endswith((".h5", ".hdf5")) else ".tmp.npz")
-        dense_model.save_weight_file(tmp, self.get_weights_dict())
-        os.replace(tmp, path)
-
     def train(self, train_dataset, val_dataset, learning_rate, epochs, layers, rpn_targets="host", mold="host", prefetch=0, optimizer=None):
         """model.py:1720-1790: the generators, set_trainable(layers), compile(learning_rate, config.LEARNING_MOMENTUM), a checkpoint per
         epoch; the keywords are DenseImageCapRCNN.train's.  layers="no_rpn" trains every ResNet convolution but only the bn3* BatchNorms:
@@ -213,36 +188,16 @@ class ROITagRCNN(DenseImageCapRCNN):
         if postprocess not in ("host", "device"):
             raise ValueError("postprocess must be 'host' or 'device', got %r" % (postprocess,))
         utils.check_mold(mold, self.config.IMAGE_PADDING)
-        assert self.mode == "inference", "Create model in inference mode."
-        assert len(images) == self.config.BATCH_SIZE, "len(images) must be equal to BATCH_SIZE"
+        _, images, windows, consts, proposals, feats = self._proposal_features(images, mold, want_consts=postprocess == "device")
         cfg, B = self.config, len(images)
-        if mold == "device":
-            images = [utils.check_device_mold_image(im) for im in images]
-        p = self.plan()
-        if mold == "device":
-            molded, windows = None, self._mold_device(p, images)
-        else:
-            molded, _, windows = self.mold_inputs(images)
-            molded = torch.as_tensor(molded)
-        if postprocess == "device":
-            consts = np.stack([dense_model.refine_constants(windows[b], cfg, images[b].shape) for b in range(B)])
-            consts = torch.as_tensor(consts).to(p.device)   # before the image upload: nothing waits on this copy
-        p.forward(molded)
-        proposals = p.proposals()
-        self.last_proposals = proposals
-        feats = p.roi_features(boxes_norm=proposals)
         K, C, M = proposals.shape[1], self.caption_model.C, int(cfg.DETECTION_MAX_INSTANCES)
         _, z = self.caption_model.logits(feats.view(B * K, cfg.POOL_SIZE, cfg.POOL_SIZE, 256))
         probs, scores = ops.tag_scores(z, cfg.DETECTION_MIN_CONFIDENCE, probs=self._buf("tag_probs", (B * K, C)), scores=self._buf("tag_scores", (B * K,)))
         self.last_tags = (probs, scores)
         if postprocess == "device":
             boxes, keep, count, _ = ops.refine_generations(proposals, consts, cfg.DETECTION_NMS_THRESHOLD, M, caption_scores=scores)
-            rows = (keep.clamp(min=0).long() + torch.arange(B, device=keep.device).unsqueeze(1) * K).reshape(-1)
-            packed = torch.cat([count, boxes.reshape(-1), probs.index_select(0, rows).view(torch.int32).reshape(-1)])
-            host = packed.cpu().numpy()                      # the one device-to-host copy
-            n = host[:B]
-            rois = host[B:B + B * M * 4].reshape(B, M, 4)
-            tags = host[B + B * M * 4:].view(np.float32).reshape(B, M, C)
+            n, rois, (tags,) = dense_model.pack_survivors(count, boxes, keep, K, [probs])
+            tags = tags.view(np.float32)
             return [{"rois": rois[b, :n[b]].copy(), "tags": tags[b, :n[b]].copy()} for b in range(B)]
         props_h, probs_h, scores_h = proposals.cpu().numpy(), probs.cpu().numpy().reshape(B, K, C), scores.cpu().numpy().reshape(B, K)
         results = []

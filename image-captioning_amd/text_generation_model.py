@@ -166,6 +166,17 @@ class RoiHead(KerasLikeModel):
     FEAT = 1024
     HEAD = (("mrcnn_class_conv1", "mrcnn_class_bn1"), ("mrcnn_class_conv2", "mrcnn_class_bn2"))
 
+    def _build_store(self, W, frozen, extra_params):
+        """The flat parameter bucket of a top: its own weights W in sorted order (frozen(name): no gradient), then extra_params'
+        (name, array, trainable) entries in their order -- the bucket's layout, and with it every captured graph, checkpoint and
+        gradient range, is this order."""
+        st = ParamStore(self.device)
+        for k in sorted(W):
+            st.add(k, W[k], not frozen(k))
+        for name, array, trainable in extra_params:
+            st.add(name, array, trainable)
+        return st.finalize()
+
     # ---------------------------------------------------------------------------------- engine
     def _act(self, key, f):
         return _Act(self, key, f)
@@ -273,18 +284,11 @@ class CaptionModelV1(RoiHead):
         W = dict(synth.head_weights(seed + 1, pool, cin, self.FEAT))
         W.update(synth.v1_weights(seed + 2, self.V, self.E, units, self.FEAT))
         W['imgcap_embedding_layer/embeddings'] = np.asarray(config.EMBEDDING_WEIGHTS, np.float32)
-        st = ParamStore(self.device)
-        own = []
-        for k in sorted(W):
-            frozen = k.startswith('imgcap_embedding') or 'moving_' in k
-            st.add(k, W[k], not frozen)
-            if not frozen and k.endswith('kernel') and 'recurrent' not in k:
-                own.append(k)
-        for name, array, trainable in extra_params:
-            st.add(name, array, trainable)
-        self.store = st.finalize()
+        frozen = lambda k: k.startswith('imgcap_embedding') or 'moving_' in k
+        self.store = self._build_store(W, frozen, extra_params)
         if compute_dtype == "bf16":
-            st.enable_bf16_shadow(own)                    # GEMM kernels only: biases, BN parameters and the recurrences stay fp32
+            own = [k for k in sorted(W) if not frozen(k) and k.endswith('kernel') and 'recurrent' not in k]
+            self.store.enable_bf16_shadow(own)            # GEMM kernels only: biases, BN parameters and the recurrences stay fp32
         self.grad_sync = None
         self._bufs = {}
         self._steps = {}                          # captured train steps by batch shape (step_graph.CapturedStep)

@@ -242,6 +242,17 @@ def mold_image(images, config):
     return images.astype(np.float32) - config.MEAN_PIXEL
 
 
+def mold_inputs(images, config):
+    """The models' mold_inputs: every image resized and padded -> (molded uint8 [B,H,W,3], image metas, windows)."""
+    molded, metas, windows = [], [], []
+    for image in images:
+        m, window, scale, padding = resize_image(image, min_dim=config.IMAGE_MIN_DIM, max_dim=config.IMAGE_MAX_DIM, padding=config.IMAGE_PADDING)
+        molded.append(m)                                # mean subtraction happens on the GPU
+        metas.append(compose_image_meta(0, image.shape, window))
+        windows.append(window)
+    return np.stack(molded), np.stack(metas), np.stack(windows)
+
+
 def generate_anchors(scales, ratios, shape, feature_stride, anchor_stride):
     """Anchors of one pyramid level, [H*W*len(ratios), (y1,x1,y2,x2)] in image pixels, ordered
     (y, x, ratio) -- the order rpn_graph's reshape gives the RPN outputs (utils.py:333-369)."""

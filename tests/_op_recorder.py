@@ -1,0 +1,70 @@
+"""The recorder of op calls that the launch-sequence tests share (test_gpu_joint_launch_sequence.py, test_gpu_inference_call_sequence.py),
+and the stand-in gradient exchange whose ready() calls it records.  A plain module, no fixtures; the package is imported inside the
+functions, as in the test files."""
+import types
+
+import torch
+
+
+class StubExchange(object):
+    """A gradient exchange of two ranks without a second process: ready() only records, the final call returns the scale 1.0."""
+    world = 2
+
+    def __init__(self):
+        self.seen = []                                     # (lo, hi) in the order announced
+
+    def ready(self, flat, lo, hi):
+        self.seen.append((lo, hi))
+
+    def __call__(self, flat):
+        return 1.0
+
+
+class Recorder(object):
+    """Wraps every public function of ops (top-level calls only: what an op calls inside itself is its own business) and a StubExchange's
+    ready() while `with` holds.  seq: the names in order; reg: [(lo, hi)] of the l2_reg calls that write a gradient range."""
+
+    def __init__(self, model):
+        self.model, self.seq, self.reg, self.depth = model, [], [], 0
+
+    def _wrap(self, name, fn):
+        def call(*a, **k):
+            if self.depth == 0:
+                side = self.model._side_stream
+                self.seq.append(name + "@side" if side is not None and torch.cuda.current_stream() == side else name)
+                if name == "l2_reg" and (len(a) > 2 and a[2] is not None or k.get("grad") is not None):
+                    lo = (a[0].data_ptr() - self.model.store.flat.data_ptr()) // 4
+                    self.reg.append((lo, lo + a[0].numel()))
+            self.depth += 1
+            try:
+                return fn(*a, **k)
+            finally:
+                self.depth -= 1
+        return call
+
+    def __enter__(self):
+        from image_captioning_amd import ops
+        st = self.model.store
+        layers = {}
+        for name in st.trainable_names:
+            layer = name.split("/")[0]
+            try:
+                layers[tuple(st.layer_range(layer))] = layer
+            except KeyError:
+                pass
+        self.saved = {n: f for n, f in vars(ops).items() if isinstance(f, types.FunctionType) and not n.startswith("_")}
+        for n, f in self.saved.items():
+            setattr(ops, n, self._wrap(n, f))
+        sync = self.model.grad_sync
+        if isinstance(sync, StubExchange):
+            sync.seen = []
+            side = lambda: "@side" if self.model._side_stream is not None and torch.cuda.current_stream() == self.model._side_stream else ""
+            sync.ready = lambda flat, lo, hi: (self.seq.append("ready:%s%s" % (layers[(lo, hi)], side())), sync.seen.append((lo, hi)))[1]
+        return self
+
+    def __exit__(self, *exc):
+        from image_captioning_amd import ops
+        for n, f in self.saved.items():
+            setattr(ops, n, f)
+        if isinstance(self.model.grad_sync, StubExchange):
+            del self.model.grad_sync.ready
