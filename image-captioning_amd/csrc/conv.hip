@@ -230,7 +230,8 @@ extern "C" size_t dc_conv2d_workspace_bytes(const dc_conv_desc* d) {
     conv_dims(d, stem, M, N, K);
     if (!stem && conv_winograd_supported(d)) return 0;
     const TileChoice t = conv_tile(d, M, N, K);
-    return t.split > 1 ? (size_t)t.split * M * N * sizeof(float) : 0;
+    const int slices = igemm_slices(K, t.split);
+    return slices > 1 ? (size_t)slices * M * N * sizeof(float) : 0;
 }
 
 extern "C" int dc_conv2d_tile_config(const dc_conv_desc* d, int* bm, int* bn, int* split_k) {
@@ -347,7 +348,8 @@ static TileChoice wgrad_tile(const dc_conv_desc* d) {
 extern "C" size_t dc_conv2d_wgrad_workspace_bytes(const dc_conv_desc* d) {
     if (wgrad_validate(d)) return 0;
     const TileChoice t = wgrad_tile(d);
-    return t.split > 1 ? (size_t)t.split * d->Cout * d->kh * d->kw * d->Cin * sizeof(float) : 0;
+    const int slices = igemm_slices(d->N * d->Ho * d->Wo, t.split);
+    return slices > 1 ? (size_t)slices * d->Cout * d->kh * d->kw * d->Cin * sizeof(float) : 0;
 }
 
 extern "C" int dc_conv2d_wgrad_tile_config(const dc_conv_desc* d, int* bm, int* bn, int* split_k) {

@@ -122,7 +122,8 @@ extern "C" size_t dc_gemm_workspace_bytes(const dc_gemm_desc* d) {
     dc_gemm_desc bulk, tail;
     if (gemm_split_tail(d, &bulk, &tail)) d = &bulk;
     const TileChoice t = gemm_tile(d);
-    return t.split > 1 ? (size_t)t.split * d->M * d->N * sizeof(float) : 0;
+    const int slices = igemm_slices(d->K, t.split);
+    return slices > 1 ? (size_t)slices * d->M * d->N * sizeof(float) : 0;
 }
 
 extern "C" int dc_gemm_tile_config(const dc_gemm_desc* d, int* bm, int* bn, int* split_k) {

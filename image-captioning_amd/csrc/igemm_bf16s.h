@@ -220,11 +220,8 @@ template <int BM, int BN, class AL, class BL, int NP = 3>
 int launch_igemm_bs(const AL& al, const BL& bl, const Epilogue& ep, int M, int N, int K, int split_k, void* workspace,
                     size_t workspace_bytes, hipStream_t stream) {
     const int tiles = ((M + BM - 1) / BM) * ((N + BN - 1) / BN);
-    const int ktiles = (K + BK - 1) / BK;
-    if (split_k < 1) split_k = 1;
-    if (split_k > ktiles) split_k = ktiles;
-    const int klen = ((ktiles + split_k - 1) / split_k) * BK;
-    split_k = (K + klen - 1) / klen;
+    const int klen = igemm_slice_len(K, split_k);
+    split_k = igemm_slices(K, split_k);
     float* partial = nullptr;
     if (split_k > 1) {
         const size_t need = (size_t)split_k * M * N * sizeof(float);

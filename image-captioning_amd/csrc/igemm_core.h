@@ -1025,16 +1025,27 @@ bool conv_winograd_split_bf16(const dc_conv_desc* d);
 int conv_winograd_tiles(const dc_conv_desc* d);
 int conv2d_winograd(const dc_conv_desc* d, hipStream_t s);
 
+// The slices a split-K launch really runs: `split_k` (the tile rule's factor, or the caller's) cuts K into slices of whole BK-deep
+// K-tiles, so 28 asked of 256 K-tiles run as 26 slices (25 of 10 K-tiles, one of 6) and 32 asked of 144 as 29.  The launchers size their
+// grid and their slab check by it, and the dc_*_workspace_bytes queries report it: the size a query gives is the size the launch checks.
+inline int igemm_slice_len(int K, int split_k) {
+    const int ktiles = (K + BK - 1) / BK;
+    if (split_k < 1) split_k = 1;
+    if (split_k > ktiles) split_k = ktiles;
+    return ((ktiles + split_k - 1) / split_k) * BK;
+}
+inline int igemm_slices(int K, int split_k) {
+    const int klen = igemm_slice_len(K, split_k);
+    return (K + klen - 1) / klen;
+}
+
 // Host-side launch helper.  PC = true selects the producer / consumer kernel (64x64 tiles).
 template <int BM, int BN, class AL, class BL, bool PC = false>
 int launch_igemm(const AL& al, const BL& bl, const Epilogue& ep, int M, int N, int K, int split_k, void* workspace,
                  size_t workspace_bytes, hipStream_t stream) {
     const int tiles = ((M + BM - 1) / BM) * ((N + BN - 1) / BN);
-    const int ktiles = (K + BK - 1) / BK;
-    if (split_k < 1) split_k = 1;
-    if (split_k > ktiles) split_k = ktiles;
-    const int klen = ((ktiles + split_k - 1) / split_k) * BK;
-    split_k = (K + klen - 1) / klen;
+    const int klen = igemm_slice_len(K, split_k);
+    split_k = igemm_slices(K, split_k);
     float* partial = nullptr;
     if (split_k > 1) {
         const size_t need = (size_t)split_k * M * N * sizeof(float);

@@ -76,7 +76,9 @@ int    dc_gemm_f32(const dc_gemm_desc* d, void* workspace, size_t workspace_byte
  * dc_gemm_f32 picks for `d`, from the rule the launch itself applies.  For a K that is not a multiple of 32 and is run as a bulk launch
  * plus a range-checked tail launch, the answer is the bulk launch's (the tail accumulates onto it on 64 x 64 tiles, unsplit).
  * *split_k is the factor the rule hands to the launch, which then cuts K into slices of whole 32-deep K-tiles: 28 asked of 256 K-tiles
- * run as 26 slices (25 of 10 K-tiles, one of 6).  dc_conv2d_tile_config and dc_conv2d_wgrad_tile_config report it the same way. */
+ * run as 26 slices (25 of 10 K-tiles, one of 6).  dc_conv2d_tile_config and dc_conv2d_wgrad_tile_config report it the same way.
+ * dc_gemm_workspace_bytes, dc_conv2d_workspace_bytes and dc_conv2d_wgrad_workspace_bytes count the slices that run (26 slabs there):
+ * the size a query gives is the size the launch checks, and one byte less is refused with DC_EWORKSPACE. */
 int    dc_gemm_tile_config(const dc_gemm_desc* d, int* bm, int* bn, int* split_k);
 
 /* ------------------------------------------------------------------------------------------------
