@@ -46,14 +46,36 @@ class CSVLogger(object):
             w.writerow([epoch] + [logs[k] for k in self._keys])
 
 
+def target_ids(y, ids_rank, vocab=None):
+    """The targets of a Keras batch as int32 ids: y holds ids already (rank ids_rank: returned as int32, within [0, vocab) when vocab is
+    given) or the one-hot rows of those ids along one more axis, as the reference's generators yield them (each row of width vocab, when
+    given, and exactly one 1 among zeros)."""
+    y = np.asarray(y)
+    if y.ndim == ids_rank:
+        if vocab is not None and y.size and (y.min() < 0 or y.max() >= vocab):
+            raise ValueError("target ids must lie in [0, %d)" % vocab)
+        return y.astype(np.int32)
+    if (vocab is not None and y.shape[-1] != vocab) or not (np.all(y.max(-1) == 1) and np.all(y.sum(-1) == 1)):
+        raise ValueError("targets must be one-hot rows%s (as the reference's data_generator yields) or int ids of rank %d"
+                         % ("" if vocab is None else " of width %d" % vocab, ids_rank))
+    return y.argmax(-1).astype(np.int32)
+
+
 class KerasLikeModel(object):
-    """Sub-classes provide: self.store (ParamStore), self.device, self._bufs, self.grad_sync, _forward_train(), _backward(), train_step() and predict().
+    """Sub-classes provide: self.store (ParamStore), self.device, _init_runtime() in their constructor, _forward_train(), _backward(), what
+    train_step asks about a batch (_step_key, _stage_batch), the *_on_batch_device forms and predict().
     _backward() announces finished layer ranges to self.grad_sync.ready (when the exchange has one); nothing per-step is stored on the model for it."""
 
     optimizer = None
     loss = None
     MAX_STEP_GRAPHS = 4        # batch shapes kept as captured graphs; further shapes run eagerly
     use_step_graph = True      # (one GPU) replay the train step from a hipGraph; DCAP_STEP_GRAPH=0 overrides
+
+    def _init_runtime(self):
+        """What a step keeps on the model beside its weights."""
+        self.grad_sync = None                     # set by ParallelModel: called between backward and the update
+        self._bufs = {}                           # scratch buffers by name (_buf)
+        self._steps = {}                          # captured train steps by batch shape (step_graph.CapturedStep)
 
     def compile(self, optimizer, loss=None):
         """optimizer: a params.Adam / params.SGD instance, or "adam" / "sgd" (Keras' defaults)."""
@@ -98,14 +120,72 @@ class KerasLikeModel(object):
         finally:
             self._bufs = own
 
-    def _train_step_eager(self, *batch):
-        """The step launch by launch: forward (batch: what the sub-class's _forward_train takes), loss, backward, (all-reduce), the optimizer's launch."""
-        loss_rows, _ = self._forward_train(*batch, want_grad=True)
-        loss = ops.mean(loss_rows, out=self._buf('loss', (1,)))
+    def _grads_ready(self, *layers):
+        """Data parallel: these layers' gradients are final -- start their all-reduce while the backward goes on."""
+        if self.grad_sync is not None and hasattr(self.grad_sync, 'ready'):
+            for layer in layers:
+                lo, hi = self.store.layer_range(layer)
+                self.grad_sync.ready(self.store.flat_grad, lo, hi)
+
+    def _step_loss(self, loss_rows, *batch):
+        """The step's loss tensor from the forward pass's loss rows (batch: the step's, for a sub-class that reports more than the loss)."""
+        return ops.mean(loss_rows, out=self._buf('loss', (1,)))
+
+    def _step_launches(self, *batch, lr_t_dev=None, **forward_kw):
+        """THE train step, launch by launch: forward (batch, forward_kw: what the sub-class's _forward_train takes), loss, backward,
+        (all-reduce), the optimizer's launch.  Issued as it stands (lr_t_dev None: the update's step word is a launch argument and an
+        attached gradient exchange runs between backward and update) and as the body of a captured step (lr_t_dev: the device word the
+        replayed update reads it from; a step with an exchange attached is never captured, _captured_step)."""
+        loss_rows, _ = self._forward_train(*batch, want_grad=True, **forward_kw)
+        loss = self._step_loss(loss_rows, *batch)
         self._backward()
-        scale = self.grad_sync(self.store.flat_grad) if self.grad_sync is not None else 1.0
-        self.optimizer.apply(self.store, grad_scale=scale)
+        scale = self.grad_sync(self.store.flat_grad) if lr_t_dev is None and self.grad_sync is not None else 1.0
+        self.optimizer.apply(self.store, grad_scale=scale, lr_t_dev=lr_t_dev)
         return loss
+
+    def _train_step_eager(self, *batch):
+        return self._step_launches(*batch)
+
+    # What a sub-class says about its step: _step_key, _stage_batch and, with host counters of its own, the three _counters hooks.
+    def _step_key(self, *batch):
+        """What the captured launches bake of this batch, the feature shape first; None: this batch never replays."""
+        raise NotImplementedError
+
+    def _stage_batch(self, cs, new, *batch):
+        """Bring the batch into cs's persistent buffers (new: make them first) -> (the staged batch, forward_kw, the device lr_t word)."""
+        raise NotImplementedError
+
+    def _stage_lr_t(self, cs, new):
+        """The step word of the coming update as a one-word upload of its own -> its device view (for batches that are on the device already)."""
+        if new:
+            cs.scalars = step_graph.PackedInputs(self.device, [("lr_t", 1)])
+        cs.scalars.upload({"lr_t": step_graph.lr_word(self.optimizer)})
+        return cs.scalars.view("lr_t", torch.float32)
+
+    def _counters(self):
+        """The host-side counters a step advances (restored when a capture fails: the eager retry advances them again)."""
+        return self.optimizer.iterations
+
+    def _set_counters(self, v):
+        self.optimizer.iterations = v
+
+    def _advance_counters(self, cs):
+        """What the captured Python did once, by hand after every replay of cs."""
+        self.optimizer.iterations += 1
+
+    def train_step(self, *batch):
+        """forward + loss + backward + (all-reduce) + the optimizer's update on what the sub-class's _forward_train takes; the loss terms
+        as a DEVICE tensor (no sync).  With use_step_graph (one GPU; DCAP_STEP_GRAPH=0 overrides) the step is replayed from a hipGraph
+        captured on the third call with a batch shape (step_graph.py): the batch reaches it through the shape's persistent buffers."""
+        if self.optimizer is None:
+            raise RuntimeError("compile(optimizer, loss) first")
+        key = self._step_key(*batch)
+        cs, new = (None, False) if key is None else self._captured_step(tuple(key) + (self.optimizer.baked_key(),), batch[0])
+        if cs is None:
+            return self._step_launches(*batch)
+        staged, forward_kw, lr_t_dev = self._stage_batch(cs, new, *batch)
+        return self._run_captured(cs, lambda: self._step_launches(*staged, lr_t_dev=lr_t_dev, **forward_kw), self._counters, self._set_counters,
+                                  lambda: self._advance_counters(cs))
 
     @property
     def trainable_weights(self):
@@ -121,6 +201,14 @@ class KerasLikeModel(object):
     def save_weights(self, path):
         save_weight_file(path, self.get_weights_dict())
 
+    def _stored_shape(self, name):
+        """The shape `name` has in a weight file (a sub-class that holds a weight in another layout than Keras': with _to_held)."""
+        return tuple(self.store.w[name].shape)
+
+    def _to_held(self, name, array):
+        """A stored array in the layout the model holds it in."""
+        return array
+
     def load_weights(self, filepath, by_name=False, skip_mismatch=False):
         loaded = load_weight_file(filepath) if isinstance(filepath, str) else dict(filepath)
         for k, v in loaded.items():
@@ -128,11 +216,11 @@ class KerasLikeModel(object):
                 if by_name:
                     continue
                 raise KeyError("weight %s is not part of this model" % k)
-            if tuple(np.shape(v)) != tuple(self.store.w[k].shape):
+            if tuple(np.shape(v)) != self._stored_shape(k):
                 if skip_mismatch:
                     continue
-                raise ValueError("shape mismatch for %s" % k)
-            self.store.assign(k, v, refresh=False)
+                raise ValueError("shape mismatch for %s: %s vs %s" % (k, tuple(np.shape(v)), self._stored_shape(k)))
+            self.store.assign(k, self._to_held(k, v), refresh=False)
         self._weights_changed()
 
     def _weights_changed(self):
@@ -161,9 +249,19 @@ class KerasLikeModel(object):
     def train_on_batch_device(self, inputs, targets):
         raise NotImplementedError
 
+    def test_on_batch_device(self, inputs, targets):
+        raise NotImplementedError
+
     @staticmethod
     def _losses_to_api(v):
         return float(v[0])
+
+    def train_on_batch(self, inputs, targets):
+        """keras.Model.train_on_batch: the loss (a model with metrics: [loss, metrics...]) as Python floats."""
+        return self._losses_to_api(self.train_on_batch_device(inputs, targets).cpu().numpy())
+
+    def test_on_batch(self, inputs, targets):
+        return self._losses_to_api(self.test_on_batch_device(inputs, targets).cpu().numpy())
 
     def fit_generator(self, generator, epochs=1, steps_per_epoch=None, callbacks=None, validation_data=None,
                       verbose=1, max_queue_size=10, workers=1, use_multiprocessing=False, initial_epoch=0):
@@ -189,7 +287,7 @@ class KerasLikeModel(object):
                     inputs, targets = next(batches)
                     step = outer.train_on_batch_device(inputs, targets)      # device tensor; its buffer is reused by the next step
                     acc = step.clone() if acc is None else acc.add_(step)    # (bookkeeping on the step's stream, not model arithmetic)
-                logs = {"loss": self._losses_to_api((acc / steps_per_epoch).cpu().numpy())}       # the epoch's ONE host sync
+                logs = {"loss": float((acc / steps_per_epoch).cpu().numpy()[0])}       # the epoch's ONE host sync (a model's metrics come after the loss)
                 if validation_data is not None:
                     logs["val_loss"] = float(outer.test_on_batch(validation_data[0], validation_data[1]))
                 if verbose and getattr(self, "is_chief", True):

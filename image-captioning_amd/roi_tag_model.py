@@ -71,9 +71,7 @@ class TagTop(RoiHead):
         W = dict(synth.head_weights(seed + 1, pool, cin, self.FEAT))
         W.update(synth.tag_head_weights(seed + 6, self.C, self.FEAT))
         self.store = self._build_store(W, lambda k: 'moving_' in k, extra_params)
-        self.grad_sync = None
-        self._bufs = {}
-        self._steps = {}
+        self._init_runtime()
 
     def _prefix_rows(self, training):
         return False

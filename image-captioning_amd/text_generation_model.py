@@ -21,7 +21,7 @@ import torch
 
 from . import decoding, ops, step_graph, synth, utils
 from .config import Config
-from .keras_like import KerasLikeModel, ModelCheckpoint, CSVLogger  # noqa: F401
+from .keras_like import KerasLikeModel, ModelCheckpoint, CSVLogger, target_ids  # noqa: F401
 from .params import ParamStore, Adam, SGD  # noqa: F401
 from .text_generation_model_v2 import pad_sequences
 from .utils import Dataset
@@ -289,9 +289,7 @@ class CaptionModelV1(RoiHead):
         if compute_dtype == "bf16":
             own = [k for k in sorted(W) if not frozen(k) and k.endswith('kernel') and 'recurrent' not in k]
             self.store.enable_bf16_shadow(own)            # GEMM kernels only: biases, BN parameters and the recurrences stay fp32
-        self.grad_sync = None
-        self._bufs = {}
-        self._steps = {}                          # captured train steps by batch shape (step_graph.CapturedStep)
+        self._init_runtime()
         self._drop_seed, self._drop_step = (seed + 77) & 0xFFFFFFFF, 0
         self._rec_masks = (None, None)           # device masks of the current train step (lstm1, lstm2) or None
 
@@ -324,14 +322,6 @@ class CaptionModelV1(RoiHead):
             return
         self._rec_masks = tuple(ops.dropout_mask(self._buf('rec_mask%d' % l, (4, B, self.units)), rate, self._drop_seed, 2 * self._drop_step + l)
                                 for l in range(2))
-
-    def _grads_ready(self, *layers):
-        """Data parallel: these layers' gradients are final -- start their all-reduce while the backward goes on (what _backward
-        announces to when its caller hands it no `ready` of its own)."""
-        if self.grad_sync is not None and hasattr(self.grad_sync, 'ready'):
-            for layer in layers:
-                lo, hi = self.store.layer_range(layer)
-                self.grad_sync.ready(self.store.flat_grad, lo, hi)
 
     def _hidden(self, f, ids_tm, mask, B, T, Bl=None):
         """word_generation_model up to the Dense-1024 layer, over time-major token ids: a1 [T*B, 1024] (row t*B+b = the
@@ -525,63 +515,44 @@ class CaptionModelV1(RoiHead):
         self._mm(dzf, self._wview('imgcap_lstm1/kernel', (self.E, self.E + self.FEAT)), out=df, b_trans=True, accumulate=True)
         return self._head_backward(df, B, ready, want_dx)
 
-    def train_step(self, feat, caps, targets):
-        """forward + roi_caption_loss + backward + (all-reduce) + the optimizer's update; the loss as a DEVICE scalar (no sync).
-        One GPU, one mask set per RoI: the whole step is replayed from a hipGraph captured on the third call with the same batch
-        shape (step_graph.py); captions, targets, lr_t and the dropout stream position travel in ONE upload, the features in one copy."""
-        if self.optimizer is None:
-            raise RuntimeError("compile(optimizer, loss) first")
-        caps = np.asarray(caps)
-        B, T = caps.shape
-        # what the captured launches bake: the batch shape and whether (and at which rate) the mask kernels are part of the step
-        key = (tuple(feat.shape), B, T, float(self.recurrent_dropout or 0.0), self.optimizer.baked_key())
-        cs, new = (None, False) if self._prefix_rows(True) else self._captured_step(key, feat)
-        if cs is None:
-            return self._train_step_eager(feat, caps, targets)
-        opt = self.optimizer
+    # train_step(feat, caps, targets): KerasLikeModel's, the loss roi_caption_loss.  One GPU, one mask set per RoI: the step replays (the
+    # class default); captions, targets, lr_t and the dropout stream position travel in ONE upload, the features in one copy.
+    def _step_key(self, feat, caps, targets):
+        """What the captured launches bake: the batch shape and whether (and at which rate) the mask kernels are part of the step."""
+        if self._prefix_rows(True):
+            return None                                    # (the prefix tables are built on the host, step by step)
+        B, T = np.shape(caps)
+        return tuple(feat.shape), B, T, float(self.recurrent_dropout or 0.0)
+
+    def _stage_batch(self, cs, new, feat, caps, targets):
+        ids = np.asarray(caps).astype(np.int32)            # Embedding casts float ids to int32 (_tables)
+        B, T = ids.shape
         N = T * B
         if new:
             cs.inputs = step_graph.PackedInputs(self.device, [("ids_tm", N), ("targets", N), ("mask", (N + 3) // 4), ("scalars", 4)])
-        ids = caps.astype(np.int32)                        # Embedding casts float ids to int32 (_tables)
         scal = np.zeros(4, np.int32)
-        scal[0:1] = step_graph.lr_word(opt).view(np.int32)
+        scal[0:1] = step_graph.lr_word(self.optimizer).view(np.int32)
         scal[1:2] = np.array([(2 * (self._drop_step + 1)) & 0xFFFFFFFF], np.uint32).view(np.int32)      # this step's masks (lstm l: + l)
         cs.inputs.upload({"ids_tm": ids.T, "targets": np.asarray(targets, np.int32).T, "mask": (ids != 0).T.astype(np.uint8), "scalars": scal})
         cs.feat.copy_(self._dev_feat(feat))
         sc = cs.inputs.view("scalars")
-        lr_dev, drop_dev = sc[0:1].view(torch.float32), sc[1:2]
         tables = (cs.inputs.view("ids_tm"), cs.inputs.bytes_view("mask", N), cs.inputs.view("targets"), None, B, T)
         dropout = float(self.recurrent_dropout or 0.0) > 0.0
+        return (cs.feat, None), dict(device_tables=tables, drop_offset_dev=sc[1:2] if dropout else None), sc[0:1].view(torch.float32)
 
-        def body():
-            loss_rows, _ = self._forward_train(cs.feat, None, want_grad=True, device_tables=tables, drop_offset_dev=drop_dev if dropout else None)
-            loss = ops.mean(loss_rows, out=self._buf('loss', (1,)))
-            self._backward()
-            opt.apply(self.store, grad_scale=1.0, lr_t_dev=lr_dev)
-            cs.rec_masks = self._rec_masks
-            return loss
+    def _counters(self):
+        return self.optimizer.iterations, self._drop_step
 
-        def restore(v):
-            opt.iterations, self._drop_step = v
+    def _set_counters(self, v):
+        self.optimizer.iterations, self._drop_step = v
 
-        def bump():                                          # what the captured Python did once: the host-side counters
-            opt.iterations += 1
-            self._rec_masks = cs.rec_masks                   # (last_rec_masks: this shape's mask buffers, redrawn by the replay)
-            if dropout:
-                self._drop_step += 1
-
-        return self._run_captured(cs, body, lambda: (opt.iterations, self._drop_step), restore, bump)
+    def _advance_counters(self, cs):
+        self.optimizer.iterations += 1
+        self._rec_masks = tuple(cs.bufs.get('rec_mask%d' % l) for l in range(2))        # (last_rec_masks: this shape's mask buffers, redrawn by the replay)
+        if self._rec_masks[0] is not None:
+            self._drop_step += 1
 
     # ---------------------------------------------------------------------------------- Keras surface
-    @staticmethod
-    def _target_ids(y):
-        y = np.asarray(y)
-        if y.ndim == 2:
-            return y.astype(np.int32)
-        if not (np.all(y.max(-1) == 1) and np.all(y.sum(-1) == 1)):
-            raise ValueError("targets must be one-hot rows (as the reference's data_generator yields)")
-        return y.argmax(-1).astype(np.int32)
-
     def _unpack(self, probs_tm, B, T):
         return probs_tm.view(T, B, self.V).permute(1, 0, 2).contiguous().cpu().numpy()
 
@@ -596,18 +567,12 @@ class CaptionModelV1(RoiHead):
     def train_on_batch_device(self, inputs, targets):
         """train_on_batch without the host round trip: the loss as a float32 device tensor [1] (see keras_like)."""
         feat, caps = inputs
-        return self.train_step(self._dev_feat(feat), caps, self._target_ids(targets))
-
-    def train_on_batch(self, inputs, targets):
-        return float(self.train_on_batch_device(inputs, targets).item())
+        return self.train_step(self._dev_feat(feat), caps, target_ids(targets, 2))
 
     def test_on_batch_device(self, inputs, targets):
         feat, caps = inputs
-        loss_rows, _ = self._forward_train(self._dev_feat(feat), caps, self._target_ids(targets))
+        loss_rows, _ = self._forward_train(self._dev_feat(feat), caps, target_ids(targets, 2))
         return ops.mean(loss_rows)
-
-    def test_on_batch(self, inputs, targets):
-        return float(self.test_on_batch_device(inputs, targets).item())
 
     DECODERS = decoding.DECODERS
     VOCAB_MATH = (None, "f32", "bf16")

@@ -15,9 +15,9 @@ import os
 import numpy as np
 import torch
 
-from . import decoding, ops, step_graph, synth, utils
+from . import decoding, ops, synth, utils
 from .config import Config
-from .keras_like import KerasLikeModel, ModelCheckpoint, CSVLogger  # noqa: F401  (re-exported for scripts)
+from .keras_like import KerasLikeModel, ModelCheckpoint, CSVLogger, target_ids  # noqa: F401  (re-exported for scripts)
 from .layers import V2_WORD_LSTM
 from .packing import fold_bn
 from .params import ParamStore, Adam, SGD  # noqa: F401
@@ -394,8 +394,7 @@ class CaptionModelV2(KerasLikeModel):
         for k in sorted(W):
             st.add(k, W[k], k.split('/')[0] in trainable_layers)
         self.store = st.finalize()
-        self.grad_sync = None            # set by ParallelModel: called between backward and the update
-        self._bufs = {}
+        self._init_runtime()
         self._weights_changed()
 
     # frozen head: fold BN once (float64 on the host)
@@ -482,60 +481,26 @@ class CaptionModelV2(KerasLikeModel):
         ops.gemm(w['imgcap_embedding_layer/embeddings'], dz, a_trans=True, gather=tb.ids_tm, out=g[V2_WORD_LSTM + '/kernel'])
         ops.colsum(dz, out=g[V2_WORD_LSTM + '/bias'])
 
-    _forward_train = _forward          # (the name KerasLikeModel._train_step_eager calls; v1's takes captions and targets instead of tables)
-
-    def _grads_ready(self, layer):
-        """Data parallel: this layer's gradients are final -- start their all-reduce while the backward goes on."""
-        if self.grad_sync is not None and hasattr(self.grad_sync, 'ready'):
-            lo, hi = self.store.layer_range(layer)
-            self.grad_sync.ready(self.store.flat_grad, lo, hi)
+    _forward_train = _forward          # (the name KerasLikeModel's train step calls; v1's takes captions and targets instead of tables)
 
     # Replaying the step from a captured hipGraph is OPT-IN for this model: at the reference's batch (64 samples, 1024 units) every kernel
     # runs 10 us or longer, the eager step is already GPU-bound (0.70 ms) and the replay's three input copies make it 0.73 ms
     # (bench.py other_configs.configs1_gpu reports both).  The v1 decoder at B = 8 is launch-bound and replays by default.
     use_step_graph = False
 
-    def train_step(self, feat, tb):
-        """forward + backward + (all-reduce) + the optimizer's update; returns the loss as a DEVICE scalar (no sync).
-        use_step_graph (one GPU): the whole step is replayed from a hipGraph captured on the third call with the same batch shape
-        (step_graph.py); the batch reaches it through two device-to-device copies (features, packed tables) and one word (lr_t)."""
-        if self.optimizer is None:
-            raise RuntimeError("compile(optimizer, loss) first")
-        cs, new = self._captured_step((tuple(feat.shape), tb.N, tb.T, tb.Bw, self.optimizer.baked_key()), feat)
-        if cs is None:
-            return self._train_step_eager(feat, tb)
-        opt = self.optimizer
+    # train_step(feat, tb): KerasLikeModel's.  A captured step's batch reaches it through two device-to-device copies (features, packed
+    # tables) and one word (lr_t).
+    def _step_key(self, feat, tb):
+        return tuple(feat.shape), tb.N, tb.T, tb.Bw
+
+    def _stage_batch(self, cs, new, feat, tb):
         if new:
             cs.tb = tb.like(torch.empty_like(tb.packed))
-            cs.scalars = step_graph.PackedInputs(self.device, [("lr_t", 1)])
         cs.feat.copy_(self._dev_feat(feat))
         cs.tb.packed.copy_(tb.packed)
-        cs.scalars.upload({"lr_t": step_graph.lr_word(opt)})
-        lr_dev = cs.scalars.view("lr_t", torch.float32)
-
-        def body():
-            loss_rows, _ = self._forward(cs.feat, cs.tb, want_grad=True)
-            loss = ops.mean(loss_rows, out=self._buf('loss', (1,)))
-            self._backward()
-            opt.apply(self.store, grad_scale=1.0, lr_t_dev=lr_dev)
-            return loss
-
-        def bump():
-            opt.iterations += 1
-
-        return self._run_captured(cs, body, lambda: opt.iterations, lambda v: setattr(opt, "iterations", v), bump)
+        return (cs.feat, cs.tb), {}, self._stage_lr_t(cs, new)
 
     # ---------------------------------------------------------------------------------- Keras surface
-    @staticmethod
-    def _target_ids(y):
-        y = np.asarray(y)
-        if y.ndim == 1:
-            return y.astype(np.int32)
-        ids = y.argmax(-1)
-        if not (np.all(y.max(-1) == 1) and np.all(y.sum(-1) == 1)):
-            raise ValueError("targets must be one-hot rows (as the reference's data_generator yields)")
-        return ids.astype(np.int32)
-
     def predict(self, inputs, verbose=0):
         feat, words = inputs
         words = np.asarray(words)
@@ -546,20 +511,14 @@ class CaptionModelV2(KerasLikeModel):
     def train_on_batch_device(self, inputs, targets):
         """train_on_batch without the host round trip: the loss as a float32 device tensor [1] (see keras_like)."""
         feat, words = inputs
-        tb = SampleTables.from_samples(words, self._target_ids(targets), self.device)
+        tb = SampleTables.from_samples(words, target_ids(targets, 1), self.device)
         return self.train_step(self._dev_feat(feat), tb)
-
-    def train_on_batch(self, inputs, targets):
-        return float(self.train_on_batch_device(inputs, targets).item())
 
     def test_on_batch_device(self, inputs, targets):
         feat, words = inputs
-        tb = SampleTables.from_samples(words, self._target_ids(targets), self.device)
+        tb = SampleTables.from_samples(words, target_ids(targets, 1), self.device)
         loss_rows, _ = self._forward(self._dev_feat(feat), tb)
         return ops.mean(loss_rows)
-
-    def test_on_batch(self, inputs, targets):
-        return float(self.test_on_batch_device(inputs, targets).item())
 
     def train_on_captions(self, feat, captions_or_tables):
         """Algorithmic (single teacher-forced pass) train step over R RoIs and their captions."""

@@ -29,9 +29,8 @@ generate(): test.py:23-64 gen_captions for R images at once on the device (decod
 import numpy as np
 import torch
 
-from .. import decoding, ops, step_graph, synth
-from ..keras_like import KerasLikeModel
-from ..modified_dense_model import load_weight_file
+from .. import decoding, ops, synth
+from ..keras_like import KerasLikeModel, target_ids
 from ..params import ParamStore
 
 INPUT_DIM, WORD_DIM, LANGUAGE_UNITS, MERGED_UNITS = 12544, 256, 256, 1000
@@ -115,8 +114,7 @@ class WholeImageCaptioner(KerasLikeModel):
             st.add(k, self._pad(k, W[k]), True)
         self.store = st.finalize()
         self.metrics = ()
-        self.grad_sync = None
-        self._bufs = {}
+        self._init_runtime()
         self._weights_changed()
 
     # ---- Keras' shapes <-> the held (padded) ones ------------------------------------------------------------------------------------
@@ -173,19 +171,10 @@ class WholeImageCaptioner(KerasLikeModel):
             weights = dict(zip(self.weight_names, weights))
         self.load_weights(weights)
 
-    def load_weights(self, filepath, by_name=False, skip_mismatch=False):
-        loaded = load_weight_file(filepath) if isinstance(filepath, str) else dict(filepath)
-        for k, v in loaded.items():
-            if k not in self.store.w:
-                if by_name:
-                    continue
-                raise KeyError("weight %s is not part of this model" % k)
-            if tuple(np.shape(v)) != self.keras_shapes[k]:
-                if skip_mismatch:
-                    continue
-                raise ValueError("shape mismatch for %s: %s vs %s" % (k, tuple(np.shape(v)), self.keras_shapes[k]))
-            self.store.assign(k, self._pad(k, v), refresh=False)
-        self._weights_changed()
+    def _stored_shape(self, name):                      # load_weights: files hold Keras' shapes, the model the padded ones
+        return self.keras_shapes[name]
+
+    _to_held = _pad
 
     # ---- engine ----------------------------------------------------------------------------------------------------------------------
     def _image_half(self, feat, p):
@@ -230,9 +219,11 @@ class WholeImageCaptioner(KerasLikeModel):
         self._ctx = (feat, ids_tm, B, T, a, top, dlog)
         return loss_rows, probs
 
-    def _loss_and_metrics(self, loss_rows, top, targets):
-        """-> float32 device tensor [1 + len(metrics)]: the batch's mean loss, then Keras' categorical accuracy."""
-        w, B = self.store.w, loss_rows.shape[0]
+    _forward_train = _forward          # (the name KerasLikeModel's train step calls)
+
+    def _loss_and_metrics(self, loss_rows, feat, ids_tm, targets):
+        """After _forward on this batch -> float32 device tensor [1 + len(metrics)]: the batch's mean loss, then Keras' categorical accuracy."""
+        w, B, top = self.store.w, loss_rows.shape[0], self._ctx[5]
         out = self._buf('loss_acc', (1 + len(self.metrics),))
         ops.mean(loss_rows, out=out[0:1])
         if self.metrics:
@@ -240,6 +231,8 @@ class WholeImageCaptioner(KerasLikeModel):
             hit = torch.eq(best, targets, out=self._buf('hit', (B,), torch.bool))        # (bookkeeping on B flags, not model arithmetic)
             ops.mean(self._buf('hit_f', (B,)).copy_(hit), out=out[1:2])
         return out
+
+    _step_loss = _loss_and_metrics     # the train step's loss tensor: [loss, accuracy]
 
     def _backward(self):
         """Gradients of every weight into the flat gradient bucket (every view is fully overwritten: the bucket needs no zeroing)."""
@@ -270,42 +263,23 @@ class WholeImageCaptioner(KerasLikeModel):
         dx = ops.gemm(dzx, w["language_model_lstm/kernel"], b_trans=True, out=self._buf('dx', (T * B, self.D)))
         ops.embedding_grad(dx, ids_tm, g["language_model_embedding/embeddings"])
 
-    def _step_body(self, feat, ids_tm, targets, lr_dev):
-        loss_rows, _ = self._forward(feat, ids_tm, targets, want_grad=True)
-        out = self._loss_and_metrics(loss_rows, self._ctx[5], targets)
-        self._backward()
-        self.optimizer.apply(self.store, grad_scale=1.0, lr_t_dev=lr_dev)
-        return out
-
     # Replaying the step from a captured hipGraph is OPT-IN for this model, as for the v2 decoders: at the reference's batch (100 samples,
     # T = 10, V = 8192, the 1024-unit LSTM) the eager step is GPU-bound, 1.384 ms against 1.413 ms replayed with its three input copies
     # (tools/imgcap_bench.py, profiles/imgcap_bench.json).
     use_step_graph = False
 
-    def train_step(self, feat, ids_tm, targets):
-        """forward + backward + Adam on device tensors (feat [B,F], ids_tm int32 [T*B], targets int32 [B]); returns the DEVICE tensor
-        [loss, accuracy] (no sync).  use_step_graph (one GPU; DCAP_STEP_GRAPH=0 overrides): replayed from a hipGraph captured on the third
-        call with a batch shape; the batch reaches it through three device-to-device copies and one word (lr_t)."""
-        if self.optimizer is None:
-            raise RuntimeError("compile(optimizer, loss) first")
-        opt = self.optimizer
-        cs, new = self._captured_step((tuple(feat.shape), ids_tm.numel(), self.metrics, opt.baked_key()), feat)
-        if cs is None:
-            return self._step_body(feat, ids_tm, targets, None)
+    # train_step(feat, ids_tm, targets): KerasLikeModel's, on device tensors (feat [B,F], ids_tm int32 [T*B], targets int32 [B]); returns the
+    # DEVICE tensor [loss, accuracy].  A captured step's batch reaches it through three device-to-device copies and one word (lr_t).
+    def _step_key(self, feat, ids_tm, targets):
+        return tuple(feat.shape), ids_tm.numel(), self.metrics
+
+    def _stage_batch(self, cs, new, feat, ids_tm, targets):
         if new:
             cs.ids, cs.targets = torch.empty_like(ids_tm), torch.empty_like(targets)
-            cs.scalars = step_graph.PackedInputs(self.device, [("lr_t", 1)])
         cs.feat.copy_(feat)
         cs.ids.copy_(ids_tm)
         cs.targets.copy_(targets)
-        cs.scalars.upload({"lr_t": step_graph.lr_word(opt)})
-        lr_dev = cs.scalars.view("lr_t", torch.float32)
-
-        def bump():
-            opt.iterations += 1
-
-        return self._run_captured(cs, lambda: self._step_body(cs.feat, cs.ids, cs.targets, lr_dev), lambda: opt.iterations,
-                                  lambda v: setattr(opt, "iterations", v), bump)
+        return (cs.feat, cs.ids, cs.targets), {}, self._stage_lr_t(cs, new)
 
     # ---- Keras surface ---------------------------------------------------------------------------------------------------------------
     def _ids_tm(self, words):
@@ -328,16 +302,7 @@ class WholeImageCaptioner(KerasLikeModel):
         if isinstance(y, torch.Tensor):
             y = y.to(self.device)
             return (y.argmax(-1) if y.dim() == 2 else y).to(torch.int32).contiguous()
-        y = np.asarray(y)
-        if y.ndim == 2:
-            ids = y.argmax(-1)
-            if y.shape[1] != self.V or not (np.all(y.max(-1) == 1) and np.all(y.sum(-1) == 1)):
-                raise ValueError("targets must be one-hot rows [B,%d] (as the reference's data_generator yields) or int ids [B]" % self.V)
-        else:
-            ids = y
-            if ids.size and (ids.min() < 0 or ids.max() >= self.V):
-                raise ValueError("target ids must lie in [0, %d)" % self.V)
-        return torch.tensor(np.ascontiguousarray(ids.astype(np.int32)), device=self.device)
+        return torch.tensor(np.ascontiguousarray(target_ids(y, 1, self.V)), device=self.device)
 
     def _batch(self, inputs, targets=None):
         feat, words = inputs
@@ -365,18 +330,11 @@ class WholeImageCaptioner(KerasLikeModel):
     def test_on_batch_device(self, inputs, targets):
         feat, ids_tm, tg = self._batch(inputs, targets)
         loss_rows, _ = self._forward(feat, ids_tm, tg)
-        return self._loss_and_metrics(loss_rows, self._ctx[5], tg)
+        return self._loss_and_metrics(loss_rows, feat, ids_tm, tg)
 
-    def _api(self, out):
-        v = out.cpu().numpy()
+    def _losses_to_api(self, v):
+        """train_on_batch / test_on_batch: [loss, accuracy] as Keras returns them with metrics=['accuracy'] (the loss alone without)."""
         return [float(x) for x in v] if self.metrics else float(v[0])
-
-    def train_on_batch(self, inputs, targets):
-        """keras.Model.train_on_batch: [loss, accuracy] as Keras returns them with metrics=['accuracy'] (the loss alone without)."""
-        return self._api(self.train_on_batch_device(inputs, targets))
-
-    def test_on_batch(self, inputs, targets):
-        return self._api(self.test_on_batch_device(inputs, targets))
 
     # ---- beam search on the device (test.py:23-64) -----------------------------------------------------------------------------------
     check_generate = staticmethod(check_generate)

@@ -30,7 +30,7 @@ class Recorder(object):
     def _wrap(self, name, fn):
         def call(*a, **k):
             if self.depth == 0:
-                side = self.model._side_stream
+                side = getattr(self.model, "_side_stream", None)        # (the decoder-only models have no side stream)
                 self.seq.append(name + "@side" if side is not None and torch.cuda.current_stream() == side else name)
                 if name == "l2_reg" and (len(a) > 2 and a[2] is not None or k.get("grad") is not None):
                     lo = (a[0].data_ptr() - self.model.store.flat.data_ptr()) // 4
@@ -58,7 +58,7 @@ class Recorder(object):
         sync = self.model.grad_sync
         if isinstance(sync, StubExchange):
             sync.seen = []
-            side = lambda: "@side" if self.model._side_stream is not None and torch.cuda.current_stream() == self.model._side_stream else ""
+            side = lambda: "@side" if getattr(self.model, "_side_stream", None) is not None and torch.cuda.current_stream() == self.model._side_stream else ""
             sync.ready = lambda flat, lo, hi: (self.seq.append("ready:%s%s" % (layers[(lo, hi)], side())), sync.seen.append((lo, hi)))[1]
         return self
 

@@ -148,6 +148,55 @@ def test_captured_step_is_bit_equal_to_the_eager_step(gpu, monkeypatch):
     assert torch.equal(fe, fg)
 
 
+class _Exchange(object):
+    """A gradient hook without `.world` (KerasLikeModel._captured_step counts it as an exchange: the step runs eagerly): counts its calls,
+    keeps what it was handed and returns `scale`."""
+
+    def __init__(self, scale):
+        self.scale, self.calls = scale, []
+
+    def __call__(self, flat_grad):
+        self.calls.append(flat_grad)
+        return self.scale
+
+
+def test_eager_step_runs_the_gradient_exchange_and_applies_its_scale(gpu, monkeypatch):
+    """An attached exchange is called once per step with the gradient bucket, between backward and update, and the step stays eager
+    although graphs are asked for; with scale 1.0 two steps leave every weight bit-equal to a twin without the hook; the scale 0.5
+    reaches the update: one step equals a twin's whose bucket was halved by hand before optimizer.apply (a power of two: exact)."""
+    batches = [_batch(50 + i, 5, 4, 64, 52) for i in range(2)]
+    monkeypatch.setenv("DCAP_STEP_GRAPH", "1")
+    hooked, _ = _model(seed=4)
+    hooked.use_step_graph = True
+    hooked.grad_sync = _Exchange(1.0)
+    for i, (feat, words, tgt) in enumerate(batches):
+        hooked.train_on_batch_device([feat, words], tgt)
+        assert len(hooked.grad_sync.calls) == i + 1 and hooked.grad_sync.calls[i] is hooked.store.flat_grad
+    assert all(cs.graph is None for cs in hooked._steps.values())
+    monkeypatch.setenv("DCAP_STEP_GRAPH", "0")
+    plain, _ = _model(seed=4)
+    for feat, words, tgt in batches:
+        plain.train_on_batch_device([feat, words], tgt)
+    assert plain.optimizer.iterations == hooked.optimizer.iterations == 2
+    for k in plain.weight_names:
+        assert torch.equal(plain.store.w[k], hooked.store.w[k]), k
+
+    feat, words, tgt = batches[0]
+    half, _ = _model(seed=4)
+    half.grad_sync = _Exchange(0.5)
+    half.train_on_batch_device([feat, words], tgt)
+    assert len(half.grad_sync.calls) == 1
+    twin, _ = _model(seed=4)
+    twin._forward_train(*twin._batch([feat, words], tgt), want_grad=True)
+    twin._backward()
+    twin.store.flat_grad.mul_(0.5)
+    twin.optimizer.apply(twin.store)
+    one, _ = _model(seed=4)
+    one.train_on_batch_device([feat, words], tgt)
+    assert torch.equal(half.store.flat, twin.store.flat)
+    assert not torch.equal(half.store.flat, one.store.flat)
+
+
 # ---- beam search -----------------------------------------------------------------------------------------------------------------------
 SEARCH_SEED, SEARCH_SCALE = 38, 8.0          # chosen on the CPU with the float64 model: see test_search_seed_has_no_near_ties
 

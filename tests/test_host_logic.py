@@ -626,6 +626,46 @@ def test_fit_generator_runs_the_generator_on_a_background_thread_like_keras():
     e.stop()
 
 
+def test_target_ids_takes_one_hot_rows_or_ids_at_both_ranks_and_refuses_the_rest():
+    """keras_like.target_ids, the one helper behind every decoder's train_on_batch / test_on_batch targets: one-hot rows (the reference's
+    generators) become int32 ids, ids pass through as int32, at rank 1 ([B]: the v2 and whole-image models) and rank 2 ([B,T]: Model 3);
+    a row that is not one-hot is refused at both ranks, and with a vocabulary size so are an id outside [0, V) and rows of another width."""
+    from image_captioning_amd.keras_like import target_ids
+    V = 7
+    ids1 = np.array([3, 0, 6, 6], np.int64)
+    ids2 = np.array([[1, 0, 6], [5, 5, 2]], np.int64)
+    for ids, rank in ((ids1, 1), (ids2, 2)):
+        for vocab in (None, V):
+            got = target_ids(np.eye(V)[ids], rank, vocab)                  # float64 one-hot rows
+            assert got.dtype == np.int32 and np.array_equal(got, ids)
+            got = target_ids(ids, rank, vocab)
+            assert got.dtype == np.int32 and np.array_equal(got, ids)
+            got = target_ids(ids.astype(np.int32), rank, vocab)
+            assert got.dtype == np.int32 and np.array_equal(got, ids)
+            assert np.array_equal(target_ids(ids.tolist(), rank, vocab), ids)          # (lists, as np.asarray takes them)
+        for bad in (0.0, 2.0, 0.5):                                         # an all-zero row; a 2; two halves (their sum is 1, their maximum is not)
+            rows = np.eye(V)[ids]
+            rows[(1,) + (0,) * (rank - 1)] = 0.0
+            rows[(1,) + (0,) * (rank - 1)][:2] = bad if bad != 0.5 else (0.5, 0.5)
+            for vocab in (None, V):
+                with pytest.raises(ValueError, match="one-hot"):
+                    target_ids(rows, rank, vocab)
+        two = np.eye(V)[ids]
+        two[..., 0] = 1.0                                                   # a second 1 in every row that did not have its 1 there
+        with pytest.raises(ValueError, match="one-hot"):
+            target_ids(two, rank)
+        for out in (-1, V):
+            beyond = ids.copy()
+            beyond.flat[-1] = out
+            with pytest.raises(ValueError, match=r"target ids must lie in \[0, 7\)"):
+                target_ids(beyond, rank, V)
+            assert np.array_equal(target_ids(beyond, rank), beyond)        # no size given: nothing to check against
+        with pytest.raises(ValueError, match="one-hot rows of width 7"):
+            target_ids(np.eye(V + 1)[ids], rank, V)
+        assert np.array_equal(target_ids(np.eye(V + 1)[ids], rank), ids)
+    assert target_ids(np.zeros((0,), np.int64), 1, V).shape == (0,)
+
+
 def test_encoder_plan_per_layer_arithmetic_rule():
     """EncoderPlan._layer_math (host logic, no GPU): in the fp32-grade plan the stem, the projection shortcuts and the short-K pointwise
     layers that measured faster in split-bf16 arithmetic are the ones handed to DC_MATH_BF16X3; everything else, external layers and
