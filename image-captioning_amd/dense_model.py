@@ -679,7 +679,9 @@ class DenseImageCapRCNN(object):
         if backbone_changed:
             self._plan, self._plans = None, []
             self._invalidate_graphs()
-        st.refresh_shadow()                  # the bf16 operand copies: once per call, not once per weight
+        # what the top derives from weights (its bf16 operand copies, folded BatchNorm operands): once per call, not once per weight.
+        # The bucket was written in place: this model's captured step stays valid (the top drops only steps of its own).
+        self.caption_model._weights_changed()
 
     def load_weights(self, filepath, by_name=False, exclude=None):
         loaded = load_weight_file(filepath)
@@ -740,8 +742,9 @@ class DenseImageCapRCNN(object):
         return "\n".join(rows)
 
     def _weights_changed(self):
-        """Master weights rewritten from outside the optimizer (ParallelModel.broadcast_weights): re-cast the bf16 mirror."""
-        self.store.refresh_shadow()
+        """Master weights rewritten in place from outside the optimizer (ParallelModel.broadcast_weights): the top's hook re-casts the
+        bf16 mirror and drops what it folds from weights."""
+        self.caption_model._weights_changed()
 
     @property
     def trainable_weights(self):
@@ -1606,6 +1609,16 @@ class DenseImageCapRCNN(object):
         if self.PIPELINED_FIT and self.backbone_from is None and os.environ.get("DCAP_JOINT_PIPELINE", "1") != "0":
             from .pipeline import JointTrainPipeline
             pipe = JointTrainPipeline(self._outer)
+        try:
+            self._fit_epochs(pipe, train_generator, val_batch, epochs, names, history)
+        finally:
+            if pipe is not None:
+                pipe.close()                                 # the model steps serially again, with the step-graph choice it had
+        self.epoch = max(self.epoch, epochs)
+        return history
+
+    def _fit_epochs(self, pipe, train_generator, val_batch, epochs, names, history):
+        cfg = self.config
         for epoch in range(self.epoch, epochs):
             acc = None                                           # raw loss terms summed on the device: one host copy per epoch
             for i in range(cfg.STEPS_PER_EPOCH + (1 if pipe is not None else 0)):
@@ -1627,5 +1640,3 @@ class DenseImageCapRCNN(object):
                 self.save_weights(self.checkpoint_path.format(epoch=epoch + 1))      # Keras ModelCheckpoint numbers epochs from 1
             if self.grad_sync is not None:
                 self.grad_sync.barrier()                     # every rank sees the finished checkpoint before going on
-        self.epoch = max(self.epoch, epochs)
-        return history

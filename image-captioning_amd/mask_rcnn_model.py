@@ -208,6 +208,11 @@ class DetectTop(RoiHead):
                 self._folded.append((scale, shift))
         return self._folded
 
+    def _weights_changed(self):
+        """Weights rewritten (the model's set_weights, load_weights on this top, a broadcast): the folded operands are of the old ones."""
+        self._folded = None
+        RoiHead._weights_changed(self)
+
     def mask_layer(self, i, x, out=None):
         """mrcnn_mask_conv<i+1> + mrcnn_mask_bn<i+1> (frozen) + ReLU on x [M,P,P,256], one dc_conv2d_nhwc_f32 launch."""
         conv = MASK_CONVS[i][0]
@@ -285,8 +290,7 @@ class MaskRCNN(DenseImageCapRCNN):
         W = dict(weights)
         W.update(top.to_stored({k: v for k, v in W.items() if k.split("/")[0] in ("mrcnn_class_logits", "mrcnn_mask") or
                                 k.startswith("mrcnn_mask_conv")}))
-        DenseImageCapRCNN.set_weights(self, W)
-        top._folded = None
+        DenseImageCapRCNN.set_weights(self, W)             # (ends in the top's _weights_changed: the folded mask BatchNorms go)
 
     # ---- inference -----------------------------------------------------------------------------
     def detect(self, images, verbose=0, postprocess="host", mold="host", device_masks=False):

@@ -138,7 +138,8 @@ class JointTrainPipeline(object):
             raise ValueError("JointTrainPipeline: ResNet stages are trainable (backbone_from = %r): the backbone pass of the next batch depends on "
                              "this batch's update" % (inner.backbone_from,))
         self.model, self.inner = model, inner
-        self.plans = inner.plan_pair()
+        self._found_path = (inner._path.use_graph, inner._path.auto)   # what close() puts back
+        self.plans = inner.plan_pair()                               # (the model's own list: a backbone set_weights replaces it, _check_plans)
         dev = inner.device
         # (tried: the rest of the step on a HIGH-priority stream of its own, the backbone pass at normal priority -- 11.9 - 12.3 ms per step
         # against 6.89 - 6.93 with both at the default priority, same box, alternating runs; the backbone stream restricted to 30 / 28 / 24 / 20 of
@@ -201,6 +202,17 @@ class JointTrainPipeline(object):
             plan.forward_trunk(None)
             self.ev_trunk[j].record(self.s_trunk)
 
+    def _check_plans(self):
+        """The plans pack the frozen backbone: set_weights / load_weights with a backbone tensor drops the model's pair (a new list), and
+        this pipeline must not go on running the old one.  Nothing pending: fetch the new pair.  A batch pending: its backbone pass ran on
+        the old weights and the plan that holds its C2..C5 is gone from the model -- refused."""
+        if self.inner._plans is self.plans:
+            return
+        if self.pending is not None:
+            raise RuntimeError("JointTrainPipeline: backbone weights changed (set_weights / load_weights) while a batch is pending, whose "
+                               "backbone pass ran on the old weights: flush() before changing backbone weights")
+        self.plans = self.inner.plan_pair()
+
     def _rest(self, inputs, j):
         torch.cuda.current_stream(self.inner.device).wait_event(self.ev_trunk[j])
         self.inner.use_plan(j)
@@ -210,6 +222,7 @@ class JointTrainPipeline(object):
     def step(self, inputs):
         """Enqueue the backbone pass of `inputs` and the rest of the previous batch's step.  Returns the previous batch's raw loss terms
         (device tensor [4]) or None on the first call."""
+        self._check_plans()
         j = self.n & 1
         if self.model is not self.inner:
             inputs = self.model.shard_inputs(inputs)                 # ParallelModel: this rank's share of the global batch (tf.split)
@@ -226,7 +239,20 @@ class JointTrainPipeline(object):
         """The rest of the last enqueued batch's step; joins the backbone stream into the caller's."""
         losses = None
         if self.pending is not None:
+            self._check_plans()
             losses = self._rest(*self.pending)
             self.pending = None
         torch.cuda.current_stream(self.inner.device).wait_stream(self.s_trunk)
+        return losses
+
+    def close(self):
+        """The end of the pipeline's use of the model: flush() (a batch still pending: its losses are returned), then the model steps
+        serially again as it did before -- on the first plan of the pair (the one a step graph captured before this pipeline has baked)
+        and with the use_step_graph / automatic path choice the constructor found.  The pipeline must not be used afterwards."""
+        losses = self.flush()
+        inner = self.inner
+        if inner._plans is self.plans:
+            inner.use_plan(0)
+        inner._path.use_graph, inner._path.auto = self._found_path
+        self._hold = []
         return losses
