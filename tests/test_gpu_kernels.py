@@ -171,7 +171,8 @@ def test_conv2d_winograd_matches_oracle_and_direct(ops, case, products):
     """dc_conv_desc.w_wino: a 3x3 / stride 1 / 'same' layer in the Winograd F(2x2, 3x3) form (fp32 transforms, fp32 MFMA, 16 products
     per 2x2 tile instead of 36) against the float64 oracle at the direct kernel's own tolerance, and against the direct kernel.
     products = 'b3' (dc_conv_desc.w_wino_b3, round 5): the same form with the products on the BF16 matrix pipe in split arithmetic
-    (U pre-split into three bf16 pieces, V split in registers, six MFMA products per fp32 product) -- held to the SAME tolerance."""
+    (U pre-split into three bf16 pieces, V split in registers, six MFMA products per fp32 product) -- held to the SAME tolerance here;
+    test_gpu_split_products.py holds the arithmetic to its grade: each of the six piece products present exactly once."""
     from image_captioning_amd.packing import pack_conv_kernel
     N, H, W, Cin, Cout, relu, affine = case
     rng = np.random.default_rng(sum(int(v) * (i + 3) for i, v in enumerate(case)))
@@ -308,7 +309,8 @@ def test_pw_chain_two_pointwise_convolutions_in_one_launch(ops, case, products):
     folded BN + ReLU) in one launch -- both outputs against the float64 oracle at the convolution kernels' tolerance and against the two
     separate dc_conv2d_nhwc_f32 launches the plan used to make.  Cases: the stage-4 shape at two images (256 blocks = one per CU), a
     ragged pixel count (the last block has 8 rows), the stage-3 shape, tiny M, K1 = N1, a K1 whose 16-channel groups do not fill the
-    weight ring (10 groups).  products = 'b3': both layers on the bf16 pipe in split arithmetic (dc_pw_chain_pack_b3) -- SAME tolerance.
+    weight ring (10 groups).  products = 'b3': both layers on the bf16 pipe in split arithmetic (dc_pw_chain_pack_b3) -- SAME tolerance
+    here; test_gpu_split_products.py holds the arithmetic to its grade: each of the six piece products present exactly once, in both layers.
     The 64 -> 256 -> 64 cases are the stage-2 seam: the streaming form (pw_chain_stream_kernel: layer 1's accumulators are layer 2's
     B operands), fp32 products only -- two strips per wave, a ragged last strip, fewer strips than waves."""
     M, K1, N1, N2, res, sc = case
