@@ -217,8 +217,10 @@ def image_level_features(roi_feats):
 # RoI head  mrcnn_class_conv1/bn1/conv2/bn2 (text_generation_model.py:250-262; _v2.py:141-150)
 # --------------------------------------------------------------------------------------------
 
-def roi_head_forward(feat, Wt):
-    """[R,7,7,256] -> conv7x7 valid -> BN -> ReLU -> conv1x1 -> BN -> ReLU -> squeeze -> [R,1024]."""
+def roi_head_forward(feat, Wt, mag=False):
+    """[R,7,7,256] -> conv7x7 valid -> BN -> ReLU -> conv1x1 -> BN -> ReLU -> squeeze -> [R,1024].
+    The cache carries the two pre-activations z1, z2 (g * n + b, before the ReLU) and the two GEMM results acc1, acc2 (y - bias); with
+    mag=True also the magnitude sums |x| @ |K1| and |a1| @ |K2| that bound a fp32 GEMM's error (parity tests: tests/_parity_cuts.py)."""
     R = feat.shape[0]
     x = np.asarray(feat, F64).reshape(R, -1)                       # (h,w,c) row-major == HWIO flatten
     K1 = np.asarray(Wt['mrcnn_class_conv1/kernel'], F64).reshape(-1, 1024)
@@ -226,27 +228,36 @@ def roi_head_forward(feat, Wt):
     bn = lambda y, n: (np.asarray(Wt[n + '/gamma'], F64), np.asarray(Wt[n + '/beta'], F64),
                        np.asarray(Wt[n + '/moving_mean'], F64),
                        np.sqrt(np.asarray(Wt[n + '/moving_variance'], F64) + O.BN_EPS))
-    y1 = x @ K1 + np.asarray(Wt['mrcnn_class_conv1/bias'], F64)
+    acc1 = x @ K1
+    y1 = acc1 + np.asarray(Wt['mrcnn_class_conv1/bias'], F64)
     g1, b1, m1, s1 = bn(y1, 'mrcnn_class_bn1')
     n1 = (y1 - m1) / s1
-    a1 = O.relu(g1 * n1 + b1)
-    y2 = a1 @ K2 + np.asarray(Wt['mrcnn_class_conv2/bias'], F64)
+    z1 = g1 * n1 + b1
+    a1 = O.relu(z1)
+    acc2 = a1 @ K2
+    y2 = acc2 + np.asarray(Wt['mrcnn_class_conv2/bias'], F64)
     g2, b2, m2, s2 = bn(y2, 'mrcnn_class_bn2')
     n2 = (y2 - m2) / s2
-    f = O.relu(g2 * n2 + b2)
-    cache = dict(x=x, K1=K1, K2=K2, n1=n1, a1=a1, n2=n2, f=f, g1=g1, s1=s1, g2=g2, s2=s2)
+    z2 = g2 * n2 + b2
+    f = O.relu(z2)
+    cache = dict(x=x, K1=K1, K2=K2, n1=n1, a1=a1, n2=n2, f=f, g1=g1, s1=s1, g2=g2, s2=s2, z1=z1, z2=z2, acc1=acc1, acc2=acc2)
+    if mag:
+        cache.update(mag1=np.abs(x) @ np.abs(K1), mag2=np.abs(a1) @ np.abs(K2))
     return f, cache
 
 
-def roi_head_backward(df, cache):
-    """Gradients of the trainable head weights (v1 / joint model: kernels, biases, BN gamma/beta)."""
+def roi_head_backward(df, cache, masks=None):
+    """Gradients of the trainable head weights (v1 / joint model: kernels, biases, BN gamma/beta).
+    masks = (m1, m2), boolean [R,1024] each: the two ReLU decisions handed in by the caller -- they stand for (a1 > 0) and (f > 0)
+    in this backward (the forward is not touched).  A parity test passes the decisions the device took, after it has checked them."""
     c = cache
-    dz2 = df * (c['f'] > 0)
+    m1, m2 = (c['a1'] > 0, c['f'] > 0) if masks is None else (np.asarray(masks[0], bool), np.asarray(masks[1], bool))
+    dz2 = df * m2
     G = {'mrcnn_class_bn2/gamma': (dz2 * c['n2']).sum(0), 'mrcnn_class_bn2/beta': dz2.sum(0)}
     dy2 = dz2 * c['g2'] / c['s2']
     G['mrcnn_class_conv2/kernel'] = (c['a1'].T @ dy2).reshape(1, 1, 1024, 1024)
     G['mrcnn_class_conv2/bias'] = dy2.sum(0)
-    dz1 = (dy2 @ c['K2'].T) * (c['a1'] > 0)
+    dz1 = (dy2 @ c['K2'].T) * m1
     G['mrcnn_class_bn1/gamma'] = (dz1 * c['n1']).sum(0)
     G['mrcnn_class_bn1/beta'] = dz1.sum(0)
     dy1 = dz1 * c['g1'] / c['s1']
@@ -402,12 +413,13 @@ def v1_targets(caps):
     return np.concatenate([caps[:, 1:], np.zeros((caps.shape[0], 1))], axis=1).astype(np.int32)
 
 
-def v1_training_forward(Wt, feat, caps, rec_masks=None):
+def v1_training_forward(Wt, feat, caps, rec_masks=None, head_masks=None, head_mag=False):
     """build_lstm_model(..., 'training').predict([feat, caps]) -> [B,T,V].  rec_masks: see v1_word_model_forward.  Masks of
     shape [4,B,512] are applied to every prefix of a RoI (the product's single-pass form); masks of shape [T,4,B,512] give prefix
     j its own set rec_masks[.][j] -- what Keras draws: TimeDistributed(word_model) (text_generation_model.py:187) applies the
-    LSTM cells once per prefix and each application makes its own K.dropout masks."""
-    f, hc = roi_head_forward(feat, Wt)
+    LSTM cells once per prefix and each application makes its own K.dropout masks.
+    head_masks: roi_head_backward's `masks`, kept in the cache for v1_backward_from_dlogits; head_mag: roi_head_forward's `mag`."""
+    f, hc = roi_head_forward(feat, Wt, mag=head_mag)
     P = v1_prefixes(caps)
     T = P.shape[1]
     outs, caches = [], []
@@ -416,7 +428,7 @@ def v1_training_forward(Wt, feat, caps, rec_masks=None):
         p, c = v1_word_model_forward(Wt, f, P[:, j], rm)
         outs.append(p)
         caches.append(c)
-    return np.stack(outs, axis=1), dict(head=hc, f=f, caches=caches)
+    return np.stack(outs, axis=1), dict(head=hc, f=f, caches=caches, head_masks=head_masks)
 
 
 def v1_loss_and_grads(Wt, feat, caps, rec_masks=None):
@@ -438,16 +450,17 @@ def v1_loss_and_grads(Wt, feat, caps, rec_masks=None):
     return loss, G, probs
 
 
-def v1_backward_from_dlogits(Wt, cache, dlog):
+def v1_backward_from_dlogits(Wt, cache, dlog, head_masks=None):
     """Backward of v1_training_forward for an arbitrary gradient w.r.t. the softmax LOGITS [B,T,V] (the joint
-    model's masked sparse-CE).  Returns (grads dict incl. '_dx' = d RoI features [B,12544])."""
+    model's masked sparse-CE).  Returns (grads dict incl. '_dx' = d RoI features [B,12544]).
+    head_masks: the RoI head's ReLU decisions (roi_head_backward's `masks`); default: the ones the forward was given, if any."""
     G, df = {}, np.zeros_like(cache['f'])
     for j in range(dlog.shape[1]):
         dfj, Gj = v1_word_model_backward(Wt, dlog[:, j], cache['caches'][j])
         df += dfj
         for k, v in Gj.items():
             G[k] = G.get(k, 0.0) + v
-    G.update(roi_head_backward(df, cache['head']))
+    G.update(roi_head_backward(df, cache['head'], cache.get('head_masks') if head_masks is None else head_masks))
     return G
 
 
@@ -551,7 +564,7 @@ def joint_trainable(Wt):
 
 
 def joint_loss_and_grads(Wt, image_u8, rpn_match, rpn_bbox_target, gt_captions, gt_boxes_px, cfg, shuffle=None, stage4_blocks=22,
-                         targets_override=None, backbone_from=None, term_weights=None, trunk_cache=None):
+                         targets_override=None, backbone_from=None, term_weights=None, trunk_cache=None, head_masks=None):
     """One training step's losses and gradients for ONE image (IMAGES_PER_GPU = 1, train_dense_captions.py:27).
     term_weights = dict(imgcap_loss=, rpn_class_loss=, rpn_bbox_loss=, reg_loss=): every loss term AND its gradient is scaled by its
     weight -- how joint_loss_and_grads_batch pools a batch (below).  trunk_cache: a dict that keeps the frozen ResNet's C2..C5 of this
@@ -560,6 +573,9 @@ def joint_loss_and_grads(Wt, image_u8, rpn_match, rpn_bbox_target, gt_captions, 
     cfg: dict(mean_pixel, scales, ratios, strides, proposal_count, nms, train_rois, positive_ratio, weight_decay, T).
     targets_override = (rois [R,4] normalised, caps [R,T]) replaces the DetectionTargetLayer's sample (which carries no
     gradient): parity tests hand in the sample the device drew, since near-tied proposal scores may order differently.
+    head_masks = (m1, m2) boolean [R,1024]: the RoI head's two ReLU decisions for the backward (roi_head_backward); parity tests hand
+    in the device's, which they check against aux['head_z'] (the float64 pre-activations) with the bound aux['head_mag'] /
+    aux['head_acc'] give (tests/_parity_cuts.py).  aux['rpn_cls'] / aux['rpn_box']: the RPN head outputs per pyramid level [1,h,w,2A] / [1,h,w,4A].
     Returns (losses dict, grads dict over joint_trainable(Wt), aux dict)."""
     x = O.mold_image(image_u8[None], cfg['mean_pixel'])
     _, H, W, _ = x.shape
@@ -600,7 +616,7 @@ def joint_loss_and_grads(Wt, image_u8, rpn_match, rpn_bbox_target, gt_captions, 
         rois, caps = np.asarray(targets_override[0], np.float32), np.asarray(targets_override[1])
     maps = [P[2], P[3], P[4], P[5]]
     feats = O.pyramid_roi_align(rois[None], maps, (H, W, 3), 7)[0]
-    cap_probs, cache = v1_training_forward(Wt, feats, caps.astype(np.float64))
+    cap_probs, cache = v1_training_forward(Wt, feats, caps.astype(np.float64), head_masks=head_masks, head_mag=True)
     tg = v1_targets(caps)                                             # remove <start>, append 0
     w = (tg > 0).astype(F64)
     cnt = w.sum()
@@ -654,12 +670,14 @@ def joint_loss_and_grads(Wt, image_u8, rpn_match, rpn_bbox_target, gt_captions, 
         G.update(resnet_backward(dC, trunk_caches, Wt, backbone_from))
     for k in reg_keys:
         G[k] = G[k] + tw['reg_loss'] * 2.0 * cfg['weight_decay'] * np.asarray(Wt[k], F64) / np.asarray(Wt[k]).size
-    aux = dict(proposals=proposals, rois=rois, caps=caps, npos=npos, nneg=nneg, count=cnt, cap_probs=cap_probs, anchors=anchors)
+    hc = cache['head']
+    aux = dict(proposals=proposals, rois=rois, caps=caps, npos=npos, nneg=nneg, count=cnt, cap_probs=cap_probs, anchors=anchors,
+               head_z=(hc['z1'], hc['z2']), head_mag=(hc['mag1'], hc['mag2']), head_acc=(hc['acc1'], hc['acc2']), rpn_cls=cls, rpn_box=box)
     return losses, {k: G[k] for k in train}, aux
 
 
 def joint_loss_and_grads_batch(Wt, images_u8, rpn_match, rpn_bbox_target, gt_captions, gt_boxes_px, cfg, targets_override, stage4_blocks=22,
-                               trunk_caches=None):
+                               trunk_caches=None, head_masks=None):
     """The reference's BATCHED training graph (IMAGES_PER_GPU = B, dense_img_cap/config.py:35): DetectionTargetLayer slices the batch
     (utils.batch_slice, dense_model.py:531-572), every loss gathers over ALL images before its mean --
       rpn_class_loss   mean over the non-neutral anchors of the batch               (:877-900)
@@ -667,7 +685,8 @@ def joint_loss_and_grads_batch(Wt, images_u8, rpn_match, rpn_bbox_target, gt_cap
       imgcap_loss      mean over the caption positions with target > 0 of the batch  (:936-946)
     -- so the batch loss is NOT the mean of the per-image losses when the images' counts differ: image b's per-image mean enters
     with the weight count_b / sum(count).  The weight regulariser is counted once.  Arguments carry the image axis first;
-    targets_override = (rois [B,R,4], caps [B,R,T]) as in joint_loss_and_grads.  Returns (losses, grads, [aux per image])."""
+    targets_override = (rois [B,R,4], caps [B,R,T]) as in joint_loss_and_grads; head_masks = (m1, m2) boolean [B*R,1024] in the device's
+    row order: image b's are rows [b*R, (b+1)*R).  Returns (losses, grads, [aux per image])."""
     B = len(images_u8)
     rpn_match = [np.asarray(m).reshape(-1) for m in rpn_match]
     n_sel = np.array([(m != 0).sum() for m in rpn_match], F64)
@@ -677,11 +696,13 @@ def joint_loss_and_grads_batch(Wt, images_u8, rpn_match, rpn_bbox_target, gt_cap
     share = lambda n: n / max(n.sum(), 1.0)
     w_cls, w_box, w_cap = share(n_sel), share(n_pos), share(n_tok)
     losses, grads, auxes = {}, {}, []
+    R = np.asarray(targets_override[0]).shape[1]
     for b in range(B):
         tw = dict(imgcap_loss=w_cap[b], rpn_class_loss=w_cls[b], rpn_bbox_loss=w_box[b], reg_loss=1.0 if b == 0 else 0.0)
         l, g, aux = joint_loss_and_grads(Wt, images_u8[b], rpn_match[b], rpn_bbox_target[b], gt_captions[b], gt_boxes_px[b], cfg,
                                          stage4_blocks=stage4_blocks, targets_override=(targets_override[0][b], caps[b]), term_weights=tw,
-                                         trunk_cache=None if trunk_caches is None else trunk_caches[b])
+                                         trunk_cache=None if trunk_caches is None else trunk_caches[b],
+                                         head_masks=None if head_masks is None else tuple(np.asarray(m)[b * R:(b + 1) * R] for m in head_masks))
         for k, v in l.items():
             losses[k] = losses.get(k, 0.0) + v
         for k, v in g.items():

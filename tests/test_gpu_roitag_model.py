@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from _joint_cases import joint_inputs
+import _parity_cuts as PC
 import _roitag_ref as R
 
 pytestmark = pytest.mark.gpu
@@ -124,6 +125,14 @@ def test_tag_model_step_matches_the_float64_reference(gpu):
     assert tg['caps'].shape == (12, C) and live.sum() > 0, "no live RoI: the tag loss is not exercised"
     agree = sum(1 for r in tg['rois'] if np.abs(s['aux']['proposals'] - r).sum(1).min() < 1e-5)
     assert agree >= 0.8 * (tg['npos'] + tg['nneg'])
+    # exactly: the proposals from the device's own scores, every sampled RoI one of them bit for bit, and the sample what
+    # DetectionTargetLayer selects from them and the step's GT rows.  (tests/_roitag_ref.py restates the tag step behind the sample, not
+    # the sampler; the tag model samples with the joint model's DetectionTargetLayer, whose reference is the oracle's, with the tag rows
+    # in the captions' place.  The reference's aux carries no RPN head outputs: the heads are compared in the joint model's tests.)
+    plan, inputs = s['model'].plan(), s['inputs']
+    props = PC.check_proposals_from_device_scores(plan, plan.anchors.cpu().numpy(), oracle_cfg(s['cfg']), 1)
+    PC.assert_rois_are_proposals(tg['rois'], tg['npos'] + tg['nneg'], props[0])
+    PC.check_sample(tg, props, inputs[4], inputs[5], S, S, s['cfg'])
     assert want['roi_tag_classes_loss'] > 0
     for k in LOSSES:
         print("  %s: got %.8f want %.8f" % (k, losses[k], want[k]))
