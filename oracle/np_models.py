@@ -8,6 +8,19 @@ cannot run here); the host-side geometry they call is pinned -- see the np_oracl
 
 Weights are a dict keyed '<keras layer name>/<weight name>' with Keras shapes
 (kernel HWIO / [in,out], LSTM gate blocks i,f,c,o).
+
+The rounding hook `quant` (joint model and what it is made of: trunk, FPN / RPN, RoI head, Model-3 decoder, vocabulary loss).
+quant(site, role, array) returns the array the matrix product at `site` reads; a model that runs that product from bf16 copies of its
+operands is restated by a quant that returns O.to_bf16(array) there and the array itself everywhere else (tests/_bf16_sites.py).
+  site  '<layer>:fwd' | '<layer>:dgrad' | '<layer>:wgrad'.  <layer> is the Keras layer name; a layer whose product the models split
+        names the part ('imgcap_lstm1.emb' / '.feat' / '.rec': the embedding rows, the feature rows and the recurrent kernel;
+        'imgcap_lstm_d1.h' / '.feat'), and a layer applied to several maps names the map ('rpn_conv_shared@P2').
+  role  'x' (the layer's input), 'w' (its kernel), 'dy' (the gradient w.r.t. its output), 'out' (an output that is stored rounded and
+        read back: the materialised logits of the vocabulary layer).
+A weight gradient is q(x)^T q(dy), a data gradient q(dy) q(w)^T; biases, BatchNorm parameters, the LSTM recurrences, every
+reduction and every elementwise step stay float64.  With a quant the Model-3 decoder is evaluated in its single-pass form (one LSTM
+pass over the caption serves all T prefixes: the same function, v1_single_pass_forward), because where a sum over the prefixes is
+rounded is part of the specification.  quant=None leaves every function on the code path it had before the hook existed.
 """
 import numpy as np
 
@@ -16,74 +29,78 @@ from . import np_oracle as O
 F64 = np.float64
 
 
+def _q(quant, site, role, a):
+    return a if quant is None else np.asarray(quant(site, role, a))      # (the hook's dtype is kept: a float32 stand-in multiplies in float32)
+
+
 # --------------------------------------------------------------------------------------------
 # Encoder: ResNet-101 + FPN (feature_generation/dense_model.py:82-173, :1404-1427;
 # dense_img_cap_separate_models/modified_dense_model.py:1410-1433)
 # --------------------------------------------------------------------------------------------
 
-def _conv_bn(x, Wt, conv, bn, stride=1, padding='valid', act=True):
-    y = O.conv2d_nhwc(x, Wt[conv + '/kernel'], Wt[conv + '/bias'], stride, padding)
+def _conv_bn(x, Wt, conv, bn, stride=1, padding='valid', act=True, quant=None):
+    y = O.conv2d_nhwc(x, Wt[conv + '/kernel'], Wt[conv + '/bias'], stride, padding, quant=quant, site=conv)
     y = O.batchnorm_inference(y, Wt[bn + '/gamma'], Wt[bn + '/beta'],
                               Wt[bn + '/moving_mean'], Wt[bn + '/moving_variance'])
     return O.relu(y) if act else y
 
 
-def _bottleneck(x, Wt, stage, block, stride, shortcut_conv):
+def _bottleneck(x, Wt, stage, block, stride, shortcut_conv, quant=None):
     cn, bn = 'res%d%s_branch' % (stage, block), 'bn%d%s_branch' % (stage, block)
-    y = _conv_bn(x, Wt, cn + '2a', bn + '2a', stride=stride)            # stride on the first 1x1
-    y = _conv_bn(y, Wt, cn + '2b', bn + '2b', padding='same')
-    y = _conv_bn(y, Wt, cn + '2c', bn + '2c', act=False)
-    sc = _conv_bn(x, Wt, cn + '1', bn + '1', stride=stride, act=False) if shortcut_conv else x
+    y = _conv_bn(x, Wt, cn + '2a', bn + '2a', stride=stride, quant=quant)            # stride on the first 1x1
+    y = _conv_bn(y, Wt, cn + '2b', bn + '2b', padding='same', quant=quant)
+    y = _conv_bn(y, Wt, cn + '2c', bn + '2c', act=False, quant=quant)
+    sc = _conv_bn(x, Wt, cn + '1', bn + '1', stride=stride, act=False, quant=quant) if shortcut_conv else x
     return O.relu(y + sc)
 
 
-def _conv_bn_cached(x, Wt, conv, bn, stride=1, padding='valid'):
+def _conv_bn_cached(x, Wt, conv, bn, stride=1, padding='valid', quant=None):
     """conv + frozen-statistics BN (no activation) with what the backward needs."""
-    a = O.conv2d_nhwc(x, Wt[conv + '/kernel'], Wt[conv + '/bias'], stride, padding)
+    a = O.conv2d_nhwc(x, Wt[conv + '/kernel'], Wt[conv + '/bias'], stride, padding, quant=quant, site=conv)
     rstd = 1.0 / np.sqrt(np.asarray(Wt[bn + '/moving_variance'], F64) + O.BN_EPS)
     xhat = (a - np.asarray(Wt[bn + '/moving_mean'], F64)) * rstd
     y = np.asarray(Wt[bn + '/gamma'], F64) * xhat + np.asarray(Wt[bn + '/beta'], F64)
     return y, dict(x=x, xhat=xhat, rstd=rstd, conv=conv, bn=bn, stride=stride, padding=padding)
 
 
-def _conv_bn_backward(dy, c, Wt, G):
+def _conv_bn_backward(dy, c, Wt, G, quant=None):
     """dy = d(loss)/d(BN output).  Adds the gradients of kernel / bias / gamma / beta to G, returns d(loss)/d(conv input)."""
     G[c['bn'] + '/gamma'] = (dy * c['xhat']).sum(axis=(0, 1, 2))
     G[c['bn'] + '/beta'] = dy.sum(axis=(0, 1, 2))
     da = dy * (np.asarray(Wt[c['bn'] + '/gamma'], F64) * c['rstd'])
-    dx, dw, db = O.conv2d_nhwc_backward(c['x'], Wt[c['conv'] + '/kernel'], da, c['stride'], c['padding'])
+    dx, dw, db = O.conv2d_nhwc_backward(c['x'], Wt[c['conv'] + '/kernel'], da, c['stride'], c['padding'], quant=quant, site=c['conv'])
     G[c['conv'] + '/kernel'], G[c['conv'] + '/bias'] = dw, db
     return dx
 
 
-def _bottleneck_cached(x, Wt, stage, block, stride, shortcut_conv):
+def _bottleneck_cached(x, Wt, stage, block, stride, shortcut_conv, quant=None):
     cn, bn = 'res%d%s_branch' % (stage, block), 'bn%d%s_branch' % (stage, block)
-    ya, ca = _conv_bn_cached(x, Wt, cn + '2a', bn + '2a', stride)
+    ya, ca = _conv_bn_cached(x, Wt, cn + '2a', bn + '2a', stride, quant=quant)
     m1 = O.relu(ya)
-    yb, cb = _conv_bn_cached(m1, Wt, cn + '2b', bn + '2b', 1, 'same')
+    yb, cb = _conv_bn_cached(m1, Wt, cn + '2b', bn + '2b', 1, 'same', quant=quant)
     m2 = O.relu(yb)
-    yc, cc = _conv_bn_cached(m2, Wt, cn + '2c', bn + '2c')
+    yc, cc = _conv_bn_cached(m2, Wt, cn + '2c', bn + '2c', quant=quant)
     c1 = None
     if shortcut_conv:
-        sc, c1 = _conv_bn_cached(x, Wt, cn + '1', bn + '1', stride)
+        sc, c1 = _conv_bn_cached(x, Wt, cn + '1', bn + '1', stride, quant=quant)
     else:
         sc = x
     out = O.relu(yc + sc)
     return out, dict(a=ca, b=cb, c=cc, s=c1, m1=m1, m2=m2, out=out)
 
 
-def _bottleneck_backward(d_out, k, Wt, G):
+def _bottleneck_backward(d_out, k, Wt, G, quant=None):
     ds = d_out * (k['out'] > 0)
-    dm2 = _conv_bn_backward(ds, k['c'], Wt, G)
-    dm1 = _conv_bn_backward(dm2 * (k['m2'] > 0), k['b'], Wt, G)
-    dx = _conv_bn_backward(dm1 * (k['m1'] > 0), k['a'], Wt, G)
-    return dx + (ds if k['s'] is None else _conv_bn_backward(ds, k['s'], Wt, G))
+    dm2 = _conv_bn_backward(ds, k['c'], Wt, G, quant)
+    dm1 = _conv_bn_backward(dm2 * (k['m2'] > 0), k['b'], Wt, G, quant)
+    dx = _conv_bn_backward(dm1 * (k['m1'] > 0), k['a'], Wt, G, quant)
+    return dx + (ds if k['s'] is None else _conv_bn_backward(ds, k['s'], Wt, G, quant))
 
 
-def resnet_graph_cached(image, Wt, stage4_blocks=22):
+def resnet_graph_cached(image, Wt, stage4_blocks=22, quant=None):
     """resnet_graph with the per-block caches the backward of trainable stages needs (train(layers="3+" ...))."""
     x = np.pad(np.asarray(image, F64), ((0, 0), (3, 3), (3, 3), (0, 0)))
-    y1, c_stem = _conv_bn_cached(x, Wt, 'conv1', 'bn_conv1', 2)
+    y1, c_stem = _conv_bn_cached(x, Wt, 'conv1', 'bn_conv1', 2, quant=quant)
     r1 = O.relu(y1)
     x = C1 = O.maxpool3x3s2_same(r1)
     caches = {1: dict(stem=c_stem, r1=r1, pooled=C1), 2: [], 3: [], 4: [], 5: []}
@@ -91,7 +108,7 @@ def resnet_graph_cached(image, Wt, stage4_blocks=22):
     Cs = {1: C1}
     for stage, blocks, stride in plan:
         for i, blk in enumerate(blocks):
-            x, k = _bottleneck_cached(x, Wt, stage, blk, stride if i == 0 else 1, i == 0)
+            x, k = _bottleneck_cached(x, Wt, stage, blk, stride if i == 0 else 1, i == 0, quant=quant)
             caches[stage].append(k)
         Cs[stage] = x
     return Cs, caches
@@ -121,7 +138,7 @@ def maxpool3x3s2_same_backward(x, y, dy):
     return dx
 
 
-def resnet_backward(dC, caches, Wt, backbone_from):
+def resnet_backward(dC, caches, Wt, backbone_from, quant=None):
     """dC: {stage: gradient w.r.t. that stage's output C_stage} (the FPN laterals' data gradients).  Walks the trainable stages
     top-down; returns the gradients of their kernels, biases, gammas and betas."""
     G = {}
@@ -131,11 +148,11 @@ def resnet_backward(dC, caches, Wt, backbone_from):
             break
         d = dC[stage] if d is None else dC[stage] + d
         for k in reversed(caches[stage]):
-            d = _bottleneck_backward(d, k, Wt, G)
+            d = _bottleneck_backward(d, k, Wt, G, quant)
     if backbone_from == 1:
         st = caches[1]
         d1 = maxpool3x3s2_same_backward(st['r1'], st['pooled'], d)
-        _conv_bn_backward(d1 * (st['r1'] > 0), st['stem'], Wt, G)
+        _conv_bn_backward(d1 * (st['r1'] > 0), st['stem'], Wt, G, quant)
     return G
 
 
@@ -153,33 +170,33 @@ def backbone_trainable(Wt, backbone_from, stage4_blocks=22):
     return keys
 
 
-def resnet_graph(image, Wt, stage4_blocks=22):
+def resnet_graph(image, Wt, stage4_blocks=22, quant=None):
     """resnet_graph(input_image, 'resnet101', stage5=True) (dense_model.py:143-173).
     stage4_blocks=22 is ResNet-101 (5 = the file's 'resnet50' option, used for fast tests)."""
     x = np.pad(np.asarray(image, F64), ((0, 0), (3, 3), (3, 3), (0, 0)))   # ZeroPadding2D((3,3))
-    x = _conv_bn(x, Wt, 'conv1', 'bn_conv1', stride=2)
+    x = _conv_bn(x, Wt, 'conv1', 'bn_conv1', stride=2, quant=quant)
     x = C1 = O.maxpool3x3s2_same(x)
-    x = _bottleneck(x, Wt, 2, 'a', 1, True)
-    x = _bottleneck(x, Wt, 2, 'b', 1, False)
-    x = C2 = _bottleneck(x, Wt, 2, 'c', 1, False)
-    x = _bottleneck(x, Wt, 3, 'a', 2, True)
+    x = _bottleneck(x, Wt, 2, 'a', 1, True, quant)
+    x = _bottleneck(x, Wt, 2, 'b', 1, False, quant)
+    x = C2 = _bottleneck(x, Wt, 2, 'c', 1, False, quant)
+    x = _bottleneck(x, Wt, 3, 'a', 2, True, quant)
     for blk in 'bcd':
-        x = _bottleneck(x, Wt, 3, blk, 1, False)
+        x = _bottleneck(x, Wt, 3, blk, 1, False, quant)
     C3 = x
-    x = _bottleneck(x, Wt, 4, 'a', 2, True)
+    x = _bottleneck(x, Wt, 4, 'a', 2, True, quant)
     for i in range(stage4_blocks):
-        x = _bottleneck(x, Wt, 4, chr(98 + i), 1, False)
+        x = _bottleneck(x, Wt, 4, chr(98 + i), 1, False, quant)
     C4 = x
-    x = _bottleneck(x, Wt, 5, 'a', 2, True)
-    x = _bottleneck(x, Wt, 5, 'b', 1, False)
-    x = C5 = _bottleneck(x, Wt, 5, 'c', 1, False)
+    x = _bottleneck(x, Wt, 5, 'a', 2, True, quant)
+    x = _bottleneck(x, Wt, 5, 'b', 1, False, quant)
+    x = C5 = _bottleneck(x, Wt, 5, 'c', 1, False, quant)
     return C1, C2, C3, C4, C5
 
 
-def fpn_graph(C2, C3, C4, C5, Wt):
-    """Top-down pathway (dense_model.py:1406-1423). Returns P2,P3,P4,P5,P6."""
+def fpn_graph(C2, C3, C4, C5, Wt, quant=None):
+    """Top-down pathway (dense_model.py:1406-1423). Returns P2,P3,P4,P5,P6.  quant: the rounding hook (module header)."""
     def conv(x, name, padding='valid'):
-        return O.conv2d_nhwc(x, Wt[name + '/kernel'], Wt[name + '/bias'], 1, padding)
+        return O.conv2d_nhwc(x, Wt[name + '/kernel'], Wt[name + '/bias'], 1, padding, quant=quant, site=name)
     P5 = conv(C5, 'fpn_c5p5')
     P4 = O.upsample2x(P5) + conv(C4, 'fpn_c4p4')
     P3 = O.upsample2x(P4) + conv(C3, 'fpn_c3p3')
@@ -217,10 +234,12 @@ def image_level_features(roi_feats):
 # RoI head  mrcnn_class_conv1/bn1/conv2/bn2 (text_generation_model.py:250-262; _v2.py:141-150)
 # --------------------------------------------------------------------------------------------
 
-def roi_head_forward(feat, Wt, mag=False):
+def roi_head_forward(feat, Wt, mag=False, quant=None):
     """[R,7,7,256] -> conv7x7 valid -> BN -> ReLU -> conv1x1 -> BN -> ReLU -> squeeze -> [R,1024].
     The cache carries the two pre-activations z1, z2 (g * n + b, before the ReLU) and the two GEMM results acc1, acc2 (y - bias); with
-    mag=True also the magnitude sums |x| @ |K1| and |a1| @ |K2| that bound a fp32 GEMM's error (parity tests: tests/_parity_cuts.py)."""
+    mag=True also the magnitude sums |x| @ |K1| and |a1| @ |K2| that bound a fp32 GEMM's error (parity tests: tests/_parity_cuts.py).
+    quant: the rounding hook (module header), sites mrcnn_class_conv1 / mrcnn_class_conv2; the magnitude sums are then those of the
+    operands the products read."""
     R = feat.shape[0]
     x = np.asarray(feat, F64).reshape(R, -1)                       # (h,w,c) row-major == HWIO flatten
     K1 = np.asarray(Wt['mrcnn_class_conv1/kernel'], F64).reshape(-1, 1024)
@@ -228,13 +247,15 @@ def roi_head_forward(feat, Wt, mag=False):
     bn = lambda y, n: (np.asarray(Wt[n + '/gamma'], F64), np.asarray(Wt[n + '/beta'], F64),
                        np.asarray(Wt[n + '/moving_mean'], F64),
                        np.sqrt(np.asarray(Wt[n + '/moving_variance'], F64) + O.BN_EPS))
-    acc1 = x @ K1
+    xq, K1q = _q(quant, 'mrcnn_class_conv1:fwd', 'x', x), _q(quant, 'mrcnn_class_conv1:fwd', 'w', K1)
+    acc1 = xq @ K1q
     y1 = acc1 + np.asarray(Wt['mrcnn_class_conv1/bias'], F64)
     g1, b1, m1, s1 = bn(y1, 'mrcnn_class_bn1')
     n1 = (y1 - m1) / s1
     z1 = g1 * n1 + b1
     a1 = O.relu(z1)
-    acc2 = a1 @ K2
+    a1q, K2q = _q(quant, 'mrcnn_class_conv2:fwd', 'x', a1), _q(quant, 'mrcnn_class_conv2:fwd', 'w', K2)
+    acc2 = a1q @ K2q
     y2 = acc2 + np.asarray(Wt['mrcnn_class_conv2/bias'], F64)
     g2, b2, m2, s2 = bn(y2, 'mrcnn_class_bn2')
     n2 = (y2 - m2) / s2
@@ -242,28 +263,31 @@ def roi_head_forward(feat, Wt, mag=False):
     f = O.relu(z2)
     cache = dict(x=x, K1=K1, K2=K2, n1=n1, a1=a1, n2=n2, f=f, g1=g1, s1=s1, g2=g2, s2=s2, z1=z1, z2=z2, acc1=acc1, acc2=acc2)
     if mag:
-        cache.update(mag1=np.abs(x) @ np.abs(K1), mag2=np.abs(a1) @ np.abs(K2))
+        cache.update(mag1=np.abs(xq) @ np.abs(K1q), mag2=np.abs(a1q) @ np.abs(K2q))
     return f, cache
 
 
-def roi_head_backward(df, cache, masks=None):
+def roi_head_backward(df, cache, masks=None, quant=None):
     """Gradients of the trainable head weights (v1 / joint model: kernels, biases, BN gamma/beta).
     masks = (m1, m2), boolean [R,1024] each: the two ReLU decisions handed in by the caller -- they stand for (a1 > 0) and (f > 0)
-    in this backward (the forward is not touched).  A parity test passes the decisions the device took, after it has checked them."""
+    in this backward (the forward is not touched).  A parity test passes the decisions the device took, after it has checked them.
+    quant: the rounding hook (module header) on the four products of this backward."""
     c = cache
     m1, m2 = (c['a1'] > 0, c['f'] > 0) if masks is None else (np.asarray(masks[0], bool), np.asarray(masks[1], bool))
     dz2 = df * m2
     G = {'mrcnn_class_bn2/gamma': (dz2 * c['n2']).sum(0), 'mrcnn_class_bn2/beta': dz2.sum(0)}
     dy2 = dz2 * c['g2'] / c['s2']
-    G['mrcnn_class_conv2/kernel'] = (c['a1'].T @ dy2).reshape(1, 1, 1024, 1024)
+    s2 = 'mrcnn_class_conv2'
+    G['mrcnn_class_conv2/kernel'] = (_q(quant, s2 + ':wgrad', 'x', c['a1']).T @ _q(quant, s2 + ':wgrad', 'dy', dy2)).reshape(1, 1, 1024, 1024)
     G['mrcnn_class_conv2/bias'] = dy2.sum(0)
-    dz1 = (dy2 @ c['K2'].T) * m1
+    dz1 = (_q(quant, s2 + ':dgrad', 'dy', dy2) @ _q(quant, s2 + ':dgrad', 'w', c['K2']).T) * m1
     G['mrcnn_class_bn1/gamma'] = (dz1 * c['n1']).sum(0)
     G['mrcnn_class_bn1/beta'] = dz1.sum(0)
     dy1 = dz1 * c['g1'] / c['s1']
-    G['mrcnn_class_conv1/kernel'] = (c['x'].T @ dy1).reshape(7, 7, 256, 1024)
+    s1 = 'mrcnn_class_conv1'
+    G['mrcnn_class_conv1/kernel'] = (_q(quant, s1 + ':wgrad', 'x', c['x']).T @ _q(quant, s1 + ':wgrad', 'dy', dy1)).reshape(7, 7, 256, 1024)
     G['mrcnn_class_conv1/bias'] = dy1.sum(0)
-    G['_dx'] = dy1 @ c['K1'].T                        # gradient w.r.t. the flattened RoI features [R,12544]
+    G['_dx'] = _q(quant, s1 + ':dgrad', 'dy', dy1) @ _q(quant, s1 + ':dgrad', 'w', c['K1']).T     # gradient w.r.t. the flattened RoI features [R,12544]
     return G
 
 
@@ -413,13 +437,85 @@ def v1_targets(caps):
     return np.concatenate([caps[:, 1:], np.zeros((caps.shape[0], 1))], axis=1).astype(np.int32)
 
 
-def v1_training_forward(Wt, feat, caps, rec_masks=None, head_masks=None, head_mag=False):
+def v1_single_pass_forward(Wt, f, caps, quant=None):
+    """The T prefix evaluations of v1_word_model_forward as ONE pass over the caption: prefix j is the caption's first j tokens followed by
+    zeros, which the mask carries the state over, so the state after prefix j is the state of the single pass after step j - 1 and row
+    [b, j - 1] of the result is word_model(prefix j of RoI b).  The same function as the loop in v1_training_forward (no recurrent
+    dropout); it exists because it is the form in which the sums over the prefixes are formed BEFORE an operand is rounded.
+    f [B,1024], caps [B,T] -> probs [B,T,V], cache.  quant: the rounding hook (module header)."""
+    q = lambda site, role, a: _q(quant, site, role, a)
+    caps = np.asarray(caps, F64)
+    B, T = caps.shape
+    emb, mask = O.embedding(caps, Wt['imgcap_embedding_layer/embeddings'])
+    E = emb.shape[2]
+    W1 = np.asarray(Wt['imgcap_lstm1/kernel'], F64)
+    x = np.concatenate([q('imgcap_lstm1.emb:fwd', 'x', emb), np.repeat(q('imgcap_lstm1.feat:fwd', 'x', f)[:, None, :], T, axis=1)], axis=2)
+    W1q = np.concatenate([q('imgcap_lstm1.emb:fwd', 'w', W1[:E]), q('imgcap_lstm1.feat:fwd', 'w', W1[E:])], axis=0)
+    H1, c1 = O.lstm_forward(x, mask, W1q, Wt['imgcap_lstm1/recurrent_kernel'], Wt['imgcap_lstm1/bias'])
+    H2, c2 = O.lstm_forward(q('imgcap_lstm2:fwd', 'x', H1), mask, q('imgcap_lstm2:fwd', 'w', np.asarray(Wt['imgcap_lstm2/kernel'], F64)),
+                            Wt['imgcap_lstm2/recurrent_kernel'], Wt['imgcap_lstm2/bias'])
+    u = H2.shape[2]
+    Wd1, Wd2 = np.asarray(Wt['imgcap_lstm_d1/kernel'], F64), np.asarray(Wt['imgcap_lstm_d2/kernel'], F64)
+    zdf = q('imgcap_lstm_d1.feat:fwd', 'x', f) @ q('imgcap_lstm_d1.feat:fwd', 'w', Wd1[u:])
+    z1 = q('imgcap_lstm_d1.h:fwd', 'x', H2) @ q('imgcap_lstm_d1.h:fwd', 'w', Wd1[:u]) + np.asarray(Wt['imgcap_lstm_d1/bias'], F64) + zdf[:, None, :]
+    a1 = O.relu(z1)
+    logits = q('imgcap_lstm_d2:fwd', 'x', a1) @ q('imgcap_lstm_d2:fwd', 'w', Wd2) + np.asarray(Wt['imgcap_lstm_d2/bias'], F64)
+    logits = q('imgcap_lstm_d2:fwd', 'out', logits)
+    probs = O.softmax(logits)
+    return probs, dict(emb=emb, f=f, H1=H1, H2=H2, c1=c1, c2=c2, a1=a1, E=E, u=u, logits=logits)
+
+
+def v1_single_pass_backward(Wt, dlog, c, quant=None):
+    """Backward of v1_single_pass_forward for dlog = d(loss)/d(logits) [B,T,V]: (df [B,1024], grads dict).  The products are formed where
+    the single pass forms them: the per-RoI halves of imgcap_lstm1 / imgcap_lstm_d1 from the gradients SUMMED over the prefixes, the
+    recurrent kernels' gradients as one product over all steps."""
+    q = lambda site, role, a: _q(quant, site, role, a)
+    B, T, V = dlog.shape
+    E, u, f = c['E'], c['u'], c['f']
+    flat = lambda a: a.reshape(B * T, -1)
+    prev = lambda H: np.concatenate([np.zeros_like(H[:, :1]), H[:, :-1]], axis=1)          # the state each step starts from
+    W1, W2 = np.asarray(Wt['imgcap_lstm1/kernel'], F64), np.asarray(Wt['imgcap_lstm2/kernel'], F64)
+    Wd1, Wd2 = np.asarray(Wt['imgcap_lstm_d1/kernel'], F64), np.asarray(Wt['imgcap_lstm_d2/kernel'], F64)
+    G = {'imgcap_lstm_d2/kernel': flat(q('imgcap_lstm_d2:wgrad', 'x', c['a1'])).T @ flat(q('imgcap_lstm_d2:wgrad', 'dy', dlog)),
+         'imgcap_lstm_d2/bias': flat(dlog).sum(0)}
+    dz1 = (q('imgcap_lstm_d2:dgrad', 'dy', dlog) @ q('imgcap_lstm_d2:dgrad', 'w', Wd2).T) * (c['a1'] > 0)
+    dzf = dz1.sum(1)                                                                        # [B,D1]: the per-RoI half, summed over the prefixes
+    G['imgcap_lstm_d1/kernel'] = np.concatenate([
+        flat(q('imgcap_lstm_d1.h:wgrad', 'x', c['H2'])).T @ flat(q('imgcap_lstm_d1.h:wgrad', 'dy', dz1)),
+        q('imgcap_lstm_d1.feat:wgrad', 'x', f).T @ q('imgcap_lstm_d1.feat:wgrad', 'dy', dzf)], axis=0)
+    G['imgcap_lstm_d1/bias'] = flat(dz1).sum(0)
+    df = q('imgcap_lstm_d1.feat:dgrad', 'dy', dzf) @ q('imgcap_lstm_d1.feat:dgrad', 'w', Wd1[u:]).T
+    dh2 = q('imgcap_lstm_d1.h:dgrad', 'dy', dz1) @ q('imgcap_lstm_d1.h:dgrad', 'w', Wd1[:u]).T
+    _, _, _, db, dz = O.lstm_backward(dh2, c['c2'], want_dz=True)
+    G['imgcap_lstm2/recurrent_kernel'] = flat(q('imgcap_lstm2.rec:wgrad', 'x', prev(c['H2']))).T @ flat(q('imgcap_lstm2.rec:wgrad', 'dy', dz))
+    G['imgcap_lstm2/kernel'] = flat(q('imgcap_lstm2:wgrad', 'x', c['H1'])).T @ flat(q('imgcap_lstm2:wgrad', 'dy', dz))
+    G['imgcap_lstm2/bias'] = db
+    dh1 = q('imgcap_lstm2:dgrad', 'dy', dz) @ q('imgcap_lstm2:dgrad', 'w', W2).T
+    _, _, _, db, dz = O.lstm_backward(dh1, c['c1'], want_dz=True)
+    G['imgcap_lstm1/recurrent_kernel'] = flat(q('imgcap_lstm1.rec:wgrad', 'x', prev(c['H1']))).T @ flat(q('imgcap_lstm1.rec:wgrad', 'dy', dz))
+    dzf = dz.sum(1)
+    G['imgcap_lstm1/kernel'] = np.concatenate([
+        flat(q('imgcap_lstm1.emb:wgrad', 'x', c['emb'])).T @ flat(q('imgcap_lstm1.emb:wgrad', 'dy', dz)),
+        q('imgcap_lstm1.feat:wgrad', 'x', f).T @ q('imgcap_lstm1.feat:wgrad', 'dy', dzf)], axis=0)
+    G['imgcap_lstm1/bias'] = db
+    df = df + q('imgcap_lstm1.feat:dgrad', 'dy', dzf) @ q('imgcap_lstm1.feat:dgrad', 'w', W1[E:]).T
+    return df, G
+
+
+def v1_training_forward(Wt, feat, caps, rec_masks=None, head_masks=None, head_mag=False, quant=None):
     """build_lstm_model(..., 'training').predict([feat, caps]) -> [B,T,V].  rec_masks: see v1_word_model_forward.  Masks of
     shape [4,B,512] are applied to every prefix of a RoI (the product's single-pass form); masks of shape [T,4,B,512] give prefix
     j its own set rec_masks[.][j] -- what Keras draws: TimeDistributed(word_model) (text_generation_model.py:187) applies the
     LSTM cells once per prefix and each application makes its own K.dropout masks.
-    head_masks: roi_head_backward's `masks`, kept in the cache for v1_backward_from_dlogits; head_mag: roi_head_forward's `mag`."""
-    f, hc = roi_head_forward(feat, Wt, mag=head_mag)
+    head_masks: roi_head_backward's `masks`, kept in the cache for v1_backward_from_dlogits; head_mag: roi_head_forward's `mag`.
+    quant: the rounding hook (module header); the decoder then runs as v1_single_pass_forward (no recurrent dropout), and the cache
+    keeps the hook for v1_backward_from_dlogits."""
+    f, hc = roi_head_forward(feat, Wt, mag=head_mag, quant=quant)
+    if quant is not None:
+        if rec_masks is not None:
+            raise ValueError("the rounding hook restates the step without recurrent dropout")
+        probs, sp = v1_single_pass_forward(Wt, f, caps, quant)
+        return probs, dict(head=hc, f=f, single=sp, head_masks=head_masks, quant=quant)
     P = v1_prefixes(caps)
     T = P.shape[1]
     outs, caches = [], []
@@ -454,6 +550,10 @@ def v1_backward_from_dlogits(Wt, cache, dlog, head_masks=None):
     """Backward of v1_training_forward for an arbitrary gradient w.r.t. the softmax LOGITS [B,T,V] (the joint
     model's masked sparse-CE).  Returns (grads dict incl. '_dx' = d RoI features [B,12544]).
     head_masks: the RoI head's ReLU decisions (roi_head_backward's `masks`); default: the ones the forward was given, if any."""
+    if cache.get('quant') is not None:                    # the forward ran with the rounding hook: the single-pass form, same hook
+        df, G = v1_single_pass_backward(Wt, dlog, cache['single'], cache['quant'])
+        G.update(roi_head_backward(df, cache['head'], cache.get('head_masks') if head_masks is None else head_masks, quant=cache['quant']))
+        return G
     G, df = {}, np.zeros_like(cache['f'])
     for j in range(dlog.shape[1]):
         dfj, Gj = v1_word_model_backward(Wt, dlog[:, j], cache['caches'][j])
@@ -564,7 +664,7 @@ def joint_trainable(Wt):
 
 
 def joint_loss_and_grads(Wt, image_u8, rpn_match, rpn_bbox_target, gt_captions, gt_boxes_px, cfg, shuffle=None, stage4_blocks=22,
-                         targets_override=None, backbone_from=None, term_weights=None, trunk_cache=None, head_masks=None):
+                         targets_override=None, backbone_from=None, term_weights=None, trunk_cache=None, head_masks=None, quant=None):
     """One training step's losses and gradients for ONE image (IMAGES_PER_GPU = 1, train_dense_captions.py:27).
     term_weights = dict(imgcap_loss=, rpn_class_loss=, rpn_bbox_loss=, reg_loss=): every loss term AND its gradient is scaled by its
     weight -- how joint_loss_and_grads_batch pools a batch (below).  trunk_cache: a dict that keeps the frozen ResNet's C2..C5 of this
@@ -576,22 +676,27 @@ def joint_loss_and_grads(Wt, image_u8, rpn_match, rpn_bbox_target, gt_captions, 
     head_masks = (m1, m2) boolean [R,1024]: the RoI head's two ReLU decisions for the backward (roi_head_backward); parity tests hand
     in the device's, which they check against aux['head_z'] (the float64 pre-activations) with the bound aux['head_mag'] /
     aux['head_acc'] give (tests/_parity_cuts.py).  aux['rpn_cls'] / aux['rpn_box']: the RPN head outputs per pyramid level [1,h,w,2A] / [1,h,w,4A].
+    quant: the rounding hook (module header) on every matrix product of the step: the trunk's convolutions, the FPN / RPN convolutions
+    (the RPN layers per map: 'rpn_conv_shared@P2' ...), the head, the decoder and the vocabulary layer.  A trunk_cache keeps the frozen
+    trunk of a rounded step apart from the unrounded one's; it serves ONE quant per dict.
     Returns (losses dict, grads dict over joint_trainable(Wt), aux dict)."""
     x = O.mold_image(image_u8[None], cfg['mean_pixel'])
     _, H, W, _ = x.shape
     tw = dict(imgcap_loss=1.0, rpn_class_loss=1.0, rpn_bbox_loss=1.0, reg_loss=1.0)
     tw.update(term_weights or {})
+    cs_key = 'Cs' if quant is None else 'Cs_quant'
     if backbone_from is None:
-        if trunk_cache is not None and 'Cs' in trunk_cache:
-            Cs = trunk_cache['Cs']
+        if trunk_cache is not None and cs_key in trunk_cache:
+            Cs = trunk_cache[cs_key]
         else:
-            _, C2, C3, C4, C5 = resnet_graph(x, Wt, stage4_blocks)
+            _, C2, C3, C4, C5 = resnet_graph(x, Wt, stage4_blocks, quant=quant)
             Cs = {2: C2, 3: C3, 4: C4, 5: C5}
             if trunk_cache is not None:
-                trunk_cache['Cs'] = Cs
+                trunk_cache[cs_key] = Cs
     else:                                                           # train(layers="3+" | "4+" | "5+" | "all"): ResNet stages train too
-        Cs, trunk_caches = resnet_graph_cached(x, Wt, stage4_blocks)
-    conv = lambda t, n, pad='valid': O.conv2d_nhwc(t, Wt[n + '/kernel'], Wt[n + '/bias'], 1, pad)
+        Cs, trunk_caches = resnet_graph_cached(x, Wt, stage4_blocks, quant=quant)
+    conv = lambda t, n, pad='valid', at='': O.conv2d_nhwc(t, Wt[n + '/kernel'], Wt[n + '/bias'], 1, pad, quant=quant, site=n + at)
+    conv_bwd = lambda t, n, d, pad='valid', at='': O.conv2d_nhwc_backward(t, Wt[n + '/kernel'], d, 1, pad, quant=quant, site=n + at)
     C5 = Cs[5]
     pre = {5: conv(C5, 'fpn_c5p5')}
     for k in (4, 3, 2):
@@ -601,9 +706,9 @@ def joint_loss_and_grads(Wt, image_u8, rpn_match, rpn_bbox_target, gt_captions, 
     # RPN
     shared, cls, box = {}, {}, {}
     for k in (2, 3, 4, 5, 6):
-        shared[k] = O.relu(conv(P[k], 'rpn_conv_shared', 'same'))
-        cls[k] = conv(shared[k], 'rpn_class_raw')
-        box[k] = conv(shared[k], 'rpn_bbox_pred')
+        shared[k] = O.relu(conv(P[k], 'rpn_conv_shared', 'same', '@P%d' % k))
+        cls[k] = conv(shared[k], 'rpn_class_raw', at='@P%d' % k)
+        box[k] = conv(shared[k], 'rpn_bbox_pred', at='@P%d' % k)
     logits = np.concatenate([cls[k].reshape(1, -1, 2) for k in (2, 3, 4, 5, 6)], axis=1)[0]
     bbox = np.concatenate([box[k].reshape(1, -1, 4) for k in (2, 3, 4, 5, 6)], axis=1)[0]
     probs = O.softmax(logits)
@@ -616,7 +721,7 @@ def joint_loss_and_grads(Wt, image_u8, rpn_match, rpn_bbox_target, gt_captions, 
         rois, caps = np.asarray(targets_override[0], np.float32), np.asarray(targets_override[1])
     maps = [P[2], P[3], P[4], P[5]]
     feats = O.pyramid_roi_align(rois[None], maps, (H, W, 3), 7)[0]
-    cap_probs, cache = v1_training_forward(Wt, feats, caps.astype(np.float64), head_masks=head_masks, head_mag=True)
+    cap_probs, cache = v1_training_forward(Wt, feats, caps.astype(np.float64), head_masks=head_masks, head_mag=True, quant=quant)
     tg = v1_targets(caps)                                             # remove <start>, append 0
     w = (tg > 0).astype(F64)
     cnt = w.sum()
@@ -645,18 +750,18 @@ def joint_loss_and_grads(Wt, image_u8, rpn_match, rpn_bbox_target, gt_captions, 
         dcls = dlogits[off:off + n].reshape(cls[k].shape)
         dbox = dbbox[off:off + n].reshape(box[k].shape)
         off += n
-        ds1, dw, db = O.conv2d_nhwc_backward(shared[k], Wt['rpn_class_raw/kernel'], dcls)
+        ds1, dw, db = conv_bwd(shared[k], 'rpn_class_raw', dcls, at='@P%d' % k)
         acc('rpn_class_raw/kernel', dw); acc('rpn_class_raw/bias', db)
-        ds2, dw, db = O.conv2d_nhwc_backward(shared[k], Wt['rpn_bbox_pred/kernel'], dbox)
+        ds2, dw, db = conv_bwd(shared[k], 'rpn_bbox_pred', dbox, at='@P%d' % k)
         acc('rpn_bbox_pred/kernel', dw); acc('rpn_bbox_pred/bias', db)
         dsh = (ds1 + ds2) * (shared[k] > 0)
-        dpk, dw, db = O.conv2d_nhwc_backward(P[k], Wt['rpn_conv_shared/kernel'], dsh, 1, 'same')
+        dpk, dw, db = conv_bwd(P[k], 'rpn_conv_shared', dsh, 'same', '@P%d' % k)
         acc('rpn_conv_shared/kernel', dw); acc('rpn_conv_shared/bias', db)
         dP[k] = dP[k] + dpk
     dP[5][:, ::2, ::2, :] += dP[6]                                    # MaxPooling2D(1, strides 2) backward
     dpre = {}
     for k in (2, 3, 4, 5):
-        dpre[k], dw, db = O.conv2d_nhwc_backward(pre[k], Wt['fpn_p%d/kernel' % k], dP[k], 1, 'same')
+        dpre[k], dw, db = conv_bwd(pre[k], 'fpn_p%d' % k, dP[k], 'same')
         G['fpn_p%d/kernel' % k], G['fpn_p%d/bias' % k] = dw, db
     for k in (2, 3, 4):                                               # top-down: pre[k] = up(pre[k+1]) + lateral
         g = dpre[k]
@@ -664,10 +769,10 @@ def joint_loss_and_grads(Wt, image_u8, rpn_match, rpn_bbox_target, gt_captions, 
         dpre[k + 1] = dpre[k + 1] + g.reshape(N_, h_ // 2, 2, w_ // 2, 2, c_).sum(axis=(2, 4))
     dC = {}
     for k in (2, 3, 4, 5):
-        dC[k], dw, db = O.conv2d_nhwc_backward(Cs[k], Wt['fpn_c%dp%d/kernel' % (k, k)], dpre[k])
+        dC[k], dw, db = conv_bwd(Cs[k], 'fpn_c%dp%d' % (k, k), dpre[k])
         G['fpn_c%dp%d/kernel' % (k, k)], G['fpn_c%dp%d/bias' % (k, k)] = dw, db
     if backbone_from is not None:
-        G.update(resnet_backward(dC, trunk_caches, Wt, backbone_from))
+        G.update(resnet_backward(dC, trunk_caches, Wt, backbone_from, quant))
     for k in reg_keys:
         G[k] = G[k] + tw['reg_loss'] * 2.0 * cfg['weight_decay'] * np.asarray(Wt[k], F64) / np.asarray(Wt[k]).size
     hc = cache['head']
@@ -677,7 +782,7 @@ def joint_loss_and_grads(Wt, image_u8, rpn_match, rpn_bbox_target, gt_captions, 
 
 
 def joint_loss_and_grads_batch(Wt, images_u8, rpn_match, rpn_bbox_target, gt_captions, gt_boxes_px, cfg, targets_override, stage4_blocks=22,
-                               trunk_caches=None, head_masks=None):
+                               trunk_caches=None, head_masks=None, quant=None):
     """The reference's BATCHED training graph (IMAGES_PER_GPU = B, dense_img_cap/config.py:35): DetectionTargetLayer slices the batch
     (utils.batch_slice, dense_model.py:531-572), every loss gathers over ALL images before its mean --
       rpn_class_loss   mean over the non-neutral anchors of the batch               (:877-900)
@@ -686,7 +791,8 @@ def joint_loss_and_grads_batch(Wt, images_u8, rpn_match, rpn_bbox_target, gt_cap
     -- so the batch loss is NOT the mean of the per-image losses when the images' counts differ: image b's per-image mean enters
     with the weight count_b / sum(count).  The weight regulariser is counted once.  Arguments carry the image axis first;
     targets_override = (rois [B,R,4], caps [B,R,T]) as in joint_loss_and_grads; head_masks = (m1, m2) boolean [B*R,1024] in the device's
-    row order: image b's are rows [b*R, (b+1)*R).  Returns (losses, grads, [aux per image])."""
+    row order: image b's are rows [b*R, (b+1)*R).  quant: joint_loss_and_grads' rounding hook, the same for every image (each image's
+    products are rounded on their own; a policy that counts sites sees every site once per image).  Returns (losses, grads, [aux per image])."""
     B = len(images_u8)
     rpn_match = [np.asarray(m).reshape(-1) for m in rpn_match]
     n_sel = np.array([(m != 0).sum() for m in rpn_match], F64)
@@ -702,7 +808,8 @@ def joint_loss_and_grads_batch(Wt, images_u8, rpn_match, rpn_bbox_target, gt_cap
         l, g, aux = joint_loss_and_grads(Wt, images_u8[b], rpn_match[b], rpn_bbox_target[b], gt_captions[b], gt_boxes_px[b], cfg,
                                          stage4_blocks=stage4_blocks, targets_override=(targets_override[0][b], caps[b]), term_weights=tw,
                                          trunk_cache=None if trunk_caches is None else trunk_caches[b],
-                                         head_masks=None if head_masks is None else tuple(np.asarray(m)[b * R:(b + 1) * R] for m in head_masks))
+                                         head_masks=None if head_masks is None else tuple(np.asarray(m)[b * R:(b + 1) * R] for m in head_masks),
+                                         quant=quant)
         for k, v in l.items():
             losses[k] = losses.get(k, 0.0) + v
         for k, v in g.items():

@@ -49,12 +49,16 @@ def _resolve_pad(H, W, kh, kw, stride, padding):
     return pt, pb, pl, pr
 
 
-def conv2d_nhwc(x, w, b=None, stride=1, padding='valid'):
+def conv2d_nhwc(x, w, b=None, stride=1, padding='valid', quant=None, site=None):
     """Keras Conv2D, channels_last, kernel HWIO [kh,kw,cin,cout]
     (dense_model.py:85-97 identity_block, :120-136 conv_block, :146-147 stem, :1406-1421 FPN).
-    padding: 'same' | 'valid' | (top, bottom, left, right)."""
+    padding: 'same' | 'valid' | (top, bottom, left, right).
+    quant(site + ':fwd', role, array) (optional; see np_models' header): the arrays the product reads, roles 'x' and 'w'; the bias is
+    added unrounded.  quant=None: the plain float64 convolution."""
     x = np.asarray(x, F64)
     w = np.asarray(w, F64)
+    if quant is not None:
+        x, w = np.asarray(quant(site + ':fwd', 'x', x)), np.asarray(quant(site + ':fwd', 'w', w))        # (the hook's dtype is kept)
     N, H, W, C = x.shape
     kh, kw, C2, O = w.shape
     assert C == C2
@@ -142,23 +146,31 @@ def conv2d_nhwc_loops(x, w, b=None, stride=1, padding='valid'):
     return out
 
 
-def conv2d_nhwc_backward(x, w, dy, stride=1, padding='valid'):
+def conv2d_nhwc_backward(x, w, dy, stride=1, padding='valid', quant=None, site=None):
     """Gradients of conv2d_nhwc w.r.t. x, w and bias (the joint model trains fpn_*/rpn_* convs,
-    dense_img_cap/dense_model.py:1829-1831).  float64."""
+    dense_img_cap/dense_model.py:1829-1831).  float64.
+    quant (optional; see np_models' header): the weight gradient is the product of quant(site + ':wgrad', 'x', x) and
+    quant(site + ':wgrad', 'dy', dy), the data gradient of quant(site + ':dgrad', 'dy', dy) and quant(site + ':dgrad', 'w', w); the
+    bias gradient sums the unrounded dy.  quant=None: every product reads x, w, dy themselves."""
     x, w, dy = np.asarray(x, F64), np.asarray(w, F64), np.asarray(dy, F64)
     N, H, W, C = x.shape
     kh, kw, _, Oc = w.shape
     pt, pb, pl, pr = _resolve_pad(H, W, kh, kw, stride, padding)
-    xp = np.pad(x, ((0, 0), (pt, pb), (pl, pr), (0, 0)))
+    x_w, dy_w, dy_d, w_d = x, dy, dy, w                                  # operands of the weight gradient / of the data gradient
+    if quant is not None:
+        x_w, dy_w = np.asarray(quant(site + ':wgrad', 'x', x)), np.asarray(quant(site + ':wgrad', 'dy', dy))       # (the hook's dtype is kept)
+        dy_d, w_d = np.asarray(quant(site + ':dgrad', 'dy', dy)), np.asarray(quant(site + ':dgrad', 'w', w))
+    xp = np.pad(x_w, ((0, 0), (pt, pb), (pl, pr), (0, 0)))
     dxp = np.zeros_like(xp)
     Ho, Wo = dy.shape[1:3]
     dw = np.zeros_like(w)
     d2 = dy.reshape(-1, Oc)
+    d2w, d2d = dy_w.reshape(-1, Oc), dy_d.reshape(-1, Oc)
     for ky in range(kh):
         for kx in range(kw):
             sl = (slice(None), slice(ky, ky + (Ho - 1) * stride + 1, stride), slice(kx, kx + (Wo - 1) * stride + 1, stride), slice(None))
-            dw[ky, kx] = xp[sl].reshape(-1, C).T @ d2
-            dxp[sl] += (d2 @ w[ky, kx].T).reshape(N, Ho, Wo, C)
+            dw[ky, kx] = xp[sl].reshape(-1, C).T @ d2w
+            dxp[sl] += (d2d @ w_d[ky, kx].T).reshape(N, Ho, Wo, C)
     dx = dxp[:, pt:pt + H, pl:pl + W, :]
     return dx, dw, d2.sum(0)
 
@@ -360,9 +372,10 @@ def lstm_forward(x, mask, W, U, b, h0=None, c0=None, rec_masks=None):
     return H, cache
 
 
-def lstm_backward(dH, cache, dh_last=None):
+def lstm_backward(dH, cache, dh_last=None, want_dz=False):
     """Backward of lstm_forward.  dH [B,T,Uh] gradient w.r.t. every step's output (or None),
-    dh_last [B,Uh] extra gradient on the final output.  Returns dx, dW, dU, db."""
+    dh_last [B,Uh] extra gradient on the final output.  Returns dx, dW, dU, db; with want_dz also dz [B,T,4Uh], the gradient
+    w.r.t. the gates' pre-activations (a caller that forms the three weight / data products itself, from rounded operands)."""
     x, mask, W, U = cache['x'], cache['mask'], cache['W'], cache['U']
     B, T, _ = x.shape
     Uh = U.shape[0]
@@ -371,6 +384,7 @@ def lstm_backward(dH, cache, dh_last=None):
     dh = np.zeros((B, Uh)) if dh_last is None else np.asarray(dh_last, F64).copy()
     dc = np.zeros((B, Uh))
     rm = cache.get('rec_masks')
+    dz_all = np.zeros((B, T, 4 * Uh)) if want_dz else None
     for t in reversed(range(T)):
         if dH is not None:
             dh = dh + dH[:, t]
@@ -385,6 +399,8 @@ def lstm_backward(dH, cache, dh_last=None):
             dcn * i * (1.0 - g * g),
             do * hard_sigmoid_grad(z[:, 3 * Uh:]),
         ], axis=1)
+        if want_dz:
+            dz_all[:, t] = dz
         dW += x[:, t].T @ dz
         db += dz.sum(0)
         dx[:, t] = dz @ W.T
@@ -399,6 +415,8 @@ def lstm_backward(dH, cache, dh_last=None):
                 dh_rec += rm[g] * (dz[:, sl] @ U[:, sl].T)
         dh = dh * (1.0 - m) + dh_rec
         dc = dc * (1.0 - m) + dcn * f
+    if want_dz:
+        return dx, dW, dU, db, dz_all
     return dx, dW, dU, db
 
 

@@ -4,10 +4,9 @@ imported inside the functions, as in the test files."""
 import numpy as np
 
 
-def make_joint(S=128, V=24, T=5, blocks=1, rois=12, compute_dtype="f32", conv_math=None):
-    from image_captioning_amd import synth
+def joint_config(S=128, V=24, T=5, rois=12):
+    """The small joint model's config (no device needed)."""
     from image_captioning_amd.config import Config
-    from image_captioning_amd.dense_model import DenseImageCapRCNN
 
     class Cfg(Config):
         NAME = "joint"
@@ -20,7 +19,12 @@ def make_joint(S=128, V=24, T=5, blocks=1, rois=12, compute_dtype="f32", conv_ma
         VOCABULARY_SIZE = V
         EMBEDDING_SIZE = 300
         RECURRENT_DROPOUT = 0.0          # parity against the deterministic oracle graph (the training default is the reference's 0.2)
-    cfg = Cfg()
+    return Cfg()
+
+
+def joint_weights(V=24, blocks=1):
+    """The small joint model's synthetic weights (no device needed)."""
+    from image_captioning_amd import synth
     Wt = dict(synth.encoder_weights(0, blocks), **synth.rpn_weights(4))
     Wt['rpn_conv_shared/kernel'] = Wt['rpn_conv_shared/kernel'] * np.float32(0.05)
     Wt['rpn_bbox_pred/kernel'] = Wt['rpn_bbox_pred/kernel'] * np.float32(0.3)
@@ -28,6 +32,19 @@ def make_joint(S=128, V=24, T=5, blocks=1, rois=12, compute_dtype="f32", conv_ma
     Wt['mrcnn_class_conv1/kernel'] = Wt['mrcnn_class_conv1/kernel'] * np.float32(0.05)   # random FPN maps are O(10): keep the
     Wt.update(synth.v1_weights(2, V))                                                    # vocabulary softmax out of saturation
     Wt['imgcap_embedding_layer/embeddings'] = synth.embedding_matrix(3, V)
+    return Wt
+
+
+def oracle_cfg(cfg, mean_pixel=(123.7, 116.8, 103.9)):
+    """The config values oracle.np_models.joint_loss_and_grads reads."""
+    return dict(mean_pixel=list(mean_pixel), scales=cfg.RPN_ANCHOR_SCALES, ratios=cfg.RPN_ANCHOR_RATIOS, strides=cfg.BACKBONE_STRIDES,
+                proposal_count=cfg.POST_NMS_ROIS_TRAINING, nms=cfg.RPN_NMS_THRESHOLD, train_rois=cfg.TRAIN_ROIS_PER_IMAGE,
+                positive_ratio=cfg.ROI_POSITIVE_RATIO, weight_decay=cfg.WEIGHT_DECAY, T=cfg.PADDING_SIZE)
+
+
+def make_joint(S=128, V=24, T=5, blocks=1, rois=12, compute_dtype="f32", conv_math=None):
+    from image_captioning_amd.dense_model import DenseImageCapRCNN
+    cfg, Wt = joint_config(S, V, T, rois), joint_weights(V, blocks)
     cfg.EMBEDDING_WEIGHTS = Wt['imgcap_embedding_layer/embeddings']
     model = DenseImageCapRCNN("training", cfg, "logs", stage4_blocks=blocks, compute_dtype=compute_dtype, conv_math=conv_math)
     model.set_weights(Wt)

@@ -361,7 +361,11 @@ def test_configs4_joint_step_at_512px_22_blocks_50k_vocabulary(gpu, dtype):
     of each tensor's largest entry.  (The bf16 leg is not handed masks of its own: re-running the oracle's backward with them would be a
     second decoder evaluation; it keeps its tolerances against the fp32 leg's result.)  bf16 model (compute_dtype
     'bf16' + bf16 storage between the convolutions -- configs[4] as specified): losses 1e-2, gradients 5e-2 ... 1e-1 in relative L2
-    norm (the tolerances of the reduced-size bf16 tests)."""
+    norm (the tolerances of the reduced-size bf16 tests).  That states how far bf16 training is from fp32; how the bf16 step is WIRED --
+    which products run on the bf16 pipe, what each of them reads, every scale and count -- is held at 128 px by
+    tests/test_gpu_models.py::test_joint_model_bf16_step_tracks_the_fp32_oracle against the oracle that rounds where the device rounds
+    (3e-7 ... 3e-6), with the product sites asserted equal to this size's (tests/_bf16_sites.py); a second float64 evaluation at 512 px
+    would cost minutes."""
     bf = dtype == "bf16"
     blocks = 22
     model, cfg, Wt, inputs = _joint_full("bf16" if bf else "f32", "bf16" if bf else None)
