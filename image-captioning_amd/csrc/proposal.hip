@@ -3,6 +3,9 @@
 // descending, lower anchor index first among ties), box decode / clip / normalise in TF's float32 operation order, and
 // tf.image.non_max_suppression as a 64-bit suppression-mask kernel followed by a single-workgroup greedy
 // scan.  All index decisions (sort order, ties, IoU > threshold) are float32 like the TF graph.
+// Further down: the models' NumPy stages behind the heads on the device -- dc_refine_generations_f64 (GenerationMatchLayer +
+// unmold_generations) and dc_refine_detections_f32 (Mask R-CNN's refine_detections + the box unmolding, one launch, no scratch) --
+// and the DetectionTargetLayer.
 #include "dcap_internal.h"
 #include <string.h>
 #include <algorithm>
@@ -925,6 +928,201 @@ extern "C" int dc_refine_generations_f64(const dc_refine_desc* d, void* workspac
                        kept_rank);
     hipLaunchKernelGGL(refine_finish_kernel, dim3(d->B), dim3(64), 0, s, *d, kept_boxes, kept_rank, order);
     return check_launch("refine_generations kernels");
+}
+
+// ------------------------------------------------------------------------------------------------
+// refine_detections from the line after the class selection + the box part of unmold_detections (mask_rcnn/mask_rcnn_model.py
+// :689-738, :2281-2301; the product's host functions mask_rcnn_model.refine_detections / unmold_boxes), one workgroup per image, the
+// image's whole state in LDS: no global scratch.  The number formats are the host path's, one rounding per NumPy operation (float32
+// boxes, float64 where a float64 operand enters, float32 IoU); this file compiles without fma contraction.
+//   a  every thread's RoIs (i = tid, tid + threads, ...): candidate or not, a 32-bit sort key (0 = not a candidate);
+//   b  rank of every candidate among the candidates (refine_rank_kernel's compare), its refined int32 box, class and index scattered
+//      to its rank;
+//   c  greedy NMS over the ranks: one block-uniform read of the candidate's class word (0 = suppressed) per rank, a barrier only
+//      after a candidate that is kept -- only then the class words behind it change --, at most max_instances such rounds;
+//   d  one wave unmolds the survivors, drops the empty boxes (ballot + popcount, as refine_finish_kernel) and fills the tail.
+// ------------------------------------------------------------------------------------------------
+namespace dcap {
+
+constexpr int RD_THREADS = 1024;
+
+// larger key = earlier in np.argsort(scores, kind="stable")[::-1]; a candidate's key is never 0 (-inf maps to 0x007fffff)
+__device__ __forceinline__ unsigned refine_det_key(float s) {
+    if (s != s) return ~0u;
+    if (s == 0.f) s = 0.f;
+    const unsigned b = __float_as_uint(s);
+    return b ^ ((b >> 31) ? ~0u : 0x80000000u);
+}
+
+// np.maximum(np.minimum(v, hi), lo) in float32: a NaN stays a NaN
+__device__ __forceinline__ float clip_window_f32(float v, float lo, float hi) {
+    if (v != v) return v;
+    v = v < hi ? v : hi;
+    return v > lo ? v : lo;
+}
+
+// utils.compute_iou on int32 boxes taken as float32 (utils.non_max_suppression's astype): the 0/0 of two empty boxes exceeds nothing
+__device__ __forceinline__ bool refine_det_exceeds(const int4 a, const int4 b, float thr) {
+    const float ay1 = (float)a.x, ax1 = (float)a.y, ay2 = (float)a.z, ax2 = (float)a.w;
+    const float by1 = (float)b.x, bx1 = (float)b.y, by2 = (float)b.z, bx2 = (float)b.w;
+    const float area_a = mul_rn(sub_rn(ay2, ay1), sub_rn(ax2, ax1)), area_b = mul_rn(sub_rn(by2, by1), sub_rn(bx2, bx1));
+    const float ih = fmaxf(sub_rn(fminf(ay2, by2), fmaxf(ay1, by1)), 0.f);
+    const float iw = fmaxf(sub_rn(fminf(ax2, bx2), fmaxf(ax1, bx1)), 0.f);
+    const float inter = mul_rn(iw, ih);
+    return div_rn(inter, sub_rn(add_rn(area_a, area_b), inter)) > thr;
+}
+
+// a row of four words, 4 bytes at a time: the outputs are a few hundred words and carry no alignment rule beyond their element's
+template <class T>
+__device__ __forceinline__ void store4(T* p, T a, T b, T c, T e) {
+    p[0] = a;
+    p[1] = b;
+    p[2] = c;
+    p[3] = e;
+}
+
+__global__ __launch_bounds__(RD_THREADS) void refine_detections_kernel(dc_refine_det_desc d) {
+    __shared__ int4 sbox[DC_REFINE_DET_MAX_ROIS];                // by rank: the refined box in the molded image
+    __shared__ int scls[DC_REFINE_DET_MAX_ROIS];                 // by rank: the class id; 0 once suppressed
+    __shared__ int sidx[DC_REFINE_DET_MAX_ROIS];                 // by rank: the RoI's index
+    __shared__ unsigned skey[DC_REFINE_DET_MAX_ROIS];            // by RoI: the sort key; from phase c on the survivors' ranks
+    __shared__ int s_ncand;
+    const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x, N = d.N, M = d.max_instances;
+    const double* c = d.image_consts + (long)b * DC_REFINE_CONSTS;
+    const int* ids = d.class_ids + (long)b * N;
+    const float* sc = d.scores + (long)b * N;
+    if (tid == 0) s_ncand = 0;
+    __syncthreads();
+
+    // a: candidates and keys
+    const float min_conf = (float)d.min_confidence;             // NumPy compares a float32 array with a Python float in float32
+    int mine_cand = 0;
+    for (int i = tid; i < N; i += nt) {
+        const float s = sc[i];
+        const bool cand = ids[i] > 0 && (d.min_confidence == 0. || s >= min_conf);
+        skey[i] = cand ? refine_det_key(s) : 0u;
+        mine_cand += cand;
+    }
+    if (mine_cand) atomicAdd(&s_ncand, mine_cand);
+    __syncthreads();
+    const int ncand = s_ncand;
+
+    // b: a candidate's rank = the candidates with a larger key, or the same key and a HIGHER index; its box goes to that rank
+    const float wy1 = (float)c[0], wx1 = (float)c[1], wy2 = (float)c[2], wx2 = (float)c[3];
+    for (int i = tid; i < N; i += nt) {
+        const unsigned mine = skey[i];
+        if (mine == 0u) continue;
+        int rank = 0;
+#pragma unroll 8
+        for (int j = 0; j < N; ++j) {
+            const unsigned o = skey[j];
+            rank += (o > mine) || (o == mine && j > i);
+        }
+        const float* r = d.rois + ((long)b * N + i) * 4;
+        const float* dl = d.deltas + ((long)b * N + i) * 4;
+        const double d0 = dmul_rn((double)dl[0], d.std_dev[0]), d1 = dmul_rn((double)dl[1], d.std_dev[1]);
+        const double d2 = dmul_rn((double)dl[2], d.std_dev[2]), d3 = dmul_rn((double)dl[3], d.std_dev[3]);
+        float height = sub_rn(r[2], r[0]), width = sub_rn(r[3], r[1]);
+        float cy = add_rn(r[0], mul_rn(0.5f, height)), cx = add_rn(r[1], mul_rn(0.5f, width));
+        cy = (float)dadd_rn((double)cy, dmul_rn(d0, (double)height));
+        cx = (float)dadd_rn((double)cx, dmul_rn(d1, (double)width));
+        height = (float)dmul_rn((double)height, exp(d2));
+        width = (float)dmul_rn((double)width, exp(d3));
+        float y1 = sub_rn(cy, mul_rn(0.5f, height)), x1 = sub_rn(cx, mul_rn(0.5f, width));
+        float y2 = add_rn(y1, height), x2 = add_rn(x1, width);
+        y1 = clip_window_f32((float)dmul_rn((double)y1, d.image_h), wy1, wy2);
+        x1 = clip_window_f32((float)dmul_rn((double)x1, d.image_w), wx1, wx2);
+        y2 = clip_window_f32((float)dmul_rn((double)y2, d.image_h), wy1, wy2);
+        x2 = clip_window_f32((float)dmul_rn((double)x2, d.image_w), wx1, wx2);
+        sbox[rank] = make_int4((int)rintf(y1), (int)rintf(x1), (int)rintf(y2), (int)rintf(x2));
+        scls[rank] = ids[i];
+        sidx[rank] = i;
+    }
+    __syncthreads();
+
+    // c: greedy scan.  scls[i] is final once every candidate kept before rank i has run its round, and a round writes only behind
+    // its own rank: threads that run ahead over suppressed ranks read nothing a slower thread's round still writes.
+    int* kept = reinterpret_cast<int*>(skey);                    // (the keys were last read before the barrier above)
+    const float thr = (float)d.threshold;
+    int nk = 0;
+    for (int i = 0; i < ncand; ++i) {
+        const int ci = scls[i];
+        if (ci <= 0) continue;
+        if (tid == 0) kept[nk] = i;
+        if (++nk == M) break;
+        const int4 bi = sbox[i];
+        for (int j = i + 1 + tid; j < ncand; j += nt)
+            if (scls[j] == ci && refine_det_exceeds(bi, sbox[j], thr)) scls[j] = 0;
+        __syncthreads();
+    }
+    __syncthreads();
+    if (tid >= 64) return;
+
+    // d: unmold, drop the empty boxes, compact in order, fill the tail
+    const int lane = tid;
+    const double sy = c[6], sx = c[7], scale = c[8];
+    const int* sc_words = reinterpret_cast<const int*>(sc);
+    int* score_words_out = reinterpret_cast<int*>(d.scores_out);
+    int total = 0;
+    for (int s0 = 0; s0 < nk; s0 += 64) {
+        const int s = s0 + lane;
+        int4 q = make_int4(0, 0, 0, 0), u = make_int4(0, 0, 0, 0);
+        int r = 0;
+        bool ok = false;
+        if (s < nk) {
+            r = kept[s];
+            q = sbox[r];
+            u.x = (int)dmul_rn(dsub_rn((double)q.x, sy), scale);
+            u.y = (int)dmul_rn(dsub_rn((double)q.y, sx), scale);
+            u.z = (int)dmul_rn(dsub_rn((double)q.z, sy), scale);
+            u.w = (int)dmul_rn(dsub_rn((double)q.w, sx), scale);
+            ok = (int)((unsigned)(u.z - u.x) * (unsigned)(u.w - u.y)) > 0;
+        }
+        const unsigned long long live = __ballot(ok);
+        if (ok) {
+            const long o = (long)b * M + total + __builtin_popcountll(live & ((1ull << lane) - 1ull));
+            const int idx = sidx[r];
+            store4(d.boxes_out + 4 * o, q.x, q.y, q.z, q.w);
+            store4(d.rois_out + 4 * o, u.x, u.y, u.z, u.w);
+            store4(d.norm_out + 4 * o, (float)ddiv_rn((double)(float)q.x, d.image_h), (float)ddiv_rn((double)(float)q.y, d.image_w),
+                   (float)ddiv_rn((double)(float)q.z, d.image_h), (float)ddiv_rn((double)(float)q.w, d.image_w));
+            d.class_ids_out[o] = scls[r];
+            score_words_out[o] = sc_words[idx];
+            d.keep_out[o] = idx;
+        }
+        total += __builtin_popcountll(live);
+    }
+    for (int s = total + lane; s < M; s += 64) {
+        const long o = (long)b * M + s;
+        store4(d.boxes_out + 4 * o, 0, 0, 0, 0);
+        store4(d.rois_out + 4 * o, 0, 0, 0, 0);
+        store4(d.norm_out + 4 * o, 0.f, 0.f, 0.f, 0.f);
+        d.class_ids_out[o] = -1;
+        score_words_out[o] = 0;
+        d.keep_out[o] = -1;
+    }
+    if (lane == 0) d.count_out[b] = total;
+}
+
+}  // namespace dcap
+
+extern "C" int dc_refine_detections_f32(const dc_refine_det_desc* d, void* stream) {
+    DC_REQUIRE(d && d->rois && d->class_ids && d->scores && d->deltas && d->image_consts && d->count_out && d->boxes_out && d->rois_out &&
+                   d->norm_out && d->class_ids_out && d->scores_out && d->keep_out,
+               DC_EINVAL, "dc_refine_detections: null pointer");
+    DC_REQUIRE(d->B > 0 && d->N > 0 && d->max_instances > 0, DC_EINVAL, "dc_refine_detections: bad sizes");
+    DC_REQUIRE(d->N <= DC_REFINE_DET_MAX_ROIS, DC_EINVAL, "dc_refine_detections: N = %d exceeds the limit of %d RoIs per image (one image's state "
+               "stays in LDS)", d->N, DC_REFINE_DET_MAX_ROIS);
+    const uintptr_t words = reinterpret_cast<uintptr_t>(d->rois) | reinterpret_cast<uintptr_t>(d->class_ids) | reinterpret_cast<uintptr_t>(d->scores) |
+                            reinterpret_cast<uintptr_t>(d->deltas) | reinterpret_cast<uintptr_t>(d->count_out) | reinterpret_cast<uintptr_t>(d->boxes_out) |
+                            reinterpret_cast<uintptr_t>(d->rois_out) | reinterpret_cast<uintptr_t>(d->norm_out) |
+                            reinterpret_cast<uintptr_t>(d->class_ids_out) | reinterpret_cast<uintptr_t>(d->scores_out) |
+                            reinterpret_cast<uintptr_t>(d->keep_out);
+    DC_REQUIRE((words & 3u) == 0 && (reinterpret_cast<uintptr_t>(d->image_consts) & 7u) == 0, DC_EINVAL,
+               "dc_refine_detections: a pointer off its element's boundary (4 bytes; image_consts 8)");
+    const int threads = std::min(RD_THREADS, (d->N + 63) / 64 * 64);
+    hipLaunchKernelGGL(refine_detections_kernel, dim3(d->B), dim3(threads), 0, static_cast<hipStream_t>(stream), *d);
+    return check_launch("refine_detections_kernel");
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -10,6 +10,8 @@ unmold_detections :2253-2312, detect :2314-2354; mask_rcnn/utils.py: apply_box_d
   -> PyramidROIAlign(MASK_POOL_SIZE) -> mrcnn_mask_conv1..4 + frozen BN + ReLU (four dc_conv2d_nhwc_f32 launches)
   -> ops.mask_head_tail: mrcnn_mask_deconv + ReLU + mrcnn_mask + sigmoid for each detection's OWN class: [M,28,28]
   -> utils.unmold_mask: postprocess="host" in NumPy / PIL, "device" ops.mask_paste and one copy of the [M,H,W] bytes.
+detect(refine="device") replaces the three middle steps by ops.refine_detections on the device (one launch, no host read before the
+results come down) and runs the mask head on DETECTION_MAX_INSTANCES rows per image.
 
 Everything below the heads is DenseImageCapRCNN's, unchanged: MaskRCNN sub-classes it and puts DetectTop where the caption model sits.
 detect() starts with the parent's inference front (_proposal_features: mold, encoder pass, proposals, RoIAlign(7)); save_weights is the
@@ -102,6 +104,26 @@ def unmold_boxes(boxes, image_shape, window):
     """The box part of unmold_detections (:2281-2301): shift by the window, scale to the original image in float64, truncate to int32.
     Returns (boxes int32 [K,4], mask of the boxes with a positive area: the others are deleted there)."""
     return dense_model.unmold_generations(boxes, image_shape, window)
+
+
+def detection_constants(window, config, image_shape):
+    """One image's row of ops.refine_detections' image_consts (float64 [_lib.REFINE_CONSTS]).  dense_model.refine_constants' row fits as
+    it is: the window (the kernel reads it as the float32 values the DetectionLayer sees, np.asarray(window, np.float32)) and
+    unmold_boxes' shift (y, x) and scale, computed as that function computes them; IMAGE_SHAPE's h and w sit in the row too, but
+    ops.refine_detections takes them as image_hw."""
+    return dense_model.refine_constants(window, config, image_shape)
+
+
+def pack_detections(count, boxes, rois, class_ids, scores, keep):
+    """ops.refine_detections' outputs (all but the normalised boxes) as ONE int32 buffer and ONE device-to-host copy, in the manner of
+    dense_model.pack_survivors.  Returns on the host (n [B], boxes [B,M,4], rois [B,M,4], class_ids [B,M], scores float32 [B,M],
+    keep [B,M]): image b's first n[b] rows count."""
+    B, M = keep.shape
+    packed = torch.cat([count, boxes.reshape(-1), rois.reshape(-1), class_ids.reshape(-1), scores.view(torch.int32).reshape(-1), keep.reshape(-1)])
+    host = packed.cpu().numpy()                          # the one small device-to-host copy
+    cuts = np.cumsum([0, B, B * M * 4, B * M * 4, B * M, B * M, B * M])
+    n, bx, ro, ci, sc, kp = (host[lo:hi] for lo, hi in zip(cuts[:-1], cuts[1:]))
+    return n, bx.reshape(B, M, 4), ro.reshape(B, M, 4), ci.reshape(B, M), sc.view(np.float32).reshape(B, M), kp.reshape(B, M)
 
 
 def bytescale(mask):
@@ -293,24 +315,38 @@ class MaskRCNN(DenseImageCapRCNN):
         DenseImageCapRCNN.set_weights(self, W)             # (ends in the top's _weights_changed: the folded mask BatchNorms go)
 
     # ---- inference -----------------------------------------------------------------------------
-    def detect(self, images, verbose=0, postprocess="host", mold="host", device_masks=False):
+    def detect(self, images, verbose=0, postprocess="host", mold="host", device_masks=False, refine="host"):
         """The inference graph + detect (:2314-2354).  Returns, per image, {"rois": int32 [N,4] in the original image, "class_ids": int32
         [N], "scores": float32 [N], "masks": uint8 [H,W,N] (a transposed view of [N,H,W]); (0,28,28) floats when nothing is detected, as
         the reference returns it}.  postprocess="host": the [N,28,28] class masks come to the host and utils.unmold_mask runs in NumPy /
         PIL; "device": ops.mask_paste and one copy of the finished bytes -- the same bytes.  mold: as DenseImageCapRCNN.generate_captions.
-        device_masks=True (postprocess="device"): "masks" stays a uint8 [N,H,W] tensor on the device."""
+        device_masks=True (postprocess="device"): "masks" stays a uint8 [N,H,W] tensor on the device.
+        refine="host" (default): the selection comes to the host (a device synchronisation in the middle of the call), refine_detections
+        and unmold_boxes run in NumPy and the detections go up again; last_selection holds per image the four host arrays.
+        refine="device": class_select -> ops.refine_detections (one launch) -> the mask head, with no host read in between; the mask
+        head then always runs on B x DETECTION_MAX_INSTANCES rows (rows behind an image's last detection carry a zero box and class id
+        -1 and give zero masks), whatever the images hold.  ONE small packed copy brings the counts and per row the boxes, rois, id,
+        score and kept index (pack_detections); postprocess="device" pastes all rows first and, without device_masks, copies the [:n]
+        mask bytes second; postprocess="host" copies the [B,M,28,28] class masks second.  last_selection holds the four DEVICE tensors
+        (proposals [B,K,4], ids [B,K], scores [B,K], deltas [B,K,4]: buffers the next call reuses), last_class_masks device views as
+        with postprocess="device".  Equal scores are ordered as np.argsort(kind="stable")[::-1] orders them (the host path's default
+        sort promises no order), and the device's float64 exp is not np.exp bit for bit: see dc_refine_detections_f32."""
         if postprocess not in ("host", "device"):
             raise ValueError("postprocess must be 'host' or 'device', got %r" % (postprocess,))
         if device_masks and postprocess != "device":
             raise ValueError("device_masks=True needs postprocess='device'")
+        if refine not in ("host", "device"):
+            raise ValueError("refine must be 'host' or 'device', got %r" % (refine,))
         utils.check_mold(mold, self.config.IMAGE_PADDING)
         cfg, top, B = self.config, self.caption_model, len(images)
         if verbose:
             print("Processing %d images" % B)
-        p, images, windows, _, proposals, feats = self._proposal_features(images, mold, want_consts=False)
+        p, images, windows, consts, proposals, feats = self._proposal_features(images, mold, want_consts=refine == "device")
         K = proposals.shape[1]
         z, d = top.heads(feats.view(B * K, cfg.POOL_SIZE, cfg.POOL_SIZE, 256))
         self.last_heads = (z, d)
+        if refine == "device":
+            return self._detect_refined_on_device(p, images, consts, proposals, z, d, postprocess, device_masks)
         # proposals, ids, scores and deltas leave in one buffer of 10 words per RoI: ids as their bits
         sel = self._buf("selection", (B * K, 10))
         sel[:, :4].copy_(proposals.view(B * K, 4))
@@ -378,4 +414,36 @@ class MaskRCNN(DenseImageCapRCNN):
         for b, full in keep:
             results[b]["masks"] = full if device_masks else full.cpu().numpy().transpose(1, 2, 0)
         self.last_class_masks = [masks[b, :counts[b]] for b in range(B)]     # (device views of a buffer the next call reuses)
+        return results
+
+    def _detect_refined_on_device(self, p, images, consts, proposals, z, d, postprocess, device_masks):
+        """detect(refine="device") behind the heads: nothing here reads the device before pack_detections."""
+        cfg, top, (B, K) = self.config, self.caption_model, proposals.shape[:2]
+        M, P = int(cfg.DETECTION_MAX_INSTANCES), top.mask_pool
+        ids, scores, deltas = ops.class_select(z, d, class_ids=self._buf("sel_ids", (B * K,), torch.int32), scores=self._buf("sel_scores", (B * K,)),
+                                               deltas_out=self._buf("sel_deltas", (B * K, 4)))
+        self.last_selection = (proposals, ids.view(B, K), scores.view(B, K), deltas.view(B, K, 4))
+        count, boxes, rois, norm, cls, sc, keep = ops.refine_detections(*self.last_selection, consts, cfg.BBOX_STD_DEV, cfg.DETECTION_MIN_CONFIDENCE,
+                                                                        cfg.DETECTION_NMS_THRESHOLD, M, cfg.IMAGE_SHAPE[:2])
+        x = ops.roi_align_pyramid(list(p.P), norm, float(p.H * p.W), P, out=self._buf("mask_rois_fixed", (B, M, P, P, 256)))
+        masks = top.class_masks(x.view(B * M, P, P, 256), cls.view(B * M), out=self._buf("class_masks_fixed", (B * M, 2 * P, 2 * P))).view(B, M, 2 * P, 2 * P)
+        full = [ops.mask_paste(masks[b], rois[b], *images[b].shape[:2]) for b in range(B)] if postprocess == "device" else None
+        n, boxes_h, rois_h, cls_h, sc_h, _ = pack_detections(count, boxes, rois, cls, sc, keep)
+        self.last_detections = [dict(boxes=boxes_h[b, :n[b]], class_ids=cls_h[b, :n[b]], scores=sc_h[b, :n[b]], rois=rois_h[b, :n[b]]) for b in range(B)]
+        results = [{"rois": dt["rois"], "class_ids": dt["class_ids"], "scores": dt["scores"],
+                    "masks": np.empty((0, 2 * P, 2 * P))} for dt in self.last_detections]
+        if postprocess == "host":
+            masks_h = masks.cpu().numpy()
+            self.last_class_masks = [masks_h[b, :n[b]].copy() for b in range(B)]
+            for b in range(B):
+                if n[b]:
+                    full_b = np.stack([unmold_mask(masks_h[b, i], rois_h[b, i], images[b].shape) for i in range(n[b])])
+                    results[b]["masks"] = full_b.transpose(1, 2, 0)
+            return results
+        for b in range(B):
+            if device_masks:
+                results[b]["masks"] = full[b][:n[b]]
+            elif n[b]:
+                results[b]["masks"] = full[b][:n[b]].cpu().numpy().transpose(1, 2, 0)
+        self.last_class_masks = [masks[b, :n[b]] for b in range(B)]          # (device views of a buffer the next call reuses)
         return results

@@ -12,7 +12,7 @@ import torch
 
 from . import _lib
 from ._lib import (RpnTargetsDesc, PwChainDesc, ConvBf16Desc, AmsgradDesc, DetectionTargetsDesc, BnReluDesc, ConvDesc, ConvWgradBf16Desc, GemmBf16Desc, VocabCeDesc, ProposalDesc, RpnLossDesc, GemmDesc, LstmBwdDesc, LstmFwdDesc, RoialignDesc, RoiGroupsDesc,
-                   SoftmaxCeDesc, TagFocalDesc, VocabTop1Desc, VocabTopkDesc, VocabTop1Bf16Desc, VocabTopkBf16Desc, VocabSampleDesc, VocabSampleBf16Desc, BeamSelectDesc, BeamStepDesc, LstmStepDesc, RefineDesc, ResizePadDesc, MaskHeadTailDesc, MaskPasteDesc, check)
+                   SoftmaxCeDesc, TagFocalDesc, VocabTop1Desc, VocabTopkDesc, VocabTop1Bf16Desc, VocabTopkBf16Desc, VocabSampleDesc, VocabSampleBf16Desc, BeamSelectDesc, BeamStepDesc, LstmStepDesc, RefineDesc, RefineDetDesc, ResizePadDesc, MaskHeadTailDesc, MaskPasteDesc, check)
 
 
 def _stream():
@@ -1119,6 +1119,60 @@ def class_select(logits, deltas, class_ids=None, scores=None, deltas_out=None):
     check(lib.dc_class_select_f32(_ptr(logits), logits.stride(0) if R > 1 else Cn, _ptr(deltas), deltas.stride(0) if R > 1 else 4 * Cn, R, Cn,
                                   _ptr(class_ids), _ptr(scores), _ptr(deltas_out), _stream()), "dc_class_select_f32")
     return class_ids, scores, deltas_out
+
+
+def refine_detections(rois, class_ids, scores, deltas, image_consts, std, min_confidence, threshold, max_instances, image_hw):
+    """refine_detections from the line after the class selection + the box part of unmold_detections for B images x N RoIs in ONE launch
+    (dc_refine_detections_f32), by the host path's operations (mask_rcnn_model.refine_detections / unmold_boxes): rois float32 [B,N,4]
+    normalised; class_ids int32 [B,N], scores float32 [B,N] and deltas float32 [B,N,4] as ops.class_select leaves them; image_consts
+    float64 [B,_lib.REFINE_CONSTS] (mask_rcnn_model.detection_constants: the window, the unmolding's shift and scale); std the four
+    BBOX_STD_DEV; image_hw IMAGE_SHAPE's (h, w).  Returns seven device tensors of max_instances rows per image -- (count int32 [B],
+    boxes int32 [B,M,4] in the molded image, rois int32 [B,M,4] in the original image, norm float32 [B,M,4] = boxes / (h,w,h,w),
+    class_ids int32 [B,M], scores float32 [B,M], keep int32 [B,M]: the RoI's index) -- best first; rows behind the last survivor hold a
+    zero box, class id -1, score 0 and keep -1.  Equal scores: the higher RoI index first.  N <= _lib.REFINE_DET_MAX_ROIS.  No
+    workspace, no host synchronisation; B = 0 or N = 0 returns the empty result without a launch.  Everything is checked before the
+    library is loaded."""
+    if rois.dim() != 3 or rois.shape[2] != 4:
+        raise _lib.DcapError("refine_detections: rois must be a float32 [B,N,4] tensor, got %s" % (tuple(rois.shape),))
+    B, N = int(rois.shape[0]), int(rois.shape[1])
+    for name, t, dtype, shape in (("rois", rois, torch.float32, (B, N, 4)), ("class_ids", class_ids, torch.int32, (B, N)),
+                                  ("scores", scores, torch.float32, (B, N)), ("deltas", deltas, torch.float32, (B, N, 4)),
+                                  ("image_consts", image_consts, torch.float64, (B, _lib.REFINE_CONSTS))):
+        if t.dtype != dtype:
+            raise _lib.DcapError("refine_detections: %s must be %s, got %s" % (name, dtype, t.dtype))
+        if tuple(t.shape) != shape or not t.is_contiguous():
+            raise _lib.DcapError("refine_detections: %s must be a contiguous %s tensor, got shape %s strides %s"
+                                 % (name, list(shape), tuple(t.shape), tuple(t.stride())))
+    if N > _lib.REFINE_DET_MAX_ROIS:
+        raise _lib.DcapError("refine_detections: N = %d exceeds the limit of %d RoIs per image" % (N, _lib.REFINE_DET_MAX_ROIS))
+    if isinstance(max_instances, bool) or int(max_instances) != max_instances or max_instances < 1:
+        raise _lib.DcapError("refine_detections: max_instances must be a positive integer, got %r" % (max_instances,))
+    if len(std) != 4 or len(image_hw) != 2:
+        raise _lib.DcapError("refine_detections: std must hold four values and image_hw two, got %r and %r" % (std, image_hw))
+    _on_gpu("refine_detections", rois=rois, class_ids=class_ids, scores=scores, deltas=deltas, image_consts=image_consts)
+    M, dev = int(max_instances), rois.device
+    if B == 0 or N == 0:
+        return (torch.zeros((B,), dtype=torch.int32, device=dev), torch.zeros((B, M, 4), dtype=torch.int32, device=dev),
+                torch.zeros((B, M, 4), dtype=torch.int32, device=dev), torch.zeros((B, M, 4), dtype=torch.float32, device=dev),
+                torch.full((B, M), -1, dtype=torch.int32, device=dev), torch.zeros((B, M), dtype=torch.float32, device=dev),
+                torch.full((B, M), -1, dtype=torch.int32, device=dev))
+    lib = _lib.load()
+    count = torch.empty((B,), dtype=torch.int32, device=dev)
+    boxes, final = (torch.empty((B, M, 4), dtype=torch.int32, device=dev) for _ in range(2))
+    norm = torch.empty((B, M, 4), dtype=torch.float32, device=dev)
+    ids_out, keep = (torch.empty((B, M), dtype=torch.int32, device=dev) for _ in range(2))
+    scores_out = torch.empty((B, M), dtype=torch.float32, device=dev)
+    d = RefineDetDesc()
+    d.B, d.N, d.max_instances = B, N, M
+    d.rois, d.class_ids, d.scores, d.deltas, d.image_consts = (rois.data_ptr(), class_ids.data_ptr(), scores.data_ptr(), deltas.data_ptr(),
+                                                               image_consts.data_ptr())
+    for i in range(4):
+        d.std_dev[i] = float(std[i])
+    d.image_h, d.image_w, d.min_confidence, d.threshold = float(image_hw[0]), float(image_hw[1]), float(min_confidence), float(threshold)
+    d.count_out, d.boxes_out, d.rois_out, d.norm_out, d.class_ids_out, d.scores_out, d.keep_out = (
+        count.data_ptr(), boxes.data_ptr(), final.data_ptr(), norm.data_ptr(), ids_out.data_ptr(), scores_out.data_ptr(), keep.data_ptr())
+    check(lib.dc_refine_detections_f32(C.byref(d), _stream()), "dc_refine_detections_f32")
+    return count, boxes, final, norm, ids_out, scores_out, keep
 
 
 def mask_head_tail(x, wd, bd, wm_t, bm, class_ids, out=None):

@@ -500,6 +500,67 @@ typedef struct {
 size_t dc_refine_generations_workspace_bytes(const dc_refine_desc* d);
 int    dc_refine_generations_f64(const dc_refine_desc* d, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * refine_detections from the line after the class selection + the box part of unmold_detections (mask_rcnn/mask_rcnn_model.py :689-738,
+ * :2281-2301) for B images with N RoIs each, by the operations of the NumPy host path (mask_rcnn_model.refine_detections /
+ * unmold_boxes) in its order and its number formats, one rounding per NumPy operation.
+ *   rois [B][N][4] float32, normalised (y1,x1,y2,x2); class_ids int32 [B][N], scores float32 [B][N] and deltas float32 [B][N][4]: what
+ *   dc_class_select_f32 leaves.  std_dev: BBOX_STD_DEV as four doubles; image_h, image_w: IMAGE_SHAPE's, as doubles.
+ *   image_consts [B][DC_REFINE_CONSTS] float64 in DEVICE memory, a row as dc_refine_generations_f64 takes it: words 0-3 the window
+ *   y1, x1, y2, x2 (read as the float32 values the DetectionLayer sees), words 6-8 unmold_detections' shift y, x and scale; words 4, 5
+ *   and 9 are not read.
+ *   Boxes: d_k = (double) delta_k * std_k; height = r2 - r0, width = r3 - r1, cy = r0 + 0.5f height, cx alike, in float32;
+ *   cy = (float)((double) cy + d0 (double) height), cx alike; height = (float)((double) height * exp(d2)), width alike, exp in float64;
+ *   y1 = cy - 0.5f height, x1 alike, y2 = y1 + height, x2 = x1 + width in float32; each coordinate (float)((double) v * image_h or
+ *   image_w); clipped to the window in float32 as max(min(v, hi), lo); rounded half to even to int32.
+ *   Candidates: class_id > 0 and (min_confidence == 0 or score >= (float) min_confidence -- NumPy compares the float32 scores with the
+ *   Python float in float32).  Every other RoI neither suppresses nor survives.
+ *   Order: np.argsort(scores, kind="stable")[::-1] -- score descending, the HIGHER RoI index first among equal scores (-0 equals +0,
+ *   NaN before everything), the rule of dc_refine_generations_f64.  (The reference's default sort promises no order among ties.)
+ *   NMS: greedy in that order; box j is suppressed by a kept box i OF THE SAME CLASS when, on the int32 boxes taken as float32,
+ *   ih*iw / (area_i + area_j - ih*iw) > (float) threshold in float32, ih = max(min(y2_i,y2_j) - max(y1_i,y1_j), 0), iw alike; a 0/0 NaN
+ *   suppresses nothing.  This one global scan with suppression inside a class only keeps what the reference's per-class NMS, the union
+ *   of its results and the final sort by score keep, in the same order: a box's fate depends on the kept boxes of its own class ahead
+ *   of it alone, and the global order restricted to a class is that class's order.
+ *   The first max_instances survivors go on; each gives (int32) trunc(((double) box - shift) * scale); boxes with
+ *   (y2-y1)*(x2-x1) <= 0 there are dropped, the others keep their order.
+ * Outputs, each [B][max_instances] rows; rows behind the last survivor hold a zero box, class id -1, score 0 and keep -1:
+ *   count_out int32 [B]; boxes_out int32 [..][4] in the molded image; rois_out int32 [..][4] in the original image; norm_out float32
+ *   [..][4] = (float)((double) box / (double)(h,w,h,w)), what the mask head's RoIAlign takes; class_ids_out int32; scores_out float32
+ *   (the words copied); keep_out int32, the RoI's index.  Every access is of one element: no alignment rule beyond the element's own.
+ * Not bit equality without condition: np.exp and the device library's float64 exp are each within 1 ulp of the true value and are not
+ * the same function.  A difference in that last bit reaches the output only where it flips the float32 rounding of a height or width
+ * and that flip in turn moves an rint or an NMS decision; everything else is the host path's result bit for bit.  Deltas are
+ * expected finite.
+ * Limit: N <= DC_REFINE_DET_MAX_ROIS (one workgroup per image holds the image's boxes, classes, indices and keys in 56 KB of static
+ * LDS); larger N, B < 1, N < 1, max_instances < 1, a null pointer or one off its element's boundary is DC_EINVAL.  ONE launch on `stream` (B workgroups of up to 1024
+ * threads), no workspace, no allocation, no synchronisation, capturable; identical bits from call to call.
+ * ------------------------------------------------------------------------------------------------ */
+#define DC_REFINE_DET_MAX_ROIS 2048
+
+typedef struct {
+    int B, N;
+    const float* rois;
+    const int32_t* class_ids;
+    const float* scores;
+    const float* deltas;
+    const double* image_consts;
+    double std_dev[4];
+    double image_h, image_w;
+    double min_confidence;
+    double threshold;
+    int max_instances;
+    int32_t* count_out;
+    int32_t* boxes_out;
+    int32_t* rois_out;
+    float* norm_out;
+    int32_t* class_ids_out;
+    float* scores_out;
+    int32_t* keep_out;
+} dc_refine_det_desc;
+
+int dc_refine_detections_f32(const dc_refine_det_desc* d, void* stream);
+
 /* PyramidROIAlign backward: d(maps) += bilinear scatter of d(out) (gradients to the boxes are stopped in the
  * reference, dense_model.py:378-379).  dmaps[l] must be zero-initialised by the caller; accumulation uses
  * float atomics (order-dependent in the last bits).  Same descriptor as the forward; `out` holds d(out) and

@@ -11,7 +11,14 @@
    all classes (81 padded to 84 columns), torch sigmoid, gather of each RoI's class, pixel shuffle of the small result.  The two
    alternate call by call in one process.  fused_wins: composed - fused > the run-to-run spread of the composition's repeats.
 
+4. --refine (alone: --refine --no-kernels --no-detect): what detect(refine="device") buys.  The host stage it replaces --
+   mask_rcnn_model.refine_detections + unmold_boxes in NumPy on the model's own selection (1000 RoIs x 81 classes) -- wall clock, alone;
+   the one launch that replaces it (ops.refine_detections on that selection), device events; and detect() with refine="host" and
+   "device" alternating call by call in one process, for postprocess="device" with and without device_masks.  device_refine_wins:
+   host - device > the run-to-run spread of the host mode's repeats.  There is no threshold: the mode is opt-in.
+
     python tools/maskrcnn_bench.py --out profiles/maskrcnn_bench.json
+    python tools/maskrcnn_bench.py --refine --no-kernels --no-detect --out profiles/maskrcnn_refine_bench.json
 """
 import argparse
 import json
@@ -117,7 +124,8 @@ def kernels(own, rows):
     return wins
 
 
-def detect(own, rows):
+def build_model(own):
+    """The model and the image of the detect legs (built once per process)."""
     from image_captioning_amd import synth
     from image_captioning_amd.mask_rcnn_model import MaskRCNN, MaskRCNNConfig
     S = own.side
@@ -135,7 +143,28 @@ def detect(own, rows):
     scaled = {"rpn_conv_shared/kernel": 0.05, "rpn_bbox_pred/kernel": 0.3, "mrcnn_class_conv1/kernel": 0.05, "mrcnn_class_logits/kernel": 10.0,
               "mrcnn_bbox_fc/kernel": 0.3}
     model.set_weights({k: W[k] * np.float32(f) for k, f in scaled.items()})
-    img = synth.images(7, 1, own.image[0], own.image[1])[0]
+    return model, synth.images(7, 1, own.image[0], own.image[1])[0]
+
+
+def wall_alternating(model, img, modes, own):
+    """{mode: per-repeat medians (ms)} of detect(): wall clock around each call, the modes alternating call by call."""
+    wall = {k: [] for k in modes}
+    for _ in range(own.repeats):
+        ts = {k: [] for k in modes}
+        for _ in range(own.detect_calls):
+            for k in ts:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                model.detect([img], **modes[k])
+                torch.cuda.synchronize()
+                ts[k].append((time.perf_counter() - t0) * 1e3)
+        for k in ts:
+            wall[k].append(float(np.median(ts[k])))
+    return wall
+
+
+def detect(own, rows, model, img):
+    S = own.side
     modes = {"host": dict(postprocess="host"), "device": dict(postprocess="device"),
              "device_masks": dict(postprocess="device", device_masks=True)}      # the last leaves the [N,H,W] bytes on the device
     res = {}
@@ -143,18 +172,7 @@ def detect(own, rows):
         for _ in range(own.detect_warmup):
             res[post] = model.detect([img], **kw)[0]
     same = bool(np.array_equal(res["host"]["masks"], res["device"]["masks"]) and np.array_equal(res["host"]["rois"], res["device"]["rois"]))
-    wall = {k: [] for k in modes}
-    for _ in range(own.repeats):
-        ts = {k: [] for k in modes}
-        for _ in range(own.detect_calls):
-            for post in ts:
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                model.detect([img], **modes[post])
-                torch.cuda.synchronize()
-                ts[post].append((time.perf_counter() - t0) * 1e3)
-        for post in ts:
-            wall[post].append(float(np.median(ts[post])))
+    wall = wall_alternating(model, img, modes, own)
     for post in wall:
         emit(rows, what="detect", postprocess=post, image=list(img.shape[:2]), molded=S, proposals=own.proposals, classes=own.classes,
              detections=int(len(res[post]["rois"])), mask_pixels=int(res[post]["masks"].sum()), same_results_both_modes=same,
@@ -162,6 +180,58 @@ def detect(own, rows):
              conv_math=model.conv_math_name, stage4_blocks=own.stage4_blocks,
              timing="wall clock around each detect() call (it returns host arrays), the modes alternating call by call, median of %d calls per "
                     "repeat, median of %d repeats" % (own.detect_calls, own.repeats), **summary(wall[post]))
+
+
+def refine(own, rows, model, img):
+    """Leg 4: the host stage alone, the launch alone, detect() with refine="host" and "device" alternating."""
+    from image_captioning_amd import mask_rcnn_model as MR, ops
+    cfg, dev = model.config, model.device
+    base = model.detect([img])[0]
+    rois, ids, scores, deltas = model.last_selection[0]
+    window = model.mold_inputs([img])[2][0]
+
+    def host_stage():
+        boxes, cls, sc, _ = MR.refine_detections(rois, ids, scores, deltas, np.asarray(window, np.float32), cfg)
+        return MR.unmold_boxes(boxes, img.shape, window)
+    per = []
+    for _ in range(own.repeats):
+        ts = []
+        for _ in range(own.detect_calls):
+            t0 = time.perf_counter()
+            host_stage()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        per.append(float(np.median(ts)))
+    emit(rows, what="refine_stage", where="host", stage="mask_rcnn_model.refine_detections + unmold_boxes (NumPy)", proposals=len(ids), classes=own.classes,
+         candidates=int((ids > 0).sum()), detections=int(len(base["rois"])),
+         timing="wall clock around each call on the host, median of %d calls per repeat, median of %d repeats" % (own.detect_calls, own.repeats), **summary(per))
+    t = lambda a, dt: torch.tensor(np.ascontiguousarray(a), dtype=dt, device=dev)
+    args = (t(rois[None], torch.float32), t(ids[None], torch.int32), t(scores[None], torch.float32), t(deltas[None], torch.float32),
+            t(MR.detection_constants(window, cfg, img.shape)[None], torch.float64), cfg.BBOX_STD_DEV, cfg.DETECTION_MIN_CONFIDENCE,
+            cfg.DETECTION_NMS_THRESHOLD, cfg.DETECTION_MAX_INSTANCES, cfg.IMAGE_SHAPE[:2])
+    r = timed_alternating({"refine": lambda: ops.refine_detections(*args)}, own.launches, own.repeats, own.warmup)
+    emit(rows, what="refine_stage", where="device", kernel="dc_refine_detections_f32", proposals=len(ids), classes=own.classes,
+         detections=int(ops.refine_detections(*args)[0].item()),
+         timing="device events around each call (the wrapper allocates its seven outputs inside), median of %d calls per repeat, median of %d repeats"
+                % (own.launches, own.repeats), **summary(r["refine"]))
+    modes = {"%s/%s" % (rf, name): dict(refine=rf, **kw) for name, kw in (("device", dict(postprocess="device")),
+                                                                          ("device_masks", dict(postprocess="device", device_masks=True)))
+             for rf in ("host", "device")}
+    res = {}
+    for k, kw in modes.items():
+        for _ in range(own.detect_warmup):
+            res[k] = model.detect([img], **kw)[0]
+    same = bool(all(np.array_equal(res["host/device"][key], res["device/device"][key]) for key in ("rois", "class_ids", "scores", "masks")))
+    wall = wall_alternating(model, img, modes, own)
+    for name in ("device", "device_masks"):
+        h, d = summary(wall["host/" + name]), summary(wall["device/" + name])
+        wins = bool(h["ms"] - d["ms"] > h["spread_ms"])
+        for rf, s in (("host", h), ("device", d)):
+            emit(rows, what="detect_refine", refine=rf, postprocess="device", device_masks=name == "device_masks", image=list(img.shape[:2]), molded=own.side,
+                 proposals=own.proposals, classes=own.classes, detections=int(len(res["%s/%s" % (rf, name)]["rois"])),
+                 mask_head_rows=int(cfg.DETECTION_MAX_INSTANCES if rf == "device" else len(res["%s/%s" % (rf, name)]["rois"])),
+                 same_results_both_refines=same, device_refine_wins=wins, conv_math=model.conv_math_name, stage4_blocks=own.stage4_blocks,
+                 timing="wall clock around each detect() call, the four modes alternating call by call, median of %d calls per repeat, median of %d "
+                        "repeats" % (own.detect_calls, own.repeats), **s)
 
 
 def main():
@@ -178,13 +248,19 @@ def main():
     ap.add_argument("--detect-calls", type=int, default=10)
     ap.add_argument("--detect-warmup", type=int, default=3)
     ap.add_argument("--no-detect", action="store_true")
+    ap.add_argument("--no-kernels", action="store_true")
+    ap.add_argument("--refine", action="store_true", help="leg 4: detect(refine='host') against refine='device'")
     ap.add_argument("--out", default=None)
     own = ap.parse_args()
     torch.cuda.set_device(0)
     rows = []
-    kernels(own, rows)
+    if not own.no_kernels:
+        kernels(own, rows)
+    model, img = build_model(own) if own.refine or not own.no_detect else (None, None)
     if not own.no_detect:
-        detect(own, rows)
+        detect(own, rows, model, img)
+    if own.refine:
+        refine(own, rows, model, img)
     if own.out:
         os.makedirs(os.path.dirname(own.out) or ".", exist_ok=True)
         with open(own.out, "w") as f:
