@@ -15,6 +15,9 @@
 //   dc_mask_paste_u8        utils.unmold_mask for the detections of one image: scipy's bytescale on the mask's own range, PIL's 8-bit
 //                           bilinear resize to the box (the coefficient code of resize_core.h, shared with resize.hip), threshold at
 //                           128, pasted into a zeroed [H][W] plane.  Every byte of the output is written.
+//   dc_mask_rle_u32         the same planes as COCO run lengths without ever storing them: the paste's first three launches, then
+//                           one wave per box column takes the transitions of 64 rows a step from a ballot, two prefix sums place
+//                           them, a second walk stores their positions and a last launch differences them into counts.
 #include "igemm_core.h"
 #include "resize_core.h"
 #include <limits.h>
@@ -271,6 +274,31 @@ __global__ __launch_bounds__(MP_THREADS) void paste_v_kernel(const int* __restri
     }
 }
 
+static void paste_layout(int M_, int h, int w, int H, int W, PasteWs* L) {
+    const size_t M = (size_t)M_;
+    // a table of `out` entries from `in` source samples holds out * (2 + ksize) ints with ksize <= 2 in / out + 3 taps when shrinking
+    // and 3 when not: never more than 2 in + 5 out, and out is at most the image's side
+    L->ax = 2 * w + 5 * W;
+    L->ay = 2 * h + 5 * H;
+    L->bytes = 0;
+    L->mids = (M * h * w + 15) & ~(size_t)15;
+    L->tables = (L->mids + M * h * W + 15) & ~(size_t)15;
+    L->total = L->tables + M * ((size_t)L->ax + L->ay) * sizeof(int);
+}
+
+static unsigned paste_blocks(int n) { return (unsigned)((n + MP_THREADS - 1) / MP_THREADS); }
+
+// the three launches dc_mask_paste_u8 and dc_mask_rle_u32 share: byte images, both axes' coefficient tables, the horizontal pass
+static void paste_front(const float* masks, const int32_t* boxes, int M, int h, int w, int H, int W, const PasteWs& L, uint8_t* base, hipStream_t s) {
+    uint8_t* bytes = base + L.bytes;
+    uint8_t* mids = base + L.mids;
+    int* tables = reinterpret_cast<int*>(base + L.tables);
+    const int side = H > W ? H : W;
+    hipLaunchKernelGGL(paste_bytescale_kernel, dim3(M), dim3(MP_THREADS), 0, s, masks, bytes, h * w);
+    hipLaunchKernelGGL(paste_coef_kernel, dim3(paste_blocks(side), 2, M), dim3(MP_THREADS), 0, s, boxes, tables, h, w, H, W, L.ax, L.ay);
+    hipLaunchKernelGGL(paste_h_kernel, dim3(paste_blocks(W), h, M), dim3(MP_THREADS), 0, s, boxes, tables, bytes, mids, h, w, H, W, L.ax, L.ay);
+}
+
 static int paste_plan(const dc_mask_paste_desc* d, PasteWs* L) {
     DC_REQUIRE(d, DC_EINVAL, "dc_mask_paste_u8: null descriptor");
     DC_REQUIRE(d->M >= 0 && d->M <= MP_MAX_GRID, DC_EINVAL, "dc_mask_paste_u8: M in 0..%d, got %d", MP_MAX_GRID, d->M);
@@ -281,15 +309,163 @@ static int paste_plan(const dc_mask_paste_desc* d, PasteWs* L) {
     DC_REQUIRE(d->M == 0 || (d->masks && d->boxes && d->out), DC_EINVAL, "dc_mask_paste_u8: null masks, boxes or output");
     DC_REQUIRE((reinterpret_cast<uintptr_t>(d->masks) & 3u) == 0 && (reinterpret_cast<uintptr_t>(d->boxes) & 3u) == 0, DC_EINVAL,
                "dc_mask_paste_u8: masks (float32) and boxes (int32) must sit on 4-byte boundaries");
+    paste_layout(d->M, d->h, d->w, d->H, d->W, L);
+    return DC_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ mask run lengths
+// The plane of detection m is never stored.  Slot s of a detection is column x1 + s of its box for s < bw, and for s = bw the column
+// right of the box, which can hold one transition only (the end of a run of ones that reaches the image's last row).  Slots are
+// numbered 0..W per detection whatever the box is (the host cannot know the boxes); those behind the box count zero.
+constexpr int RL_THREADS = 256, RL_WAVES = RL_THREADS / 64, RL_DIFF_BLOCKS = 8;
+
+struct RleWs {
+    PasteWs paste;
+    size_t slots, totals, pos, total;      // byte offsets: int [M][W + 1], int [M], uint32 [capacity]
+};
+
+// One wave per (detection, slot).  COUNT: slot_n[m][s] = the slot's transitions.  Otherwise slot_n holds the exclusive prefix sums
+// within the detection and transition j of the slot stores its pixel index at pos[offsets[m] + slot_n[m][s] + j], below capacity only.
+template <bool COUNT>
+__global__ __launch_bounds__(RL_THREADS) void rle_walk_kernel(const int* __restrict__ boxes, const int* __restrict__ tables,
+                                                             const uint8_t* __restrict__ mids, int* __restrict__ slot_n,
+                                                             const int* __restrict__ offsets, uint32_t* __restrict__ pos, int capacity, int h,
+                                                             int H, int W, int ax, int ay) {
+    const int m = blockIdx.z, lane = threadIdx.x & 63;
+    const int s = blockIdx.x * RL_WAVES + (threadIdx.x >> 6);
+    if (s > W) return;                                            // whole waves leave: the ballots below see full waves
+    int y1, x1, bh, bw;
+    const bool ok = paste_box(boxes, m, H, W, y1, x1, bh, bw);
+    int* const mine = slot_n + (size_t)m * (W + 1) + s;
+    if (!ok || s > bw || (s == bw && x1 + bw == W)) {             // (wave-uniform)
+        if (COUNT && lane == 0) *mine = 0;
+        return;
+    }
+    const int* bounds = tables + (size_t)m * (ax + ay) + ax;
+    const int* coefs = bounds + 2 * (size_t)bh;
+    const uint8_t* mid = mids + (size_t)m * h * W;
+    // paste_v_kernel's arithmetic for box pixel (y, xx)
+    auto bit = [&](int y, int xx) -> bool {
+        const int ymin = bounds[2 * y], n = bounds[2 * y + 1];
+        const uint8_t* p = mid + (size_t)ymin * W + xx;
+        int acc = 1 << (RS_PRECISION_BITS - 1);
+        for (int t = 0; t < n; ++t) acc += coefs[(size_t)t * bh + y] * (int)p[(size_t)t * W];
+        return resize_clip8(acc) >= 128;
+    };
+    // the pixel before this column's first: the last row of the column to the left, set only where the box reaches that row
+    const bool pred = s > 0 && y1 + bh == H && bit(bh - 1, s - 1);
+    const int base = (x1 + s) * H;                                // (x1 + s < W here: below H * W < 2^31)
+    const int at = COUNT ? 0 : offsets[m] + *mine;
+    auto store = [&](int j, int index) {
+        if (at + j < capacity) pos[at + j] = (uint32_t)index;
+    };
+    int n = 0;
+    if (s == bw || y1 > 0) {                                      // row 0 of this column is outside the box: a zero
+        if (pred) {
+            if (!COUNT && lane == 0) store(0, base);
+            n = 1;
+        }
+    }
+    if (s < bw) {
+        unsigned long long carry = y1 > 0 ? 0ull : (unsigned long long)pred;
+        const int rows = bh + 1 < H - y1 ? bh + 1 : H - y1;      // box rows, and the zero below the box where the image has that row
+        for (int y0 = 0; y0 < rows; y0 += 64) {
+            const int y = y0 + lane;
+            const unsigned long long bits = __ballot(y < bh && bit(y, s));
+            const unsigned long long valid = rows - y0 >= 64 ? ~0ull : (1ull << (rows - y0)) - 1;
+            const unsigned long long trans = (bits ^ ((bits << 1) | carry)) & valid;
+            carry = bits >> 63;
+            if (!COUNT && ((trans >> lane) & 1)) store(n + __popcll(trans & ((1ull << lane) - 1)), base + y1 + y);
+            n += __popcll(trans);
+        }
+    }
+    if (COUNT && lane == 0) *mine = n;
+}
+
+// exclusive prefix sum of one value per thread over the block, and the block's total; part holds RL_WAVES ints
+__device__ __forceinline__ int rle_block_scan(int v, int* part, int& total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int x = v;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int up = __shfl_up(x, off);
+        if (lane >= off) x += up;
+    }
+    if (lane == 63) part[wave] = x;
+    __syncthreads();
+    int before = 0;
+    total = 0;
+#pragma unroll
+    for (int wv = 0; wv < RL_WAVES; ++wv) {
+        if (wv < wave) before += part[wv];
+        total += part[wv];
+    }
+    __syncthreads();                                              // part is free again
+    return before + x - v;
+}
+
+// block m: slot_n[m][0..W] becomes its own exclusive prefix sums, totals[m] the detection's transitions
+__global__ __launch_bounds__(RL_THREADS) void rle_scan_slots_kernel(int* __restrict__ slot_n, int* __restrict__ totals, int W) {
+    __shared__ int part[RL_WAVES];
+    int* row = slot_n + (size_t)blockIdx.x * (W + 1);
+    int carry = 0;
+    for (int c0 = 0; c0 <= W; c0 += RL_THREADS) {
+        const int i = c0 + threadIdx.x;
+        int total;
+        const int e = rle_block_scan(i <= W ? row[i] : 0, part, total);
+        if (i <= W) row[i] = carry + e;
+        carry += total;
+    }
+    if (threadIdx.x == 0) totals[blockIdx.x] = carry;
+}
+
+// one block: offsets[m] = the entries of the detections before m, each its transitions + 1
+__global__ __launch_bounds__(RL_THREADS) void rle_scan_dets_kernel(const int* __restrict__ totals, int* __restrict__ offsets, int M) {
+    __shared__ int part[RL_WAVES];
+    int carry = 0;
+    for (int c0 = 0; c0 < M; c0 += RL_THREADS) {
+        const int i = c0 + threadIdx.x;
+        int total;
+        const int e = rle_block_scan(i < M ? totals[i] + 1 : 0, part, total);
+        if (i < M) offsets[i] = carry + e;
+        carry += total;
+    }
+    if (threadIdx.x == 0) offsets[M] = carry;
+}
+
+// counts[j] = t - t' with t the position at j (H W at a detection's last entry) and t' the one before (0 at its first)
+__global__ __launch_bounds__(RL_THREADS) void rle_diff_kernel(const int* __restrict__ offsets, const uint32_t* __restrict__ pos,
+                                                             uint32_t* __restrict__ counts, int capacity, int HW) {
+    const int m = blockIdx.y;
+    const int lo = offsets[m], hi = offsets[m + 1];
+    const int end = hi < capacity ? hi : capacity;
+    for (int j = lo + blockIdx.x * RL_THREADS + threadIdx.x; j < end; j += gridDim.x * RL_THREADS) {
+        const uint32_t t = j == hi - 1 ? (uint32_t)HW : pos[j];
+        counts[j] = t - (j == lo ? 0u : pos[j - 1]);
+    }
+}
+
+static int rle_plan(const dc_mask_rle_desc* d, RleWs* L) {
+    DC_REQUIRE(d, DC_EINVAL, "dc_mask_rle_u32: null descriptor");
+    DC_REQUIRE(d->M >= 0 && d->M <= MP_MAX_GRID, DC_EINVAL, "dc_mask_rle_u32: M in 0..%d, got %d", MP_MAX_GRID, d->M);
+    DC_REQUIRE(d->h >= 1 && d->h <= MP_MAX_SIDE && d->w >= 1 && d->w <= MP_MAX_SIDE, DC_EINVAL,
+               "dc_mask_rle_u32: a mask of 1 x 1 to %d x %d, got %d x %d", MP_MAX_SIDE, MP_MAX_SIDE, d->h, d->w);
+    DC_REQUIRE(d->H >= 1 && d->W >= 1 && d->H <= (1 << 24) && d->W <= (1 << 24) && (size_t)d->H * d->W < ((size_t)1 << 31), DC_EINVAL,
+               "dc_mask_rle_u32: an image of at least 1 x 1, sides of at most 2^24 and fewer than 2^31 pixels, got %d x %d", d->H, d->W);
+    DC_REQUIRE((size_t)d->M * ((size_t)d->H * d->W + 1) < ((size_t)1 << 31), DC_EINVAL,
+               "dc_mask_rle_u32: M * (H * W + 1) must stay below 2^31 (the int32 offsets), got M %d, %d x %d", d->M, d->H, d->W);
+    DC_REQUIRE(d->capacity >= 0, DC_EINVAL, "dc_mask_rle_u32: capacity must not be negative, got %d", d->capacity);
+    DC_REQUIRE(d->offsets && (d->counts || d->capacity == 0), DC_EINVAL, "dc_mask_rle_u32: null offsets or counts");
+    DC_REQUIRE(d->M == 0 || (d->masks && d->boxes), DC_EINVAL, "dc_mask_rle_u32: null masks or boxes");
+    DC_REQUIRE(((reinterpret_cast<uintptr_t>(d->masks) | reinterpret_cast<uintptr_t>(d->boxes) | reinterpret_cast<uintptr_t>(d->offsets) |
+                 reinterpret_cast<uintptr_t>(d->counts)) & 3u) == 0, DC_EINVAL,
+               "dc_mask_rle_u32: masks (float32), boxes and offsets (int32) and counts (uint32) must sit on 4-byte boundaries");
     const size_t M = (size_t)d->M;
-    // a table of `out` entries from `in` source samples holds out * (2 + ksize) ints with ksize <= 2 in / out + 3 taps when shrinking
-    // and 3 when not: never more than 2 in + 5 out, and out is at most the image's side
-    L->ax = 2 * d->w + 5 * d->W;
-    L->ay = 2 * d->h + 5 * d->H;
-    L->bytes = 0;
-    L->mids = (M * d->h * d->w + 15) & ~(size_t)15;
-    L->tables = (L->mids + M * d->h * d->W + 15) & ~(size_t)15;
-    L->total = L->tables + M * ((size_t)L->ax + L->ay) * sizeof(int);
+    paste_layout(d->M, d->h, d->w, d->H, d->W, &L->paste);
+    L->slots = (L->paste.total + 15) & ~(size_t)15;
+    L->totals = L->slots + ((M * ((size_t)d->W + 1) * sizeof(int) + 15) & ~(size_t)15);
+    L->pos = L->totals + ((M * sizeof(int) + 15) & ~(size_t)15);
+    L->total = L->pos + (size_t)d->capacity * sizeof(uint32_t);
     return DC_OK;
 }
 
@@ -357,16 +533,45 @@ extern "C" int dc_mask_paste_u8(const dc_mask_paste_desc* d, void* workspace, si
                "dc_mask_paste_u8: needs %zu workspace bytes (16-byte aligned), got %zu", L.total, workspace_bytes);
     hipStream_t s = static_cast<hipStream_t>(stream);
     uint8_t* base = static_cast<uint8_t*>(workspace);
-    uint8_t* bytes = base + L.bytes;
-    uint8_t* mids = base + L.mids;
-    int* tables = reinterpret_cast<int*>(base + L.tables);
-    auto blocks = [](int n) { return (unsigned)((n + MP_THREADS - 1) / MP_THREADS); };
-    const int M = d->M, side = d->H > d->W ? d->H : d->W;
-    hipLaunchKernelGGL(paste_bytescale_kernel, dim3(M), dim3(MP_THREADS), 0, s, d->masks, bytes, d->h * d->w);
-    hipLaunchKernelGGL(paste_coef_kernel, dim3(blocks(side), 2, M), dim3(MP_THREADS), 0, s, d->boxes, tables, d->h, d->w, d->H, d->W, L.ax, L.ay);
-    hipLaunchKernelGGL(paste_h_kernel, dim3(blocks(d->W), d->h, M), dim3(MP_THREADS), 0, s, d->boxes, tables, bytes, mids, d->h, d->w, d->H, d->W, L.ax,
-                       L.ay);
-    hipLaunchKernelGGL(paste_v_kernel, dim3(blocks(d->W), d->H < MP_MAX_GRID ? d->H : MP_MAX_GRID, M), dim3(MP_THREADS), 0, s, d->boxes, tables, mids,
-                       d->out, d->h, d->H, d->W, L.ax, L.ay);
+    paste_front(d->masks, d->boxes, d->M, d->h, d->w, d->H, d->W, L, base, s);
+    hipLaunchKernelGGL(paste_v_kernel, dim3(paste_blocks(d->W), d->H < MP_MAX_GRID ? d->H : MP_MAX_GRID, d->M), dim3(MP_THREADS), 0, s, d->boxes,
+                       reinterpret_cast<int*>(base + L.tables), base + L.mids, d->out, d->h, d->H, d->W, L.ax, L.ay);
     return check_launch("mask_paste kernels");
+}
+
+extern "C" size_t dc_mask_rle_workspace_bytes(const dc_mask_rle_desc* d) {
+    RleWs L;
+    if (rle_plan(d, &L)) return 0;
+    return L.total;
+}
+
+extern "C" int dc_mask_rle_u32(const dc_mask_rle_desc* d, void* stream) {
+    RleWs L;
+    int rc = rle_plan(d, &L);
+    if (rc) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int M = d->M;
+    if (M == 0) {
+        const hipError_t e = hipMemsetAsync(d->offsets, 0, sizeof(int32_t), s);
+        DC_REQUIRE(e == hipSuccess, DC_ELAUNCH, "dc_mask_rle_u32: hipMemsetAsync: %s", hipGetErrorString(e));
+        return DC_OK;
+    }
+    DC_REQUIRE(d->workspace && d->workspace_bytes >= L.total && aligned16(d->workspace), DC_EWORKSPACE,
+               "dc_mask_rle_u32: needs %zu workspace bytes (16-byte aligned), got %zu", L.total, d->workspace_bytes);
+    uint8_t* base = static_cast<uint8_t*>(d->workspace);
+    const int* tables = reinterpret_cast<const int*>(base + L.paste.tables);
+    const uint8_t* mids = base + L.paste.mids;
+    int* slot_n = reinterpret_cast<int*>(base + L.slots);
+    int* totals = reinterpret_cast<int*>(base + L.totals);
+    uint32_t* pos = reinterpret_cast<uint32_t*>(base + L.pos);
+    paste_front(d->masks, d->boxes, M, d->h, d->w, d->H, d->W, L.paste, base, s);
+    const dim3 walk((unsigned)((d->W + 1 + RL_WAVES - 1) / RL_WAVES), 1, M);
+    hipLaunchKernelGGL(rle_walk_kernel<true>, walk, dim3(RL_THREADS), 0, s, d->boxes, tables, mids, slot_n, d->offsets, pos, d->capacity, d->h, d->H,
+                       d->W, L.paste.ax, L.paste.ay);
+    hipLaunchKernelGGL(rle_scan_slots_kernel, dim3(M), dim3(RL_THREADS), 0, s, slot_n, totals, d->W);
+    hipLaunchKernelGGL(rle_scan_dets_kernel, dim3(1), dim3(RL_THREADS), 0, s, totals, d->offsets, M);
+    hipLaunchKernelGGL(rle_walk_kernel<false>, walk, dim3(RL_THREADS), 0, s, d->boxes, tables, mids, slot_n, d->offsets, pos, d->capacity, d->h,
+                       d->H, d->W, L.paste.ax, L.paste.ay);
+    hipLaunchKernelGGL(rle_diff_kernel, dim3(RL_DIFF_BLOCKS, M), dim3(RL_THREADS), 0, s, d->offsets, pos, d->counts, d->capacity, d->H * d->W);
+    return check_launch("mask_rle kernels");
 }

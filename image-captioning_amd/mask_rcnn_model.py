@@ -12,6 +12,8 @@ unmold_detections :2253-2312, detect :2314-2354; mask_rcnn/utils.py: apply_box_d
   -> utils.unmold_mask: postprocess="host" in NumPy / PIL, "device" ops.mask_paste and one copy of the [M,H,W] bytes.
 detect(refine="device") replaces the three middle steps by ops.refine_detections on the device (one launch, no host read before the
 results come down) and runs the mask head on DETECTION_MAX_INSTANCES rows per image.
+detect(mask_format="rle") returns the masks as COCO run-length encodings (mask_rle.py); with postprocess="device" ops.mask_rle builds
+them from the [M,28,28] masks and the boxes in place of ops.mask_paste, and the [M,H,W] bytes never exist.
 
 Everything below the heads is DenseImageCapRCNN's, unchanged: MaskRCNN sub-classes it and puts DetectTop where the caption model sits.
 detect() starts with the parent's inference front (_proposal_features: mold, encoder pass, proposals, RoIAlign(7)); save_weights is the
@@ -23,7 +25,7 @@ targets and the class, box and mask losses are not built), compute_dtype="bf16",
 import numpy as np
 import torch
 
-from . import dense_model, ops, synth, utils
+from . import dense_model, mask_rle, ops, synth, utils
 from .config import Config
 from .dense_model import DenseImageCapRCNN
 from .packing import pack_conv_kernel, pack_mask_tail
@@ -315,7 +317,7 @@ class MaskRCNN(DenseImageCapRCNN):
         DenseImageCapRCNN.set_weights(self, W)             # (ends in the top's _weights_changed: the folded mask BatchNorms go)
 
     # ---- inference -----------------------------------------------------------------------------
-    def detect(self, images, verbose=0, postprocess="host", mold="host", device_masks=False, refine="host"):
+    def detect(self, images, verbose=0, postprocess="host", mold="host", device_masks=False, refine="host", mask_format="dense"):
         """The inference graph + detect (:2314-2354).  Returns, per image, {"rois": int32 [N,4] in the original image, "class_ids": int32
         [N], "scores": float32 [N], "masks": uint8 [H,W,N] (a transposed view of [N,H,W]); (0,28,28) floats when nothing is detected, as
         the reference returns it}.  postprocess="host": the [N,28,28] class masks come to the host and utils.unmold_mask runs in NumPy /
@@ -330,13 +332,26 @@ class MaskRCNN(DenseImageCapRCNN):
         mask bytes second; postprocess="host" copies the [B,M,28,28] class masks second.  last_selection holds the four DEVICE tensors
         (proposals [B,K,4], ids [B,K], scores [B,K], deltas [B,K,4]: buffers the next call reuses), last_class_masks device views as
         with postprocess="device".  Equal scores are ordered as np.argsort(kind="stable")[::-1] orders them (the host path's default
-        sort promises no order), and the device's float64 exp is not np.exp bit for bit: see dc_refine_detections_f32."""
+        sort promises no order), and the device's float64 exp is not np.exp bit for bit: see dc_refine_detections_f32.
+        mask_format="rle": "masks" is a list of N COCO run-length encodings {"size": [H, W] of the original image, "counts": uint32
+        ndarray} (mask_rle.py: decode, area, to_coco), an empty list when nothing is detected; decoded, each is the dense mode's plane
+        byte for byte.  postprocess="host" encodes unmold_mask's planes with mask_rle.encode; postprocess="device" builds the encodings
+        on the device (ops.mask_rle per image, in place of ops.mask_paste) and no [N,H,W] buffer exists anywhere.  The device mode
+        makes TWO device-to-host copies per batch with refine="device" -- the detections pack and one pack of every image's offsets
+        and counts -- and with refine="host" the selection copy and that one RLE pack; nothing reads the device between the image
+        upload (refine="host": the detections' upload) and those copies.  Only where an image's encodings outgrow ops.mask_rle's
+        capacity does that image cost a second launch and a copy of its own.  Not with device_masks=True."""
         if postprocess not in ("host", "device"):
             raise ValueError("postprocess must be 'host' or 'device', got %r" % (postprocess,))
         if device_masks and postprocess != "device":
             raise ValueError("device_masks=True needs postprocess='device'")
         if refine not in ("host", "device"):
             raise ValueError("refine must be 'host' or 'device', got %r" % (refine,))
+        if mask_format not in ("dense", "rle"):
+            raise ValueError("mask_format must be 'dense' or 'rle', got %r" % (mask_format,))
+        if mask_format == "rle" and device_masks:
+            raise ValueError("mask_format='rle' returns host run-length encodings: device_masks=True is not available with it")
+        rle = mask_format == "rle"
         utils.check_mold(mold, self.config.IMAGE_PADDING)
         cfg, top, B = self.config, self.caption_model, len(images)
         if verbose:
@@ -346,7 +361,7 @@ class MaskRCNN(DenseImageCapRCNN):
         z, d = top.heads(feats.view(B * K, cfg.POOL_SIZE, cfg.POOL_SIZE, 256))
         self.last_heads = (z, d)
         if refine == "device":
-            return self._detect_refined_on_device(p, images, consts, proposals, z, d, postprocess, device_masks)
+            return self._detect_refined_on_device(p, images, consts, proposals, z, d, postprocess, device_masks, rle)
         # proposals, ids, scores and deltas leave in one buffer of 10 words per RoI: ids as their bits
         sel = self._buf("selection", (B * K, 10))
         sel[:, :4].copy_(proposals.view(B * K, 4))
@@ -371,7 +386,7 @@ class MaskRCNN(DenseImageCapRCNN):
         M = max(counts)
         self.last_class_masks = [np.zeros((0, 2 * top.mask_pool, 2 * top.mask_pool), np.float32) for _ in range(B)]
         results = [{"rois": dt["rois"], "class_ids": dt["class_ids"], "scores": dt["scores"],
-                    "masks": np.empty((0, 2 * top.mask_pool, 2 * top.mask_pool))} for dt in dets]
+                    "masks": [] if rle else np.empty((0, 2 * top.mask_pool, 2 * top.mask_pool))} for dt in dets]
         if M == 0:
             if device_masks:
                 for b in range(B):
@@ -397,9 +412,17 @@ class MaskRCNN(DenseImageCapRCNN):
             for b in range(B):
                 n = counts[b]
                 self.last_class_masks[b] = masks_h[b, :n].copy()
-                if n:
+                if n and rle:
+                    results[b]["masks"] = [mask_rle.encode(unmold_mask(masks_h[b, i], dets[b]["rois"][i], images[b].shape)) for i in range(n)]
+                elif n:
                     full = np.stack([unmold_mask(masks_h[b, i], dets[b]["rois"][i], images[b].shape) for i in range(n)])
                     results[b]["masks"] = full.transpose(1, 2, 0)
+            return results
+        if rle:
+            runs = {b: ops.mask_rle(masks[b, :counts[b]], up[b, :counts[b], 5:].contiguous(), *images[b].shape[:2]) for b in range(B) if counts[b]}
+            for b, found in self._rle_lists(runs).items():
+                results[b]["masks"] = found
+            self.last_class_masks = [masks[b, :counts[b]] for b in range(B)]
             return results
         keep = []
         for b in range(B):
@@ -416,7 +439,16 @@ class MaskRCNN(DenseImageCapRCNN):
         self.last_class_masks = [masks[b, :counts[b]] for b in range(B)]     # (device views of a buffer the next call reuses)
         return results
 
-    def _detect_refined_on_device(self, p, images, consts, proposals, z, d, postprocess, device_masks):
+    @staticmethod
+    def _rle_lists(runs):
+        """{image: ops.MaskRle} -> {image: list of RLE dicts}, with ONE device-to-host copy for all of them."""
+        if not runs:
+            return {}
+        host = torch.cat([r.pack for r in runs.values()]).cpu().numpy()
+        cuts = np.cumsum([0] + [r.pack.numel() for r in runs.values()])
+        return {b: r.rles(host[lo:hi]) for (b, r), lo, hi in zip(runs.items(), cuts[:-1], cuts[1:])}
+
+    def _detect_refined_on_device(self, p, images, consts, proposals, z, d, postprocess, device_masks, rle=False):
         """detect(refine="device") behind the heads: nothing here reads the device before pack_detections."""
         cfg, top, (B, K) = self.config, self.caption_model, proposals.shape[:2]
         M, P = int(cfg.DETECTION_MAX_INSTANCES), top.mask_pool
@@ -427,18 +459,29 @@ class MaskRCNN(DenseImageCapRCNN):
                                                                         cfg.DETECTION_NMS_THRESHOLD, M, cfg.IMAGE_SHAPE[:2])
         x = ops.roi_align_pyramid(list(p.P), norm, float(p.H * p.W), P, out=self._buf("mask_rois_fixed", (B, M, P, P, 256)))
         masks = top.class_masks(x.view(B * M, P, P, 256), cls.view(B * M), out=self._buf("class_masks_fixed", (B * M, 2 * P, 2 * P))).view(B, M, 2 * P, 2 * P)
-        full = [ops.mask_paste(masks[b], rois[b], *images[b].shape[:2]) for b in range(B)] if postprocess == "device" else None
+        full = runs = None
+        if postprocess == "device" and rle:              # padded rows carry zero boxes: they encode as [H * W] and are dropped below
+            runs = {b: ops.mask_rle(masks[b], rois[b], *images[b].shape[:2]) for b in range(B)}
+        elif postprocess == "device":
+            full = [ops.mask_paste(masks[b], rois[b], *images[b].shape[:2]) for b in range(B)]
         n, boxes_h, rois_h, cls_h, sc_h, _ = pack_detections(count, boxes, rois, cls, sc, keep)
         self.last_detections = [dict(boxes=boxes_h[b, :n[b]], class_ids=cls_h[b, :n[b]], scores=sc_h[b, :n[b]], rois=rois_h[b, :n[b]]) for b in range(B)]
         results = [{"rois": dt["rois"], "class_ids": dt["class_ids"], "scores": dt["scores"],
-                    "masks": np.empty((0, 2 * P, 2 * P))} for dt in self.last_detections]
+                    "masks": [] if rle else np.empty((0, 2 * P, 2 * P))} for dt in self.last_detections]
         if postprocess == "host":
             masks_h = masks.cpu().numpy()
             self.last_class_masks = [masks_h[b, :n[b]].copy() for b in range(B)]
             for b in range(B):
-                if n[b]:
+                if n[b] and rle:
+                    results[b]["masks"] = [mask_rle.encode(unmold_mask(masks_h[b, i], rois_h[b, i], images[b].shape)) for i in range(n[b])]
+                elif n[b]:
                     full_b = np.stack([unmold_mask(masks_h[b, i], rois_h[b, i], images[b].shape) for i in range(n[b])])
                     results[b]["masks"] = full_b.transpose(1, 2, 0)
+            return results
+        if rle:
+            for b, found in self._rle_lists(runs).items():
+                results[b]["masks"] = found[:n[b]]
+            self.last_class_masks = [masks[b, :n[b]] for b in range(B)]
             return results
         for b in range(B):
             if device_masks:

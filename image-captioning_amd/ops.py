@@ -12,7 +12,7 @@ import torch
 
 from . import _lib
 from ._lib import (RpnTargetsDesc, PwChainDesc, ConvBf16Desc, AmsgradDesc, DetectionTargetsDesc, BnReluDesc, ConvDesc, ConvWgradBf16Desc, GemmBf16Desc, VocabCeDesc, ProposalDesc, RpnLossDesc, GemmDesc, LstmBwdDesc, LstmFwdDesc, RoialignDesc, RoiGroupsDesc,
-                   SoftmaxCeDesc, TagFocalDesc, VocabTop1Desc, VocabTopkDesc, VocabTop1Bf16Desc, VocabTopkBf16Desc, VocabSampleDesc, VocabSampleBf16Desc, BeamSelectDesc, BeamStepDesc, LstmStepDesc, RefineDesc, RefineDetDesc, ResizePadDesc, MaskHeadTailDesc, MaskPasteDesc, check)
+                   SoftmaxCeDesc, TagFocalDesc, VocabTop1Desc, VocabTopkDesc, VocabTop1Bf16Desc, VocabTopkBf16Desc, VocabSampleDesc, VocabSampleBf16Desc, BeamSelectDesc, BeamStepDesc, LstmStepDesc, RefineDesc, RefineDetDesc, ResizePadDesc, MaskHeadTailDesc, MaskPasteDesc, MaskRleDesc, check)
 
 
 def _stream():
@@ -1243,6 +1243,85 @@ def mask_paste(masks, boxes, H, W, out=None):
     d.masks, d.boxes, d.out = masks.data_ptr(), boxes.data_ptr(), out.data_ptr()
     _launch_ws(lib.dc_mask_paste_u8_workspace_bytes(C.byref(d)), masks.device, lib.dc_mask_paste_u8, C.byref(d))
     return out
+
+
+def mask_rle_capacity(M, H, W):
+    """ops.mask_rle's default capacity in words for M detections in an H x W image: one word per detection and image column, at least
+    4096 (DESIGN.md section 6.1m has the run counts it was sized from).  The whole capacity is what rles() copies, and only the cost
+    of a second launch depends on it, never a result."""
+    return max(4096, int(M) * int(W))
+
+
+class MaskRle(object):
+    """What ops.mask_rle returns: `pack`, ONE int32 device tensor [M + 1 + capacity] -- `offsets` [M + 1] and `counts` [capacity]
+    (uint32 bits) are views of it -- so that a caller holding several can bring them down in one copy (torch.cat of the packs).
+    rles() makes the host list; nothing reads the device before it."""
+
+    def __init__(self, masks, boxes, H, W, capacity):
+        self.masks, self.boxes, self.size, self.capacity = masks, boxes, (int(H), int(W)), int(capacity)
+        self.M = int(masks.shape[0])
+        self.launches = 0
+        self._launch()
+
+    def _launch(self):
+        M, (H, W) = self.M, self.size
+        self.pack = torch.empty((M + 1 + self.capacity,), dtype=torch.int32, device=self.masks.device)
+        self.offsets, self.counts = self.pack[:M + 1], self.pack[M + 1:]
+        lib = _lib.load()
+        d = MaskRleDesc()
+        d.M, d.h, d.w, d.H, d.W, d.capacity = M, int(self.masks.shape[1]), int(self.masks.shape[2]), H, W, self.capacity
+        d.masks, d.boxes, d.offsets, d.counts = self.masks.data_ptr(), self.boxes.data_ptr(), self.offsets.data_ptr(), self.counts.data_ptr()
+        ws, wsb = WORKSPACE.get(lib.dc_mask_rle_workspace_bytes(C.byref(d)), self.masks.device)
+        d.workspace, d.workspace_bytes = None if ws is None else ws.data_ptr(), wsb
+        check(lib.dc_mask_rle_u32(C.byref(d), _stream()), "dc_mask_rle_u32")
+        self.launches += 1
+
+    def rles(self, host=None):
+        """The M encodings as a list of {"size": [H, W], "counts": uint32 ndarray}.  host: this object's pack as an int32 host array,
+        where the caller has copied it already; otherwise the pack is copied here (the one device-to-host copy).  When the
+        encodings need more words than `capacity`, the entry runs a second time with exactly the capacity offsets[M] asks for and
+        that result is copied: the list is always complete."""
+        M = self.M
+        if host is None:
+            host = self.pack.cpu().numpy()
+        need = int(host[M])
+        if need > self.capacity:
+            self.capacity = need
+            self._launch()
+            host = self.pack.cpu().numpy()
+            if int(host[M]) != need:
+                raise _lib.DcapError("mask_rle: the second run needs %d words where the first asked for %d" % (int(host[M]), need))
+        offsets, counts = host[:M + 1], host[M + 1:].view(np.uint32)
+        return [{"size": list(self.size), "counts": counts[offsets[m]:offsets[m + 1]].copy()} for m in range(M)]
+
+
+def mask_rle(masks, boxes, H, W, capacity=None):
+    """The planes ops.mask_paste would write, as COCO run-length encodings built on the device without the planes (dc_mask_rle_u32;
+    the format: mask_rle.py).  masks float32 [M,h,w] (h, w <= 64), boxes int32 [M,4] (y1, x1, y2, x2) in the original H x W image,
+    both on the device.  Returns a MaskRle: .offsets int32 [M+1] and .counts int32 [capacity] (uint32 bits) on the device, views of
+    its .pack, and .rles(), which copies the pack once and returns the list of {"size", "counts"} -- after a second launch with
+    capacity = offsets[M] where the first capacity was too small, so no result depends on `capacity` (default:
+    mask_rle_capacity(M, H, W)).  An empty box or one that leaves the image encodes as [H * W].  No host synchronisation before
+    rles().  Shapes and dtypes are checked before the library is loaded."""
+    H, W = int(H), int(W)
+    if masks.dim() != 3 or not (1 <= masks.shape[1] <= 64 and 1 <= masks.shape[2] <= 64):
+        raise _lib.DcapError("mask_rle: masks must be [M,h,w] with h, w in 1..64, got %s" % (tuple(masks.shape),))
+    M, h, w = masks.shape
+    if H < 1 or W < 1 or max(H, W) > 1 << 24 or H * W >= 1 << 31 or M > 65535 or M * (H * W + 1) >= 1 << 31:
+        raise _lib.DcapError("mask_rle: an image of at least 1 x 1 and below 2^31 pixels, at most 65535 detections and M * (H * W + 1) below 2^31, "
+                             "got %d x %d, M %d" % (H, W, M))
+    if capacity is None:
+        capacity = mask_rle_capacity(M, H, W)
+    if isinstance(capacity, bool) or int(capacity) != capacity or not 0 <= capacity < (1 << 31) - M - 1:
+        raise _lib.DcapError("mask_rle: capacity must be an integer in 0..2^31 - M - 2, got %r" % (capacity,))
+    for name, t, dtype, shape in (("masks", masks, torch.float32, (M, h, w)), ("boxes", boxes, torch.int32, (M, 4))):
+        if t.dtype != dtype:
+            raise _lib.DcapError("mask_rle: %s must be %s, got %s" % (name, dtype, t.dtype))
+        if tuple(t.shape) != shape or not t.is_contiguous():
+            raise _lib.DcapError("mask_rle: %s must be a contiguous %s tensor, got shape %s strides %s"
+                                 % (name, list(shape), tuple(t.shape), tuple(t.stride())))
+    _on_gpu("mask_rle", masks=masks, boxes=boxes)
+    return MaskRle(masks, boxes, H, W, capacity)
 
 
 def _caption_rows(fn, name, t, rows=None, dim=2):

@@ -1393,6 +1393,42 @@ typedef struct {
 size_t dc_mask_paste_u8_workspace_bytes(const dc_mask_paste_desc* d);
 int    dc_mask_paste_u8(const dc_mask_paste_desc* d, void* workspace, size_t workspace_bytes, void* stream);
 
+/* dc_mask_rle_u32: the planes dc_mask_paste_u8 would write for the M detections of one image, as COCO's uncompressed run-length
+ * encoding, built on the device without the planes: no [M][H][W] buffer is allocated, written or read.  masks, boxes, h, w, H, W and
+ * M are dc_mask_paste_u8's, with its limits.
+ * The encoding of one [H][W] plane.  Pixels are read column-major, pixel (y, x) at index i = x * H + y; bit[-1] = 0.  With
+ * t_0 < t_1 < ... < t_{T-1} the indices at which bit[i] != bit[i-1], the counts are the T + 1 differences of
+ * [0, t_0, ..., t_{T-1}, H * W]: runs of zeros and ones in turn, starting with zeros, so counts[0] = 0 exactly when pixel (0, 0) is
+ * set.  The last entry is the final run, whatever its value: a plane whose last pixel is set ends on its run of ones, and NO
+ * zero-length run of zeros is appended.  A plane of zeros is [H * W]; sum(counts) = H * W always.  (mask_rle.py encodes by the same
+ * rule on the host.)
+ * Outputs: offsets int32 [M + 1] and counts uint32 [capacity], both in device memory.  counts[offsets[m] .. offsets[m+1] - 1] is
+ * detection m's encoding.  offsets is exact whatever capacity is, and offsets[M] is the number of words the encodings need: entries at
+ * flat indices below min(offsets[M], capacity) are written, nothing at or beyond capacity is touched, and a caller that finds
+ * offsets[M] > capacity calls again with that capacity.  A box with non-positive area, or one that leaves the image, encodes as
+ * [H * W].  M = 0 writes offsets[0] = 0 and nothing else.
+ * The work: dc_mask_paste_u8's bytescale, coefficient and horizontal launches as they are; then one wave per (detection, box column)
+ * walks 64 rows a step, takes the transitions from a ballot of the thresholded bits and counts them; a prefix sum over the columns
+ * of each detection and one over the detections give every transition its slot; the walk runs again and stores the positions; a
+ * last launch differences them.  Integer work without atomics: the same bytes on every run.  Seven launches whatever M is.
+ * The scratch memory travels in the descriptor: workspace (16-byte aligned) of at least dc_mask_rle_workspace_bytes(d) bytes, which
+ * depends on M, h, w, H, W and capacity -- dc_mask_paste_u8's three regions, one int per (detection, column 0..W), one per
+ * detection and capacity words of positions.  DC_EWORKSPACE when it is null (with M > 0), too small or misaligned.
+ * DC_EINVAL: dc_mask_paste_u8's cases, a null offsets, a null counts with capacity > 0, a negative capacity, offsets or counts off
+ * a 4-byte boundary, and M * (H * W + 1) >= 2^31 (the int32 offsets could not hold the worst case). */
+typedef struct {
+    int M, h, w, H, W, capacity;
+    const float* masks;
+    const int32_t* boxes;
+    int32_t* offsets;
+    uint32_t* counts;
+    void* workspace;
+    size_t workspace_bytes;
+} dc_mask_rle_desc;
+
+size_t dc_mask_rle_workspace_bytes(const dc_mask_rle_desc* d);
+int    dc_mask_rle_u32(const dc_mask_rle_desc* d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

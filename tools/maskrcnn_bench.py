@@ -17,8 +17,15 @@
    "device" alternating call by call in one process, for postprocess="device" with and without device_masks.  device_refine_wins:
    host - device > the run-to-run spread of the host mode's repeats.  There is no threshold: the mode is opt-in.
 
+5. --rle (alone: --rle --no-kernels --no-detect): what detect(mask_format="rle") buys a caller who wants the masks on the host.  detect()
+   with postprocess="device" and the dense [N,H,W] bytes copied down against mask_format="rle" (the encodings built on the device, two
+   small copies), for refine="host" and "device", the four alternating call by call in one process; the bytes each mode copies; the
+   run counts of the detections and ops.mask_rle's default capacity; and ops.mask_rle's seven launches beside ops.mask_paste's four on
+   the model's own detections.  rle_wins: dense - rle > the run-to-run spread of the dense mode's repeats.
+
     python tools/maskrcnn_bench.py --out profiles/maskrcnn_bench.json
     python tools/maskrcnn_bench.py --refine --no-kernels --no-detect --out profiles/maskrcnn_refine_bench.json
+    python tools/maskrcnn_bench.py --rle --no-kernels --no-detect --out profiles/maskrcnn_rle_bench.json
 """
 import argparse
 import json
@@ -234,6 +241,56 @@ def refine(own, rows, model, img):
                         "repeats" % (own.detect_calls, own.repeats), **s)
 
 
+def rle(own, rows, model, img):
+    """Leg 5: detect() with dense masks copied to the host against mask_format="rle", both with postprocess="device", for refine="host"
+    and "device", the four modes alternating; then ops.mask_rle's launches beside ops.mask_paste's on the model's own detections."""
+    from image_captioning_amd import mask_rle, ops
+    H, W = img.shape[:2]
+    modes = {"%s/%s" % (rf, fmt): dict(postprocess="device", refine=rf, mask_format=fmt) for rf in ("host", "device") for fmt in ("dense", "rle")}
+    res = {}
+    for k, kw in modes.items():
+        for _ in range(own.detect_warmup):
+            res[k] = model.detect([img], **kw)[0]
+    same = {rf: bool(len(res[rf + "/rle"]["masks"]) == len(res[rf + "/dense"]["rois"]) and
+                     all(np.array_equal(mask_rle.decode(r), res[rf + "/dense"]["masks"][:, :, i]) for i, r in enumerate(res[rf + "/rle"]["masks"])))
+            for rf in ("host", "device")}
+    wall = wall_alternating(model, img, modes, own)
+    cfg = model.config
+    for rf in ("host", "device"):
+        dense, runs = summary(wall[rf + "/dense"]), summary(wall[rf + "/rle"])
+        n = int(len(res[rf + "/dense"]["rois"]))
+        rows_encoded = int(cfg.DETECTION_MAX_INSTANCES) if rf == "device" else n
+        words = [int(len(r["counts"])) for r in res[rf + "/rle"]["masks"]]
+        capacity = ops.mask_rle_capacity(rows_encoded, H, W)
+        for fmt, s in (("dense", dense), ("rle", runs)):
+            copied = n * H * W if fmt == "dense" else 4 * (rows_encoded + 1 + capacity)
+            emit(rows, what="detect_rle", refine=rf, postprocess="device", mask_format=fmt, image=[int(H), int(W)], molded=own.side, proposals=own.proposals,
+                 classes=own.classes, detections=n, mask_bytes_copied=int(copied), rle_decodes_to_the_dense_planes=same[rf],
+                 rle_wins=bool(dense["ms"] - runs["ms"] > dense["spread_ms"]), conv_math=model.conv_math_name, stage4_blocks=own.stage4_blocks,
+                 timing="wall clock around each detect() call, the four modes alternating call by call, median of %d calls per repeat, median of %d "
+                        "repeats" % (own.detect_calls, own.repeats), **s)
+        emit(rows, what="rle_run_counts", refine=rf, detections=n, rows_encoded=rows_encoded, words_of_the_detections=int(sum(words)),
+             words_with_padded_rows=int(sum(words) + rows_encoded - n), most_words_one_detection=int(max(words) if words else 0),
+             median_words_one_detection=float(np.median(words)) if words else 0.0, default_capacity_words=int(capacity),
+             mask_pixels=int(sum(mask_rle.area(r) for r in res[rf + "/rle"]["masks"])))
+    # the launches alone, on the class masks and boxes of a refine="device" call's detections
+    model.detect([img], postprocess="device", refine="device", device_masks=True)
+    n = len(model.last_detections[0]["rois"])
+    masks = model.last_class_masks[0].clone()
+    boxes = torch.tensor(model.last_detections[0]["rois"], dtype=torch.int32, device=model.device)
+    full = torch.empty((n, H, W), dtype=torch.uint8, device=model.device)
+    capacity = ops.mask_rle_capacity(n, H, W)
+    first = ops.mask_rle(masks, boxes, H, W)
+    need = int(first.offsets[-1].item())
+    r = timed_alternating({"mask_paste": lambda: ops.mask_paste(masks, boxes, H, W, out=full), "mask_rle": lambda: ops.mask_rle(masks, boxes, H, W)},
+                          max(own.launches // 4, 10), own.repeats, own.warmup)
+    note = ("device events around each call (mask_rle allocates its pack inside), median of %d calls per repeat, the two alternating call by call, median of "
+            "%d repeats" % (max(own.launches // 4, 10), own.repeats))
+    emit(rows, what="kernel", kernel="dc_mask_paste_u8", M=n, H=int(H), W=int(W), bytes_written=int(n * H * W), timing=note, **summary(r["mask_paste"]))
+    emit(rows, what="kernel", kernel="dc_mask_rle_u32", M=n, H=int(H), W=int(W), launches_per_call=7, words_needed=need, capacity_words=int(capacity),
+         bytes_written=int(4 * (n + 1 + min(need, capacity))), timing=note, **summary(r["mask_rle"]))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--side", type=int, default=1024)
@@ -250,17 +307,20 @@ def main():
     ap.add_argument("--no-detect", action="store_true")
     ap.add_argument("--no-kernels", action="store_true")
     ap.add_argument("--refine", action="store_true", help="leg 4: detect(refine='host') against refine='device'")
+    ap.add_argument("--rle", action="store_true", help="leg 5: detect(mask_format='rle') against dense masks copied to the host")
     ap.add_argument("--out", default=None)
     own = ap.parse_args()
     torch.cuda.set_device(0)
     rows = []
     if not own.no_kernels:
         kernels(own, rows)
-    model, img = build_model(own) if own.refine or not own.no_detect else (None, None)
+    model, img = build_model(own) if own.refine or own.rle or not own.no_detect else (None, None)
     if not own.no_detect:
         detect(own, rows, model, img)
     if own.refine:
         refine(own, rows, model, img)
+    if own.rle:
+        rle(own, rows, model, img)
     if own.out:
         os.makedirs(os.path.dirname(own.out) or ".", exist_ok=True)
         with open(own.out, "w") as f:
