@@ -14,6 +14,8 @@ detect(refine="device") replaces the three middle steps by ops.refine_detections
 results come down) and runs the mask head on DETECTION_MAX_INSTANCES rows per image.
 detect(mask_format="rle") returns the masks as COCO run-length encodings (mask_rle.py); with postprocess="device" ops.mask_rle builds
 them from the [M,28,28] masks and the boxes in place of ops.mask_paste, and the [M,H,W] bytes never exist.
+evaluate() scores detect()'s results against annotated images -- utils.compute_ap's rule (detection_eval.py) on mask IoU of the
+run-length encodings or on box IoU --; backend="device" keeps the encodings on the device (ops.rle_iou / ops.box_iou, ops.detection_ap).
 
 Everything below the heads is DenseImageCapRCNN's, unchanged: MaskRCNN sub-classes it and puts DetectTop where the caption model sits.
 detect() starts with the parent's inference front (_proposal_features: mold, encoder pass, proposals, RoIAlign(7)); save_weights is the
@@ -450,15 +452,9 @@ class MaskRCNN(DenseImageCapRCNN):
 
     def _detect_refined_on_device(self, p, images, consts, proposals, z, d, postprocess, device_masks, rle=False):
         """detect(refine="device") behind the heads: nothing here reads the device before pack_detections."""
-        cfg, top, (B, K) = self.config, self.caption_model, proposals.shape[:2]
-        M, P = int(cfg.DETECTION_MAX_INSTANCES), top.mask_pool
-        ids, scores, deltas = ops.class_select(z, d, class_ids=self._buf("sel_ids", (B * K,), torch.int32), scores=self._buf("sel_scores", (B * K,)),
-                                               deltas_out=self._buf("sel_deltas", (B * K, 4)))
-        self.last_selection = (proposals, ids.view(B, K), scores.view(B, K), deltas.view(B, K, 4))
-        count, boxes, rois, norm, cls, sc, keep = ops.refine_detections(*self.last_selection, consts, cfg.BBOX_STD_DEV, cfg.DETECTION_MIN_CONFIDENCE,
-                                                                        cfg.DETECTION_NMS_THRESHOLD, M, cfg.IMAGE_SHAPE[:2])
-        x = ops.roi_align_pyramid(list(p.P), norm, float(p.H * p.W), P, out=self._buf("mask_rois_fixed", (B, M, P, P, 256)))
-        masks = top.class_masks(x.view(B * M, P, P, 256), cls.view(B * M), out=self._buf("class_masks_fixed", (B * M, 2 * P, 2 * P))).view(B, M, 2 * P, 2 * P)
+        B, P = proposals.shape[0], self.caption_model.mask_pool
+        count, boxes, rois, norm, cls, sc, keep = self._refine_on_device(consts, proposals, z, d)
+        masks = self._class_masks_fixed(p, norm, cls)
         full = runs = None
         if postprocess == "device" and rle:              # padded rows carry zero boxes: they encode as [H * W] and are dropped below
             runs = {b: ops.mask_rle(masks[b], rois[b], *images[b].shape[:2]) for b in range(B)}
@@ -490,3 +486,212 @@ class MaskRCNN(DenseImageCapRCNN):
                 results[b]["masks"] = full[b][:n[b]].cpu().numpy().transpose(1, 2, 0)
         self.last_class_masks = [masks[b, :n[b]] for b in range(B)]          # (device views of a buffer the next call reuses)
         return results
+
+    def _refine_on_device(self, consts, proposals, z, d):
+        """class_select -> ops.refine_detections: its seven device tensors of DETECTION_MAX_INSTANCES rows per image."""
+        cfg, (B, K) = self.config, proposals.shape[:2]
+        ids, scores, deltas = ops.class_select(z, d, class_ids=self._buf("sel_ids", (B * K,), torch.int32), scores=self._buf("sel_scores", (B * K,)),
+                                               deltas_out=self._buf("sel_deltas", (B * K, 4)))
+        self.last_selection = (proposals, ids.view(B, K), scores.view(B, K), deltas.view(B, K, 4))
+        return ops.refine_detections(*self.last_selection, consts, cfg.BBOX_STD_DEV, cfg.DETECTION_MIN_CONFIDENCE, cfg.DETECTION_NMS_THRESHOLD,
+                                     int(cfg.DETECTION_MAX_INSTANCES), cfg.IMAGE_SHAPE[:2])
+
+    def _class_masks_fixed(self, p, norm, cls):
+        """The mask head on every row of ops.refine_detections' result: float32 [B,M,2P,2P] on the device."""
+        top, (B, M) = self.caption_model, cls.shape
+        P = top.mask_pool
+        x = ops.roi_align_pyramid(list(p.P), norm, float(p.H * p.W), P, out=self._buf("mask_rois_fixed", (B, M, P, P, 256)))
+        return top.class_masks(x.view(B * M, P, P, 256), cls.view(B * M), out=self._buf("class_masks_fixed", (B * M, 2 * P, 2 * P))).view(B, M, 2 * P, 2 * P)
+
+    # ---- evaluation ----------------------------------------------------------------------------
+    EVAL_RLE_CAPACITY = None       # evaluate(backend="device"): ops.mask_rle's first capacity in words; None: ops.mask_rle_capacity's
+
+    @staticmethod
+    def _eval_ground_truth(b, image, gt, overlap):
+        """One image's ground truth, checked: (class_ids int32 [G], rles: list of G encodings or None, rois int32 [G,4], iscrowd uint8 [G])."""
+        who = "evaluate: ground_truth[%d]" % b
+        H, W = (int(v) for v in image.shape[:2])
+        class_ids = np.asarray(gt["class_ids"]).reshape(-1)
+        if class_ids.size and class_ids.dtype.kind not in "iu":
+            raise ValueError("%s: class_ids must be integers, got %s" % (who, class_ids.dtype))
+        G = class_ids.size
+        if G > ops.EVAL_MAX:
+            raise ValueError("%s: %d ground truths: more than %d ground truths in an image are not available" % (who, G, ops.EVAL_MAX))
+        rles, masks = None, gt.get("masks")
+        if masks is not None and not isinstance(masks, (list, tuple)):
+            masks = np.asarray(masks)
+            if masks.ndim != 3 or masks.dtype not in (np.dtype(bool), np.dtype(np.uint8)) or masks.shape[2] != G:
+                raise ValueError("%s: dense masks must be a bool or uint8 [H,W,%d] array, got %s %s" % (who, G, masks.dtype, masks.shape))
+            if tuple(masks.shape[:2]) != (H, W):
+                raise ValueError("%s: the masks are %d x %d, the image %d x %d: a ground-truth mask of another size than its image is not "
+                                 "available" % (who, masks.shape[0], masks.shape[1], H, W))
+            rles = [mask_rle.encode(masks[:, :, g]) for g in range(G)]
+        elif masks is not None:
+            if len(masks) != G:
+                raise ValueError("%s: %d masks for %d class ids" % (who, len(masks), G))
+            for r in masks:
+                if [int(v) for v in r["size"]] != [H, W]:
+                    raise ValueError("%s: a mask is %s, the image %d x %d: a ground-truth mask of another size than its image is not "
+                                     "available" % (who, list(r["size"]), H, W))
+            rles = [{"size": [H, W], "counts": mask_rle._size_and_counts(r, "iou")[2].astype(np.uint32)} for r in masks]
+        if overlap == "mask" and rles is None:
+            raise ValueError("%s: overlap='mask' needs \"masks\"" % who)
+        if gt.get("rois") is not None:
+            rois = np.asarray(gt["rois"]).astype(np.int32).reshape(-1, 4)
+            if rois.shape[0] != G:
+                raise ValueError("%s: %d rois for %d class ids" % (who, rois.shape[0], G))
+        elif rles is not None:
+            rois = np.stack([mask_rle.to_bbox(r) for r in rles]).astype(np.int32) if G else np.zeros((0, 4), np.int32)
+        else:
+            raise ValueError("%s: overlap='box' needs \"rois\" or \"masks\" to take them from" % who)
+        crowd = np.zeros(G, np.uint8) if gt.get("iscrowd") is None else (np.asarray(gt["iscrowd"]).reshape(-1) != 0).astype(np.uint8)
+        if crowd.size != G:
+            raise ValueError("%s: %d iscrowd flags for %d class ids" % (who, crowd.size, G))
+        if overlap == "box" and crowd.any():
+            raise ValueError("%s: iscrowd changes the mask IoU only: crowd flags with overlap='box' are not available" % who)
+        return class_ids.astype(np.int32), rles, rois, crowd
+
+    def evaluate(self, images, ground_truth, overlap="mask", iou_thresholds=None, backend="device", mold="host", verbose=0, **other):
+        """Average precision of detect()'s results against annotated images: utils.compute_ap's rule (detection_eval.py states it and
+        its two tie rules) on mask IoU (overlap="mask": pycocotools' rleIou on run-length encodings, mask_rle.iou) or box IoU
+        (overlap="box": utils.compute_overlaps), at every threshold of iou_thresholds (default detection_eval.DEFAULT_THRESHOLDS, 0.5 to
+        0.95; at most 16).  ground_truth[b]: {"class_ids": int [G]; "masks": dense [H,W,G] bool / uint8 or a list of G RLE dictionaries,
+        in the original image; "rois": int32 [G,4], optional with masks (mask_rle.to_bbox derives them), needed for overlap="box"
+        without masks; "iscrowd": optional [G], changes the mask IoU only (I / a_d)}.
+        Returns {"AP": float64 [B,T], NaN for an image without ground truth; "mAP": float64 [T], the mean over the images that have
+        ground truth; "thresholds"; "n_det", "n_gt": int32 [B]; "skipped": the images without ground truth; "pred_match": per image
+        int32 [T,n_det] in rank order, "gt_match": per image int32 [T,n_gt], "order": per image int32 [n_det]
+        (detection_eval.ap_from_overlaps)}.  The detections are those of detect(refine="device", postprocess="device") either way.
+        backend="host": detect(mask_format="rle") as it stands, then mask_rle.iou or utils.compute_overlaps and
+        detection_eval.ap_from_overlaps in NumPy.  backend="device": the same path up to ops.mask_rle per image, whose pack stays on
+        the device; the ground truth (encodings, boxes, classes, thresholds) goes up in ONE packed upload; ops.rle_iou per image or
+        ops.box_iou, then ops.detection_ap; ONE copy brings AP, matches, counts and status down, and nothing reads the device before
+        it.  Only an image whose encodings outgrow ops.mask_rle's capacity costs a second launch, and the batch a second copy.  Both
+        backends return the same dictionary, bit for bit.
+        Not available: device_masks, a ground-truth mask of another size than its image, more than 1024 ground truths or detections an
+        image (and, refused where the model is built, compute_dtype="bf16" and GPU_COUNT > 1).  Out of scope: COCO's 101-point
+        interpolation, area ranges, maxDets and crowd regions as "ignore" in the matching."""
+        from . import detection_eval
+        if "device_masks" in other:
+            raise ValueError("evaluate: device_masks is not available: the masks are scored as run-length encodings and never returned")
+        if other:
+            raise TypeError("evaluate() got an unexpected keyword argument %r" % sorted(other)[0])
+        if overlap not in ("mask", "box"):
+            raise ValueError("overlap must be 'mask' or 'box', got %r" % (overlap,))
+        if backend not in ("host", "device"):
+            raise ValueError("backend must be 'host' or 'device', got %r" % (backend,))
+        cfg, B = self.config, len(images)
+        M = int(cfg.DETECTION_MAX_INSTANCES)
+        if M > ops.EVAL_MAX:
+            raise ValueError("evaluate: DETECTION_MAX_INSTANCES = %d: more than %d detections in an image are not available" % (M, ops.EVAL_MAX))
+        if len(ground_truth) != B:
+            raise ValueError("evaluate: %d images but %d ground-truth entries" % (B, len(ground_truth)))
+        thresholds = np.ascontiguousarray(detection_eval.DEFAULT_THRESHOLDS if iou_thresholds is None else iou_thresholds, np.float64).reshape(-1)
+        T = len(thresholds)
+        if not 1 <= T <= detection_eval.MAX_THRESHOLDS:
+            raise ValueError("evaluate: 1 to %d IoU thresholds, got %d" % (detection_eval.MAX_THRESHOLDS, T))
+        utils.check_mold(mold, cfg.IMAGE_PADDING)
+        gts = [self._eval_ground_truth(b, images[b], ground_truth[b], overlap) for b in range(B)]
+        n_gt = np.array([len(g[0]) for g in gts], np.int32)
+        if backend == "host":
+            found = self.detect(images, verbose=verbose, postprocess="device", mold=mold, refine="device", mask_format="rle")
+            n_det = np.array([len(r["rois"]) for r in found], np.int32)
+            ap, pred_match, gt_match, order = np.full((B, T), np.nan), [], [], []
+            for b, (r, (gt_ids, rles, rois, crowd)) in enumerate(zip(found, gts)):
+                if overlap == "mask":
+                    ov = mask_rle.iou(r["masks"], rles, crowd)
+                else:
+                    with np.errstate(divide="ignore", invalid="ignore"):
+                        ov = utils.compute_overlaps(r["rois"].astype(np.int32).reshape(-1, 4), rois)
+                ap[b], pm, gm, od = detection_eval.ap_from_overlaps(ov, gt_ids, r["class_ids"], r["scores"], thresholds)
+                pred_match.append(pm)
+                gt_match.append(gm)
+                order.append(od.astype(np.int32))
+        else:
+            n_det, ap, pred_match, gt_match, order = self._evaluate_on_device(images, gts, n_gt, overlap, thresholds, mold, verbose)
+        have = n_gt > 0
+        return {"AP": ap, "mAP": ap[have].mean(axis=0) if have.any() else np.full(T, np.nan), "thresholds": thresholds.copy(), "n_det": n_det,
+                "n_gt": n_gt, "skipped": int((~have).sum()), "pred_match": pred_match, "gt_match": gt_match, "order": order}
+
+    def _evaluate_on_device(self, images, gts, n_gt, overlap, thresholds, mold, verbose):
+        """evaluate(backend="device") behind the checks: (n_det [B], AP [B,T], pred_match, gt_match, order) on the host after ONE copy."""
+        cfg, top, B, T = self.config, self.caption_model, len(images), len(thresholds)
+        M, Gmax, masked = int(cfg.DETECTION_MAX_INSTANCES), int(n_gt.max()) if B else 0, overlap == "mask"
+        if verbose:
+            print("Evaluating %d images" % B)
+        # ONE packed upload of int32 words: thresholds (float64 bits), boxes [B,Gmax,4] on a 16-byte boundary, n_gt [B], classes
+        # [B,Gmax], then per image with ground truth its offsets [G+1], counts and crowd flags (bytes, padded to words)
+        head = [np.zeros((2 * T + 3) // 4 * 4, np.int32), np.zeros((B, Gmax, 4), np.int32), n_gt, np.zeros((B, Gmax), np.int32)]
+        head[0][:2 * T] = thresholds.view(np.int32)
+        per_image, words = {}, []
+        for b, (gt_ids, rles, rois, crowd) in enumerate(gts):
+            G = len(gt_ids)
+            head[1][b, :G], head[3][b, :G] = rois, gt_ids
+            if masked and G:
+                lengths = [len(r["counts"]) for r in rles]
+                flags = np.zeros((G + 3) // 4 * 4, np.uint8)
+                flags[:G] = crowd
+                per_image[b] = (G, int(np.sum(lengths)))
+                words += [np.cumsum([0] + lengths).astype(np.int32), np.concatenate([r["counts"] for r in rles]).astype(np.uint32).view(np.int32),
+                          flags.view(np.int32)]
+        parts = [a.reshape(-1) for a in head] + words
+        up_host = np.concatenate(parts) if parts else np.zeros(0, np.int32)
+        p, images, windows, consts, proposals, feats = self._proposal_features(images, mold, want_consts=True)
+        up = torch.from_numpy(up_host).to(self.device)
+        cuts = np.cumsum([0] + [a.size for a in parts])
+        thr_d = up[:2 * T].view(torch.float64)
+        gt_boxes, n_gt_d, gt_cls = up[cuts[1]:cuts[2]].view(B, Gmax, 4), up[cuts[2]:cuts[3]], up[cuts[3]:cuts[4]].view(B, Gmax)
+        K = proposals.shape[1]
+        z, d = top.heads(feats.view(B * K, cfg.POOL_SIZE, cfg.POOL_SIZE, 256))
+        self.last_heads = (z, d)
+        count, boxes, rois, norm, cls, sc, keep = self._refine_on_device(consts, proposals, z, d)
+        # everything that comes down, in one int32 buffer: AP (float64 bits), pred_match, gt_match, order, counts, status
+        sizes = [2 * B * T, B * T * M, B * T * Gmax, B * M, B, 4 * B]
+        down = torch.zeros((int(np.sum(sizes)),), dtype=torch.int32, device=self.device)
+        dcut = np.cumsum([0] + sizes)
+        ap_d, pm_d, gm_d = down[:dcut[1]].view(torch.float64).view(B, T), down[dcut[1]:dcut[2]].view(B, T, M), down[dcut[2]:dcut[3]].view(B, T, Gmax)
+        od_d, cnt_d, st_d = down[dcut[3]:dcut[4]].view(B, M), down[dcut[4]:dcut[5]], down[dcut[5]:].view(B, 4)
+        overlaps = torch.empty((B, M, Gmax), dtype=torch.float64, device=self.device)
+        runs = {}
+
+        def mask_overlaps(b, at):
+            G, n_words = per_image[b]
+            offs_g, counts_g, crowd = up[at:at + G + 1], up[at + G + 1:at + G + 1 + n_words], up[at + G + 1 + n_words:at + G + 1 + n_words + (G + 3) // 4]
+            ops.rle_iou(runs[b].offsets, runs[b].counts, offs_g, counts_g, *images[b].shape[:2], n_det=count[b:b + 1],
+                        iscrowd=crowd.view(torch.uint8)[:G], out=overlaps[b, :, :G], status=st_d[b])
+
+        def score():
+            cnt_d.copy_(count)
+            ops.detection_ap(overlaps, count, n_gt_d, cls, sc, gt_cls, thr_d, ap=ap_d, pred_match=pm_d, gt_match=gm_d, order=od_d)
+            return down.cpu().numpy()                    # the ONE device-to-host copy
+
+        where = {}
+        if masked:
+            masks = self._class_masks_fixed(p, norm, cls)
+            at = int(cuts[4])
+            for b in sorted(per_image):
+                H0, W0 = images[b].shape[:2]
+                runs[b] = ops.mask_rle(masks[b], rois[b], H0, W0, capacity=self.EVAL_RLE_CAPACITY)
+                where[b] = at
+                mask_overlaps(b, at)
+                at += per_image[b][0] + 1 + per_image[b][1] + (per_image[b][0] + 3) // 4
+        else:
+            ops.box_iou(rois, gt_boxes, out=overlaps)
+        host = score()
+        status = host[dcut[5]:].reshape(B, 4)
+        if status[:, 1:3].any():
+            raise ops._lib.DcapError("evaluate: ops.rle_iou reports a ground-truth encoding it could not read (status %s)" % status.tolist())
+        short = [b for b in range(B) if status[b, 0]]
+        for b in short:                                  # the detections' encodings outgrew the capacity: once more with what they need
+            runs[b].relaunch(int(status[b, 0]))
+            mask_overlaps(b, where[b])
+        if short:
+            host = score()
+            if host[dcut[5]:].reshape(B, 4)[:, :3].any():
+                raise ops._lib.DcapError("evaluate: the second ops.mask_rle run still does not fit (status %s)" % host[dcut[5]:].reshape(B, 4).tolist())
+        self.last_eval_relaunched = short
+        n_det = host[dcut[4]:dcut[5]].copy()
+        ap = host[:dcut[1]].view(np.float64).reshape(B, T).copy()
+        pm, gm, od = host[dcut[1]:dcut[2]].reshape(B, T, M), host[dcut[2]:dcut[3]].reshape(B, T, Gmax), host[dcut[3]:dcut[4]].reshape(B, M)
+        return (n_det, ap, [pm[b, :, :n_det[b]].copy() for b in range(B)], [gm[b, :, :n_gt[b]].copy() for b in range(B)],
+                [od[b, :n_det[b]].copy() for b in range(B)])

@@ -9,7 +9,10 @@ whatever its value: a mask whose last pixel is set ends on its run of ones, no z
 
 The string form is pycocotools' rleToString / rleFrString: each count, from the fourth on minus the count two places before it, goes
 out in 5-bit groups, low group first, bit 0x20 saying that more follow, each group as chr(group + 48).  to_coco gives the
-{"size", "counts": str} entry of a COCO results file."""
+{"size", "counts": str} entry of a COCO results file.
+
+iou is pycocotools' rleIou on this form and to_bbox the box utils.extract_bboxes takes from the dense plane; ops.rle_iou
+(dc_rle_iou_f64, include/dcap.h) is held to iou bit for bit."""
 import numpy as np
 
 
@@ -106,3 +109,63 @@ def to_coco(rle):
     """{"size", "counts": array} -> {"size": [H, W], "counts": str}: the "segmentation" of a COCO results entry."""
     H, W, counts = _size_and_counts(rle, "to_coco")
     return {"size": [H, W], "counts": to_string(counts)}
+
+
+def _intersection(a, b):
+    """The pixels set in both of two encodings of one size: a two-pointer walk over the runs (lists of Python ints)."""
+    i = j = inter = 0
+    ca, cb = a[0], b[0]
+    while True:
+        c = ca if ca < cb else cb
+        if i & j & 1:
+            inter += c
+        ca -= c
+        cb -= c
+        if ca == 0:
+            i += 1
+            if i == len(a):
+                return inter
+            ca = a[i]
+        if cb == 0:
+            j += 1
+            if j == len(b):
+                return inter
+            cb = b[j]
+
+
+def iou(dt, gt, iscrowd=None):
+    """pycocotools' rleIou: float64 [len(dt), len(gt)] for two lists of {"size", "counts"} of ONE size.  The intersection I is an
+    exact integer, iou = I / (a_d + a_g - I) one float64 division; for a crowd gt (iscrowd[g] non-zero) iou = I / a_d; 0 where the
+    denominator is 0.  Lists whose masks differ in size and counts that do not sum to H * W are refused."""
+    sides = [_size_and_counts(r, "iou") for r in list(dt) + list(gt)]
+    if len({(H, W) for H, W, _ in sides}) > 1:
+        raise ValueError("mask_rle.iou: every mask must have one size, got %s" % sorted({(H, W) for H, W, _ in sides}))
+    crowd = np.zeros(len(gt), bool) if iscrowd is None else np.asarray(iscrowd).reshape(-1) != 0
+    if crowd.size != len(gt):
+        raise ValueError("mask_rle.iou: iscrowd must hold one flag per gt mask, got %d for %d" % (crowd.size, len(gt)))
+    runs = [[int(v) for v in c] for _, _, c in sides]
+    areas = [sum(r[1::2]) for r in runs]
+    D = len(dt)
+    out = np.zeros((D, len(gt)), np.float64)
+    for d in range(D):
+        for g in range(len(gt)):
+            inter = _intersection(runs[d], runs[D + g]) if areas[d] and areas[D + g] else 0
+            den = areas[d] if crowd[g] else areas[d] + areas[D + g] - inter
+            if den:
+                out[d, g] = np.float64(inter) / np.float64(den)
+    return out
+
+
+def to_bbox(rle):
+    """int32 [4] (y1, x1, y2, x2), the end exclusive: utils.extract_bboxes' box of the decoded plane, zeros for an empty mask."""
+    H, W, counts = _size_and_counts(rle, "to_bbox")
+    ends = np.cumsum(counts)
+    s, e = (ends - counts)[1::2], ends[1::2]
+    s, e = s[e > s], e[e > s]
+    if s.size == 0:
+        return np.zeros(4, np.int32)
+    last = e - 1
+    wraps = (s // H != last // H).any()                   # a run that leaves its column touches row H - 1 and row 0
+    y1 = 0 if wraps else int((s % H).min())
+    y2 = H if wraps else int((last % H).max()) + 1
+    return np.array([y1, int(s[0] // H), y2, int(last[-1] // H) + 1], np.int32)

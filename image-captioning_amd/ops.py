@@ -12,7 +12,7 @@ import torch
 
 from . import _lib
 from ._lib import (RpnTargetsDesc, PwChainDesc, ConvBf16Desc, AmsgradDesc, DetectionTargetsDesc, BnReluDesc, ConvDesc, ConvWgradBf16Desc, GemmBf16Desc, VocabCeDesc, ProposalDesc, RpnLossDesc, GemmDesc, LstmBwdDesc, LstmFwdDesc, RoialignDesc, RoiGroupsDesc,
-                   SoftmaxCeDesc, TagFocalDesc, VocabTop1Desc, VocabTopkDesc, VocabTop1Bf16Desc, VocabTopkBf16Desc, VocabSampleDesc, VocabSampleBf16Desc, BeamSelectDesc, BeamStepDesc, LstmStepDesc, RefineDesc, RefineDetDesc, ResizePadDesc, MaskHeadTailDesc, MaskPasteDesc, MaskRleDesc, check)
+                   SoftmaxCeDesc, TagFocalDesc, VocabTop1Desc, VocabTopkDesc, VocabTop1Bf16Desc, VocabTopkBf16Desc, VocabSampleDesc, VocabSampleBf16Desc, BeamSelectDesc, BeamStepDesc, LstmStepDesc, RefineDesc, RefineDetDesc, ResizePadDesc, MaskHeadTailDesc, MaskPasteDesc, MaskRleDesc, RleIouDesc, DetectionApDesc, check)
 
 
 def _stream():
@@ -1276,6 +1276,12 @@ class MaskRle(object):
         check(lib.dc_mask_rle_u32(C.byref(d), _stream()), "dc_mask_rle_u32")
         self.launches += 1
 
+    def relaunch(self, capacity):
+        """Run the entry again with `capacity` words (a caller that read offsets[M] itself, as MaskRCNN.evaluate does from ops.rle_iou's
+        status): pack, offsets and counts are new tensors afterwards."""
+        self.capacity = int(capacity)
+        self._launch()
+
     def rles(self, host=None):
         """The M encodings as a list of {"size": [H, W], "counts": uint32 ndarray}.  host: this object's pack as an int32 host array,
         where the caller has copied it already; otherwise the pack is copied here (the one device-to-host copy).  When the
@@ -1322,6 +1328,145 @@ def mask_rle(masks, boxes, H, W, capacity=None):
                                  % (name, list(shape), tuple(t.shape), tuple(t.stride())))
     _on_gpu("mask_rle", masks=masks, boxes=boxes)
     return MaskRle(masks, boxes, H, W, capacity)
+
+
+EVAL_MAX = 1024      # include/dcap.h, dc_rle_iou_f64 / dc_box_iou_f64 / dc_detection_ap_f64: masks, boxes or predictions per set
+
+
+def _eval_tensors(fn, specs):
+    """(name, tensor or None, dtype, shape) rows: a given tensor is a contiguous device tensor of that dtype and shape."""
+    given = {}
+    for name, t, dtype, shape in specs:
+        if t is None:
+            continue
+        if t.dtype != dtype:
+            raise _lib.DcapError("%s: %s must be %s, got %s" % (fn, name, dtype, t.dtype))
+        if tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+            raise _lib.DcapError("%s: %s must be a contiguous %s tensor, got shape %s strides %s" % (fn, name, list(shape), tuple(t.shape), tuple(t.stride())))
+        given[name] = t
+    _on_gpu(fn, **given)
+
+
+def _eval_rows(fn, name, t, rows, cols):
+    """An IoU matrix given as `out`: float64 [..., rows, cols] on the device, unit stride along the columns, dense above the rows.
+    Returns the row stride."""
+    if t.dtype != torch.float64 or tuple(t.shape[-2:]) != (rows, cols):
+        raise _lib.DcapError("%s: %s must be a float64 [..., %d, %d] tensor, got %s %s" % (fn, name, rows, cols, t.dtype, tuple(t.shape)))
+    ld = t.stride(-2) if rows > 1 else max(cols, 1)
+    if rows * cols and ((cols > 1 and t.stride(-1) != 1) or ld < cols or (t.dim() == 3 and t.shape[0] > 1 and t.stride(0) != rows * ld)):
+        raise _lib.DcapError("%s: %s needs unit stride along its columns and images one behind the other, got strides %s" % (fn, name, tuple(t.stride())))
+    _on_gpu(fn, **{name: t})
+    return int(ld)
+
+
+def rle_iou(offsets_d, counts_d, offsets_g, counts_g, H, W, n_det=None, iscrowd=None, out=None, status=None):
+    """pycocotools' rleIou on the device (dc_rle_iou_f64; the host statement: mask_rle.iou): two packed sets of run-length encodings as
+    ops.mask_rle leaves them -- offsets int32 [D+1] / [G+1] and counts int32 (uint32 bits) [capacity] -- of masks of one size H x W.
+    n_det: int32 [1] on the device, rows at or beyond it are 0; iscrowd: uint8 [G] on the device.  Returns (iou float64 [D,G], inter int32
+    [D,G], area int32 [D+G], status int32 [4]) on the device: `out` (a float64 [D,G] view with any row stride) and `status` are used
+    when given.  status[0] / status[1] non-zero: that set needs so many words, everything is NaN / -1 and the caller reruns ops.mask_rle;
+    status[2]: masks whose counts do not sum to H * W (their row or column is NaN).  With D = 0 or G = 0 only status is computed (area
+    is -1).  No host synchronisation.  Shapes and dtypes are checked before the library is loaded."""
+    fn = "rle_iou"
+    H, W = int(H), int(W)
+    if offsets_d.dim() != 1 or offsets_g.dim() != 1 or offsets_d.numel() < 1 or offsets_g.numel() < 1 or counts_d.dim() != 1 or counts_g.dim() != 1:
+        raise _lib.DcapError("rle_iou: offsets must be int32 [D+1] and [G+1] and counts one-dimensional, got %s, %s, %s, %s"
+                             % (tuple(offsets_d.shape), tuple(offsets_g.shape), tuple(counts_d.shape), tuple(counts_g.shape)))
+    D, G = offsets_d.numel() - 1, offsets_g.numel() - 1
+    if D > EVAL_MAX or G > EVAL_MAX or H < 1 or W < 1 or H * W >= 1 << 31 or max(counts_d.numel(), counts_g.numel()) >= 1 << 31:
+        raise _lib.DcapError("rle_iou: at most %d masks a set and an image of at least 1 x 1 and below 2^31 pixels, got D %d, G %d, %d x %d"
+                             % (EVAL_MAX, D, G, H, W))
+    _eval_tensors(fn, (("offsets_d", offsets_d, torch.int32, (D + 1,)), ("counts_d", counts_d, torch.int32, (counts_d.numel(),)),
+                       ("offsets_g", offsets_g, torch.int32, (G + 1,)), ("counts_g", counts_g, torch.int32, (counts_g.numel(),)),
+                       ("n_det", n_det, torch.int32, (1,)), ("iscrowd", iscrowd, torch.uint8, (G,)), ("status", status, torch.int32, (4,))))
+    dev = offsets_d.device
+    if out is None:
+        out = torch.empty((D, G), dtype=torch.float64, device=dev)
+    ld = _eval_rows(fn, "out", out, D, G)
+    if out.dim() != 2:
+        raise _lib.DcapError("rle_iou: out must be a [D,G] tensor, got shape %s" % (tuple(out.shape),))
+    if status is None:
+        status = torch.empty((4,), dtype=torch.int32, device=dev)
+    empty = D == 0 or G == 0
+    inter = torch.empty((D, ld), dtype=torch.int32, device=dev)[:, :G]            # (`out` may be a view with its own row stride)
+    area = torch.full((D + G,), -1, dtype=torch.int32, device=dev) if empty else torch.empty((D + G,), dtype=torch.int32, device=dev)
+    lib = _lib.load()
+    d = RleIouDesc()
+    d.D, d.G, d.H, d.W, d.capacity_d, d.capacity_g, d.ld = D, G, H, W, counts_d.numel(), counts_g.numel(), ld
+    d.offsets_d, d.offsets_g, d.status = offsets_d.data_ptr(), offsets_g.data_ptr(), status.data_ptr()
+    d.counts_d, d.counts_g = (counts_d.data_ptr() if counts_d.numel() else None), (counts_g.data_ptr() if counts_g.numel() else None)
+    d.n_det, d.iscrowd = (None if n_det is None else n_det.data_ptr()), (None if iscrowd is None or G == 0 else iscrowd.data_ptr())
+    if not empty:
+        d.iou, d.inter, d.area = out.data_ptr(), inter.data_ptr(), area.data_ptr()
+    ws, wsb = WORKSPACE.get(lib.dc_rle_iou_workspace_bytes(C.byref(d)), dev)
+    d.workspace, d.workspace_bytes = None if ws is None else ws.data_ptr(), wsb
+    check(lib.dc_rle_iou_f64(C.byref(d), _stream()), "dc_rle_iou_f64")
+    return out, inter, area, status
+
+
+def box_iou(boxes, gt_boxes, out=None):
+    """utils.compute_overlaps for B images in one launch (dc_box_iou_f64): boxes int32 [B,Dmax,4] and gt_boxes int32 [B,Gmax,4] as
+    (y1, x1, y2, x2) on the device -> float64 [B,Dmax,Gmax], every entry written (`out`: a view of that shape with any row stride).
+    NumPy's int32 formula in int64 with one float64 division; a zero union gives NaN as NumPy's 0 / 0 does.  No host synchronisation;
+    an empty result launches nothing."""
+    fn = "box_iou"
+    if boxes.dim() != 3 or gt_boxes.dim() != 3 or boxes.shape[2] != 4 or gt_boxes.shape[2] != 4 or boxes.shape[0] != gt_boxes.shape[0]:
+        raise _lib.DcapError("box_iou: boxes must be [B,Dmax,4] and gt_boxes [B,Gmax,4], got %s and %s" % (tuple(boxes.shape), tuple(gt_boxes.shape)))
+    B, Dmax, Gmax = int(boxes.shape[0]), int(boxes.shape[1]), int(gt_boxes.shape[1])
+    if B > 65535 or Dmax > EVAL_MAX or Gmax > EVAL_MAX:
+        raise _lib.DcapError("box_iou: at most 65535 images and %d boxes a set, got B %d, Dmax %d, Gmax %d" % (EVAL_MAX, B, Dmax, Gmax))
+    _eval_tensors(fn, (("boxes", boxes, torch.int32, (B, Dmax, 4)), ("gt_boxes", gt_boxes, torch.int32, (B, Gmax, 4))))
+    if out is None:
+        out = torch.empty((B, Dmax, Gmax), dtype=torch.float64, device=boxes.device)
+    ld = _eval_rows(fn, "out", out, Dmax, Gmax)
+    if out.dim() != 3 or out.shape[0] != B:
+        raise _lib.DcapError("box_iou: out must be a [%d,%d,%d] tensor, got shape %s" % (B, Dmax, Gmax, tuple(out.shape)))
+    if B * Dmax * Gmax == 0:
+        return out
+    lib = _lib.load()
+    check(lib.dc_box_iou_f64(_ptr(boxes), _ptr(gt_boxes), B, Dmax, Gmax, ld, _ptr(out), _stream()), "dc_box_iou_f64")
+    return out
+
+
+def detection_ap(overlaps, n_det, n_gt, pred_class, pred_score, gt_class, thresholds, ap=None, pred_match=None, gt_match=None, order=None):
+    """utils.compute_ap's matching and average precision on given IoU matrices, for B images and T thresholds in ONE launch
+    (dc_detection_ap_f64; the host statement and the rules: detection_eval.ap_from_overlaps).  overlaps float64 [B,Dmax,Gmax] (any row
+    stride); n_det, n_gt int32 [B] ON THE DEVICE: the block of an image that counts; pred_class int32 [B,Dmax], pred_score float32
+    [B,Dmax], gt_class int32 [B,Gmax]; thresholds float64 [T] on the device, T in 1..16.  Returns (ap float64 [B,T] -- NaN for an image
+    without ground truth --, pred_match int32 [B,T,Dmax], gt_match int32 [B,T,Gmax], order int32 [B,Dmax]), -1 behind the counts; the
+    four are allocated when not given.  No workspace, no host synchronisation; B = 0 launches nothing."""
+    fn = "detection_ap"
+    if overlaps.dim() != 3 or thresholds.dim() != 1:
+        raise _lib.DcapError("detection_ap: overlaps must be [B,Dmax,Gmax] and thresholds [T], got %s and %s" % (tuple(overlaps.shape), tuple(thresholds.shape)))
+    (B, Dmax, Gmax), T = (int(v) for v in overlaps.shape), int(thresholds.numel())
+    if B > 65535 or Dmax > EVAL_MAX or Gmax > EVAL_MAX or not 1 <= T <= 16:
+        raise _lib.DcapError("detection_ap: at most 65535 images, %d predictions and ground truths an image and 1..16 thresholds, got B %d, Dmax %d, "
+                             "Gmax %d, T %d" % (EVAL_MAX, B, Dmax, Gmax, T))
+    ld = _eval_rows(fn, "overlaps", overlaps, Dmax, Gmax)
+    dev = overlaps.device
+    made = {}
+    for name, t, dtype, shape in (("ap", ap, torch.float64, (B, T)), ("pred_match", pred_match, torch.int32, (B, T, Dmax)),
+                                  ("gt_match", gt_match, torch.int32, (B, T, Gmax)), ("order", order, torch.int32, (B, Dmax))):
+        made[name] = torch.empty(shape, dtype=dtype, device=dev) if t is None else t
+    ap, pred_match, gt_match, order = made["ap"], made["pred_match"], made["gt_match"], made["order"]
+    _eval_tensors(fn, (("n_det", n_det, torch.int32, (B,)), ("n_gt", n_gt, torch.int32, (B,)), ("pred_class", pred_class, torch.int32, (B, Dmax)),
+                       ("pred_score", pred_score, torch.float32, (B, Dmax)), ("gt_class", gt_class, torch.int32, (B, Gmax)),
+                       ("thresholds", thresholds, torch.float64, (T,)), ("ap", ap, torch.float64, (B, T)),
+                       ("pred_match", pred_match, torch.int32, (B, T, Dmax)), ("gt_match", gt_match, torch.int32, (B, T, Gmax)),
+                       ("order", order, torch.int32, (B, Dmax))))
+    for name, t in (("n_det", n_det), ("n_gt", n_gt), ("pred_class", pred_class), ("pred_score", pred_score), ("gt_class", gt_class)):
+        if t is None:
+            raise _lib.DcapError("detection_ap: %s is missing" % name)
+    if B == 0:
+        return ap, pred_match, gt_match, order
+    lib = _lib.load()
+    d = DetectionApDesc()
+    d.B, d.Dmax, d.Gmax, d.ld, d.T = B, Dmax, Gmax, ld, T
+    d.overlaps, d.n_det, d.n_gt, d.thresholds, d.ap = overlaps.data_ptr(), n_det.data_ptr(), n_gt.data_ptr(), thresholds.data_ptr(), ap.data_ptr()
+    d.pred_class, d.pred_score, d.gt_class = pred_class.data_ptr(), pred_score.data_ptr(), gt_class.data_ptr()
+    d.pred_match, d.gt_match, d.order = pred_match.data_ptr(), gt_match.data_ptr(), order.data_ptr()
+    check(lib.dc_detection_ap_f64(C.byref(d), _stream()), "dc_detection_ap_f64")
+    return ap, pred_match, gt_match, order
 
 
 def _caption_rows(fn, name, t, rows=None, dim=2):

@@ -1429,6 +1429,97 @@ typedef struct {
 size_t dc_mask_rle_workspace_bytes(const dc_mask_rle_desc* d);
 int    dc_mask_rle_u32(const dc_mask_rle_desc* d, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Scoring detections against ground truth (csrc/detect_eval.hip): the evaluation side of mask_rcnn/utils.py (compute_overlaps,
+ * compute_ap :568-633) and pycocotools' rleIou.  Integer and float64 work in a fixed order without atomics: the same bytes on every
+ * run.  The host statements they are held to, bit for bit: mask_rle.iou, utils.compute_overlaps, detection_eval.ap_from_overlaps.
+ * ------------------------------------------------------------------------------------------------ */
+
+/* dc_rle_iou_f64: mask IoU of D detections with G ground truths, both as packed run-length encodings in DEVICE memory, in the form
+ * dc_mask_rle_u32 writes: offsets_d int32 [D + 1] with counts_d uint32 [capacity_d], offsets_g int32 [G + 1] with counts_g uint32
+ * [capacity_g], every mask of the one size H x W.  n_det (optional, device): rows at or beyond n_det[0] are written as 0 without a
+ * walk (the rows behind an image's last detection under refine="device").  iscrowd (optional, device uint8 [G]): a non-zero flag
+ * makes column g the crowd IoU.
+ * Outputs: iou float64 [D][ld]; where non-null, inter int32 [D][ld], the intersections, and area int32 [D + G], the detections' areas
+ * then the ground truths'; status int32 [4].  With I the pixels set in both masks and a_d, a_g the areas, exact integers,
+ * iou = I / (a_d + a_g - I) as ONE float64 division, for a crowd column I / a_d, and 0 where the denominator is 0.
+ * status[0] / status[1]: where offsets_d[D] > capacity_d (offsets_g[G] > capacity_g) the words that set needs, else 0.  With either
+ * non-zero nothing at or beyond a capacity is read, every iou is NaN and every inter and area -1: the caller reruns dc_mask_rle_u32
+ * with that capacity.  status[2]: the masks whose counts do not sum to H W (or whose offsets are not increasing inside 0..capacity):
+ * such a mask's row or column is NaN (inter, area: -1).  status[3] = min(max(n_det[0], 0), D), the rows computed.
+ * The work: pass 1, one wave per mask of either set, scans the counts into run ends and the set pixels below each end, and takes the
+ * area and the first and last set index; pass 2, one wave per pair, is 0 at once where the two set-index ranges do not meet;
+ * otherwise the lanes take the shorter encoding's runs of ones 64 at a time and count the other mask's set pixels inside each by two
+ * binary searches in its run ends; a wave sum gives I.  Three launches; D = 0 or G = 0 launches the status write alone (area is not
+ * written then) and needs no workspace.
+ * The scratch memory travels in the descriptor: workspace (16-byte aligned) of at least dc_rle_iou_workspace_bytes bytes -- two words
+ * per count word of capacity_d + capacity_g and four per mask.  DC_EWORKSPACE when it is null, too small or misaligned.
+ * DC_EINVAL: a null descriptor, offsets_d, offsets_g or status; a null iou with D, G > 0; a null counts with its capacity above 0; D
+ * or G outside 0..1024; H or W below 1 or H W >= 2^31; a negative capacity; ld < G; a pointer off its element's boundary. */
+typedef struct {
+    int D, G, H, W, capacity_d, capacity_g, ld;
+    const int32_t* offsets_d;
+    const uint32_t* counts_d;
+    const int32_t* offsets_g;
+    const uint32_t* counts_g;
+    const int32_t* n_det;
+    const uint8_t* iscrowd;
+    double* iou;
+    int32_t* inter;
+    int32_t* area;
+    int32_t* status;
+    void* workspace;
+    size_t workspace_bytes;
+} dc_rle_iou_desc;
+
+size_t dc_rle_iou_workspace_bytes(const dc_rle_iou_desc* d);
+int    dc_rle_iou_f64(const dc_rle_iou_desc* d, void* stream);
+
+/* dc_box_iou_f64: utils.compute_overlaps for B images: boxes int32 [B][Dmax][4] and gt_boxes int32 [B][Gmax][4] as (y1, x1, y2, x2)
+ * -> out float64 [B][Dmax][ld], every entry of the Dmax x Gmax block written.  compute_iou's formula on integers -- areas, clipped
+ * intersection sides, inter = iw * ih, union = area + area - inter, in int64 (NumPy's int32 results wherever those do not wrap) --
+ * and ONE float64 division; a zero union gives the NaN NumPy's 0 / 0 gives.  One launch; B Dmax Gmax = 0 launches nothing.
+ * DC_EINVAL: B outside 0..65535, Dmax or Gmax outside 0..1024, ld < Gmax, and with something to compute a null pointer, a box array
+ * off a 16-byte boundary or out off an 8-byte boundary. */
+int dc_box_iou_f64(const int32_t* boxes, const int32_t* gt_boxes, int B, int Dmax, int Gmax, int ld, double* out, void* stream);
+
+/* dc_detection_ap_f64: utils.compute_ap's matching and average precision on a GIVEN IoU matrix, for B images and T thresholds at
+ * once (detection_eval.ap_from_overlaps on the host).  overlaps float64 [B][Dmax][ld], row = prediction in the caller's order; n_det,
+ * n_gt int32 [B] in DEVICE memory (under refine="device" the host does not know n_det), clipped to 0..Dmax and 0..Gmax: only the
+ * leading n_det x n_gt block of an image is read; pred_class int32 [B][Dmax], pred_score float32 [B][Dmax], gt_class int32
+ * [B][Gmax]; thresholds float64 [T].
+ * Outputs: ap float64 [B][T]; where non-null, pred_match int32 [B][T][Dmax] -- per prediction IN RANK ORDER the ground truth matched
+ * to it or -1 --, gt_match int32 [B][T][Gmax] -- the rank of the prediction matched to it or -1 -- and order int32 [B][Dmax], the
+ * prediction at each rank; entries behind n_det / n_gt are -1.
+ * The rule.  Predictions are ranked by score, descending, equal scores the HIGHER index first (np.argsort(kind="stable")[::-1]; a
+ * NaN score ranks first).  In rank order each takes, among the still unmatched ground truths of its class with IoU >= threshold, the
+ * one of the highest IoU, on equal IoU the higher index; a NaN IoU is never eligible.  Then, as the reference: precisions
+ * hits / (rank + 1) in float64; recalls hits / n_gt as a FLOAT32 quotient widened to float64; [0] and [0] / [0] and [1] around them;
+ * the right-to-left maximum of the precisions; the sum of (recall step) * precision over the indices where the recall changes, in
+ * NumPy's order for fewer than 128 terms at any length: a plain loop below 8 terms, otherwise eight accumulators over the whole
+ * groups of 8 combined as ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)) and the remainder in sequence.  n_gt = 0 gives NaN.
+ * One launch of T x B workgroups: a rank sort by all threads, the matching by one wave that keeps the matched set in registers (no
+ * barrier inside the loop), the sums by one thread.  No workspace.  B = 0 launches nothing.
+ * DC_EINVAL: a null descriptor; B outside 0..65535; Dmax or Gmax outside 0..1024; T outside 1..16; ld < Gmax; with B > 0 a null
+ * n_det, n_gt, thresholds or ap, a null overlaps with Dmax, Gmax > 0, a null pred_class or pred_score with Dmax > 0, a null gt_class
+ * with Gmax > 0, or a pointer off its element's boundary. */
+typedef struct {
+    int B, Dmax, Gmax, ld, T;
+    const double* overlaps;
+    const int32_t* n_det;
+    const int32_t* n_gt;
+    const int32_t* pred_class;
+    const float* pred_score;
+    const int32_t* gt_class;
+    const double* thresholds;
+    double* ap;
+    int32_t* pred_match;
+    int32_t* gt_match;
+    int32_t* order;
+} dc_detection_ap_desc;
+
+int dc_detection_ap_f64(const dc_detection_ap_desc* d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
